@@ -10,6 +10,12 @@ DISPOSED OF per second: every hypothesis' outcome in the reference's sequential 
 the (512-point tile, hypothesis) pairs that can hold an inlier are evaluated point by point, and hypotheses whose
 upper bound cannot reach an earlier hypothesis' count are pruned (both exact).
 
+A plain run does what the headline needs: set-up (cloud, priming fits), W warm-up steps, K timed steps, the line.  `roofline`
+(except `attainable`) is read from the timed steps themselves.  Every other object below takes runs of its own and is
+measured only with --full.  --dump-outputs DIR writes the last timed step's results (params, inliers, summary = ret,
+best_index, n_inliers, count, iterations) as float64 .npy files; the inputs are seeded, so two builds
+can be compared output for output.
+
 JSON objects besides the contract's fields:
   roofline     the bound that actually binds the dominant kernel score_screen_k<plane>: VALU issue.
                achieved = (tile, hypothesis) pairs the timed launches evaluated (counted inside the kernel,
@@ -40,11 +46,11 @@ launcher (WORLD_SIZE set) it is one of the ranks.  Control plane (rendezvous, ba
 --scaling weak (the DEFAULT at every N: ONE headline workload, per-GPU work fixed, so that the driver can derive an efficiency
 from the per-N values): --hyp hypotheses PER GPU of one stream, value = N x hyp / t.  `scaling: "weak"` in the line says so:
 the per-N values are NOT the north_star's strong-scaling curve.  That question -- fixed TOTAL work -- is answered by the
-`strong_scaling` block every N > 1 line carries (C2, C3 cylinder, C3 sphere: one-GPU time measured in the same job, the
+`strong_scaling` block every N > 1 line carries with --full (C2, C3 cylinder, C3 sphere: one-GPU time measured in the same job, the
 term-by-term model's prediction beside each), and what N GPUs deliver on independent jobs by the `replicas` block (no collective).
---scaling strong: --hyp hypotheses in total, value = hyp / t; a `weak_scaling` block rides along instead.
+--scaling strong: --hyp hypotheses in total, value = hyp / t; with --full a `weak_scaling` block rides along instead.
 
-More objects of the N = 1 line:
+More objects of the N = 1 line (--full):
   fp64_only    the same K steps with m3d_config.score_fp32_screen = 0, cull_fp32 = 0 (the reference's arithmetic only) and
                the VALU-issue fraction of score_mask_k on them: `value` read on the reference's own arithmetic.
   setup_ms     m3d_cloud_create (SetPointCloud's copy: upload, transpose, Hilbert sort, tile boxes), which the timed steps
@@ -117,7 +123,34 @@ def parse():
     ap.add_argument("--no-strong-extra", action="store_true", help="N > 1: skip the strong-scaling block")
     ap.add_argument("--kernel-detail", action="store_true",
                     help="extra stand-alone launches: fp64-VALU fraction on the unpruned launch, cull kernel, dense kernel")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline as well: cold, without_kernel_timing_events, fp64_only, plane_bound, "
+                         "setup_ms, oneshot_ms, cpu_baseline, roofline.attainable; N > 1: strong_scaling, weak_scaling, replicas")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (params, inliers, summary) to DIR/<name>.npy as float64")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_MAX_ELEMENTS = 6_000_000      # 48 MB of float64: a longer inlier list is dumped as a fixed, seeded sample
+
+
+def dump_outputs(d, res):
+    """What a caller of the timed step receives (Cloud.fit: ret, params, inlier list, stats), as float64 arrays.  Indices
+    and counts are exact in float64; of the stats only the integer results are kept (the timings differ from run to run,
+    inlier_rmse is NaN on this path and fitness is n_inliers / N)."""
+    os.makedirs(d, exist_ok=True)
+    st = res.stats
+    inl = np.asarray(res.inliers)
+    if len(inl) > DUMP_MAX_ELEMENTS:
+        inl = inl[np.sort(np.random.default_rng(0).choice(len(inl), DUMP_MAX_ELEMENTS, replace=False))]
+    arrays = {"params": np.asarray(res.params, dtype=np.float64),
+              "inliers": inl.astype(np.float64),
+              "summary": np.array([res.ret, st["best_index"], st["n_inliers"], st["count"], st["iterations"]], dtype=np.float64)}
+    for name, v in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), v)
 
 
 def respawn_ranks(n):
@@ -353,7 +386,7 @@ def main():
     # priming in front of them (clocks on their way up, the lane's scratch allocated by the first fit).  Measured first, so that
     # nothing has warmed anything; the contract's steady-state value follows behind the priming fits.
     cold = None
-    if world == 1 and comm is None:
+    if a.full and world == 1 and comm is None:
         barrier()
         t0 = time.perf_counter()
         step()
@@ -401,28 +434,33 @@ def main():
     ms_per_step = dt / a.steps * 1e3
     value = H_total * a.steps / dt
     coll_per_step = comm.collectives / float(PRIMING_FITS + a.warmup + a.steps) if comm is not None else 0.0
+    # here, before any further fit: res.inliers is a view of the cloud's output buffer (copy=False), which the next fit overwrites
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, res)
     # the same steps as a caller gets them (no timing events in the stream): reported beside the contract's number
-    capi.set_config(kernel_timing=0)
-    for _ in range(5):
-        step()
-    barrier()
-    gc.disable()
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
-        step()
-    barrier()
-    dt_plain = time.perf_counter() - t0
-    gc.enable()
-    if world > 1:
-        t = torch.tensor([dt_plain], dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt_plain = float(t.item())
-    capi.set_config(kernel_timing=1)
+    dt_plain = None
+    if a.full:
+        capi.set_config(kernel_timing=0)
+        for _ in range(5):
+            step()
+        barrier()
+        gc.disable()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            step()
+        barrier()
+        dt_plain = time.perf_counter() - t0
+        gc.enable()
+        if world > 1:
+            t = torch.tensor([dt_plain], dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt_plain = float(t.item())
+        capi.set_config(kernel_timing=1)
 
     # ---- N = 1: the same steps on the reference's own arithmetic, the set-up the timed steps do not contain, and the
     # reference-shaped call (host arrays in, results out: py_common.cpp:11-27 has no resident handle) ----------------
     fp64_only, setup, oneshot, plane_bound = None, None, None, None
-    if world == 1 and comm is None:
+    if a.full and world == 1 and comm is None:
         old_cfg = capi.set_config(score_fp32_screen=0, cull_fp32=0)
         try:
             for _ in range(5):
@@ -542,7 +580,7 @@ def main():
 
     # ---- N > 1: strong scaling at fixed total work, one-GPU time measured in the same job (rank 0 alone) ----------
     strong = None
-    if world > 1 and not a.no_strong_extra:
+    if a.full and world > 1 and not a.no_strong_extra:
         strong = {}
         for wl in ("c2", "c3cyl", "c3sph"):
             k2, h2, thr2, seed2, label2 = WORKLOADS[wl]
@@ -582,7 +620,7 @@ def main():
 
     # ---- N > 1 with the strong headline: the weak-scaling number rides along (N x hyp hypotheses of one stream) ---------
     weak = None
-    if world > 1 and a.scaling == "strong" and not a.no_strong_extra:
+    if a.full and world > 1 and a.scaling == "strong" and not a.no_strong_extra:
         Hw = H * world
         for _ in range(3):
             cloud.fit_sharded(comm, kind, thr, Hw, prob, seed=seed, copy=False, want_inliers=(rank == 0))
@@ -599,7 +637,7 @@ def main():
     # ---- N > 1: what N GPUs deliver on INDEPENDENT fits (replicas: every rank fits its own job on its own GPU, no collective,
     # no replicated sampler / MinimalFit / RefineModel beyond its own) -- the throughput figure next to the one-stream numbers
     replicas = None
-    if world > 1:
+    if a.full and world > 1:
         for _ in range(3):
             cloud.fit(kind, thr, H, prob, seed=seed + rank, copy=False)
         barrier()
@@ -675,15 +713,16 @@ def main():
                                 "CPU).  Exceeds the HBM peak BY CONSTRUCTION: each point load is re-used from VGPRs by "
                                 "all hypotheses of the launch, box-culled (tile, hypothesis) pairs and pruned hypotheses "
                                 "are never evaluated.  Reported for SURVEY.md 8(d); it is not a roofline fraction."}}
-        try:
-            # what the chip SUSTAINS on independent fp64 mul / add chains (it clocks below 2.4 GHz under that load):
-            # the attainable counterpart of `peak`, measured here, right after the timed steps
-            att, att_ms = capi.fp64_issue_rate(local, 3.0)
-            roofline["attainable"] = {"peak_measured": att, "unit": roofline["unit"], "frac_of_measured_peak": v_tops / att,
-                                      "probe": f"m3d_bench_fp64_issue_rate: 2048 workgroups x 256 threads of independent v_mul_f64 / "
-                                               f"v_add_f64 chains for {att_ms:.2f} ms; `frac` above stays quoted on the nominal peak"}
-        except Exception as e:      # noqa: BLE001 -- a probe, never fatal
-            roofline["attainable"] = {"error": str(e)}
+        if a.full:
+            try:
+                # what the chip SUSTAINS on independent fp64 mul / add chains (it clocks below 2.4 GHz under that load):
+                # the attainable counterpart of `peak`, measured here, after the timed steps
+                att, att_ms = capi.fp64_issue_rate(local, 3.0)
+                roofline["attainable"] = {"peak_measured": att, "unit": roofline["unit"], "frac_of_measured_peak": v_tops / att,
+                                          "probe": f"m3d_bench_fp64_issue_rate: 2048 workgroups x 256 threads of independent v_mul_f64 / "
+                                                   f"v_add_f64 chains for {att_ms:.2f} ms; `frac` above stays quoted on the nominal peak"}
+            except Exception as e:      # noqa: BLE001 -- a probe, never fatal
+                roofline["attainable"] = {"error": str(e)}
         if a.kernel_detail:
             Hk = min(H, 16384)
             samples = capi.draw_samples(N, kind, Hk, seed)
@@ -717,11 +756,12 @@ def main():
                "result": {"best_index": int(res.stats["best_index"]), "n_inliers": int(n_in),
                           "params": [float(v) for v in res.params]},
                "roofline": roofline,
-               "timing_breakdown_ms": {k: res.stats[k] for k in ("ms_sample", "ms_score", "ms_refine", "ms_total")},
-               "without_kernel_timing_events": {"ms_per_step": dt_plain / a.steps * 1e3, "value": H_total * a.steps / dt_plain,
-                                                "note": "the same K steps again with m3d_config.kernel_timing = 0, the library's "
-                                                        "default: `value` above carries the four HIP-event commands per chunk "
-                                                        "that `roofline.launch_ms` is measured with"}}
+               "timing_breakdown_ms": {k: res.stats[k] for k in ("ms_sample", "ms_score", "ms_refine", "ms_total")}}
+        if dt_plain is not None:
+            out["without_kernel_timing_events"] = {"ms_per_step": dt_plain / a.steps * 1e3, "value": H_total * a.steps / dt_plain,
+                                                   "note": "the same K steps again with m3d_config.kernel_timing = 0, the library's "
+                                                           "default: `value` above carries the four HIP-event commands per chunk "
+                                                           "that `roofline.launch_ms` is measured with"}
         if fp64_only:
             out["fp64_only"] = fp64_only
         if cold:
@@ -751,7 +791,7 @@ def main():
                               "per round costs what an eighth of the scoring saves (DESIGN.md 5).  What N GPUs are good for on this path "
                               "is N independent scenes in flight: m3d_segment_plane_iterative per device, tools/time_c5_plain.py "
                               "--devices N (replicas, no collective)")
-        if world == 1 and not a.no_cpu_baseline and a.workload == "c2":
+        if a.full and world == 1 and not a.no_cpu_baseline and a.workload == "c2":
             import oracle
             cb, (cmodel, ccnt, cbi, ch) = cpu_baseline(pts, thr, seed, a.cpu_seconds, H_total)
             out["cpu_baseline"] = cb

@@ -17,7 +17,7 @@ def test_bench_starts_its_own_ranks_and_prints_one_json_line():
     env = dict(os.environ, M3D_BENCH_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2",
-                        "--points", "200000"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--points", "200000", "--full"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]

@@ -1,6 +1,6 @@
 """Per-kernel timeline of ONE bench step from a rocprofv3 kernel trace (csv): start offset, duration and the gap to the
 previous kernel, for one step of the trace.  Usage: python tools/step_timeline.py <trace.csv> [first-kernel-substring] [step index]
-(default: the last complete step; bench.py ends with its one-shot fits, so the resident-cloud step wants an index,
+(default: the last complete step; bench.py --full ends with its one-shot fits, so the resident-cloud step wants an index,
 e.g. 15 = inside the timed region)"""
 import csv
 import sys
