@@ -293,6 +293,35 @@ int m3d_normals_from_map(const double *xyz, uint32_t w, uint32_t h, uint32_t k, 
 int m3d_detect_boundary_points(const double *xyz, const double *normals, size_t n, int search, double radius,
                                int max_nn, double angle_threshold_deg, int device, size_t *indices, size_t *k);
 
+/* ---- misc3d::preprocessing::FarthestPointSampling, src/filter.cpp:13-52 ------------------------------------------ */
+/* indices (capacity num_samples) = the reference's samples, bit for bit: index 0 first, then at every step the lowest
+ * index of the largest min-over-samples squared distance (3-element sum in the library's M3D_FP_ORDER association); when
+ * no distance is > 0 the previous index repeats.  num_samples == 0: nothing; == n: 0 .. n-1; > n or < 0:
+ * M3D_ERR_INVALID_ARG "Illegal number of samples: S, must <= point size: N" -- all three decided before any device is
+ * touched.  n >= 2^31: M3D_ERR_INVALID_ARG.  stats may be NULL.  Re-entrant: concurrent calls take lanes of the device. */
+#define M3D_FPS_PATH_SINGLE 1   /* one workgroup, all steps in one launch (small clouds) */
+#define M3D_FPS_PATH_PRUNED 2   /* Hilbert-sorted 512-point tiles, one launch per sample, tiles skipped by a box bound */
+#define M3D_FPS_PATH_DENSE 3    /* the same steps with every tile updated (measurement hook only: m3d_bench_fps_force_path) */
+typedef struct m3d_fps_stats {
+    double ms_total;            /* the call, host clock */
+    double ms_device;           /* the sampling launches, HIP events (0 for the early cases) */
+    int32_t path;               /* M3D_FPS_PATH_*, 0 = no device work */
+    int32_t pad;
+    uint64_t tiles_updated;     /* tile updates the steps ran (tiled paths) */
+    uint64_t tile_steps;        /* tiles x steps: 1 - tiles_updated / tile_steps = the fraction pruned */
+} m3d_fps_stats;
+int m3d_farthest_point_sampling(const double *xyz, size_t n, int64_t num_samples, int device, size_t *indices,
+                                m3d_fps_stats *stats);
+
+/* ---- misc3d::preprocessing::CropROIPointCloud's indexing, src/filter.cpp:54-101 (host only, no device) ----------- */
+/* n points of an organised cloud of shape (width, height), roi = (tl_x, tl_y, br_x, br_y): *k = (roi_w + 1) (roi_h + 1)
+ * indices, indices[i] = (i / roi_w + tl_y) width + i % roi_w + tl_x with roi_w = br_x - tl_x, roi_h = br_y - tl_y -- the
+ * reference's formula, rows roi_w wide, quirk included.  indices may be NULL (only *k).  n != width height:
+ * M3D_ERR_INVALID_ARG "The size of point cloud is wrong."; roi_w <= 0 (the reference divides by it), roi_h < -1 or an
+ * index outside [0, n) (the reference reads outside the cloud): M3D_ERR_INVALID_ARG. */
+int m3d_crop_roi_indices(size_t n, int width, int height, int tl_x, int tl_y, int br_x, int br_y, size_t *indices,
+                         size_t *k);
+
 /* ---- point-to-point ICP refinement of the RANSAC pose ----------------------- */
 /* open3d::pipelines::registration::RegistrationICP(source, target, max_correspondence_distance, init,
  * TransformationEstimationPointToPoint(), ICPConvergenceCriteria(relative_fitness, relative_rmse,

@@ -62,6 +62,12 @@ int m3d_bench_reg_checkers(const double *ps, const double *pd, const double *T, 
  * 0 (the product build): those switches are ignored and m3d_bench_mfma_probe returns an error. */
 int m3d_bench_experimental(void);
 
+/* MEASUREMENT / TEST hook (tools/bench_configs.py P1 / P2, tests/test_gpu_fps.py): the device path of every later
+ * m3d_farthest_point_sampling in the process -- 0 = by size (the default), M3D_FPS_PATH_SINGLE (n <= 8192),
+ * M3D_FPS_PATH_PRUNED, M3D_FPS_PATH_DENSE (the pruned path's steps with no tile skipped: the A/B reference).  The
+ * result does not depend on it. */
+int m3d_bench_fps_force_path(int path);
+
 /* TEST hook (tests/test_gpu_match_sliced.py): which way the CALLING THREAD's last m3d_match_mutual_nn went -- bit 0: the split-fp16
  * MFMA screen produced the result, bit 1: the matrices went up in slices under the scan (m3d_config.match_pipeline), bit 2: a
  * later slice did not fit the scale chosen from the first ones and the search was redone whole on the resident matrices,

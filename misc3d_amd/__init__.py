@@ -12,6 +12,8 @@ Drop-in for the reference's python API on this path (module layout of python/py_
     T        = m3d.registration.compute_transformation_least_square(src, dst)
     T, info  = m3d.registration_icp(src, dst, 0.02, T)      # the Open3D call the reference's examples chain next
     index    = m3d.features.detect_boundary_points(plane, ("hybrid", 0.02, 30))
+    index    = m3d.preprocessing.farthest_point_sampling(pcd, 1000)
+    roi      = m3d.preprocessing.crop_roi_pointcloud(pcd, (tl_x, tl_y, br_x, br_y), (width, height))
     normals  = m3d.common.estimate_normals(pcd, (848, 480), 3)
     ok, T, info = m3d.reconstruction.global_registration(frag_s, frag_t, fpfh_s, fpfh_t, voxel_size)   # pipeline.cpp:790-828
     results  = m3d.reconstruction.register_fragment_pairs(fragments, fpfhs, voxel_size=voxel_size)     # pipeline.cpp:428-439
@@ -169,11 +171,71 @@ class _Reconstruction:
 reconstruction = _Reconstruction()
 
 
+class _Preprocessing:
+    """misc3d.preprocessing (python/py_preprocessing.cpp): farthest_point_sampling, crop_roi_pointcloud, project_into_plane"""
+
+    _FPS_INFO = ("This method has been added to Open3D official branch and hence it will be deprecated in the future.")
+
+    @staticmethod
+    def farthest_point_sampling(pc, num_points, *, as_arrays=False, device=0):
+        """FarthestPointSampling (src/filter.cpp:13-52), bit for bit.  pc: (N, 3) array or an object with .points.
+        Returns list[int], or an int64 array with as_arrays=True."""
+        import numpy as _np
+
+        from . import capi as _capi
+        _ext._log_info(_Preprocessing._FPS_INFO)   # src/filter.cpp:15-17
+        try:
+            idx = _capi.farthest_point_sampling(_xyz(pc), int(num_points), device)
+        except _capi.M3DError as e:
+            raise RuntimeError(str(e)) from e
+        if as_arrays:
+            return idx.astype(_np.int64)
+        return [int(i) for i in idx]
+
+    @staticmethod
+    def crop_roi_pointcloud(pc, roi, shape):
+        """CropROIPointCloud (src/filter.cpp:54-101): roi = (tl_x, tl_y, br_x, br_y), shape = (width, height) of the
+        organised cloud.  Returns an open3d PointCloud (points, and normals / colours when pc has them) when open3d
+        imports, else the (K, 3) points array (the fallback of segmentation.segment_plane_iterative)."""
+        import numpy as _np
+
+        from . import capi as _capi
+        pts = _xyz(pc)
+        try:
+            idx = _capi.crop_roi_indices(len(pts), roi, shape).astype(_np.int64)
+        except _capi.M3DError as e:
+            raise RuntimeError(str(e)) from e
+        out_pts = pts[idx]
+        try:
+            import open3d as _o3d
+        except ImportError:
+            return out_pts
+        pcd = _o3d.geometry.PointCloud(_o3d.utility.Vector3dVector(out_pts))
+        for attr in ("normals", "colors"):
+            v = getattr(pc, attr, None)
+            if v is not None:
+                v = _np.asarray(v, dtype=_np.float64).reshape(-1, 3)
+                if len(v) == len(pts):
+                    setattr(pcd, attr, _o3d.utility.Vector3dVector(v[idx]))
+        return pcd
+
+    @staticmethod
+    def project_into_plane(pc):
+        """ProjectIntoPlane: not on the accelerated path (its sums go through Eigen's dynamic-size GEMM, so no exact
+        association can be stated for it)."""
+        raise RuntimeError(
+            "[Misc3D Error] project_into_plane is outside the MI355X-accelerated hot path of this build (its sums go "
+            "through Eigen's dynamic-size GEMM: no bit-exact restatement exists); project with numpy instead")
+
+
+preprocessing = _Preprocessing()
+
+
 def registration_session(*args, **kwargs):
     """capi.RegSession: compute_transformation_ransac cut into begin_chunk / validate / replay, the unit
     misc3d_amd.distributed.registration_ransac_sharded shards over ranks."""
     from . import capi as _capi
     return _capi.RegSession(*args, **kwargs)
 
-__all__ = ["common", "registration", "segmentation", "features", "reconstruction", "registration_icp", "registration_session", "VerbosityLevel", "set_verbosity_level",
+__all__ = ["common", "registration", "segmentation", "features", "preprocessing", "reconstruction", "registration_icp", "registration_session", "VerbosityLevel", "set_verbosity_level",
            "get_verbosity_level", "device_count"]

@@ -160,6 +160,10 @@ def lib():
                                              C.c_void_p, C.c_void_p]
         L.m3d_detect_boundary_points.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_int, C.c_double,
                                                  C.c_int, C.c_void_p, C.c_void_p]
+        L.m3d_farthest_point_sampling.argtypes = [C.c_void_p, C.c_size_t, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
+        L.m3d_crop_roi_indices.argtypes = [C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_void_p]
+        L.m3d_bench_fps_force_path.argtypes = [C.c_int]
         L.m3d_match_last_fallbacks.restype = C.c_uint64
         L.m3d_match_last_fallbacks.argtypes = []
         L.m3d_match_mutual_nn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
@@ -1023,6 +1027,48 @@ def detect_boundary_points(xyz, normals=None, search=SEARCH_HYBRID, radius=0.01,
     _check(lib().m3d_detect_boundary_points(_p(xyz), _p(nrm), len(xyz), search, radius, max_nn, angle_threshold, device,
                                             _p(out), C.cast(C.byref(k), C.c_void_p)))
     return out[: k.value].copy()
+
+
+FPS_PATH_SINGLE, FPS_PATH_PRUNED, FPS_PATH_DENSE = 1, 2, 3
+
+
+class FpsStats(C.Structure):
+    """m3d_fps_stats"""
+    _fields_ = [("ms_total", C.c_double), ("ms_device", C.c_double), ("path", C.c_int32), ("pad", C.c_int32),
+                ("tiles_updated", C.c_uint64), ("tile_steps", C.c_uint64)]
+
+    def asdict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+        d["pruned_fraction"] = 1.0 - self.tiles_updated / self.tile_steps if self.tile_steps else 0.0
+        return d
+
+
+def farthest_point_sampling(xyz, num_samples, device=0, stats=False):
+    """m3d_farthest_point_sampling -> the sampled indices (uint64), and the stats dict when stats=True."""
+    xyz = _f64(xyz).reshape(-1, 3)
+    num_samples = int(num_samples)
+    out = np.zeros(max(num_samples, 1), dtype=np.uint64)
+    st = FpsStats()
+    _check(lib().m3d_farthest_point_sampling(_p(xyz), len(xyz), num_samples, device, _p(out), C.cast(C.byref(st), C.c_void_p)))
+    idx = out[: max(num_samples, 0)].copy()
+    return (idx, st.asdict()) if stats else idx
+
+
+def crop_roi_indices(n, roi, shape):
+    """m3d_crop_roi_indices: roi = (tl_x, tl_y, br_x, br_y), shape = (width, height) -> the source index of every
+    point of CropROIPointCloud's output (uint64)."""
+    tl_x, tl_y, br_x, br_y = (int(v) for v in roi)
+    width, height = (int(v) for v in shape)
+    k = C.c_size_t(0)
+    _check(lib().m3d_crop_roi_indices(int(n), width, height, tl_x, tl_y, br_x, br_y, None, C.cast(C.byref(k), C.c_void_p)))
+    out = np.zeros(max(k.value, 1), dtype=np.uint64)
+    _check(lib().m3d_crop_roi_indices(int(n), width, height, tl_x, tl_y, br_x, br_y, _p(out), C.cast(C.byref(k), C.c_void_p)))
+    return out[: k.value].copy()
+
+
+def fps_force_path(path: int):
+    """measurement / test hook m3d_bench_fps_force_path: 0 = by size, FPS_PATH_SINGLE / _PRUNED / _DENSE"""
+    _check(lib().m3d_bench_fps_force_path(int(path)))
 
 
 def information_matrix(src, dst, max_correspondence_distance, T, device=0):

@@ -499,6 +499,8 @@ PYBIND11_MODULE(_py_misc3d, m) {
     m.def("set_verbosity_level", &misc3d::SetVerbosityLevel, "Set global verbosity level of Misc3D",
           py::arg("verbosity_level"));
     m.def("get_verbosity_level", &misc3d::GetVerbosityLevel, "Get global verbosity level of Misc3D");
+    // the Info lines of the reference functions this package implements in python (misc3d_amd.preprocessing)
+    m.def("_log_info", [](const std::string& msg) { misc3d::LogInfo(msg); }, py::arg("msg"));
     m.def("device_count", []() { return m3d_device_count(); });
     m.def("release_host_scratch", []() {
         misc3d::ReleaseHostScratch();

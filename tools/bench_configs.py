@@ -5,6 +5,7 @@ bench.py); these lines feed DESIGN.md section 6 and check that the full sizes ru
   C1 fit_plane 50k pts, 100 iters (plumbing)            C2 fit_plane 1M pts, 10k hyp (= bench.py)
   C3 fit_cylinder + fit_sphere 1M pts, 50k hyp          C4 match + compute_transformation_ransac 200k<->200k, 100k hyp
   C5 segment_plane_iterative 10M pts (single GPU leg)
+  P1 / P2 farthest_point_sampling 5 841 x 1 000 (the reference example) / 1M x 10 000, every device path (A/B)
 """
 import json
 import os
@@ -502,3 +503,68 @@ if "C5" in which:
                                        "note": "1000 hypotheses on ~1 M clutter points each, the round's kernels back to back: ~58 us of box tests and scoring (latency-bound launches, 8 % of the (tile, hypothesis) pairs survive), ~24 us of RefineModel's compaction + the partition in creation order at 3.6 TB/s, ~8 us for the previous round's tombstone pass riding in minimal_fit_k's launch; no host wait but the records' (profiles/r03_c5_round_timeline.txt)"}},
                    "note": "whole call (PCIe upload of 240 MB and 76 MB of index lists back included)"},
          cpu_baseline=cpu("segmentation_baseline", pts, 0.01, 1000, 0.05, 19, [c for c in clusters if len(c) > n / 8], 14.0))
+
+if "P1" in which or "P2" in which or ALL:
+    # misc3d.preprocessing.farthest_point_sampling: P1 = the reference example's shape (examples/python/farthest_point_sampling.py,
+    # 5 841 points x 1 000 samples), P2 = 1 M synthetic points x 10 000 samples
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from fps_ref_util import build_ref
+
+    def fps_cpu(pts, S, steps):
+        """the serial restatement of the reference's loop (tests/cpp/fps_ref.c, gcc -O2 -ffp-contract=off), timed on a bounded
+        number of steps and scaled linearly to S (every step is one full pass over the N points: constant cost)"""
+        if NO_CPU:
+            return None
+        ref = build_ref(tempfile.mkdtemp())
+        ref(pts, 2)
+        t0 = time.perf_counter()
+        ref(pts, steps)
+        dt = time.perf_counter() - t0
+        return {"value": dt / steps * S * 1e3, "unit": "ms (scaled)", "cores": 1, "kind": "port",
+                "sample": f"{steps} of {S} steps timed ({dt * 1e3:.1f} ms), scaled linearly: the reference's loop is serial, "
+                          "with no OpenMP (src/filter.cpp:13-52)", "ns_per_point_update": dt / (steps * len(pts)) * 1e9,
+                "flags": "-O2 -ffp-contract=off"}
+
+    for tag, n, S, paths in (("P1", 5841, 1000, (1, 2, 3)), ("P2", 1_000_000, 10_000, (2, 3))):
+        if not (tag in which or ALL):
+            continue
+        pts = np.random.default_rng(17).uniform(-1, 1, (n, 3))
+        rows = {}
+        for path in paths:
+            capi.fps_force_path(path)
+            try:
+                capi.farthest_point_sampling(pts, S)   # (sizes the lane's block free list)
+                ts = []
+                for _ in range(3):
+                    t0 = time.perf_counter()
+                    idx, st = capi.farthest_point_sampling(pts, S, stats=True)
+                    ts.append(((time.perf_counter() - t0) * 1e3, st))
+            finally:
+                capi.fps_force_path(0)
+            ms, st = sorted(ts, key=lambda r: r[0])[1]
+            rows[{1: "single", 2: "pruned", 3: "dense"}[path]] = {
+                "ms": ms, "ms_device": st["ms_device"], "ms_in_library": st["ms_total"], "pruned_fraction": st["pruned_fraction"],
+                "tiles_updated": st["tiles_updated"], "tile_steps": st["tile_steps"]}
+        default = capi.farthest_point_sampling(pts, S, stats=True)[1]
+        path_name = {1: "single", 2: "pruned", 3: "dense"}[default["path"]]
+        best = rows[path_name]
+        if tag == "P1":
+            roofline = {"bound": "latency: one workgroup, one step = update + wave argmax + one barrier",
+                        "kernel": "m3d::fps_single_k<8>", "achieved": best["ms_device"] * 1e3 / (S - 1), "unit": "us per step",
+                        "note": "a step's serial chain (8 point updates, 6 shuffle levels, LDS, __syncthreads, 16-way reduce) "
+                                "bounds it, not bandwidth: the cloud sits in registers"}
+        else:
+            dense_bytes = 32.0 * n * (S - 1)
+            d = rows["dense"]
+            roofline = {"bound": "pruned: one kernel boundary per sample (~1.5 us, MI355X_MICROARCH.md row boundary); "
+                                 "dense: HBM, 32 B per point per step",
+                        "kernel": "m3d::fps_step_k", "launches": S - 1,
+                        "pruned_us_per_step": rows["pruned"]["ms_device"] * 1e3 / (S - 1),
+                        "launch_floor_ms": 1.5e-3 * (S - 1),
+                        "frac_pruned_vs_launch_floor": 1.5e-3 * (S - 1) / rows["pruned"]["ms_device"],
+                        "dense_achieved_GBps": dense_bytes / (d["ms_device"] * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
+                        "dense_frac": dense_bytes / (d["ms_device"] * 1e-3) / 1e9 / HBM_PEAK_GBS, "unit": "GB/s (dense)"}
+        emit(f"{tag} farthest_point_sampling {n} pts x {S} samples", ms=best["ms"], ms_device=best["ms_device"], path=path_name,
+             pruned_fraction=best["pruned_fraction"], paths=rows, roofline=roofline,
+             cpu_baseline=fps_cpu(pts, S, 200 if n < 100_000 else 20))
