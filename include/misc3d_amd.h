@@ -322,6 +322,50 @@ int m3d_farthest_point_sampling(const double *xyz, size_t n, int64_t num_samples
 int m3d_crop_roi_indices(size_t n, int width, int height, int tl_x, int tl_y, int br_x, int br_y, size_t *indices,
                          size_t *k);
 
+/* ---- misc3d::segmentation::ProximityExtractor::Segment, src/proximity_extraction.cpp:51-190 ----------------------- */
+/* The clusters are the connected components of the graph with an edge i - j when j is in i's radius neighbourhood
+ * (d2 = (dx dx + dy dy) + dz dz <= radius^2, j != i) and the evaluator accepts (i, j, sqrt(d2)); a point with a non-finite
+ * coordinate has no neighbours.  Components with min_size <= |C| <= max_size are kept (a larger one is dropped whole).
+ * Order: size descending, ties by smallest member index ascending (the reference's unstable sort leaves it open); indices
+ * within a cluster ascending.  cluster_offsets[0 .. *n_clusters] (capacity n + 1) delimit the clusters in cluster_indices
+ * (capacity n).  labels (may be NULL, n entries): the rank of each point's cluster, *n_clusters for the points of no kept
+ * cluster.  stats may be NULL.
+ * Errors (M3D_ERR_INVALID_ARG): a normals evaluator with n_normals < n, "Index exceed size of data!"; a radius that is
+ * negative or not finite; n >= 2^31.  n == 0: no clusters.  Re-entrant: concurrent calls take lanes of the device. */
+#define M3D_PROX_DISTANCE 1         /* DistanceProximityEvaluator(dist):              dist < dist_thresh */
+#define M3D_PROX_NORMALS 2          /* NormalsProximityEvaluator(normals, angle_deg)  acos(dot) vs Deg2Rad(angle_deg) */
+#define M3D_PROX_DISTANCE_NORMALS 3 /* DistanceNormalsProximityEvaluator(normals, dist, angle_deg) */
+typedef struct m3d_proximity_evaluator {
+    int32_t kind;                   /* M3D_PROX_* */
+    int32_t pad;
+    double dist;                    /* distance threshold (DISTANCE, DISTANCE_NORMALS) */
+    double angle_deg;               /* angle threshold in degrees (NORMALS, DISTANCE_NORMALS; < 0: unoriented normals) */
+} m3d_proximity_evaluator;
+typedef struct m3d_proximity_stats {
+    double ms_total;                /* the call, host clock */
+    double ms_device;               /* grid + union + flatten launches, HIP events */
+    double ms_order;                /* the ordering of the components and the scatter of the indices, host clock */
+    double cell_edge;               /* edge of the grid's cells (radius * 1.001 unless the 2^27-cell cap coarsened it) */
+    uint64_t components;            /* connected components, kept or not */
+} m3d_proximity_stats;
+int m3d_proximity_segment(const double *xyz, const double *normals, size_t n_normals, size_t n, double radius,
+                          const m3d_proximity_evaluator *ev, size_t min_size, size_t max_size, int device,
+                          size_t *cluster_offsets, size_t *cluster_indices, size_t *n_clusters, size_t *labels,
+                          m3d_proximity_stats *stats);
+/* The nn_indices overload (:59-72): n_lists lists in CSR form (nn_offsets[0 .. n_lists], nn_indices); entry 0 of every
+ * list is skipped (the reference's j = 1), edge i -> nn_indices[k] with dist = norm3(p_i - p_j) (Eigen's .norm()), the
+ * clusters are the weakly connected components.  n_lists != n: M3D_ERR_INVALID_ARG "The number of input data size are not
+ * equal!"; an index outside [0, n): M3D_ERR_INVALID_ARG.  Output as m3d_proximity_segment. */
+int m3d_proximity_segment_nn(const double *xyz, const double *normals, size_t n_normals, size_t n, size_t n_lists,
+                             const size_t *nn_offsets, const size_t *nn_indices, const m3d_proximity_evaluator *ev,
+                             size_t min_size, size_t max_size, int device, size_t *cluster_offsets,
+                             size_t *cluster_indices, size_t *n_clusters, size_t *labels, m3d_proximity_stats *stats);
+/* Radius neighbour lists (j != i, d2 <= radius^2 as above), each sorted by (d2, index): the user-evaluator path of the
+ * C++ / python ProximityExtractor.  offsets (n + 1 entries) always; *total = offsets[n].  nb_indices / nb_d2 (capacity
+ * entries each) are filled when both are non-NULL and capacity >= *total -- call once with NULL to learn the size. */
+int m3d_radius_neighbors(const double *xyz, size_t n, double radius, int device, size_t *offsets, uint32_t *nb_indices,
+                         double *nb_d2, size_t capacity, size_t *total);
+
 /* ---- point-to-point ICP refinement of the RANSAC pose ----------------------- */
 /* open3d::pipelines::registration::RegistrationICP(source, target, max_correspondence_distance, init,
  * TransformationEstimationPointToPoint(), ICPConvergenceCriteria(relative_fitness, relative_rmse,

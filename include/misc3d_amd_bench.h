@@ -68,6 +68,11 @@ int m3d_bench_experimental(void);
  * result does not depend on it. */
 int m3d_bench_fps_force_path(int path);
 
+/* TEST hook (tests/test_proximity.py): the cut-offs m3d_proximity_segment derives on the host for an evaluator
+ * (m3d_proximity_fp.hpp) -- out[0] = d2_cut (Distance: dist < t <=> d2 < d2_cut; DistanceNormals: dist >= t <=>
+ * d2 >= d2_cut), out[1..4] = lo1, hi1, lo2, hi2 (the angle test accepts dot exactly on [lo1, hi1] u [lo2, hi2]). */
+int m3d_bench_proximity_cutoffs(double dist, double angle_deg, double out[5]);
+
 /* TEST hook (tests/test_gpu_match_sliced.py): which way the CALLING THREAD's last m3d_match_mutual_nn went -- bit 0: the split-fp16
  * MFMA screen produced the result, bit 1: the matrices went up in slices under the scan (m3d_config.match_pipeline), bit 2: a
  * later slice did not fit the scale chosen from the first ones and the search was redone whole on the resident matrices,

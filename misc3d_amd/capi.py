@@ -164,6 +164,15 @@ def lib():
         L.m3d_crop_roi_indices.argtypes = [C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                            C.c_void_p]
         L.m3d_bench_fps_force_path.argtypes = [C.c_int]
+        L.m3d_proximity_segment.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_double, C.c_void_p,
+                                            C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]
+        L.m3d_proximity_segment_nn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.m3d_radius_neighbors.argtypes = [C.c_void_p, C.c_size_t, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_size_t, C.c_void_p]
+        L.m3d_bench_proximity_cutoffs.argtypes = [C.c_double, C.c_double, C.c_void_p]
         L.m3d_match_last_fallbacks.restype = C.c_uint64
         L.m3d_match_last_fallbacks.argtypes = []
         L.m3d_match_mutual_nn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
@@ -1069,6 +1078,81 @@ def crop_roi_indices(n, roi, shape):
 def fps_force_path(path: int):
     """measurement / test hook m3d_bench_fps_force_path: 0 = by size, FPS_PATH_SINGLE / _PRUNED / _DENSE"""
     _check(lib().m3d_bench_fps_force_path(int(path)))
+
+
+PROX_DISTANCE, PROX_NORMALS, PROX_DISTANCE_NORMALS = 1, 2, 3
+_PROX_KINDS = {"distance": 1, "normals": 2, "distance_normals": 3}
+SIZE_MAX = 2**64 - 1
+
+
+class ProximityEvaluator(C.Structure):
+    """m3d_proximity_evaluator"""
+    _fields_ = [("kind", C.c_int32), ("pad", C.c_int32), ("dist", C.c_double), ("angle_deg", C.c_double)]
+
+
+class ProximityStats(C.Structure):
+    """m3d_proximity_stats"""
+    _fields_ = [("ms_total", C.c_double), ("ms_device", C.c_double), ("ms_order", C.c_double), ("cell_edge", C.c_double),
+                ("components", C.c_uint64)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def _prox_call(fn, xyz, normals, kind, dist, angle_deg, min_size, max_size, device, stats, between):
+    xyz = _f64(xyz).reshape(-1, 3)
+    nrm = None if normals is None else _f64(normals).reshape(-1, 3)
+    n = len(xyz)
+    ev = ProximityEvaluator(_PROX_KINDS.get(kind, kind), 0, float(dist), float(angle_deg))
+    off = np.zeros(n + 1, dtype=np.uint64)
+    idx = np.zeros(max(n, 1), dtype=np.uint64)
+    lab = np.zeros(max(n, 1), dtype=np.uint64)
+    k = C.c_size_t(0)
+    st = ProximityStats()
+    _check(fn(_p(xyz), _p(nrm), 0 if nrm is None else len(nrm), n, *between(n), C.byref(ev), int(min_size), int(max_size),
+              device, _p(off), _p(idx), C.cast(C.byref(k), C.c_void_p), _p(lab), C.cast(C.byref(st), C.c_void_p)))
+    off = off[: k.value + 1].copy()
+    res = (off, idx[: int(off[-1])].copy(), lab[:n].copy())
+    return res + (st.asdict(),) if stats else res
+
+
+def proximity_segment(xyz, radius, kind, dist=0.0, angle_deg=0.0, normals=None, min_size=1, max_size=SIZE_MAX, device=0,
+                      stats=False):
+    """m3d_proximity_segment -> (cluster offsets, cluster indices, labels) as uint64 arrays (+ the stats dict)."""
+    return _prox_call(lib().m3d_proximity_segment, xyz, normals, kind, dist, angle_deg, min_size, max_size, device, stats,
+                      lambda n: (float(radius),))
+
+
+def proximity_segment_nn(xyz, nn_offsets, nn_indices, kind, dist=0.0, angle_deg=0.0, normals=None, min_size=1,
+                         max_size=SIZE_MAX, device=0, stats=False, n_lists=None):
+    """m3d_proximity_segment_nn over CSR lists (nn_offsets: n_lists + 1 entries)."""
+    off = np.ascontiguousarray(nn_offsets, dtype=np.uint64)
+    ind = np.ascontiguousarray(nn_indices, dtype=np.uint64)
+    nl = len(off) - 1 if n_lists is None else n_lists
+    return _prox_call(lib().m3d_proximity_segment_nn, xyz, normals, kind, dist, angle_deg, min_size, max_size, device, stats,
+                      lambda n: (nl, _p(off), _p(ind) if len(ind) else None))
+
+
+def radius_neighbors(xyz, radius, device=0):
+    """m3d_radius_neighbors -> (offsets uint64 (n + 1), indices uint32, d2 float64), each list sorted by (d2, index)"""
+    xyz = _f64(xyz).reshape(-1, 3)
+    n = len(xyz)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    tot = C.c_size_t(0)
+    _check(lib().m3d_radius_neighbors(_p(xyz), n, float(radius), device, _p(off), None, None, 0,
+                                      C.cast(C.byref(tot), C.c_void_p)))
+    idx = np.zeros(max(tot.value, 1), dtype=np.uint32)
+    d2 = np.zeros(max(tot.value, 1), dtype=np.float64)
+    _check(lib().m3d_radius_neighbors(_p(xyz), n, float(radius), device, _p(off), _p(idx), _p(d2), tot.value,
+                                      C.cast(C.byref(tot), C.c_void_p)))
+    return off, idx[: tot.value].copy(), d2[: tot.value].copy()
+
+
+def proximity_cutoffs(dist, angle_deg):
+    """test hook m3d_bench_proximity_cutoffs -> (d2_cut, lo1, hi1, lo2, hi2)"""
+    out = np.zeros(5)
+    _check(lib().m3d_bench_proximity_cutoffs(float(dist), float(angle_deg), _p(out)))
+    return tuple(float(v) for v in out)
 
 
 def information_matrix(src, dst, max_correspondence_distance, T, device=0):

@@ -1,0 +1,223 @@
+// m3d_proximity.hip -- ProximityExtractor (src/proximity_extraction.cpp) on gfx950: the clusters are the connected
+// components of the graph "j in the radius neighbourhood of i and evaluator(i, j, dist)" ("Proximity
+// extraction"), found with a lock-free union-find over original point indices.
+//
+// parent[] invariant: parent[x] <= x, and only a root (parent[x] == x) is ever written -- by a compare-and-swap that hooks
+// the LARGER of two roots under the smaller.  Pointers only decrease, so every walk ends, no cycle can form, and the root
+// of a finished tree is the smallest index of its component.
+//
+// Coherence (MI355X: one L2 per XCD, a plain load may hit a line another XCD has since changed): the walks read parent[]
+// with agent-scope atomic loads, and every write is an agent-scope compare-and-swap.  Correctness rests on the CAS return
+// values alone: a stale read can only show an older -- larger or equal -- ancestor, which is still in the same tree, and a
+// CAS on a "root" that has been hooked meanwhile fails and returns the new parent to continue from.  Hooking b under a
+// non-root a < b is harmless for the same reason.  The flatten kernel runs after the union launch has ended and reads
+// with plain loads.
+#include <hip/hip_runtime.h>
+
+#include "m3d_proximity.hpp"
+
+#pragma clang fp contract(off)
+
+namespace m3d {
+
+namespace {
+
+__device__ __forceinline__ uint32_t prox_load(const uint32_t* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ uint32_t prox_find(const uint32_t* parent, uint32_t x) {
+    for (;;) {
+        const uint32_t p = prox_load(parent + x);
+        if (p == x) return x;
+        x = p;
+    }
+}
+__device__ __forceinline__ void prox_unite(uint32_t* parent, uint32_t a, uint32_t b) {
+    a = prox_find(parent, a);
+    b = prox_find(parent, b);
+    for (;;) {
+        if (a == b) return;
+        if (a > b) {
+            const uint32_t t = a;
+            a = b;
+            b = t;
+        }
+        uint32_t expected = b;   // hook root b under a < b
+        if (__hip_atomic_compare_exchange_strong(parent + b, &expected, a, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_AGENT))
+            return;
+        b = prox_find(parent, expected);   // b was hooked meanwhile: continue from its tree's root
+        a = prox_find(parent, a);
+    }
+}
+
+// the grid cell of a point (m3d_reg_kernels.hip's cell_of): false for NaN / outside [lo_pad, n - lo_pad)
+__device__ __forceinline__ bool prox_cell(const GridDesc& g, double x, double y, double z, int* ix, int* iy, int* iz) {
+    const double fx = (x - g.ox) * g.inv_h, fy = (y - g.oy) * g.inv_h, fz = (z - g.oz) * g.inv_h;
+    if (!(fx >= 1.0 && fx < (double)(g.nx - 1) && fy >= 1.0 && fy < (double)(g.ny - 1) && fz >= 1.0 &&
+          fz < (double)(g.nz - 1)))
+        return false;
+    *ix = (int)fx;
+    *iy = (int)fy;
+    *iz = (int)fz;
+    return true;
+}
+
+// visit(u, d2) for every grid slot u of the 3x3x3 block around sorted point t whose d2 is within the radius (t included)
+template <class F>
+__device__ __forceinline__ void prox_scan_block(const GridDesc& g, const uint32_t* __restrict__ cell_start,
+                                                const double* __restrict__ qx, const double* __restrict__ qy,
+                                                const double* __restrict__ qz, uint32_t t, F visit) {
+    const double px = qx[t], py = qy[t], pz = qz[t];
+    int ix, iy, iz;
+    if (!prox_cell(g, px, py, pz, &ix, &iy, &iz)) return;
+    for (int dz = -1; dz <= 1; ++dz)
+        for (int dy = -1; dy <= 1; ++dy) {
+            const uint32_t row = ((uint32_t)(iz + dz) * g.ny + (uint32_t)(iy + dy)) * g.nx + (uint32_t)ix;
+            const uint32_t b = cell_start[row - 1], e = cell_start[row + 2];
+            for (uint32_t u = b; u < e; ++u) {
+                const double d2 = prox_d2(px - qx[u], py - qy[u], pz - qz[u]);
+                if (prox_in_radius(d2, g.r2)) visit(u, d2);
+            }
+        }
+}
+
+__global__ void prox_init_k(uint32_t* __restrict__ parent, uint32_t* __restrict__ size, uint32_t n) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    parent[i] = i;
+    size[i] = 0;
+}
+
+__global__ void prox_gather_normals_k(CloudView c, const uint32_t* __restrict__ cell_orig, const uint32_t* __restrict__ n_sorted,
+                                      double* __restrict__ snx, double* __restrict__ sny, double* __restrict__ snz) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= n_sorted[0]) return;
+    const uint32_t i = cell_orig[t];
+    snx[t] = c.nx[i];
+    sny[t] = c.ny[i];
+    snz[t] = c.nz[i];
+}
+
+// one lane per point in grid order: the lanes of a wave share cells and scan the same rows
+__global__ __launch_bounds__(256) void prox_union_grid_k(GridDesc g, const uint32_t* __restrict__ cell_start,
+                                                         const double* __restrict__ qx, const double* __restrict__ qy,
+                                                         const double* __restrict__ qz,
+                                                         const uint32_t* __restrict__ cell_orig,
+                                                         const double* __restrict__ snx, const double* __restrict__ sny,
+                                                         const double* __restrict__ snz,
+                                                         const uint32_t* __restrict__ n_sorted, ProxCut cut,
+                                                         uint32_t* parent) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= n_sorted[0]) return;
+    const uint32_t i = cell_orig[t];
+    const bool normals = cut.kind != kProxDistance;
+    const double ax = normals ? snx[t] : 0.0, ay = normals ? sny[t] : 0.0, az = normals ? snz[t] : 0.0;
+    prox_scan_block(g, cell_start, qx, qy, qz, t, [&](uint32_t u, double d2) {
+        const uint32_t j = cell_orig[u];
+        if (j <= i) return;   // every unordered pair once (both built-in evaluators are symmetric)
+        const double dot = normals ? dot3(ax, ay, az, snx[u], sny[u], snz[u]) : 0.0;
+        if (prox_accept(cut, d2, dot)) prox_unite(parent, i, j);
+    });
+}
+
+__global__ __launch_bounds__(256) void prox_union_lists_k(CloudView c, const uint64_t* __restrict__ off,
+                                                          const uint32_t* __restrict__ idx, uint32_t n, ProxCut cut,
+                                                          uint32_t* parent) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const bool normals = cut.kind != kProxDistance;
+    const double px = c.x[i], py = c.y[i], pz = c.z[i];
+    const double ax = normals ? c.nx[i] : 0.0, ay = normals ? c.ny[i] : 0.0, az = normals ? c.nz[i] : 0.0;
+    const uint64_t e = off[i + 1];
+    for (uint64_t k = off[i] + 1; k < e; ++k) {   // j = 1: entry 0 is skipped
+        const uint32_t j = idx[k];
+        if (j == i) continue;
+        const double dx = px - c.x[j], dy = py - c.y[j], dz = pz - c.z[j];
+        const double d2 = dot3(dx, dy, dz, dx, dy, dz);   // (p_i - p_j).norm() before its sqrt
+        const double dot = normals ? dot3(ax, ay, az, c.nx[j], c.ny[j], c.nz[j]) : 0.0;
+        if (prox_accept(cut, d2, dot)) prox_unite(parent, i, j);
+    }
+}
+
+__global__ void prox_flatten_k(const uint32_t* __restrict__ parent, uint32_t* __restrict__ root, uint32_t* size, uint32_t n) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    uint32_t x = i;
+    for (uint32_t p = parent[x]; p != x; p = parent[x]) x = p;
+    root[i] = x;
+    atomicAdd(size + x, 1u);
+}
+
+__global__ __launch_bounds__(256) void prox_nb_count_k(GridDesc g, const uint32_t* __restrict__ cell_start,
+                                                       const double* __restrict__ qx, const double* __restrict__ qy,
+                                                       const double* __restrict__ qz, const uint32_t* __restrict__ cell_orig,
+                                                       const uint32_t* __restrict__ n_sorted, uint32_t* __restrict__ count) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= n_sorted[0]) return;
+    uint32_t m = 0;
+    prox_scan_block(g, cell_start, qx, qy, qz, t, [&](uint32_t u, double) { m += u != t; });
+    count[cell_orig[t]] = m;
+}
+
+__global__ __launch_bounds__(256) void prox_nb_fill_k(GridDesc g, const uint32_t* __restrict__ cell_start,
+                                                      const double* __restrict__ qx, const double* __restrict__ qy,
+                                                      const double* __restrict__ qz, const uint32_t* __restrict__ cell_orig,
+                                                      const uint32_t* __restrict__ n_sorted, const uint64_t* __restrict__ off,
+                                                      uint32_t* __restrict__ nb_idx, double* __restrict__ nb_d2) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= n_sorted[0]) return;
+    const uint32_t i = cell_orig[t];
+    const uint64_t b = off[i], cap = off[i + 1] - b;
+    uint64_t m = 0;
+    prox_scan_block(g, cell_start, qx, qy, qz, t, [&](uint32_t u, double d2) {
+        if (u == t || m >= cap) return;
+        const uint32_t j = cell_orig[u];
+        uint64_t pos = m++;   // insertion by (d2, index)
+        while (pos > 0 && (d2 < nb_d2[b + pos - 1] || (d2 == nb_d2[b + pos - 1] && j < nb_idx[b + pos - 1]))) {
+            nb_d2[b + pos] = nb_d2[b + pos - 1];
+            nb_idx[b + pos] = nb_idx[b + pos - 1];
+            --pos;
+        }
+        nb_d2[b + pos] = d2;
+        nb_idx[b + pos] = j;
+    });
+}
+
+inline uint32_t blocks(uint32_t n) { return (n + 255) / 256; }
+
+}  // namespace
+
+void launch_prox_init(uint32_t* parent, uint32_t* size, uint32_t n, hipStream_t st) {
+    if (n) prox_init_k<<<blocks(n), 256, 0, st>>>(parent, size, n);
+}
+void launch_prox_gather_normals(const CloudView& c, const uint32_t* cell_orig, uint32_t n, const uint32_t* n_sorted,
+                                double* snx, double* sny, double* snz, hipStream_t st) {
+    if (n) prox_gather_normals_k<<<blocks(n), 256, 0, st>>>(c, cell_orig, n_sorted, snx, sny, snz);
+}
+void launch_prox_union_grid(const GridDesc& g, const uint32_t* cell_start, const double* qx, const double* qy,
+                            const double* qz, const uint32_t* cell_orig, const double* snx, const double* sny,
+                            const double* snz, uint32_t n, const uint32_t* n_sorted, const ProxCut& cut, uint32_t* parent,
+                            hipStream_t st) {
+    if (n)
+        prox_union_grid_k<<<blocks(n), 256, 0, st>>>(g, cell_start, qx, qy, qz, cell_orig, snx, sny, snz, n_sorted, cut,
+                                                      parent);
+}
+void launch_prox_union_lists(const CloudView& c, const uint64_t* off, const uint32_t* idx, uint32_t n, const ProxCut& cut,
+                             uint32_t* parent, hipStream_t st) {
+    if (n) prox_union_lists_k<<<blocks(n), 256, 0, st>>>(c, off, idx, n, cut, parent);
+}
+void launch_prox_flatten(const uint32_t* parent, uint32_t* root, uint32_t* size, uint32_t n, hipStream_t st) {
+    if (n) prox_flatten_k<<<blocks(n), 256, 0, st>>>(parent, root, size, n);
+}
+void launch_prox_nb_count(const GridDesc& g, const uint32_t* cell_start, const double* qx, const double* qy, const double* qz,
+                          const uint32_t* cell_orig, uint32_t n, const uint32_t* n_sorted, uint32_t* count, hipStream_t st) {
+    if (n) prox_nb_count_k<<<blocks(n), 256, 0, st>>>(g, cell_start, qx, qy, qz, cell_orig, n_sorted, count);
+}
+void launch_prox_nb_fill(const GridDesc& g, const uint32_t* cell_start, const double* qx, const double* qy, const double* qz,
+                         const uint32_t* cell_orig, uint32_t n, const uint32_t* n_sorted, const uint64_t* off,
+                         uint32_t* nb_idx, double* nb_d2, hipStream_t st) {
+    if (n) prox_nb_fill_k<<<blocks(n), 256, 0, st>>>(g, cell_start, qx, qy, qz, cell_orig, n_sorted, off, nb_idx, nb_d2);
+}
+
+}  // namespace m3d

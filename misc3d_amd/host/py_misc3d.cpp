@@ -23,6 +23,7 @@
 #include <misc3d/registration/correspondence_matching.h>
 #include <misc3d/registration/transform_estimation.h>
 #include <misc3d/segmentation/iterative_plane_segmentation.h>
+#include <misc3d/segmentation/proximity_extraction.h>
 
 namespace py = pybind11;
 using arr_d = py::array_t<double, py::array::c_style | py::array::forcecast>;
@@ -244,6 +245,53 @@ static std::vector<size_t> to_index_vector(const py::handle& o) {
     }
     return py::cast<std::vector<size_t>>(o);
 }
+// ProximityEvaluator trampoline (python/py_segmentation.cpp:11-19): a python subclass's __call__ is the evaluator; a
+// subclass of a built-in that overrides __call__ gives up the built-in's device form and runs on the host path
+template <class Ev>
+class PyProximityEvaluator : public Ev {
+public:
+    using Ev::Ev;
+    bool operator()(size_t i, size_t j, double dist) const override {
+        PYBIND11_OVERRIDE_NAME(bool, Ev, "__call__", operator(), i, j, dist);
+    }
+    bool Describe(m3d_proximity_evaluator* ev, const double** normals, size_t* n_normals) const override {
+        py::gil_scoped_acquire gil;
+        if (py::get_override(static_cast<const Ev*>(this), "__call__")) return false;
+        return Ev::Describe(ev, normals, n_normals);
+    }
+};
+template <>
+class PyProximityEvaluator<misc3d::segmentation::BaseProximityEvaluator>
+    : public misc3d::segmentation::BaseProximityEvaluator {
+public:
+    bool operator()(size_t i, size_t j, double dist) const override {
+        PYBIND11_OVERRIDE_PURE_NAME(bool, misc3d::segmentation::BaseProximityEvaluator, "__call__", operator(), i, j, dist);
+    }
+};
+
+static std::vector<misc3d::Vector3d> as_normals(const py::object& o) {
+    arr_d a = as_nx3(o, "normals");
+    std::vector<misc3d::Vector3d> v((size_t)a.shape(0));
+    if (!v.empty()) std::memcpy(v.data(), a.data(), sizeof(double) * 3 * v.size());
+    return v;
+}
+
+// list[list[int]] as the reference returns it, or (as_arrays) int64 views of one array
+static py::object cluster_lists(const std::vector<std::vector<size_t>>& cl, bool as_arrays) {
+    if (!as_arrays) return py::cast(cl);
+    size_t total = 0;
+    for (const auto& c : cl) total += c.size();
+    py::array_t<int64_t> all((py::ssize_t)total);
+    int64_t* p = all.mutable_data();
+    py::list out;
+    size_t at = 0;
+    for (const auto& c : cl) {
+        for (size_t i : c) p[at++] = (int64_t)i;
+        out.append(all[py::slice((py::ssize_t)(at - c.size()), (py::ssize_t)at, 1)]);
+    }
+    return std::move(out);
+}
+
 static py::array_t<int64_t> index_array(const std::vector<size_t>& v) {
     py::array_t<int64_t> a((py::ssize_t)v.size());
     if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), sizeof(size_t) * v.size());
@@ -397,6 +445,66 @@ PYBIND11_MODULE(_py_misc3d, m) {
         "Segment plane iteratively using RANSAC plane fitting", py::arg("pcd"), py::arg("threshold"),
         py::arg("max_iteration") = 100, py::arg("min_ratio") = 0.05, py::kw_only(), py::arg("seed") = py::none(),
         py::arg("device") = 0, py::arg("return_indices") = false);
+
+    // ProximityExtractor and its evaluators (python/py_segmentation.cpp:21-85)
+    using misc3d::segmentation::BaseProximityEvaluator;
+    using misc3d::segmentation::DistanceNormalsProximityEvaluator;
+    using misc3d::segmentation::DistanceProximityEvaluator;
+    using misc3d::segmentation::NormalsProximityEvaluator;
+    using misc3d::segmentation::ProximityExtractor;
+    py::class_<BaseProximityEvaluator, PyProximityEvaluator<BaseProximityEvaluator>>(ms, "BaseProximityEvaluator")
+        .def(py::init<>())
+        .def("__call__", [](BaseProximityEvaluator& self, size_t i, size_t j, double dist) { return self(i, j, dist); });
+    py::class_<DistanceProximityEvaluator, PyProximityEvaluator<DistanceProximityEvaluator>, BaseProximityEvaluator>(
+        ms, "DistanceProximityEvaluator")
+        .def(py::init<double>(), py::arg("dist_thresh"))
+        .def("__call__", [](DistanceProximityEvaluator& self, size_t i, size_t j, double dist) { return self(i, j, dist); });
+    py::class_<NormalsProximityEvaluator, PyProximityEvaluator<NormalsProximityEvaluator>, BaseProximityEvaluator>(
+        ms, "NormalsProximityEvaluator")
+        .def(py::init([](const py::object& normals, double angle_thresh) {
+                 return new PyProximityEvaluator<NormalsProximityEvaluator>(as_normals(normals), angle_thresh);
+             }),
+             py::arg("normals"), py::arg("angle_thresh"))
+        .def("__call__", [](NormalsProximityEvaluator& self, size_t i, size_t j, double dist) { return self(i, j, dist); });
+    py::class_<DistanceNormalsProximityEvaluator, PyProximityEvaluator<DistanceNormalsProximityEvaluator>,
+               BaseProximityEvaluator>(ms, "DistanceNormalsProximityEvaluator")
+        .def(py::init([](const py::object& normals, double dist_thresh, double angle_thresh) {
+                 return new PyProximityEvaluator<DistanceNormalsProximityEvaluator>(as_normals(normals), dist_thresh,
+                                                                                    angle_thresh);
+             }),
+             py::arg("normals"), py::arg("dist_thresh"), py::arg("angle_thresh"))
+        .def("__call__",
+             [](DistanceNormalsProximityEvaluator& self, size_t i, size_t j, double dist) { return self(i, j, dist); });
+    py::class_<ProximityExtractor>(ms, "ProximityExtractor",
+                                   "Region growing: the connected components of the neighbour pairs the evaluator accepts. "
+                                   "Clusters by size descending, ties by smallest point index; indices ascending. Built-in "
+                                   "evaluators run on the device; a python subclass of BaseProximityEvaluator runs on the "
+                                   "host, one __call__ per neighbour pair -- slow by nature.")
+        .def(py::init<size_t, size_t>(), py::arg("min_size") = 1, py::arg("max_size") = std::numeric_limits<size_t>::max())
+        .def(
+            "segment",
+            [](ProximityExtractor& self, const py::object& pc, const std::vector<std::vector<size_t>>& nn_indices,
+               const BaseProximityEvaluator& evaluator, bool as_arrays, int device) {
+                HostCloud c = extract_cloud(pc);
+                self.SetDevice(device);
+                std::vector<std::vector<size_t>> cl = self.Segment(c.view(), nn_indices, evaluator);
+                return cluster_lists(cl, as_arrays);
+            },
+            "Segment point clouds with given nearest neighboor", py::arg("pc"), py::arg("nn_indices"), py::arg("evaluator"),
+            py::kw_only(), py::arg("as_arrays") = false, py::arg("device") = 0)
+        .def(
+            "segment",
+            [](ProximityExtractor& self, const py::object& pc, double search_radius, const BaseProximityEvaluator& evaluator,
+               bool as_arrays, int device) {
+                HostCloud c = extract_cloud(pc);
+                self.SetDevice(device);
+                std::vector<std::vector<size_t>> cl = self.Segment(c.view(), search_radius, evaluator);
+                return cluster_lists(cl, as_arrays);
+            },
+            "Segment point clouds with radius for nearest neighboor searching", py::arg("pc"), py::arg("search_radius"),
+            py::arg("evaluator"), py::kw_only(), py::arg("as_arrays") = false, py::arg("device") = 0)
+        .def("get_cluster_index_map", &ProximityExtractor::GetClusterIndexMap)
+        .def("get_cluster_num", &ProximityExtractor::GetClusterNum);
 
     // ---- registration (python/py_registration.cpp:11-107)
     py::module mr = m.def_submodule("registration");

@@ -6,6 +6,7 @@ bench.py); these lines feed DESIGN.md section 6 and check that the full sizes ru
   C3 fit_cylinder + fit_sphere 1M pts, 50k hyp          C4 match + compute_transformation_ransac 200k<->200k, 100k hyp
   C5 segment_plane_iterative 10M pts (single GPU leg)
   P1 / P2 farthest_point_sampling 5 841 x 1 000 (the reference example) / 1M x 10 000, every device path (A/B)
+  S1 - S4 ProximityExtractor.segment: the reference example's shape, the raw golden PLY at r = 0.01, 1 M and 10 M synthetic
 """
 import json
 import os
@@ -568,3 +569,72 @@ if "P1" in which or "P2" in which or ALL:
         emit(f"{tag} farthest_point_sampling {n} pts x {S} samples", ms=best["ms"], ms_device=best["ms_device"], path=path_name,
              pruned_fraction=best["pruned_fraction"], paths=rows, roofline=roofline,
              cpu_baseline=fps_cpu(pts, S, 200 if n < 100_000 else 20))
+
+if any(t in which for t in ("S1", "S2", "S3", "S4")) or ALL:
+    # misc3d.segmentation.ProximityExtractor: S1 = the reference example (examples/python/segmentation.py: the golden cloud
+    # voxel-averaged at 0.01, PCA normals, DistanceNormals(0.02, 30), radius 0.02, min 100), S2 = the raw 40 458-point PLY with
+    # Distance(0.01) at r = 0.01, S3 = 1 M uniform points, S4 = 10 M points on the walls of boxes in a 40 m room (the grid's
+    # 2^27-cell cap coarsens its cells)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from proximity_ref_util import golden_ply, pca_normals, voxel_average
+
+    def prox_cpu(xyz, radius, kind, dist, ang, nrm, scale=1.0):
+        """scipy cKDTree pairs + the evaluator in numpy + csgraph.connected_components (the pair search is single-threaded)"""
+        if NO_CPU:
+            return None
+        from scipy.sparse import coo_matrix
+        from scipy.sparse.csgraph import connected_components
+        from scipy.spatial import cKDTree
+        t0 = time.perf_counter()
+        p = cKDTree(xyz).query_pairs(radius, output_type="ndarray")
+        a, b = p[:, 0], p[:, 1]
+        keep = np.ones(len(a), bool)
+        if kind != "normals":
+            d = xyz[a] - xyz[b]
+            keep &= np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]) < dist
+        if kind != "distance":
+            dot = (nrm[a, 0] * nrm[b, 0] + nrm[a, 1] * nrm[b, 1]) + nrm[a, 2] * nrm[b, 2]
+            keep &= np.arccos(np.clip(dot, -1, 1)) <= np.radians(ang)
+        g = coo_matrix((np.ones(keep.sum(), np.int8), (a[keep], b[keep])), shape=(len(xyz), len(xyz)))
+        connected_components(g, directed=False)
+        dt = time.perf_counter() - t0
+        return {"value": dt * 1e3 * scale, "unit": "ms" if scale == 1.0 else "ms (scaled)", "cores": 1,
+                "kind": "scipy cKDTree.query_pairs + csgraph.connected_components",
+                "pairs": int(len(a)), **({"sample": f"1/{scale:g} of the points timed, scaled linearly"} if scale != 1.0 else {})}
+
+    def room(n, seed=5):
+        rng = np.random.default_rng(seed)
+        lo = rng.uniform(0, 38, (400, 3)) * [1, 1, 0.1]
+        hi = lo + rng.uniform(0.3, 2.0, (400, 3))
+        box = rng.integers(0, 400, n)
+        face = rng.integers(0, 6, n)
+        u = rng.uniform(0, 1, (n, 3))
+        pts = lo[box] + u * (hi[box] - lo[box])
+        ax = face % 3
+        pts[np.arange(n), ax] = np.where(face < 3, lo[box, ax], hi[box, ax])
+        return pts
+
+    cases = []
+    if "S1" in which or ALL:
+        d = voxel_average(golden_ply(), 0.01)
+        cases.append(("S1 proximity reference example", d, 0.02, "distance_normals", 0.02, 30.0, pca_normals(d, 0.02), 100, 1.0))
+    if "S2" in which or ALL:
+        cases.append(("S2 proximity golden PLY r=0.01", golden_ply(), 0.01, "distance", 0.01, 0.0, None, 1, 1.0))
+    if "S3" in which or ALL:
+        cases.append(("S3 proximity 1M uniform", np.random.default_rng(3).uniform(0, 1, (1_000_000, 3)), 0.008, "distance",
+                      0.008, 0.0, None, 1, 1.0))
+    if "S4" in which or ALL:
+        cases.append(("S4 proximity 10M room", room(10_000_000), 0.02, "distance", 0.02, 0.0, None, 100, 10.0))
+    for name, xyz, r, kind, dist, ang, nrm, mn, scale in cases:
+        capi.proximity_segment(xyz, r, kind, dist, ang, nrm, mn)
+        ts = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            off, idx, lab, st = capi.proximity_segment(xyz, r, kind, dist, ang, nrm, mn, stats=True)
+            ts.append(((time.perf_counter() - t0) * 1e3, st))
+        ms, st = sorted(ts, key=lambda t: t[0])[1]
+        sub = xyz[: len(xyz) // int(scale)] if scale != 1.0 else xyz
+        emit(name, n=len(xyz), radius=r, evaluator=kind, clusters=len(off) - 1, ms=ms, ms_in_library=st["ms_total"],
+             ms_device=st["ms_device"], ms_host_order=st["ms_order"], components=st["components"], cell_edge=st["cell_edge"],
+             cell_coarsened=st["cell_edge"] / (1.001 * r),
+             cpu_baseline=prox_cpu(sub, r, kind, dist, ang, None if nrm is None else nrm[: len(sub)], scale))
