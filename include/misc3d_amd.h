@@ -366,6 +366,63 @@ int m3d_proximity_segment_nn(const double *xyz, const double *normals, size_t n_
 int m3d_radius_neighbors(const double *xyz, size_t n, double radius, int device, size_t *offsets, uint32_t *nb_indices,
                          double *nb_d2, size_t capacity, size_t *total);
 
+/* ---- misc3d::common::KNearestSearch, include/misc3d/common/knn.h, src/knn.cpp ------------------------------------- */
+/* The EXACT answer that the reference's Annoy index approximates, for a resident dim x N matrix.
+ *   Distance key: d2(q, r) = sum over k = 0 .. dim - 1 of (q[k] - r[k])^2, accumulated serially in dimension order in
+ *     fp64 from +0.0, every subtraction, product and addition rounded (no FMA contraction): Annoy's euclidean_distance
+ *     (annoylib.h:177-188), the matcher's order, and boundary detection's (dx dx + dy dy) + dz dz for dim 3.
+ *   Order: ascending by (d2, row index) (Annoy partial_sorts pair<dist, index>).  A NaN d2 ranks after +inf, NaNs among
+ *     themselves by index (the reference leaves this open); a NaN d2 is returned as the quiet NaN 0x7FF8000000000000.
+ *   Count: a query gets kout = min(knn, N) results.
+ *   Returned distance: sqrt(max(d2, 0)), correctly rounded -- bit-equal to libm's sqrt of the same d2 (Annoy's
+ *     normalized_distance, annoylib.h:769-771); NaN stays NaN.
+ *   SearchKNN (knn.cpp:103-113): -1 and empty lists when the index is empty, query.size() != dim or knn < 0.
+ *   SearchHybrid (knn.cpp:115-139): the kout nearest; i = the first position with dist[i] > radius, or kout if none (a NaN
+ *     distance or a NaN radius compares "not greater": inside); num = i - 1 results are kept -- the last in-radius
+ *     neighbour is dropped -- and none when num == 0.  i == 0 (knn == 0, a negative radius, a nearest neighbour beyond
+ *     the radius) wraps the reference's size_t and resize(SIZE_MAX) throws std::length_error: this API reports a count
+ *     of -1 for that query (the C++ mirror throws std::length_error, python's single-query form raises ValueError).
+ *   Search(param) (knn.cpp:81-101): Knn -> SearchKNN, Hybrid -> SearchHybrid, Radius -> -1.
+ *   Limits, checked before any device is touched (M3D_ERR_INVALID_ARG): 1 <= dim <= 1024, 1 <= N < 2^31, data != NULL.
+ *     knn has no upper cap.
+ * Device paths ("k nearest neighbours"): GRID (dim 3, 1 <= kout <= 128: a density grid of about kout / 4 rows
+ * per cell, built once per kout class on first use; shells around the query's cell until the kout-th pair is provably
+ * final; queries with a non-finite coordinate take the tile path), TILE (any dim, 1 <= kout <= 128: brute force with
+ * the rows staged through LDS, the database split across workgroups, the splits' lists merged in a second launch) and
+ * SELECT (kout > 128: the tile path in pages of 128, each page strictly above the last pair of the previous one).  The
+ * result does not depend on the path. */
+typedef struct m3d_knn m3d_knn;
+#define M3D_KNN_SEARCH_KNN 0     /* KDTreeSearchParam::SearchType::Knn */
+#define M3D_KNN_SEARCH_HYBRID 2  /* KDTreeSearchParam::SearchType::Hybrid (Radius, 1, is not supported: -1) */
+#define M3D_KNN_PATH_GRID 1
+#define M3D_KNN_PATH_TILE 2
+#define M3D_KNN_PATH_SELECT 3
+typedef struct m3d_knn_stats {
+    double ms_total;        /* the call, host clock */
+    double ms_device;       /* first query upload to last result copy, HIP events (the last chunk's lane) */
+    int32_t path;           /* M3D_KNN_PATH_* of the queries with finite coordinates (0: no device work) */
+    int32_t launches;       /* kernel launches */
+    uint64_t pair_dims;     /* (query, row) distances evaluated x dim, every page counted */
+    uint64_t tile_queries;  /* queries that took the tile / select path on a grid-path call (non-finite coordinates) */
+} m3d_knn_stats;
+/* Uploads data (n rows of dim contiguous doubles: Eigen's column-major dim x N) to the device once.  NULL on failure
+ * (m3d_last_error; *status, which may be NULL, = M3D_ERR_INVALID_ARG for the limits above, M3D_ERR_DEVICE otherwise).
+ * The index is read-only afterwards: any number of threads may search it at once. */
+m3d_knn *m3d_knn_create(const double *data, size_t n, int dim, int device, int *status);
+/* Returns the device blocks to the pool.  No search on h may be running. */
+void m3d_knn_destroy(m3d_knn *h);
+size_t m3d_knn_size(const m3d_knn *h);
+int m3d_knn_dim(const m3d_knn *h);
+/* m queries (row-major m x dim).  search = M3D_KNN_SEARCH_KNN or M3D_KNN_SEARCH_HYBRID; knn >= 0 (M3D_ERR_INVALID_ARG
+ * otherwise); radius is read by HYBRID only.  Outputs are row-major m x stride, stride >= kout = min(knn, N):
+ * indices[q stride + j], dist[q stride + j] and d2 (may be NULL) for j < counts[q]; the rest of each row is padded with
+ * SIZE_MAX / +inf.  counts[q] = kout (KNN), the hybrid count num or -1 (HYBRID, see above).  Queries are processed in
+ * chunks of at most 16384 (tile, select) or 65536 (grid) queries, halved until the chunk's device scratch -- queries,
+ * the splits' lists of one page, the merged page -- fits 256 MiB; a chunk of one query needs at most 0.4 MiB.  Re-entrant: concurrent searches on one index take lanes of its device.
+ * stats may be NULL. */
+int m3d_knn_search(const m3d_knn *h, const double *queries, size_t m, int search, int64_t knn, double radius, size_t stride,
+                   size_t *indices, double *dist, double *d2, int64_t *counts, m3d_knn_stats *stats);
+
 /* ---- point-to-point ICP refinement of the RANSAC pose ----------------------- */
 /* open3d::pipelines::registration::RegistrationICP(source, target, max_correspondence_distance, init,
  * TransformationEstimationPointToPoint(), ICPConvergenceCriteria(relative_fitness, relative_rmse,

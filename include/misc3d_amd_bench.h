@@ -68,6 +68,13 @@ int m3d_bench_experimental(void);
  * result does not depend on it. */
 int m3d_bench_fps_force_path(int path);
 
+/* MEASUREMENT / TEST hook (tools/bench_configs.py K3, tests/test_gpu_knn.py): the device path of every later m3d_knn_search
+ * in the process -- 0 = by shape (the default), M3D_KNN_PATH_GRID, M3D_KNN_PATH_TILE, M3D_KNN_PATH_SELECT.  A forced
+ * path applies wherever it can: GRID only for dim 3 and kout <= 128 (else by shape), TILE for kout <= 128 (else
+ * SELECT), SELECT always (in pages of 16 rather than 128, so that small kout run several pages).  The result does not
+ * depend on it. */
+int m3d_bench_knn_force_path(int path);
+
 /* TEST hook (tests/test_proximity.py): the cut-offs m3d_proximity_segment derives on the host for an evaluator
  * (m3d_proximity_fp.hpp) -- out[0] = d2_cut (Distance: dist < t <=> d2 < d2_cut; DistanceNormals: dist >= t <=>
  * d2 >= d2_cut), out[1..4] = lo1, hi1, lo2, hi2 (the angle test accepts dot exactly on [lo1, hi1] u [lo2, hi2]). */

@@ -173,6 +173,16 @@ def lib():
         L.m3d_radius_neighbors.argtypes = [C.c_void_p, C.c_size_t, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_size_t, C.c_void_p]
         L.m3d_bench_proximity_cutoffs.argtypes = [C.c_double, C.c_double, C.c_void_p]
+        L.m3d_knn_create.restype = C.c_void_p
+        L.m3d_knn_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
+        L.m3d_knn_destroy.restype = None
+        L.m3d_knn_destroy.argtypes = [C.c_void_p]
+        L.m3d_knn_size.restype = C.c_size_t
+        L.m3d_knn_size.argtypes = [C.c_void_p]
+        L.m3d_knn_dim.argtypes = [C.c_void_p]
+        L.m3d_knn_search.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int64, C.c_double, C.c_size_t,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.m3d_bench_knn_force_path.argtypes = [C.c_int]
         L.m3d_match_last_fallbacks.restype = C.c_uint64
         L.m3d_match_last_fallbacks.argtypes = []
         L.m3d_match_mutual_nn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
@@ -1146,6 +1156,71 @@ def radius_neighbors(xyz, radius, device=0):
     _check(lib().m3d_radius_neighbors(_p(xyz), n, float(radius), device, _p(off), _p(idx), _p(d2), tot.value,
                                       C.cast(C.byref(tot), C.c_void_p)))
     return off, idx[: tot.value].copy(), d2[: tot.value].copy()
+
+
+KNN_SEARCH_KNN, KNN_SEARCH_HYBRID = 0, 2
+KNN_PATH_GRID, KNN_PATH_TILE, KNN_PATH_SELECT = 1, 2, 3
+
+
+class KnnStats(C.Structure):
+    """m3d_knn_stats"""
+    _fields_ = [("ms_total", C.c_double), ("ms_device", C.c_double), ("path", C.c_int32), ("launches", C.c_int32),
+                ("pair_dims", C.c_uint64), ("tile_queries", C.c_uint64)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class KnnIndex:
+    """m3d_knn_create / _search / _destroy: data is N rows of dim doubles (an (N, dim) array = Eigen's dim x N)."""
+
+    def __init__(self, rows, device=0):
+        rows = _f64(rows)
+        if rows.ndim != 2:
+            raise ValueError("rows: expected an (N, dim) array")
+        status = C.c_int(0)
+        self.h = lib().m3d_knn_create(_p(rows), rows.shape[0], rows.shape[1], device, C.cast(C.byref(status), C.c_void_p))
+        if not self.h:
+            raise M3DError(status.value, last_error())
+        self.n, self.dim = rows.shape
+
+    def close(self):
+        if self.h:
+            lib().m3d_knn_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def search(self, queries, knn, search=KNN_SEARCH_KNN, radius=0.0, stride=None, want_d2=True, stats=False):
+        """-> (indices int64 (m, stride), dist, d2, counts int64 (m,)) (+ the stats dict); padding: -1 / +inf"""
+        q = _f64(queries).reshape(-1, self.dim)
+        m = len(q)
+        kout = min(int(knn), self.n) if knn >= 0 else 0
+        stride = kout if stride is None else int(stride)
+        idx = np.zeros((m, stride), dtype=np.int64)
+        dist = np.zeros((m, stride))
+        d2 = np.zeros((m, stride)) if want_d2 else None
+        counts = np.zeros(m, dtype=np.int64)
+        st = KnnStats()
+        _check(lib().m3d_knn_search(self.h, _p(q), m, int(search), int(knn), float(radius), stride, _p(idx), _p(dist),
+                                    _p(d2), _p(counts), C.cast(C.byref(st), C.c_void_p)))
+        res = (idx, dist, d2, counts)
+        return res + (st.asdict(),) if stats else res
+
+
+def knn_create_status(data_ptr, n, dim, device=0):
+    """m3d_knn_create on a raw pointer (argument checks) -> (status code, last error text); the index is destroyed again"""
+    status = C.c_int(0)
+    h = lib().m3d_knn_create(data_ptr, int(n), int(dim), int(device), C.cast(C.byref(status), C.c_void_p))
+    if h:
+        lib().m3d_knn_destroy(h)
+    return status.value, ("" if h else last_error())
+
+
+def knn_force_path(path: int):
+    """test / measurement hook m3d_bench_knn_force_path: 0 = by shape, KNN_PATH_GRID / TILE / SELECT"""
+    _check(lib().m3d_bench_knn_force_path(int(path)))
 
 
 def proximity_cutoffs(dist, angle_deg):

@@ -24,6 +24,7 @@
 #include <misc3d/registration/transform_estimation.h>
 #include <misc3d/segmentation/iterative_plane_segmentation.h>
 #include <misc3d/segmentation/proximity_extraction.h>
+#include <misc3d/common/knn.h>
 
 namespace py = pybind11;
 using arr_d = py::array_t<double, py::array::c_style | py::array::forcecast>;
@@ -292,6 +293,79 @@ static py::object cluster_lists(const std::vector<std::vector<size_t>>& cl, bool
     return std::move(out);
 }
 
+// ---- KNearestSearch (python/py_common.cpp:91-154)
+struct PyKNearestSearch {
+    misc3d::common::KNearestSearch s;
+    int device = 0;
+    PyKNearestSearch(int n_trees, int dev) : s(n_trees), device(dev) { s.SetDevice(dev); }
+};
+using arr_f = py::array_t<double, py::array::f_style | py::array::forcecast>;
+// A matrix as Eigen::Ref<const MatrixXd> reads it: a 2-D array (dim, N), a 1-D array as one column.  Column-major:
+// N contiguous rows of dim doubles.
+static bool knn_set_matrix(PyKNearestSearch& self, const py::object& o) {
+    py::object np = py::module_::import("numpy");
+    py::array a = np.attr("asarray")(o, py::arg("dtype") = "float64");
+    if (a.ndim() == 1) a = a.attr("reshape")(-1, 1);
+    if (a.ndim() != 2) throw py::type_error("set_mat_data: expected a 2-D (dim, N) array");
+    arr_f f = arr_f::ensure(a);
+    const size_t rows = (size_t)f.shape(0), cols = (size_t)f.shape(1);
+    py::gil_scoped_release nogil;
+    return self.s.SetMatrixData(rows && cols ? f.data() : nullptr, rows, cols);
+}
+// knn.cpp:60-77: a point cloud (.points) or a triangle mesh (.vertices); anything else: false, the index unchanged
+static bool knn_set_geometry(PyKNearestSearch& self, const py::object& g) {
+    const char* attr = py::hasattr(g, "points") ? "points" : (py::hasattr(g, "vertices") ? "vertices" : nullptr);
+    if (!attr) return false;
+    arr_d pts = as_nx3(g.attr(attr), attr);
+    const size_t n = (size_t)pts.shape(0);
+    py::gil_scoped_release nogil;
+    return self.s.SetMatrixData(n ? pts.data() : nullptr, 3, n);
+}
+static bool knn_set_feature(PyKNearestSearch& self, const py::object& f) {
+    if (!py::hasattr(f, "data")) throw py::type_error("set_feature: expected an object with .data, a (dim, N) array");
+    return knn_set_matrix(self, f.attr("data"));
+}
+static std::vector<double> knn_query(const py::object& q) {
+    py::object np = py::module_::import("numpy");
+    arr_d a = arr_d::ensure(np.attr("ravel")(np.attr("asarray")(q, py::arg("dtype") = "float64")));
+    if (!a) throw py::type_error("query: cannot convert to a float64 array");
+    return std::vector<double>(a.data(), a.data() + a.size());
+}
+static py::tuple knn_pair(const std::vector<size_t>& idx, const std::vector<double>& dist) {
+    return py::make_tuple(py::cast(idx), py::cast(dist));
+}
+// the batched forms: queries (m, dim); ValueError where the single form returns ([], [])
+static py::tuple knn_batch(PyKNearestSearch& self, const py::object& queries, int search, double radius, int knn) {
+    py::object np = py::module_::import("numpy");
+    arr_d q = arr_d::ensure(np.attr("asarray")(queries, py::arg("dtype") = "float64"));
+    if (!q) throw py::type_error("queries: cannot convert to a float64 array");
+    if (self.s.Size() == 0) throw py::value_error("KNearestSearch: the index is empty");
+    if (q.ndim() != 2 || (size_t)q.shape(1) != self.s.Dimension())
+        throw py::value_error("queries: expected an (m, " + std::to_string(self.s.Dimension()) + ") array");
+    if (knn < 0) throw py::value_error("knn must be >= 0");
+    const size_t m = (size_t)q.shape(0);
+    std::vector<size_t> idx;
+    std::vector<double> dist;
+    std::vector<int64_t> counts;
+    int kout;
+    {
+        py::gil_scoped_release nogil;
+        kout = search == M3D_KNN_SEARCH_KNN ? self.s.SearchKNNBatch(m ? q.data() : nullptr, m, knn, idx, dist, counts)
+                                            : self.s.SearchHybridBatch(m ? q.data() : nullptr, m, radius, knn, idx, dist, counts);
+    }
+    py::array_t<int64_t> ai(std::vector<py::ssize_t>{(py::ssize_t)m, (py::ssize_t)kout});
+    py::array_t<double> ad(std::vector<py::ssize_t>{(py::ssize_t)m, (py::ssize_t)kout});
+    static_assert(sizeof(size_t) == sizeof(int64_t), "size_t is 64 bits");
+    if (!idx.empty()) {
+        std::memcpy(ai.mutable_data(), idx.data(), sizeof(int64_t) * idx.size());   // (SIZE_MAX padding reads as -1)
+        std::memcpy(ad.mutable_data(), dist.data(), sizeof(double) * dist.size());
+    }
+    if (search == M3D_KNN_SEARCH_KNN) return py::make_tuple(ai, ad);
+    py::array_t<int64_t> ac((py::ssize_t)m);
+    if (m) std::memcpy(ac.mutable_data(), counts.data(), sizeof(int64_t) * m);
+    return py::make_tuple(ai, ad, ac);
+}
+
 static py::array_t<int64_t> index_array(const std::vector<size_t>& v) {
     py::array_t<int64_t> a((py::ssize_t)v.size());
     if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), sizeof(size_t) * v.size());
@@ -363,6 +437,118 @@ PYBIND11_MODULE(_py_misc3d, m) {
         "Fit a cylinder from point clouds", py::arg("pc"), py::arg("threshold") = 0.01,
         py::arg("max_iteration") = 1000, py::arg("probability") = 0.9999, py::kw_only(),
         py::arg("seed") = py::none(), py::arg("device") = 0, py::arg("as_arrays") = false);
+
+    // KNearestSearch, python/py_common.cpp:91-154: the exact answer the reference's Annoy index approximates
+    py::class_<PyKNearestSearch>(mc, "KNearestSearch",
+                                 "Exact k nearest neighbours of the columns of a (dim, N) matrix, on the device: ascending "
+                                 "by (d2, index), d2 the serial fp64 sum of squared differences; distances are sqrt(d2). "
+                                 "Data is read as Eigen's dim x N: an (N, 3) array is N-dimensional data with 3 rows, "
+                                 "exactly as in the reference -- pass (3, N) (or pts.T) for points. n_trees is accepted and "
+                                 "has no effect.")
+        .def(py::init([](int device) { return new PyKNearestSearch(4, device); }), py::kw_only(), py::arg("device") = 0)
+        .def(py::init([](int n_trees, int device) { return new PyKNearestSearch(n_trees, device); }), py::arg("n_trees"),
+             py::kw_only(), py::arg("device") = 0)
+        .def(py::init([](const py::array& data, int n_trees, int device) {
+                 auto* k = new PyKNearestSearch(n_trees, device);
+                 knn_set_matrix(*k, data);
+                 return k;
+             }),
+             py::arg("data"), py::arg("n_trees") = 10, py::kw_only(), py::arg("device") = 0)
+        .def(py::init([](const py::object& geometry, int n_trees, int device) {
+                 auto* k = new PyKNearestSearch(n_trees, device);
+                 if (py::hasattr(geometry, "points") || py::hasattr(geometry, "vertices"))
+                     knn_set_geometry(*k, geometry);
+                 else
+                     knn_set_feature(*k, geometry);
+                 return k;
+             }),
+             py::arg("geometry"), py::arg("n_trees") = 4, py::kw_only(), py::arg("device") = 0)
+        .def("set_mat_data", &knn_set_matrix, "Set data from numpy array", py::arg("data"))
+        .def("set_geometry", &knn_set_geometry, "Set data from open3d geometry", py::arg("geometry"))
+        .def("set_feature", &knn_set_feature, "Set data from open3d feature", py::arg("feature"))
+        .def(
+            "search",
+            [](PyKNearestSearch& self, const py::object& query, const py::object& param) {
+                std::string kind;
+                double radius = 0.0;
+                int knn = 0;
+                if (py::isinstance<py::tuple>(param)) {
+                    py::tuple t = param.cast<py::tuple>();
+                    if (t.size() < 2) throw py::value_error("param: (\"knn\", k), (\"hybrid\", r, max_nn) or (\"radius\", r)");
+                    kind = py::str(t[0]).cast<std::string>();
+                    for (char& c : kind) c = (char)std::tolower((unsigned char)c);
+                    if (kind == "knn") {
+                        knn = t[1].cast<int>();
+                    } else {
+                        radius = t[1].cast<double>();
+                        knn = t.size() > 2 ? t[2].cast<int>() : 0;
+                    }
+                } else if (py::hasattr(param, "knn") && !py::hasattr(param, "radius")) {
+                    kind = "knn";
+                    knn = param.attr("knn").cast<int>();
+                } else if (py::hasattr(param, "radius")) {
+                    radius = param.attr("radius").cast<double>();
+                    kind = py::hasattr(param, "max_nn") ? "hybrid" : "radius";
+                    if (kind == "hybrid") knn = param.attr("max_nn").cast<int>();
+                }
+                std::vector<double> q = knn_query(query);
+                std::vector<size_t> idx;
+                std::vector<double> dist;
+                py::gil_scoped_release nogil;
+                if (kind == "knn")
+                    self.s.Search(q, misc3d::features::KDTreeSearchParamKNN(knn), idx, dist);
+                else if (kind == "hybrid")
+                    self.s.Search(q, misc3d::features::KDTreeSearchParamHybrid(radius, knn), idx, dist);
+                else if (kind != "radius")
+                    throw py::value_error("param: KDTreeSearchParamKNN / KDTreeSearchParamHybrid / KDTreeSearchParamRadius");
+                py::gil_scoped_acquire gil;
+                return knn_pair(idx, dist);
+            },
+            "Search knn with open3d kdtree param", py::arg("query"), py::arg("param"))
+        .def(
+            "search_knn",
+            [](PyKNearestSearch& self, const py::object& query, int knn) {
+                std::vector<double> q = knn_query(query);
+                std::vector<size_t> idx;
+                std::vector<double> dist;
+                {
+                    py::gil_scoped_release nogil;
+                    self.s.SearchKNN(q, knn, idx, dist);
+                }
+                return knn_pair(idx, dist);
+            },
+            "Search knn with given k", py::arg("query"), py::arg("knn"))
+        .def(
+            "search_hybrid",
+            [](PyKNearestSearch& self, const py::object& query, double radius, int knn) {
+                std::vector<double> q = knn_query(query);
+                std::vector<size_t> idx;
+                std::vector<double> dist;
+                {
+                    py::gil_scoped_release nogil;
+                    self.s.SearchHybrid(q, radius, knn, idx, dist);   // (std::length_error -> ValueError, as the reference)
+                }
+                return knn_pair(idx, dist);
+            },
+            "Search knn with given raidus and k", py::arg("query"), py::arg("radius"), py::arg("knn"))
+        .def(
+            "search_knn_batch",
+            [](PyKNearestSearch& self, const py::object& queries, int knn) {
+                return knn_batch(self, queries, M3D_KNN_SEARCH_KNN, 0.0, knn);
+            },
+            "Batched search_knn: queries (m, dim) -> (indices int64 (m, kout), distances float64 (m, kout)), "
+            "kout = min(knn, N). ValueError where search_knn returns ([], []).",
+            py::arg("queries"), py::arg("knn"))
+        .def(
+            "search_hybrid_batch",
+            [](PyKNearestSearch& self, const py::object& queries, double radius, int knn) {
+                return knn_batch(self, queries, M3D_KNN_SEARCH_HYBRID, radius, knn);
+            },
+            "Batched search_hybrid: -> (indices (m, kout) padded with -1, distances padded with +inf, counts int64 (m,)); "
+            "counts[q] = -1 where search_hybrid raises ValueError. ValueError where search_hybrid returns ([], []).",
+            py::arg("queries"), py::arg("radius"), py::arg("knn"))
+        .def_property_readonly("size", [](const PyKNearestSearch& self) { return self.s.Size(); })
+        .def_property_readonly("dimension", [](const PyKNearestSearch& self) { return self.s.Dimension(); });
 
     // ---- segmentation (python/py_segmentation.cpp:87-96)
     py::module ms = m.def_submodule("segmentation");

@@ -7,6 +7,8 @@ bench.py); these lines feed DESIGN.md section 6 and check that the full sizes ru
   C5 segment_plane_iterative 10M pts (single GPU leg)
   P1 / P2 farthest_point_sampling 5 841 x 1 000 (the reference example) / 1M x 10 000, every device path (A/B)
   S1 - S4 ProximityExtractor.segment: the reference example's shape, the raw golden PLY at r = 0.01, 1 M and 10 M synthetic
+  K1 - K4 KNearestSearch: 200k x 200k x 33 k=10 batched, 1 000 single-query calls, 1 M x 3 k=30 (grid, tile A/B),
+          50k x 33 k=1000 (select)
 """
 import json
 import os
@@ -638,3 +640,110 @@ if any(t in which for t in ("S1", "S2", "S3", "S4")) or ALL:
              ms_device=st["ms_device"], ms_host_order=st["ms_order"], components=st["components"], cell_edge=st["cell_edge"],
              cell_coarsened=st["cell_edge"] / (1.001 * r),
              cpu_baseline=prox_cpu(sub, r, kind, dist, ang, None if nrm is None else nrm[: len(sub)], scale))
+
+if any(t in which for t in ("K1", "K2", "K3", "K4")) or ALL:
+    # misc3d.common.KNearestSearch: K1 = every src descriptor's 10 nearest dst descriptors (synth.registration_pair_c4),
+    # K2 = 1 000 single-query search_knn(q, 10) calls on that index, K3 = every point's 30 nearest among 1 M (grid path)
+    # with a tile-path A/B on a 100 k subset, K4 = 1 000 queries x k = 1 000 on 50 000 x 33 (select path)
+    import misc3d_amd as m3d
+
+    def knn_cpu(data, q, k, sample):
+        """scipy cKDTree.query(k, workers=16) on `sample` of the queries, scaled linearly (build included once)"""
+        if NO_CPU:
+            return None
+        from scipy.spatial import cKDTree
+        t0 = time.perf_counter()
+        tree = cKDTree(data)
+        t1 = time.perf_counter()
+        tree.query(q[:sample], k, workers=16)
+        t2 = time.perf_counter()
+        scale = len(q) / min(sample, len(q))
+        return {"value": ((t1 - t0) + (t2 - t1) * scale) * 1e3, "unit": "ms" if scale == 1.0 else "ms (scaled)", "cores": 16,
+                "kind": "scipy cKDTree(data).query(q, k, workers=16)", "build_ms": (t1 - t0) * 1e3,
+                **({"sample": f"{min(sample, len(q))} of {len(q)} queries timed, scaled linearly"} if scale != 1.0 else {})}
+
+    def knn_roofline(st, dim):
+        """tile / select paths: fp64 VALU issue, 3 lane-ops (sub, mul, add) per pair-dim at the 39.3 T lane-op/s peak"""
+        ops = 3.0 * st["pair_dims"]
+        return {"bound": "fp64 valu-issue", "kernel": "m3d::knn_tile_k + knn_merge_k", "lane_ops": ops,
+                "floor_ms": ops / (FP64_VALU_PEAK_TOPS * 1e12) * 1e3, "ms_device": st["ms_device"],
+                "achieved": ops / (st["ms_device"] * 1e-3) / 1e12, "peak": FP64_VALU_PEAK_TOPS,
+                "unit": "T lane-ops/s", "frac": ops / (st["ms_device"] * 1e-3) / (FP64_VALU_PEAK_TOPS * 1e12)}
+
+    def knn_timed(ix, q, k, reps=3, path=0):
+        capi.knn_force_path(path)
+        try:
+            ix.search(q[: min(len(q), 64)], k)
+            ts = []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                out = ix.search(q, k, want_d2=False, stats=True)
+                ts.append(((time.perf_counter() - t0) * 1e3, out))
+        finally:
+            capi.knn_force_path(0)
+        ms, out = sorted(ts, key=lambda t: t[0])[len(ts) // 2]
+        return ms, out[0], out[-1]
+
+    c4 = None
+    if "K1" in which or "K2" in which or ALL:
+        c4 = synth.registration_pair_c4(200_000, seed=5)
+        fs, fd = np.ascontiguousarray(c4["feat_src"]), np.ascontiguousarray(c4["feat_dst"])
+    if "K1" in which or ALL:
+        ix = capi.KnnIndex(fd)
+        ms, idx, st = knn_timed(ix, fs, 10)
+        emit("K1 knn 200k x 200k x 33 k=10 batched", n=len(fd), m=len(fs), dim=33, k=10, ms=ms, ms_in_library=st["ms_total"],
+             ms_device=st["ms_device"], path=st["path"], pair_dims=st["pair_dims"], roofline=knn_roofline(st, 33),
+             cpu_baseline=knn_cpu(fd, fs, 10, 2000))
+        ix.close()
+    if "K2" in which or ALL:
+        s = m3d.common.KNearestSearch(fd.T)
+        qs = fs[:1000]
+        s.search_knn(qs[0], 10)
+        t0 = time.perf_counter()
+        for q in qs:
+            s.search_knn(q, 10)
+        per = (time.perf_counter() - t0) * 1e3 / len(qs)
+        ix = capi.KnnIndex(fd)
+        _, _, st = knn_timed(ix, qs[:1], 10, reps=5)
+        ix.close()
+        cpu_b = None
+        if not NO_CPU:
+            from scipy.spatial import cKDTree
+            tree = cKDTree(fd)
+            t0 = time.perf_counter()
+            for q in qs[:50]:
+                tree.query(q, 10)
+            cpu_b = {"value": (time.perf_counter() - t0) * 1e3 / 50, "unit": "ms per call", "cores": 1,
+                     "kind": "scipy cKDTree.query(q, 10), one query per call (tree built beforehand), 50 calls timed"}
+        emit("K2 knn 1000 single-query search_knn(q, 10) on 200k x 33", n=len(fd), dim=33, k=10, calls=len(qs),
+             ms_per_call=per, ms_device_one_query=st["ms_device"], roofline=knn_roofline(st, 33), cpu_baseline=cpu_b)
+    if "K3" in which or ALL:
+        pts = np.random.default_rng(3).uniform(0, 1, (1_000_000, 3))
+        ix = capi.KnnIndex(pts)
+        ms, idx, st = knn_timed(ix, pts, 30)
+        sub = np.ascontiguousarray(pts[:100_000])
+        ixs = capi.KnnIndex(sub)
+        rows = {}
+        for name, path in (("grid", capi.KNN_PATH_GRID), ("tile", capi.KNN_PATH_TILE)):
+            pms, pidx, pst = knn_timed(ixs, sub, 30, path=path)
+            rows[name] = {"ms": pms, "ms_device": pst["ms_device"], "pair_dims": pst["pair_dims"], "path": pst["path"]}
+            rows[name]["idx"] = pidx
+        same = bool(np.array_equal(rows["grid"].pop("idx"), rows["tile"].pop("idx")))
+        emit("K3 knn 1M x 3 every point's 30 nearest (grid)", n=len(pts), m=len(pts), dim=3, k=30, ms=ms,
+             ms_in_library=st["ms_total"], ms_device=st["ms_device"], path=st["path"], pair_dims=st["pair_dims"],
+             pairs_per_query=st["pair_dims"] / 3 / len(pts), ab_100k=rows, ab_equal=same,
+             roofline={"bound": "none modelled (grid path: LDS list updates and cell walks)", "tile_path_100k": knn_roofline(
+                 {"pair_dims": rows["tile"]["pair_dims"], "ms_device": rows["tile"]["ms_device"]}, 3)},
+             cpu_baseline=knn_cpu(pts, pts, 30, 100_000))
+        ix.close()
+        ixs.close()
+    if "K4" in which or ALL:
+        rng = np.random.default_rng(4)
+        data = rng.random((50_000, 33))
+        q = rng.random((1000, 33))
+        ix = capi.KnnIndex(data)
+        ms, idx, st = knn_timed(ix, q, 1000)
+        emit("K4 knn 50k x 33, 1000 queries, k=1000 (select)", n=len(data), m=len(q), dim=33, k=1000, ms=ms,
+             ms_in_library=st["ms_total"], ms_device=st["ms_device"], path=st["path"], pair_dims=st["pair_dims"],
+             pages=st["launches"] // 2, roofline=knn_roofline(st, 33), cpu_baseline=knn_cpu(data, q, 1000, 1000))
+        ix.close()
