@@ -686,6 +686,11 @@ typedef struct m3d_config {
                                        copy / pre stream shares a queue with it (its calls take turns with that lane's): a process that runs many
                                        calls side by side (m3d_cloud_fit_batch over four lanes, fragment pairs in flight) sets 4 before its first
                                        call; a single-threaded caller keeps 2 (its fits of several chunks are 10-20 % faster that way) */
+    int32_t list_mask;              /* [M3D_LIST_MASK]      default 1: a plane / sphere fit that returns its inlier list into page-locked memory
+                                       (m3d_host_alloc) gets it from the device as a bit mask -- 1 bit per point instead of 8 bytes per inlier
+                                       over the host link -- and the host writes the indices, with up to 8 threads (the caller's + a
+                                       process-wide pool of helpers, woken when the fit queues its compaction, spinning at most
+                                       wait_spin_us); N >= 2: the same with at most N writers (<= 16); 0: the device writes the list */
 } m3d_config;
 void m3d_get_config(m3d_config *out);
 int m3d_set_config(const m3d_config *in);

@@ -50,6 +50,8 @@ void sanitize(m3d_config& c) {
     if (c.device_aliases < 0) c.device_aliases = 0;
     if (c.device_aliases > 16) c.device_aliases = 16;
     if (c.lanes_eager < 1 || c.lanes_eager > 8) c.lanes_eager = 2;
+    if (c.list_mask < 0) c.list_mask = 1;
+    if (c.list_mask > 16) c.list_mask = 16;
 }
 void load_env() {
     std::memset(&g_cfg, 0, sizeof(g_cfg));
@@ -87,6 +89,7 @@ void load_env() {
     g_cfg.reg_cache = (int32_t)env_long("M3D_REG_CACHE", 1);
     g_cfg.device_aliases = (int32_t)env_long("M3D_DEVICE_ALIASES", 0);
     g_cfg.lanes_eager = (int32_t)env_long("M3D_LANES_EAGER", 2);
+    g_cfg.list_mask = (int32_t)env_long("M3D_LIST_MASK", 1);
     sanitize(g_cfg);
 }
 }  // namespace

@@ -141,6 +141,11 @@ struct DeviceCtx {
     uint32_t compact_epoch = 0;               // launch counter of the compaction scratch (compact_scratch)
     bool compaction_fused = false;            // the compaction in flight carried the moments
     uint64_t* compaction_idx_host = nullptr;  // ... and wrote the index list to this page-locked destination as well
+    // ... or, compaction_mask (m3d_config.list_mask): shipped the inliers as a bit mask + per-tile counts instead, which
+    // refine() expands into compaction_idx_host after its wait (m3d_mask_expand.hpp); the device list (idx) is not written
+    bool compaction_mask = false;
+    PinBuf h_mask, h_tile_counts;
+    uint32_t mask_seq = 0;   // ... whose last launch stores this value into h_sync word 1 (its completion: no signal_host_k)
     // segmentation: asked by refine() right before it queues RefineModel's compaction -- given the inlier count the scoring
     // pass reported, where should the partition of the NON-inliers go (null: no partition in this pass)?
     const std::function<const m3d::PartitionOut*(int64_t)>* partition_hook = nullptr;

@@ -50,6 +50,7 @@ void release_buffers(m3d_cloud* c);                    // every device buffer a 
 
 // ---- m3d_fit.cpp
 int stream_wait_spin(DeviceCtx* ctx);
+int word_wait_spin(DeviceCtx* ctx, const uint32_t* word /* page-locked */, uint32_t seq);
 int validate_fit_args(int kind, size_t n, bool has_normals, double prob);
 uint64_t resolve_seed(const uint64_t* seed);
 int finalize_deferred_refine(DeviceCtx* ctx);
@@ -74,7 +75,8 @@ double* h_best_at(DeviceCtx* ctx);
 uint8_t* h_total_at(DeviceCtx* ctx);
 int issue_refine_compaction(DeviceCtx* ctx, const CloudView& flag_view, const uint32_t* orig_dev, int kind, double thr,
                             const double* model_dev, const double* lazy_in, void* total_host, bool fused = false,
-                            uint64_t* idx_host = nullptr, const PartitionOut* part = nullptr);
+                            uint64_t* idx_host = nullptr, const PartitionOut* part = nullptr,
+                            bool allow_mask = true /* the list may come as a bit mask that refine() expands (m3d_config.list_mask) */);
 int refine(DeviceCtx* ctx, const CloudView& flag_view, const CloudView& gather_view, const uint32_t* orig_dev, int kind, double thr,
            const double* model_dev, double* params_host /* in: best minimal model, out: refined */, size_t* inliers,
            size_t* n_inliers, int* general_fit_ok, int64_t expected_ni = -1, const std::function<int(int64_t)>* before_wait = nullptr,

@@ -587,7 +587,13 @@ int stream_wait_spin(DeviceCtx* ctx) {
     const uint32_t seq = ctx->sync_seq;
     launch_signal_host(ctx->h_sync.as<uint32_t>(), seq, ctx->stream);
     HIPCHK(hipGetLastError());
-    const volatile uint32_t* p = ctx->h_sync.as<uint32_t>();
+    return word_wait_spin(ctx, ctx->h_sync.as<uint32_t>(), seq);
+}
+
+// the same wait on a completion word a kernel already queued stores (a mask compaction's tail: h_sync word 1)
+int word_wait_spin(DeviceCtx* ctx, const uint32_t* word, uint32_t seq) {
+    const int spin_us = config().wait_spin_us;
+    const volatile uint32_t* p = word;
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t spins = 1;; ++spins) {
         if (*p == seq) break;
@@ -814,7 +820,7 @@ static int run_ransac(DeviceCtx* ctx, const CloudView& v, const SortedView& sv, 
             if (e == max_iter) {   // last chunk: RefineModel's first stage on the prediction, now
                 r = issue_refine_compaction(ctx, v, orig_dev, kind, thr, ctx->pick.as<BestPick>()->params,
                                             h_best_at(ctx), h_total_at(ctx), /*fused=*/true,
-                                            idx_host);
+                                            idx_host, nullptr, /*allow_mask=*/false);   // (sharded: the device writes the list)
                 ctx->spec_compaction = r == M3D_OK;
             }
         }
@@ -1077,6 +1083,7 @@ int cloud_fit_locked(m3d_cloud* c, int kind, double thr, size_t max_iter, double
                              ? reinterpret_cast<uint64_t*>(inliers) : nullptr;
     ctx->compaction_idx_host = nullptr;
     ctx->compaction_fused = false;
+    ctx->compaction_mask = false;
     ctx->spec_hit = false;
     ctx->ev_compact_early = false;
     if (ctx->defer_refine) ctx->refine_slot ^= 1;   // (the previous fit's words may still be waiting for finalize_deferred_refine)

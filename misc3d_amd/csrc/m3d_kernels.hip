@@ -439,8 +439,10 @@ __global__ __launch_bounds__(256) void compact_count_k(CloudView c, const double
                                                         double thr, int invert,
                                                         uint32_t* __restrict__ block_counts,
                                                         double* __restrict__ model_copy,
-                                                        double* __restrict__ moment_partial) {
+                                                        double* __restrict__ moment_partial,
+                                                        uint64_t* __restrict__ mask_host = nullptr) {
     __shared__ uint32_t wsum[4];
+    __shared__ unsigned long long wmask[kCompactTile / 64];
     double m[kModelStride];
     for (int k = 0; k < kModelStride; ++k) m[k] = model[k];
     // the model record (8 doubles) also goes where the caller wants a copy (pinned host memory): no copy command
@@ -480,11 +482,17 @@ __global__ __launch_bounds__(256) void compact_count_k(CloudView c, const double
                 }
             }
         }
-        cnt += (uint32_t)__popcll(__ballot(f));
+        const unsigned long long b = __ballot(f);
+        cnt += (uint32_t)__popcll(b);
+        if (lane == 0) wmask[r * 4 + wave] = b;   // word (i / 64) of the tile: creation order
     }
     if (lane == 0) wsum[wave] = cnt;
     __syncthreads();
     if (threadIdx.x == 0) block_counts[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    // the tile's 32 mask words as ONE 256-byte store of 32 consecutive lanes (a store per wave row would cross the host link
+    // as a write of its own); the buffer holds whole tiles: words past n are zero
+    if (mask_host && threadIdx.x < kCompactTile / 64)
+        mask_host[(size_t)blockIdx.x * (kCompactTile / 64) + threadIdx.x] = wmask[threadIdx.x];
     if (SUMS) {
         __shared__ double sm[NV * 256];
         __syncthreads();
@@ -573,6 +581,9 @@ __device__ __forceinline__ void fold_moment_partials(const CompactTail& tail) {
     for (uint32_t g0 = 0; g0 < 12u; g0 += 4u) {
         const uint32_t g = g0 + gq;
         double a = 0.0;
+        // (unrolled: the loads of a lane go out together -- the sum keeps its order; in the mask form this fold is on the
+        // step's critical path, a chain of dependent loads would cost ~1 us per 64 workgroups)
+#pragma unroll 8
         for (uint32_t b = l; b < tail.nb; b += 64u) a += tail.moment_partial[(size_t)b * 16 + g];
         msum[gq * 64 + l] = a;
         __syncthreads();
@@ -779,13 +790,41 @@ __global__ __launch_bounds__(256) void compact_write_k(
     }
 }
 
+// The mask form's second launch (one workgroup): what compact_write_k's workgroup 0 and last tile delivered -- the folded
+// moment partials (fold_moment_partials: the same order, the same sums) and the total -- plus the tile counts, copied to the
+// host as one contiguous block.
+// done_word (page-locked, may be null): receives done_seq last, behind a system-scope fence -- the end of the compaction.
+__global__ __launch_bounds__(256) void compact_mask_tail_k(const uint32_t* __restrict__ block_counts, CompactTail tail,
+                                                            uint32_t* __restrict__ counts_host, uint32_t* done_word,
+                                                            uint32_t done_seq) {
+    __shared__ uint32_t wsum[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t part = 0;
+    for (uint32_t i = threadIdx.x; i < tail.nb; i += 256u) {
+        const uint32_t v = block_counts[i];
+        counts_host[i] = v;
+        part += v;
+    }
+    for (int off = 32; off > 0; off >>= 1) part += (uint32_t)__shfl_xor((int)part, off, 64);
+    if (lane == 0) wsum[wave] = part;
+    if (tail.moment_partial) fold_moment_partials(tail);   // (ends with a barrier)
+    else __syncthreads();
+    if (threadIdx.x == 0) compact_tail_total(tail, (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]));
+    if (done_word) {
+        __threadfence_system();   // (every thread: its counts, and the moments of the lanes that stored them)
+        __syncthreads();
+        if (threadIdx.x == 0) __hip_atomic_store(done_word, done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
 template <int KIND>
 static void launch_compact_kind(const CloudView& c, const double* model, double thr, int mode,
                                 const uint32_t* orig, uint64_t* out_idx, double* out_dist,
                                 double* ox, double* oy, double* oz, uint32_t* oorig,
                                 uint32_t n_pad_out, const CompactScratch& scratch, uint32_t* total,
                                 hipStream_t s, double* model_copy, double* moment_partial, double* moment_out,
-                                uint64_t* out_idx_host, uint32_t* total_host, const PartitionOut* part) {
+                                uint64_t* out_idx_host, uint32_t* total_host, const PartitionOut* part,
+                                uint64_t* mask_host, uint32_t* counts_host, uint32_t* done_word, uint32_t done_seq) {
     const uint32_t nb = (c.n + kCompactTile - 1) / kCompactTile;
     if (nb == 0) {
         (void)hipMemsetAsync(total, 0, sizeof(uint32_t), s);
@@ -798,6 +837,19 @@ static void launch_compact_kind(const CloudView& c, const double* model, double 
     const bool one = kExperimentalBuild && config().compact_one_pass != 0 && nb <= kCompactOnePassMaxTiles && scratch.tag != 0u;
     uint32_t* block_counts = scratch.slots;
     const uint32_t tag = scratch.tag;
+    if (mask_host && counts_host && sums && !orig && !part && !one) {
+        // the mask form: no list is written anywhere -- the host expands the mask (m3d_mask_expand.hpp)
+        compact_count_k<KIND == 2 ? 0 : KIND, true><<<nb, 256, 0, s>>>(c, model, thr, 0, block_counts, model_copy, moment_partial,
+                                                                       mask_host);
+        CompactTail tail;
+        tail.total = total;
+        tail.total_host = total_host;
+        tail.moment_partial = moment_partial;
+        tail.moment_out = moment_out;
+        tail.nb = nb;
+        compact_mask_tail_k<<<1, 256, 0, s>>>(block_counts, tail, counts_host, done_word, done_seq);
+        return;
+    }
     if (!one) {
         if (sums)
             compact_count_k<KIND == 2 ? 0 : KIND, true><<<nb, 256, 0, s>>>(c, model, thr, 0, block_counts, model_copy, moment_partial);
@@ -851,16 +903,17 @@ void launch_compact(int kind, const CloudView& c, const double* model, double th
                     double* oy, double* oz, uint32_t* oorig, uint32_t n_pad_out,
                     const CompactScratch& scratch, uint32_t* total, hipStream_t s, double* model_copy,
                     double* moment_partial, double* moment_out, uint64_t* out_idx_host, uint32_t* total_host,
-                    const PartitionOut* part) {
+                    const PartitionOut* part, uint64_t* mask_host, uint32_t* counts_host, uint32_t* done_word,
+                    uint32_t done_seq) {
     if (kind == 0)
-        launch_compact_kind<0>(c, model, thr, mode, orig, out_idx, out_dist, ox, oy, oz, oorig,
-                               n_pad_out, scratch, total, s, model_copy, moment_partial, moment_out, out_idx_host, total_host, part);
+        launch_compact_kind<0>(c, model, thr, mode, orig, out_idx, out_dist, ox, oy, oz, oorig, n_pad_out, scratch, total, s,
+                               model_copy, moment_partial, moment_out, out_idx_host, total_host, part, mask_host, counts_host, done_word, done_seq);
     else if (kind == 1)
-        launch_compact_kind<1>(c, model, thr, mode, orig, out_idx, out_dist, ox, oy, oz, oorig,
-                               n_pad_out, scratch, total, s, model_copy, moment_partial, moment_out, out_idx_host, total_host, part);
+        launch_compact_kind<1>(c, model, thr, mode, orig, out_idx, out_dist, ox, oy, oz, oorig, n_pad_out, scratch, total, s,
+                               model_copy, moment_partial, moment_out, out_idx_host, total_host, part, mask_host, counts_host, done_word, done_seq);
     else
-        launch_compact_kind<2>(c, model, thr, mode, orig, out_idx, out_dist, ox, oy, oz, oorig,
-                               n_pad_out, scratch, total, s, model_copy, nullptr, nullptr, out_idx_host, total_host, part);
+        launch_compact_kind<2>(c, model, thr, mode, orig, out_idx, out_dist, ox, oy, oz, oorig, n_pad_out, scratch, total, s,
+                               model_copy, nullptr, nullptr, out_idx_host, total_host, part, nullptr, nullptr, nullptr, 0u);
 }
 
 // cluster = pcd_copy->SelectByIndex(inliers) (iterative_plane_segmentation.cpp:32): the points of an index list, AoS, in

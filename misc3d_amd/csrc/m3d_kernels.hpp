@@ -134,7 +134,14 @@ void launch_compact(int kind, const CloudView& c, const double* model, double th
                                                     moments over the inliers about the model record's provisional centre */,
                     uint64_t* out_idx_host = nullptr /* mode 0: page-locked host copy of the index list, written by the kernel */,
                     uint32_t* total_host = nullptr /* device-visible host word that receives total[0] as well (no copy command) */,
-                    const PartitionOut* part = nullptr /* mode 0 with orig != null: the non-inliers' partition rides along */);
+                    const PartitionOut* part = nullptr /* mode 0 with orig != null: the non-inliers' partition rides along */,
+                    uint64_t* mask_host = nullptr /* mode 0, plane / sphere with the moments, orig and part null: page-locked,
+                                                     ceil(n / kCompactTile) x 32 words -- the inlier BIT MASK (bit i of word i / 64 =
+                                                     point i) replaces the index list, which is written nowhere ... */,
+                    uint32_t* counts_host = nullptr /* ... and the inliers per tile of kCompactTile points (page-locked, one word per
+                                                       tile): the host expands the list (m3d_mask_expand.hpp) */,
+                    uint32_t* done_word = nullptr /* the mask form: page-locked word that receives done_seq when it is complete */,
+                    uint32_t done_seq = 0);
 // moment_out layout: [0..2] sum s, [3..8] sum s s^T (xx,xy,xz,yy,yz,zz), [9..11] sum s |s|^2 (sphere), [12] inlier count;
 // s = p - c0, c0 = model[4..6] (plane: the hypothesis' first sample point) or model[0..2] (sphere: the minimal centre).
 constexpr int kFusedMomentDoubles = 16;
