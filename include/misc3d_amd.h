@@ -423,6 +423,82 @@ int m3d_knn_dim(const m3d_knn *h);
 int m3d_knn_search(const m3d_knn *h, const double *queries, size_t m, int search, int64_t knn, double radius, size_t stride,
                    size_t *indices, double *dist, double *d2, int64_t *counts, m3d_knn_stats *stats);
 
+/* ---- fragment preprocessing: PreProcessFragments, src/pipeline.cpp:379-401 ----------------------------------------- */
+/* EstimateNormals(Hybrid(2 voxel, 30)) when the fragment has no normals, OrientNormalsTowardsCameraLocation(), then
+ * ComputeFPFHFeature(Hybrid(5 voxel, 100)) -- the producer of the descriptors that m3d_match_mutual_nn,
+ * m3d_global_registration and m3d_register_fragment_pairs consume.  Open3D's source is in neither tree: the arithmetic
+ * below is a [RECALL] of Open3D 0.15.1 (pipelines/registration/Feature.cpp, geometry/EstimateNormals.cpp,
+ * PointCloud::OrientNormalsTowardsCameraLocation), as the ICP and the RANSAC registration are; THIS TEXT is the contract
+ * (tests/cpp/fpfh_ref.c restates it in plain C).
+ *
+ * Neighbourhood (both calls; the same as m3d_detect_boundary_points): search = 0, KDTreeSearchParamKNN (the max_nn
+ *   nearest) or 2, KDTreeSearchParamHybrid (the max_nn nearest among those with d2 < radius^2);
+ *   d2 = (dx dx + dy dy) + dz dz in fp64, every operation rounded; the query point itself is included; neighbours are
+ *   ordered by (d2, index); 1 <= max_nn <= 128.  A pair whose d2 is not finite is no neighbour pair: a point with a
+ *   non-finite coordinate has no neighbours and is nobody's neighbour.  m = the number of neighbours found (self included).
+ *   M3D_ERR_INVALID_ARG, all decided before any device is touched: search = 1 (Radius: unbounded lists are not
+ *   supported, the message says so), any other search value, max_nn outside [1, 128], a Hybrid radius that is negative or
+ *   NaN, n >= 2^31, a null array with n > 0.  n == 0: M3D_OK, nothing written.
+ *
+ * Normals.  m < 3: (0, 0, 1).  Otherwise the covariance in cumulant form, sums taken in neighbour order:
+ *   s = sum (x, y, z, xx, xy, xz, yy, yz, zz) / m, C = E[ab] - E[a] E[b], and the unit eigenvector of its smallest
+ *   eigenvalue by J3x3 (m3d_eig3.hpp).  Open3D's default is a closed-form solver whose roundings cannot be restated from
+ *   memory: the DIRECTION is specified, not the bits.  A zero-length result becomes (0, 0, 1).
+ *   orient != 0 (camera: 3 doubles), with v = camera - p: a zero normal becomes v / |v| ((0, 0, 1) when v is zero),
+ *   any other normal is negated when n . v < 0.
+ *
+ * FPFH.  feature_out: n rows of 33 doubles = Eigen's column-major 33 x N (Feature::data_).
+ *   Pair features of (p1, n1) with a neighbour (p2, n2): dp = p2 - p1, d = |dp|; d == 0: all features 0.
+ *     a1 = n1 . dp / d, a2 = n2 . dp / d.  If acos(|a1|) > acos(|a2|): the roles of n1 and n2 are swapped, dp = -dp,
+ *     f2 = -a2; else f2 = a1.  v = dp x n1; |v| == 0: all features 0; v /= |v|; w = n1 x v; f1 = v . n2;
+ *     f0 = atan2(w . n2, n1 . n2).  Dot products and norms are 3-element reductions of the library's M3D_FP_ORDER.
+ *     The acos of that comparison is the HOST libm's.  Estimated normals of neighbouring points often agree to an ulp, and
+ *     two acos implementations may order such arguments differently, which swaps the frame and moves the pair to other
+ *     bins.  The device therefore lists every point with a pair whose two (device) acos values are unequal arguments'
+ *     results within 64 eps of each other, relative; the host evaluates the SPFH rows of those points with the same
+ *     code and its own libm, and FPFH reads the rows after that (m3d_fpfh_stats.tie_points counts them).
+ *   SPFH of point i with m > 1 (entry 0 of the list -- the point itself -- is skipped): incr = 100 / (m - 1); every
+ *     other neighbour adds incr to the bins clamp(floor(11 (f0 + pi) / (2 pi))), 11 + clamp(floor(11 (f1 + 1) 0.5)),
+ *     22 + clamp(floor(11 (f2 + 1) 0.5)), clamped to [0, 10].  m <= 1: a zero row.  (The device counts the pairs per
+ *     bin in integers and multiplies by incr once: off the repeated addition by roundings of order 1e-14.)
+ *   FPFH of point i with m > 1: over the same neighbours k >= 1 in list order, skipping d2[k] == 0:
+ *     acc[j] += spfh[nb_k][j] / d2[k] (the SQUARED distance, as FLANN returns it), sum[j / 11] += the same value; then
+ *     sum[g] = 100 / sum[g] where sum[g] != 0, and out[j] = acc[j] sum[j / 11] + spfh[i][j].  m <= 1: a zero row.
+ *   So each of a row's three groups sums to 200 (100 when every weighted neighbour row is empty, 0 for an isolated point).
+ *
+ * Device ("FPFH"): one upload and one density grid per call (m3d_knn.hip's grid path with the cloud as its own
+ * query set); the neighbour lists of a search stay in device memory, 12 bytes per pair, until SPFH and FPFH have read
+ * them (a search whose lists would exceed 8 GiB is M3D_ERR_INVALID_ARG).  Re-entrant: concurrent calls take lanes. */
+typedef struct m3d_fpfh_stats {
+    double ms_total;        /* the call, host clock */
+    double ms_device;       /* first launch to last launch, HIP events (uploads and result copies excluded) */
+    double ms_upload;       /* grid build on the host + uploads, host clock */
+    double ms_search;       /* the neighbour searches (+ the Hybrid cut), HIP events */
+    double ms_normals;      /* normal estimation / orientation */
+    double ms_spfh;
+    double ms_fpfh;
+    uint64_t pairs;         /* neighbour pairs processed: the sum of m over the points, every search counted */
+    uint64_t pairs_seen;    /* (query, row) distances the searches evaluated */
+    int32_t launches;       /* kernel launches */
+    int32_t searches;       /* neighbour searches (0, 1 or 2) */
+    uint64_t tie_points;    /* points whose SPFH row the host redid (a near tie of the two acos values, above) */
+} m3d_fpfh_stats;
+typedef m3d_fpfh_stats m3d_normals_stats;
+/* open3d PointCloud::EstimateNormals(param) (+ OrientNormalsTowardsCameraLocation(camera) when orient != 0) for an
+ * unorganised cloud.  normals_out: n x 3.  camera may be NULL when orient == 0.  stats may be NULL. */
+int m3d_estimate_normals(const double *xyz, size_t n, int search, double radius, int max_nn, int orient,
+                         const double camera[3], int device, double *normals_out, m3d_normals_stats *stats);
+/* open3d ComputeFPFHFeature(cloud, param).  normals == NULL: M3D_ERR_INVALID_ARG "Failed because input point cloud has
+ * no normal."  stats may be NULL. */
+int m3d_compute_fpfh(const double *xyz, const double *normals, size_t n, int search, double radius, int max_nn, int device,
+                     double *feature_out, m3d_fpfh_stats *stats);
+/* PreProcessFragments for one fragment: normals by Hybrid(2 voxel_size, 30) only when normals_in == NULL, orientation
+ * towards the origin always, FPFH by Hybrid(5 voxel_size, 100); one upload, one grid, both searches on the device.
+ * normals_out (n x 3) receives the normals the descriptor was computed with; the result equals m3d_estimate_normals
+ * followed by m3d_compute_fpfh bit for bit.  voxel_size must be positive and finite. */
+int m3d_preprocess_fragment(const double *xyz, const double *normals_in, size_t n, double voxel_size, int device,
+                            double *normals_out, double *feature_out, m3d_fpfh_stats *stats);
+
 /* ---- point-to-point ICP refinement of the RANSAC pose ----------------------- */
 /* open3d::pipelines::registration::RegistrationICP(source, target, max_correspondence_distance, init,
  * TransformationEstimationPointToPoint(), ICPConvergenceCriteria(relative_fitness, relative_rmse,

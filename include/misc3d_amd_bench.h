@@ -80,6 +80,11 @@ int m3d_bench_knn_force_path(int path);
  * d2 >= d2_cut), out[1..4] = lo1, hi1, lo2, hi2 (the angle test accepts dot exactly on [lo1, hi1] u [lo2, hi2]). */
 int m3d_bench_proximity_cutoffs(double dist, double angle_deg, double out[5]);
 
+/* TEST hook (tests/test_fpfh.py): the FPFH pair features and the bin rule evaluated on the HOST by the very code the
+ * kernels compile (m3d_fpfh_fp.hpp) -- pairs: m x 12 doubles (p1, n1, p2, n2), bins: m x 3 (columns of the 33-row),
+ * features (may be NULL): m x 3 (f0, f1, f2). */
+int m3d_bench_fpfh_pair_bins(const double *pairs, size_t m, int32_t *bins, double *features);
+
 /* TEST hook (tests/test_gpu_match_sliced.py): which way the CALLING THREAD's last m3d_match_mutual_nn went -- bit 0: the split-fp16
  * MFMA screen produced the result, bit 1: the matrices went up in slices under the scan (m3d_config.match_pipeline), bit 2: a
  * later slice did not fit the scale chosen from the first ones and the search was redone whole on the resident matrices,

@@ -12,6 +12,9 @@ Drop-in for the reference's python API on this path (module layout of python/py_
     T        = m3d.registration.compute_transformation_least_square(src, dst)
     T, info  = m3d.registration_icp(src, dst, 0.02, T)      # the Open3D call the reference's examples chain next
     index    = m3d.features.detect_boundary_points(plane, ("hybrid", 0.02, 30))
+    normals  = m3d.features.estimate_normals(pcd, ("hybrid", 0.1, 30), orient_to=(0, 0, 0))   # unorganised clouds
+    fpfh     = m3d.features.compute_fpfh_feature(pcd, ("hybrid", 0.25, 100))                  # (33, N), Open3D's Feature.data
+    normals, fpfh = m3d.reconstruction.preprocess_fragment(fragment, voxel_size)              # pipeline.cpp:379-401
     index    = m3d.preprocessing.farthest_point_sampling(pcd, 1000)
     roi      = m3d.preprocessing.crop_roi_pointcloud(pcd, (tl_x, tl_y, br_x, br_y), (width, height))
     normals  = m3d.common.estimate_normals(pcd, (848, 480), 3)
@@ -65,8 +68,46 @@ def registration_icp(source, target, max_correspondence_distance, init=None, max
                                   relative_fitness, relative_rmse, device)
 
 
+def _search_param(param):
+    """An open3d KDTreeSearchParamHybrid / KDTreeSearchParamRadius / KDTreeSearchParamKNN (anything with .radius and
+    optionally .max_nn, or with .knn), or a tuple ("hybrid", radius, max_nn) / ("radius", radius) / ("knn", k)
+    -> (kind, radius, max_nn)."""
+    if isinstance(param, tuple):
+        kind = str(param[0]).lower()
+        if kind == "knn":
+            radius, max_nn = 0.0, int(param[1])
+        else:
+            radius = float(param[1])
+            max_nn = int(param[2]) if len(param) > 2 else 0
+    elif hasattr(param, "knn") and not hasattr(param, "radius"):
+        kind, radius, max_nn = "knn", 0.0, int(param.knn)
+    else:
+        radius = float(param.radius)
+        max_nn = int(getattr(param, "max_nn", 0))
+        kind = "hybrid" if hasattr(param, "max_nn") else "radius"
+    if kind not in ("hybrid", "radius", "knn"):
+        raise RuntimeError("[Misc3D Error] param: KDTreeSearchParamHybrid / KDTreeSearchParamRadius / KDTreeSearchParamKNN")
+    return kind, radius, max_nn
+
+
+def _points_normals(pc):
+    """(N, 3) array, (points, normals) tuple or an object with .points / .normals -> (points, normals or None)"""
+    import numpy as _np
+    if isinstance(pc, tuple) and len(pc) == 2:
+        pts, nrm = pc
+    else:
+        pts, nrm = getattr(pc, "points", pc), getattr(pc, "normals", None)
+    pts = _np.asarray(pts, dtype=_np.float64).reshape(-1, 3)
+    if nrm is not None:
+        nrm = _np.asarray(nrm, dtype=_np.float64).reshape(-1, 3)
+        if len(nrm) != len(pts) or len(nrm) == 0:
+            nrm = None
+    return pts, nrm
+
+
 class _Features:
-    """misc3d.features (python/py_features.cpp): detect_boundary_points"""
+    """misc3d.features (python/py_features.cpp): detect_boundary_points; and the two Open3D calls every registration entry
+    point depends on: estimate_normals (unorganised clouds) and compute_fpfh_feature"""
 
     @staticmethod
     def detect_boundary_points(pc, param=("hybrid", 0.01, 30), angle_threshold=90.0, device=0):
@@ -78,30 +119,8 @@ class _Features:
         import numpy as _np
 
         from . import capi as _capi
-        if isinstance(pc, tuple) and len(pc) == 2:
-            pts, nrm = pc
-        else:
-            pts, nrm = getattr(pc, "points", pc), getattr(pc, "normals", None)
-        pts = _np.asarray(pts, dtype=_np.float64).reshape(-1, 3)
-        if nrm is not None:
-            nrm = _np.asarray(nrm, dtype=_np.float64).reshape(-1, 3)
-            if len(nrm) != len(pts) or len(nrm) == 0:
-                nrm = None
-        if isinstance(param, tuple):
-            kind = str(param[0]).lower()
-            if kind == "knn":
-                radius, max_nn = 0.0, int(param[1])
-            else:
-                radius = float(param[1])
-                max_nn = int(param[2]) if len(param) > 2 else 0
-        elif hasattr(param, "knn") and not hasattr(param, "radius"):
-            kind, radius, max_nn = "knn", 0.0, int(param.knn)
-        else:
-            radius = float(param.radius)
-            max_nn = int(getattr(param, "max_nn", 0))
-            kind = "hybrid" if hasattr(param, "max_nn") else "radius"
-        if kind not in ("hybrid", "radius", "knn"):
-            raise RuntimeError("[Misc3D Error] param: KDTreeSearchParamHybrid / KDTreeSearchParamRadius / KDTreeSearchParamKNN")
+        pts, nrm = _points_normals(pc)
+        kind, radius, max_nn = _search_param(param)
         search = {"hybrid": _capi.SEARCH_HYBRID, "radius": _capi.SEARCH_RADIUS, "knn": _capi.SEARCH_KNN}[kind]
         try:
             idx = _capi.detect_boundary_points(pts, nrm, search, radius, max_nn, angle_threshold, device)
@@ -109,7 +128,33 @@ class _Features:
             raise RuntimeError(str(e)) from e
         return [int(i) for i in idx]
 
+    @staticmethod
+    def estimate_normals(pc, param=("hybrid", 0.1, 30), *, orient_to=None, device=0):
+        """open3d PointCloud.estimate_normals(param) for an unorganised cloud (+ orient_normals_towards_camera_location(
+        orient_to) when given).  pc: (N, 3) array or an object with .points; param as detect_boundary_points takes it
+        (Hybrid or KNN).  Returns the (N, 3) normals."""
+        from . import capi as _capi
+        kind, radius, max_nn = _search_param(param)
+        try:
+            return _capi.estimate_normals(_xyz(pc), _SEARCH[kind], radius, max_nn, orient_to, device)
+        except _capi.M3DError as e:
+            raise RuntimeError(str(e)) from e
 
+    @staticmethod
+    def compute_fpfh_feature(pc, param=("hybrid", 0.25, 100), *, device=0):
+        """open3d.pipelines.registration.compute_fpfh_feature(pc, param).  pc: a (points, normals) tuple or an object with
+        .points / .normals.  Returns a (33, N) array laid out as Open3D's Feature.data (Fortran order: the transposed view of
+        the (N, 33) rows), accepted as is by registration.match_correspondence and reconstruction.global_registration."""
+        from . import capi as _capi
+        pts, nrm = _points_normals(pc)
+        kind, radius, max_nn = _search_param(param)
+        try:
+            return _capi.compute_fpfh_feature(pts, nrm, _SEARCH[kind], radius, max_nn, device).T
+        except _capi.M3DError as e:
+            raise RuntimeError(str(e)) from e
+
+
+_SEARCH = {"knn": 0, "radius": 1, "hybrid": 2}   # capi.SEARCH_*
 features = _Features()
 
 
@@ -129,8 +174,8 @@ def _feat(f, n):
 
 
 class _Reconstruction:
-    """misc3d.reconstruction, the loop-closure half of ReconstructionPipeline (src/pipeline.cpp): GlobalRegistration
-    (:790-828) and the loop over fragment pairs that calls it (:428-439).  Calls release the GIL: Python threads that call
+    """misc3d.reconstruction, the loop-closure half of ReconstructionPipeline (src/pipeline.cpp): PreProcessFragments
+    (:379-401), GlobalRegistration (:790-828) and the loop over fragment pairs that calls it (:428-439).  Calls release the GIL: Python threads that call
     global_registration / fit_* / match_correspondence side by side run side by side on the device (lanes)."""
 
     @staticmethod
@@ -148,15 +193,31 @@ class _Reconstruction:
             raise RuntimeError(str(e)) from e
 
     @staticmethod
-    def register_fragment_pairs(fragments, features, pairs=None, voxel_size=0.01, max_iter=100000,
+    def preprocess_fragment(pc, voxel_size, *, device=0):
+        """ReconstructionPipeline::PreProcessFragments for one fragment: normals by Hybrid(2 voxel_size, 30) when pc has
+        none, oriented towards the origin, FPFH by Hybrid(5 voxel_size, 100) -- one upload, both searches on the device.
+        Returns (normals (N, 3), fpfh (33, N) as features.compute_fpfh_feature returns it)."""
+        from . import capi as _capi
+        pts, nrm = _points_normals(pc)
+        try:
+            normals, feat = _capi.preprocess_fragment(pts, voxel_size, nrm, device)
+        except _capi.M3DError as e:
+            raise RuntimeError(str(e)) from e
+        return normals, feat.T
+
+    @staticmethod
+    def register_fragment_pairs(fragments, features=None, pairs=None, voxel_size=0.01, max_iter=100000,
                                 edge_length_threshold=0.9, confidence=0.999, *, seeds=None, devices=(0,), inflight=0):
         """BuildPoseGraphForScene's loop closures: every (s, t) of `pairs` through global_registration, dealt to `devices`,
         `inflight` pairs at a time per device.  Default pairs: all s < t with t > s + 1 -- the reference sends ADJACENT fragments
         (t == s + 1) to the multi-scale ICP odometry seeded from the fragment pose graph, never to GlobalRegistration
         (src/pipeline.cpp:752-764); pass `pairs` explicitly to register those here as well.
+        features=None: the descriptors are computed first, fragment by fragment, with preprocess_fragment(voxel_size).
         Returns [(s, t, success, pose, information), ...]."""
         from . import capi as _capi
         pts = [_xyz(f) for f in fragments]
+        if features is None:
+            features = [_Reconstruction.preprocess_fragment(f, voxel_size, device=devices[0])[1] for f in fragments]
         fts = [_feat(f, len(p)) for f, p in zip(features, pts)]
         if pairs is None:
             pairs = [(s, t) for s in range(len(pts)) for t in range(s + 2, len(pts))]

@@ -183,6 +183,13 @@ def lib():
         L.m3d_knn_search.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int64, C.c_double, C.c_size_t,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.m3d_bench_knn_force_path.argtypes = [C.c_int]
+        L.m3d_estimate_normals.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                           C.c_void_p, C.c_void_p]
+        L.m3d_compute_fpfh.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p,
+                                       C.c_void_p]
+        L.m3d_preprocess_fragment.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]
+        L.m3d_bench_fpfh_pair_bins.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.m3d_match_last_fallbacks.restype = C.c_uint64
         L.m3d_match_last_fallbacks.argtypes = []
         L.m3d_match_mutual_nn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
@@ -1221,6 +1228,63 @@ def knn_create_status(data_ptr, n, dim, device=0):
 def knn_force_path(path: int):
     """test / measurement hook m3d_bench_knn_force_path: 0 = by shape, KNN_PATH_GRID / TILE / SELECT"""
     _check(lib().m3d_bench_knn_force_path(int(path)))
+
+
+class FpfhStats(C.Structure):
+    """m3d_fpfh_stats (= m3d_normals_stats)"""
+    _fields_ = [("ms_total", C.c_double), ("ms_device", C.c_double), ("ms_upload", C.c_double), ("ms_search", C.c_double),
+                ("ms_normals", C.c_double), ("ms_spfh", C.c_double), ("ms_fpfh", C.c_double), ("pairs", C.c_uint64),
+                ("pairs_seen", C.c_uint64), ("launches", C.c_int32), ("searches", C.c_int32), ("tie_points", C.c_uint64)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def estimate_normals(xyz, search=SEARCH_HYBRID, radius=0.1, max_nn=30, orient_to=None, device=0, stats=False):
+    """m3d_estimate_normals -> (N, 3) normals (+ the stats dict).  orient_to: a camera location (3 numbers) or None."""
+    xyz = _f64(xyz).reshape(-1, 3)
+    cam = _f64(orient_to).reshape(3) if orient_to is not None else None
+    out = np.zeros((len(xyz), 3))
+    st = FpfhStats()
+    _check(lib().m3d_estimate_normals(_p(xyz), len(xyz), int(search), float(radius), int(max_nn), int(cam is not None),
+                                      _p(cam), device, _p(out), C.cast(C.byref(st), C.c_void_p)))
+    return (out, st.asdict()) if stats else out
+
+
+def compute_fpfh_feature(xyz, normals, search=SEARCH_HYBRID, radius=0.1, max_nn=100, device=0, stats=False):
+    """m3d_compute_fpfh -> (N, 33) C-contiguous = Eigen's column-major 33 x N (+ the stats dict)."""
+    xyz = _f64(xyz).reshape(-1, 3)
+    nrm = _f64(normals).reshape(-1, 3) if normals is not None else None
+    if nrm is not None and len(nrm) != len(xyz):
+        raise ValueError("normals and points differ in length")
+    out = np.zeros((len(xyz), 33))
+    st = FpfhStats()
+    _check(lib().m3d_compute_fpfh(_p(xyz), _p(nrm), len(xyz), int(search), float(radius), int(max_nn), device, _p(out),
+                                  C.cast(C.byref(st), C.c_void_p)))
+    return (out, st.asdict()) if stats else out
+
+
+def preprocess_fragment(xyz, voxel_size, normals=None, device=0, stats=False):
+    """m3d_preprocess_fragment -> ((N, 3) normals, (N, 33) descriptors) (+ the stats dict)."""
+    xyz = _f64(xyz).reshape(-1, 3)
+    nrm = _f64(normals).reshape(-1, 3) if normals is not None else None
+    if nrm is not None and len(nrm) != len(xyz):
+        raise ValueError("normals and points differ in length")
+    out_n = np.zeros((len(xyz), 3))
+    out_f = np.zeros((len(xyz), 33))
+    st = FpfhStats()
+    _check(lib().m3d_preprocess_fragment(_p(xyz), _p(nrm), len(xyz), float(voxel_size), device, _p(out_n), _p(out_f),
+                                         C.cast(C.byref(st), C.c_void_p)))
+    return (out_n, out_f, st.asdict()) if stats else (out_n, out_f)
+
+
+def fpfh_pair_bins(pairs, features=False):
+    """test hook m3d_bench_fpfh_pair_bins: pairs (m, 12) = (p1, n1, p2, n2) -> bins int32 (m, 3) (+ features (m, 3))"""
+    pairs = _f64(pairs).reshape(-1, 12)
+    bins = np.zeros((len(pairs), 3), dtype=np.int32)
+    f = np.zeros((len(pairs), 3)) if features else None
+    _check(lib().m3d_bench_fpfh_pair_bins(_p(pairs), len(pairs), _p(bins), _p(f)))
+    return (bins, f) if features else bins
 
 
 def proximity_cutoffs(dist, angle_deg):

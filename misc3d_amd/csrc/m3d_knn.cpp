@@ -1,7 +1,7 @@
 // m3d_knn.cpp -- misc3d::common::KNearestSearch (src/knn.cpp) behind the C ABI: a resident dim x N matrix and exact k
 // nearest neighbour queries on it (m3d_knn.hip).  Distances are turned into the returned sqrt on the host, with libm.
 #include "m3d_driver_internal.hpp"
-#include "m3d_knn.hpp"
+#include "m3d_knn_grid.hpp"
 
 #include "../../include/misc3d_amd_bench.h"
 
@@ -16,40 +16,6 @@ std::atomic<int> g_knn_force{0};
 
 constexpr int kKnnMaxDim = 1024;                          // the matcher's cap
 constexpr size_t kKnnScratchCap = (size_t)256 << 20;      // device scratch of one call (bytes)
-constexpr int kKnnGridClasses = 4;                        // lists of <= 16, 32, 64, 128 pairs: about kout / 4 rows per cell
-constexpr int kKnnGridRowsPerCell[kKnnGridClasses] = {4, 8, 16, 32};
-constexpr uint64_t kKnnGridMaxCells = (uint64_t)1 << 22;
-
-int grid_class(int kk) { return kk <= 16 ? 0 : kk <= 32 ? 1 : kk <= 64 ? 2 : 3; }
-
-struct KnnGrid {
-    bool built = false, usable = false;
-    KnnGridDesc g{};
-    DevBuf cell_start, sx, sy, sz, sidx, slabs, out_rows;
-    KnnGridView view() const {
-        KnnGridView v;
-        v.g = g;
-        v.cell_start = cell_start.as<uint32_t>();
-        v.sx = sx.as<double>();
-        v.sy = sy.as<double>();
-        v.sz = sz.as<double>();
-        v.sidx = sidx.as<uint32_t>();
-        const int na[3] = {g.nx, g.ny, g.nz};
-        const double* s = slabs.as<double>();
-        for (int a = 0; a < 3; ++a) {
-            v.pmax[a] = s;
-            v.smin[a] = s + na[a];
-            s += 2 * (size_t)na[a];
-        }
-        v.out_rows = out_rows.as<uint32_t>();
-        v.data = nullptr;
-        return v;
-    }
-    void release() {
-        for (DevBuf* b : {&cell_start, &sx, &sy, &sz, &sidx, &slabs, &out_rows}) b->release();
-    }
-};
-
 struct KnnBufs {
     DevBuf qT, part_key, part_idx, floor, out_d2, out_idx, q3, seen;
     void release() {
@@ -69,13 +35,39 @@ struct m3d_knn {
     KnnGrid grid[kKnnGridClasses];
 };
 
-namespace {
+namespace m3d {
+
+constexpr int kKnnGridRowsPerCell[kKnnGridClasses] = {4, 8, 16, 32};   // lists of <= 16, 32, 64, 128 pairs: about kout / 4 rows per cell
+constexpr uint64_t kKnnGridMaxCells = (uint64_t)1 << 22;
+
+int knn_grid_class(int kk) { return kk <= 16 ? 0 : kk <= 32 ? 1 : kk <= 64 ? 2 : 3; }
+
+KnnGridView KnnGrid::view() const {
+    KnnGridView v;
+    v.g = g;
+    v.cell_start = cell_start.as<uint32_t>();
+    v.sx = sx.as<double>();
+    v.sy = sy.as<double>();
+    v.sz = sz.as<double>();
+    v.sidx = sidx.as<uint32_t>();
+    const int na[3] = {g.nx, g.ny, g.nz};
+    const double* s = slabs.as<double>();
+    for (int a = 0; a < 3; ++a) {
+        v.pmax[a] = s;
+        v.smin[a] = s + na[a];
+        s += 2 * (size_t)na[a];
+    }
+    v.out_rows = out_rows.as<uint32_t>();
+    v.data = nullptr;
+    return v;
+}
+void KnnGrid::release() {
+    for (DevBuf* b : {&cell_start, &sx, &sy, &sz, &sidx, &slabs, &out_rows}) b->release();
+}
 
 // The density grid of class cls over the finite rows (on the host: a counting sort by cell), uploaded on the caller's
 // lane.  Unusable (-> tile path) when there is no finite row or the extent overflows.
-int build_grid(DeviceCtx* ctx, const m3d_knn* h, int cls, KnnGrid& G) {
-    const size_t n = h->n;
-    const double* p = h->host3.data();
+int knn_build_grid(DeviceCtx* ctx, const double* p, size_t n, int cls, KnnGrid& G) {
     std::vector<uint32_t> fin, out;
     double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
     for (size_t i = 0; i < n; ++i) {
@@ -199,6 +191,10 @@ int build_grid(DeviceCtx* ctx, const m3d_knn* h, int cls, KnnGrid& G) {
     G.usable = true;
     return M3D_OK;
 }
+
+}  // namespace m3d
+
+namespace {
 
 // What one call needs to put a chunk's results in place.
 struct KnnOut {
@@ -419,11 +415,11 @@ int m3d_knn_search(const m3d_knn* h, const double* queries, size_t m, int search
         const KnnGrid* G = nullptr;
         if (path == M3D_KNN_PATH_GRID) {
             m3d_knn* hm = const_cast<m3d_knn*>(h);   // the grids are built once, under their mutex
-            KnnGrid& g = hm->grid[grid_class((int)kout)];
+            KnnGrid& g = hm->grid[knn_grid_class((int)kout)];
             {
                 std::lock_guard<std::mutex> lock(hm->grid_mu);
                 if (!g.built)
-                    if (const int r = build_grid(ctx, h, grid_class((int)kout), g); r != M3D_OK) return r;
+                    if (const int r = knn_build_grid(ctx, h->host3.data(), h->n, knn_grid_class((int)kout), g); r != M3D_OK) return r;
             }
             if (g.usable) G = &g;
         }

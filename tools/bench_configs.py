@@ -747,3 +747,32 @@ if any(t in which for t in ("K1", "K2", "K3", "K4")) or ALL:
              ms_in_library=st["ms_total"], ms_device=st["ms_device"], path=st["path"], pair_dims=st["pair_dims"],
              pages=st["launches"] // 2, roofline=knn_roofline(st, 33), cpu_baseline=knn_cpu(data, q, 1000, 1000))
         ix.close()
+
+if "F1" in which or ALL:
+    # fragment preprocessing (PreProcessFragments): normals Hybrid(2 voxel, 30) + FPFH Hybrid(5 voxel, 100) on the three-surface
+    # cloud of the FPFH tests; cpu_baseline = the plain-C brute-force restatement (tests/cpp/fpfh_ref.c) under OpenMP on 16
+    # threads -- NOT Open3D's KD-tree implementation, which is not in the image
+    import tempfile
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import fpfh_ref_util as fpfh_util
+    for n, voxel in ((50_000, 0.02), (200_000, 0.01)):
+        pts, _ = fpfh_util.three_surface_cloud(n, seed=1)
+        for _ in range(2):
+            capi.preprocess_fragment(pts, voxel)
+        ts = []
+        for _ in range(5):
+            t0 = time.perf_counter()
+            st = capi.preprocess_fragment(pts, voxel, stats=True)[2]
+            ts.append(((time.perf_counter() - t0) * 1e3, st))
+        ms, st = sorted(ts, key=lambda t: t[0])[1]
+        cpu = None
+        if not NO_CPU:
+            os.environ.setdefault("OMP_NUM_THREADS", "16")
+            ref = fpfh_util.build_ref(tempfile.mkdtemp())
+            t0 = time.perf_counter()
+            ref.preprocess(pts, voxel)
+            cpu = {"ms": (time.perf_counter() - t0) * 1e3, "what": "tests/cpp/fpfh_ref.c: brute-force restatement, OpenMP, 16 threads"}
+        emit(f"F1 preprocess_fragment {n} points, voxel {voxel}", n=n, voxel=voxel, ms=ms, ms_in_library=st["ms_total"],
+             ms_device=st["ms_device"], ms_upload=st["ms_upload"], ms_search=st["ms_search"], ms_normals=st["ms_normals"],
+             ms_spfh=st["ms_spfh"], ms_fpfh=st["ms_fpfh"], pairs=st["pairs"], pairs_seen=st["pairs_seen"],
+             launches=st["launches"], cpu_baseline=cpu)
