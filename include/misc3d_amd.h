@@ -767,6 +767,10 @@ typedef struct m3d_config {
                                        over the host link -- and the host writes the indices, with up to 8 threads (the caller's + a
                                        process-wide pool of helpers, woken when the fit queues its compaction, spinning at most
                                        wait_spin_us); N >= 2: the same with at most N writers (<= 16); 0: the device writes the list */
+    int32_t mask_early;             /* [M3D_MASK_EARLY=0]   default 1: with list_mask, the compaction's counting launch stores the tile counts beside
+                                       its mask rows and the launch behind it announces them ("mask ready") before it folds the moments:
+                                       the host writes the list under that launch and waits for its completion word afterwards; 0: the
+                                       host waits for the completion word first (same list, same parameters) */
 } m3d_config;
 void m3d_get_config(m3d_config *out);
 int m3d_set_config(const m3d_config *in);

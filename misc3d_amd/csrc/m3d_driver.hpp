@@ -146,11 +146,14 @@ struct DeviceCtx {
     bool compaction_mask = false;
     PinBuf h_mask, h_tile_counts;
     uint32_t mask_seq = 0;   // ... whose last launch stores this value into h_sync word 1 (its completion: no signal_host_k)
+    // m3d_config.mask_early: ... and, before anything else, into h_sync word 2 ("mask ready": the mask and the tile counts are in
+    // host memory) -- refine() expands the list under that launch's fold of the moments and waits for word 1 afterwards
+    bool compaction_mask_early = false;
     // segmentation: asked by refine() right before it queues RefineModel's compaction -- given the inlier count the scoring
     // pass reported, where should the partition of the NON-inliers go (null: no partition in this pass)?
     const std::function<const m3d::PartitionOut*(int64_t)>* partition_hook = nullptr;
     PinBuf h_best;             // best minimal model of a fit on its way to the host (read after RefineModel's wait)
-    PinBuf h_sync;             // stream_wait_spin's completion word
+    PinBuf h_sync;             // stream_wait_spin's completion word [0], a mask compaction's completion [1] and "mask ready" [2] words
     PinBuf h_reg;              // registration: a chunk's pass flags / counts and sums on their way to the host (polled, not waited for)
     uint32_t sync_seq = 0;
     DevBuf surv_list;          // plane_bound_k's input: the hypotheses the keep kernels kept (its length: best_count word 6)

@@ -440,7 +440,8 @@ __global__ __launch_bounds__(256) void compact_count_k(CloudView c, const double
                                                         uint32_t* __restrict__ block_counts,
                                                         double* __restrict__ model_copy,
                                                         double* __restrict__ moment_partial,
-                                                        uint64_t* __restrict__ mask_host = nullptr) {
+                                                        uint64_t* __restrict__ mask_host = nullptr,
+                                                        uint32_t* __restrict__ counts_host = nullptr) {
     __shared__ uint32_t wsum[4];
     __shared__ unsigned long long wmask[kCompactTile / 64];
     double m[kModelStride];
@@ -488,7 +489,12 @@ __global__ __launch_bounds__(256) void compact_count_k(CloudView c, const double
     }
     if (lane == 0) wsum[wave] = cnt;
     __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    if (threadIdx.x == 0) {
+        const uint32_t mine = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+        block_counts[blockIdx.x] = mine;
+        // (m3d_config.mask_early: the tile's count goes to the host beside its mask row -- the expansion needs both and nothing else)
+        if (counts_host) counts_host[blockIdx.x] = mine;
+    }
     // the tile's 32 mask words as ONE 256-byte store of 32 consecutive lanes (a store per wave row would cross the host link
     // as a write of its own); the buffer holds whole tiles: words past n are zero
     if (mask_host && threadIdx.x < kCompactTile / 64)
@@ -792,17 +798,21 @@ __global__ __launch_bounds__(256) void compact_write_k(
 
 // The mask form's second launch (one workgroup): what compact_write_k's workgroup 0 and last tile delivered -- the folded
 // moment partials (fold_moment_partials: the same order, the same sums) and the total -- plus the tile counts, copied to the
-// host as one contiguous block.
+// host as one contiguous block (counts_host; null: compact_count_k has stored them itself).
+// ready_word (page-locked, may be null): receives done_seq FIRST -- the launch in front of this one has put the mask and the
+// tile counts into host memory, and that is all the expansion reads: the host writes the list under the fold below.  The order
+// is the kernel boundary's (the mask belongs to the launch before, the word to this one), nothing inside a launch.
 // done_word (page-locked, may be null): receives done_seq last, behind a system-scope fence -- the end of the compaction.
 __global__ __launch_bounds__(256) void compact_mask_tail_k(const uint32_t* __restrict__ block_counts, CompactTail tail,
-                                                            uint32_t* __restrict__ counts_host, uint32_t* done_word,
-                                                            uint32_t done_seq) {
+                                                            uint32_t* __restrict__ counts_host, uint32_t* ready_word,
+                                                            uint32_t* done_word, uint32_t done_seq) {
     __shared__ uint32_t wsum[4];
+    if (ready_word && threadIdx.x == 0) __hip_atomic_store(ready_word, done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t part = 0;
     for (uint32_t i = threadIdx.x; i < tail.nb; i += 256u) {
         const uint32_t v = block_counts[i];
-        counts_host[i] = v;
+        if (counts_host) counts_host[i] = v;
         part += v;
     }
     for (int off = 32; off > 0; off >>= 1) part += (uint32_t)__shfl_xor((int)part, off, 64);
@@ -824,7 +834,8 @@ static void launch_compact_kind(const CloudView& c, const double* model, double 
                                 uint32_t n_pad_out, const CompactScratch& scratch, uint32_t* total,
                                 hipStream_t s, double* model_copy, double* moment_partial, double* moment_out,
                                 uint64_t* out_idx_host, uint32_t* total_host, const PartitionOut* part,
-                                uint64_t* mask_host, uint32_t* counts_host, uint32_t* done_word, uint32_t done_seq) {
+                                uint64_t* mask_host, uint32_t* counts_host, uint32_t* done_word, uint32_t done_seq,
+                                uint32_t* ready_word) {
     const uint32_t nb = (c.n + kCompactTile - 1) / kCompactTile;
     if (nb == 0) {
         (void)hipMemsetAsync(total, 0, sizeof(uint32_t), s);
@@ -839,15 +850,16 @@ static void launch_compact_kind(const CloudView& c, const double* model, double 
     const uint32_t tag = scratch.tag;
     if (mask_host && counts_host && sums && !orig && !part && !one) {
         // the mask form: no list is written anywhere -- the host expands the mask (m3d_mask_expand.hpp)
+        // (ready_word: the counting launch stores the tile counts itself and the tail announces them before anything else)
         compact_count_k<KIND == 2 ? 0 : KIND, true><<<nb, 256, 0, s>>>(c, model, thr, 0, block_counts, model_copy, moment_partial,
-                                                                       mask_host);
+                                                                       mask_host, ready_word ? counts_host : nullptr);
         CompactTail tail;
         tail.total = total;
         tail.total_host = total_host;
         tail.moment_partial = moment_partial;
         tail.moment_out = moment_out;
         tail.nb = nb;
-        compact_mask_tail_k<<<1, 256, 0, s>>>(block_counts, tail, counts_host, done_word, done_seq);
+        compact_mask_tail_k<<<1, 256, 0, s>>>(block_counts, tail, ready_word ? nullptr : counts_host, ready_word, done_word, done_seq);
         return;
     }
     if (!one) {
@@ -904,16 +916,16 @@ void launch_compact(int kind, const CloudView& c, const double* model, double th
                     const CompactScratch& scratch, uint32_t* total, hipStream_t s, double* model_copy,
                     double* moment_partial, double* moment_out, uint64_t* out_idx_host, uint32_t* total_host,
                     const PartitionOut* part, uint64_t* mask_host, uint32_t* counts_host, uint32_t* done_word,
-                    uint32_t done_seq) {
+                    uint32_t done_seq, uint32_t* ready_word) {
     if (kind == 0)
         launch_compact_kind<0>(c, model, thr, mode, orig, out_idx, out_dist, ox, oy, oz, oorig, n_pad_out, scratch, total, s,
-                               model_copy, moment_partial, moment_out, out_idx_host, total_host, part, mask_host, counts_host, done_word, done_seq);
+                               model_copy, moment_partial, moment_out, out_idx_host, total_host, part, mask_host, counts_host, done_word, done_seq, ready_word);
     else if (kind == 1)
         launch_compact_kind<1>(c, model, thr, mode, orig, out_idx, out_dist, ox, oy, oz, oorig, n_pad_out, scratch, total, s,
-                               model_copy, moment_partial, moment_out, out_idx_host, total_host, part, mask_host, counts_host, done_word, done_seq);
+                               model_copy, moment_partial, moment_out, out_idx_host, total_host, part, mask_host, counts_host, done_word, done_seq, ready_word);
     else
         launch_compact_kind<2>(c, model, thr, mode, orig, out_idx, out_dist, ox, oy, oz, oorig, n_pad_out, scratch, total, s,
-                               model_copy, nullptr, nullptr, out_idx_host, total_host, part, nullptr, nullptr, nullptr, 0u);
+                               model_copy, nullptr, nullptr, out_idx_host, total_host, part, nullptr, nullptr, nullptr, 0u, nullptr);
 }
 
 // cluster = pcd_copy->SelectByIndex(inliers) (iterative_plane_segmentation.cpp:32): the points of an index list, AoS, in

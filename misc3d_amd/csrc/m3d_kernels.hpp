@@ -141,7 +141,9 @@ void launch_compact(int kind, const CloudView& c, const double* model, double th
                     uint32_t* counts_host = nullptr /* ... and the inliers per tile of kCompactTile points (page-locked, one word per
                                                        tile): the host expands the list (m3d_mask_expand.hpp) */,
                     uint32_t* done_word = nullptr /* the mask form: page-locked word that receives done_seq when it is complete */,
-                    uint32_t done_seq = 0);
+                    uint32_t done_seq = 0,
+                    uint32_t* ready_word = nullptr /* the mask form: page-locked word that receives done_seq as soon as the mask and
+                                                      the tile counts are in host memory, ahead of the moments and the total */);
 // moment_out layout: [0..2] sum s, [3..8] sum s s^T (xx,xy,xz,yy,yz,zz), [9..11] sum s |s|^2 (sphere), [12] inlier count;
 // s = p - c0, c0 = model[4..6] (plane: the hypothesis' first sample point) or model[0..2] (sphere: the minimal centre).
 constexpr int kFusedMomentDoubles = 16;

@@ -5,7 +5,10 @@
 // clones picked at load time), ~4x the rate of drawing word by word.  Every rank of a sharded fit walks the whole
 // stream (distributed.py), so this rate bounds the multi-GPU scaling of short fits.
 #pragma once
+#include <algorithm>
+#include <cstddef>
 #include <cstdint>
+#include <cstring>
 
 // host-only multiversioning (the driver sources also pass through the device compiler, which has no ifunc)
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -16,10 +19,25 @@
 
 namespace m3d {
 
+// fill()'s repeat test over a run of whole samples: word i of a run of M-word samples is compared with word i + j where both
+// lie in the same sample -- mask[M - 2][j - 1][i] is all ones there, zero elsewhere
+struct Mt19937RepeatMasks {
+    uint32_t mask[3][3][624];
+    Mt19937RepeatMasks() {
+        for (int m = 2; m <= 4; ++m)
+            for (int j = 1; j <= 3; ++j)
+                for (int i = 0; i < 624; ++i) mask[m - 2][j - 1][i] = (i % m) + j < m ? ~0u : 0u;
+    }
+};
+inline const Mt19937RepeatMasks& mt19937_repeat_masks() {
+    static const Mt19937RepeatMasks t;
+    return t;
+}
+
 struct Mt19937Mod {
     static constexpr int kN = 624;
     uint32_t mt[kN];
-    uint32_t out[kN];   // tempered outputs of the current block, already reduced mod d
+    uint32_t out[kN + 4] = {};   // tempered outputs of the current block, already reduced mod d (+ 4: run_has_repeat's masked reads)
     int pos = kN;       // next unread entry of out (kN: block exhausted)
     uint32_t d = 0, magic = 0, shift = 0;
 
@@ -62,28 +80,71 @@ struct Mt19937Mod {
         if (pos == kN) refill();
         return out[pos++];
     }
-    // m distinct indices per hypothesis, duplicates redrawn (utils.h:88-95)
+    // does any of the len / m whole samples at p (m words each, len <= kN) hold a repeat?  Plain loops over arrays, like refill's:
+    // the words beyond a sample's end are read and masked away (at most m - 1 words past the run: out's padding)
+    M3D_HOST_SIMD_CLONES static bool run_has_repeat(const uint32_t* p, int len, int m, const Mt19937RepeatMasks& t) {
+        const uint32_t *m1 = t.mask[m - 2][0], *m2 = t.mask[m - 2][1], *m3 = t.mask[m - 2][2];
+        uint32_t acc = 0;
+        if (m == 2) {
+            for (int i = 0; i < len; ++i) acc |= (0u - (uint32_t)(p[i] == p[i + 1])) & m1[i];
+        } else if (m == 3) {
+            for (int i = 0; i < len; ++i)
+                acc |= ((0u - (uint32_t)(p[i] == p[i + 1])) & m1[i]) | ((0u - (uint32_t)(p[i] == p[i + 2])) & m2[i]);
+        } else {
+            for (int i = 0; i < len; ++i)
+                acc |= ((0u - (uint32_t)(p[i] == p[i + 1])) & m1[i]) | ((0u - (uint32_t)(p[i] == p[i + 2])) & m2[i]) |
+                       ((0u - (uint32_t)(p[i] == p[i + 3])) & m3[i]);
+        }
+        return acc != 0;
+    }
+    // m distinct indices per hypothesis, duplicates redrawn (utils.h:88-95).  The samples that lie wholly inside the current block
+    // are accepted as ONE run -- a copy and run_has_repeat -- when none of them holds a repeat (the usual case: a repeat among three
+    // draws from a million points happens once in 300 000 samples); a run that holds one, and the sample across a block's end, go
+    // through the scalar code below sample by sample, up to the next refill: the stream and the table are the scalar ones.
     template <int M>
     void fill(uint32_t* s, size_t n_hyp) {
-        for (size_t h = 0; h < n_hyp; ++h, s += M) {
-            if (pos + M <= kN) {   // the whole sample sits in the current block: accept it if it has no repeat
-                const uint32_t* p = out + pos;
-                bool distinct = true;
-                for (int k = 1; k < M; ++k)
-                    for (int j = 0; j < k; ++j) distinct = distinct && (p[k] != p[j]);
-                if (distinct) {
-                    for (int k = 0; k < M; ++k) s[k] = p[k];
-                    pos += M;
-                    continue;
-                }
+        static_assert(M >= 2 && M <= 4, "run_has_repeat's masks");
+        const Mt19937RepeatMasks& masks = mt19937_repeat_masks();
+        size_t h = 0;
+        while (h < n_hyp) {
+            const size_t run = std::min<size_t>((size_t)(kN - pos) / M, n_hyp - h);
+            if (run && !run_has_repeat(out + pos, (int)(run * M), M, masks)) {
+                std::memcpy(s, out + pos, sizeof(uint32_t) * run * M);
+                pos += (int)(run * M);
+                s += run * M;
+                h += run;
+                continue;
             }
-            int valid = 0;
-            while (valid < M) {
-                const uint32_t idx = next();
-                bool dup = false;
-                for (int k = 0; k < valid; ++k) dup = dup || (s[k] == idx);
-                if (!dup) s[valid++] = idx;
+            for (const size_t stop = h + std::max<size_t>(run, 1); h < stop;) {
+                const int before = pos;
+                fill_one<M>(s);
+                ++h;
+                s += M;
+                if (pos < before) break;   // (refilled: the new block's samples are tried as a run again)
             }
+        }
+    }
+
+    // one sample by the reference's loop (the scalar stream)
+    template <int M>
+    void fill_one(uint32_t* s) {
+        if (pos + M <= kN) {   // the whole sample sits in the current block: accept it if it has no repeat
+            const uint32_t* p = out + pos;
+            bool distinct = true;
+            for (int k = 1; k < M; ++k)
+                for (int j = 0; j < k; ++j) distinct = distinct && (p[k] != p[j]);
+            if (distinct) {
+                for (int k = 0; k < M; ++k) s[k] = p[k];
+                pos += M;
+                return;
+            }
+        }
+        int valid = 0;
+        while (valid < M) {
+            const uint32_t idx = next();
+            bool dup = false;
+            for (int k = 0; k < valid; ++k) dup = dup || (s[k] == idx);
+            if (!dup) s[valid++] = idx;
         }
     }
 };

@@ -325,6 +325,7 @@ int issue_refine_compaction(DeviceCtx* ctx, const CloudView& flag_view, const ui
     }
     // the list as a bit mask: the list has no consumer on the device (creation-order view, no partition, no device
     // destination) and refine() is the one to expand it (not a deferred RefineModel, which never waits)
+    const bool early = config().mask_early != 0;   // the tail announces the mask before it folds the moments (h_sync word 2)
     const bool mask = allow_mask && fused && idx_host && nb && !orig_dev && !part && !ctx->idx_out_override &&
                       !ctx->defer_refine && config().list_mask != 0;
     if (mask) {
@@ -334,7 +335,7 @@ int issue_refine_compaction(DeviceCtx* ctx, const CloudView& flag_view, const ui
             RESERVE(ctx->h_sync, 64);
             std::memset(ctx->h_sync.p, 0, 64);
         }
-        if (++ctx->mask_seq == 0) ++ctx->mask_seq;   // (never 0: the word's initial value)
+        if (++ctx->mask_seq == 0) ++ctx->mask_seq;   // (never 0: the words' initial value)
         MaskPool::get().arm();   // (the helpers wake under the device work still ahead)
     }
     launch_compact(kind, flag_view, model_dev, thr, 0, orig_dev,
@@ -344,15 +345,18 @@ int issue_refine_compaction(DeviceCtx* ctx, const CloudView& flag_view, const ui
                    fused ? ctx->moment_partial.as<double>() : nullptr, fused ? h_moments_at(ctx) : nullptr,
                    idx_host, static_cast<uint32_t*>(total_host) /* pinned: the kernel writes the total there itself */, part,
                    mask ? ctx->h_mask.as<uint64_t>() : nullptr, mask ? ctx->h_tile_counts.as<uint32_t>() : nullptr,
-                   mask ? ctx->h_sync.as<uint32_t>() + 1 : nullptr, ctx->mask_seq);
+                   mask ? ctx->h_sync.as<uint32_t>() + 1 : nullptr, ctx->mask_seq,
+                   mask && early ? ctx->h_sync.as<uint32_t>() + 2 : nullptr);
     ctx->compaction_fused = fused;
     ctx->compaction_idx_host = idx_host;
     ctx->compaction_mask = mask;
+    ctx->compaction_mask_early = mask && early;
     return M3D_OK;
 }
 
-// the list of a mask compaction into the caller's page-locked array, once the stream is past it; false: the mask disagrees
-// with `expected` or with its own counts (the caller redoes RefineModel with the device writing the list)
+// the list of a mask compaction into the caller's page-locked array, once the mask and the tile counts have arrived (the
+// completion word, or the "mask ready" word of m3d_config.mask_early); false: the mask disagrees with `expected` or with its
+// own counts (the caller redoes RefineModel with the device writing the list).  Nothing is stored outside dst[0, expected).
 static bool expand_compaction_mask(DeviceCtx* ctx, uint32_t n, uint32_t expected, uint64_t* dst) {
     const uint32_t nb = (n + kCompactTile - 1) / kCompactTile;
     const uint32_t* counts = ctx->h_tile_counts.as<const uint32_t>();
@@ -430,10 +434,20 @@ int refine(DeviceCtx* ctx, const CloudView& flag_view, const CloudView& gather_v
         // everything RefineModel reads is complete at ev_compact when the moments rode on the compaction (or no fit is
         // due): what the hook queued behind it (segmentation: the removal of these inliers, tens of microseconds of
         // kernels) is not waited for -- the caller goes on preparing the next round under it
+        bool expanded = false, expand_ok = true;   // (mask_early: the list is written before the completion word is waited for)
         if (hooked && (have_moments || !need_fit_e)) {
             HIPCHK(hipEventSynchronize(ctx->ev_compact));
         } else if (ctx->compaction_mask && !hooked) {
             // nothing of RefineModel follows the compaction: its last launch stored the completion word itself
+            if (ctx->compaction_mask_early && ni_e) {
+                // ... and the "mask ready" word first: the mask and the tile counts came with the launch before it, and the list
+                // needs nothing else -- it is written while that launch folds the moments; the total is checked further down
+                // (here: the sum of the tile counts against the expectation, before the first store)
+                const int erc = word_wait_spin(ctx, ctx->h_sync.as<uint32_t>() + 2, ctx->mask_seq);
+                if (erc != M3D_OK) return erc;
+                expand_ok = expand_compaction_mask(ctx, n, ni_e, reinterpret_cast<uint64_t*>(inliers));
+                expanded = true;
+            }
             const int wrc = word_wait_spin(ctx, ctx->h_sync.as<uint32_t>() + 1, ctx->mask_seq);
             if (wrc != M3D_OK) return wrc;
         } else {
@@ -449,7 +463,8 @@ int refine(DeviceCtx* ctx, const CloudView& flag_view, const CloudView& gather_v
         std::memcpy(&ni_chk, h_total, 4);
         // (a mask compaction: the host writes the list now -- the total it checks is the sum of the tile counts)
         if (ni_chk != ni_e ||   // should not happen: redo in the order that does not rely on the expectation
-            (ctx->compaction_mask && ni_e && !expand_compaction_mask(ctx, n, ni_e, reinterpret_cast<uint64_t*>(inliers))))
+            (ctx->compaction_mask && ni_e &&
+             !(expanded ? expand_ok : expand_compaction_mask(ctx, n, ni_e, reinterpret_cast<uint64_t*>(inliers)))))
             return refine(ctx, flag_view, gather_view, orig_dev, kind, thr, model_dev, params_host, inliers, n_inliers,
                           general_fit_ok, -1, nullptr, nullptr, nullptr);
         *n_inliers = ni_e;
