@@ -9,6 +9,8 @@
 
 #include <array>
 #include <cstddef>
+#include <stdexcept>
+#include <string>
 #include <vector>
 
 #ifdef MISC3D_WITH_OPEN3D
@@ -24,18 +26,21 @@ using Matrix4d = std::array<double, 16>;  // row-major
 struct PointCloud {
     std::vector<Vector3d> points_;
     std::vector<Vector3d> normals_;
+    std::vector<Vector3d> colors_;   // Open3D's: RGB in [0, 1], one per point or none
     PointCloud() = default;
     explicit PointCloud(std::vector<Vector3d> points) : points_(std::move(points)) {}
     bool HasPoints() const { return !points_.empty(); }
     bool HasNormals() const { return !points_.empty() && normals_.size() == points_.size(); }
-    // open3d::geometry::PointCloud::SelectByIndex: order preserved, normals follow
+    bool HasColors() const { return !points_.empty() && colors_.size() == points_.size(); }
+    // open3d::geometry::PointCloud::SelectByIndex: order preserved, normals and colours follow
     PointCloud SelectByIndex(const std::vector<size_t>& indices, bool invert = false) const {
         PointCloud out;
-        const bool nrm = HasNormals();
+        const bool nrm = HasNormals(), col = HasColors();
         if (!invert) {
             for (size_t i : indices) {
                 out.points_.push_back(points_[i]);
                 if (nrm) out.normals_.push_back(normals_[i]);
+                if (col) out.colors_.push_back(colors_[i]);
             }
         } else {
             std::vector<char> mask(points_.size(), 0);
@@ -44,10 +49,16 @@ struct PointCloud {
                 if (!mask[i]) {
                     out.points_.push_back(points_[i]);
                     if (nrm) out.normals_.push_back(normals_[i]);
+                    if (col) out.colors_.push_back(colors_[i]);
                 }
         }
         return out;
     }
+    // open3d::geometry::PointCloud::VoxelDownSample on the device (m3d_voxel_down_sample): the per-voxel means of points,
+    // normals and colours bit for bit the reference's (members added in ascending index); the voxels come in ascending
+    // order of their lowest member index (the reference's order is that of an unordered_map).  Defined in
+    // the end of this header.  Errors throw std::runtime_error with the reference's text.
+    PointCloud VoxelDownSample(double voxel_size, int device = 0) const;
 };
 
 struct CloudView {
@@ -103,6 +114,32 @@ inline PinnedScratch& host_scratch(int which) {   // 0: index lists, 1: gathered
     return s[which & 1];
 }
 }  // namespace detail
+namespace detail {
+// the rows of level l after an m3d_voxel_down_sample* call that wrote m of them into clouds sized for n
+inline void voxel_shrink(PointCloud& pc, size_t m, bool nrm, bool col) {
+    pc.points_.resize(m);
+    pc.normals_.resize(nrm ? m : 0);
+    pc.colors_.resize(col ? m : 0);
+}
+}  // namespace detail
+
+inline PointCloud PointCloud::VoxelDownSample(double voxel_size, int device) const {
+    const size_t n = points_.size();
+    const bool nrm = HasNormals(), col = HasColors();
+    PointCloud out;
+    out.points_.resize(n);
+    if (nrm) out.normals_.resize(n);
+    if (col) out.colors_.resize(n);
+    size_t m = 0;
+    const int rc = m3d_voxel_down_sample(n ? points_[0].data() : nullptr, nrm ? normals_[0].data() : nullptr,
+                                         col ? colors_[0].data() : nullptr, n, voxel_size, device,
+                                         n ? out.points_[0].data() : nullptr, nrm ? out.normals_[0].data() : nullptr,
+                                         col ? out.colors_[0].data() : nullptr, nullptr, nullptr, &m, nullptr);
+    if (rc < 0) throw std::runtime_error(std::string("[Misc3D Error] ") + m3d_last_error());   // (logging.h's LogError)
+    detail::voxel_shrink(out, m, nrm, col);
+    return out;
+}
+
 inline void ReleaseHostScratch() {
     detail::host_scratch(0).release();
     detail::host_scratch(1).release();

@@ -40,6 +40,7 @@ extern "C" {
 #define M3D_ERR_INVALID_ARG (-5) /* null pointer / out-of-range index / N >= 2^31 */
 #define M3D_ERR_DEVICE (-6) /* no HIP device, HIP runtime error, or out of device memory */
 #define M3D_ERR_INTERNAL (-7) /* self-check failed (counts from the scoring kernel and the refine pass disagree) */
+#define M3D_ERR_NON_FINITE (-8) /* m3d_voxel_down_sample: a point with a non-finite coordinate (the reference's int(floor(..)) is undefined) */
 
 enum m3d_model_kind { M3D_PLANE = 0, M3D_SPHERE = 1, M3D_CYLINDER = 2 };
 
@@ -321,6 +322,51 @@ int m3d_farthest_point_sampling(const double *xyz, size_t n, int64_t num_samples
  * index outside [0, n) (the reference reads outside the cloud): M3D_ERR_INVALID_ARG. */
 int m3d_crop_roi_indices(size_t n, int width, int height, int tl_x, int tl_y, int br_x, int br_y, size_t *indices,
                          size_t *k);
+
+/* ---- open3d::geometry::PointCloud::VoxelDownSample (the first call of every example and of MultiScaleICP) --------- */
+/* [RECALL] Open3D 0.15.1 PointCloud::VoxelDownSample / AccumulatedPoint, restated (tests/cpp/voxel_ref.c is the checker):
+ *   1. voxel_size <= 0 or NaN: M3D_ERR_INVALID_ARG "[VoxelDownSample] voxel_size <= 0."
+ *   2. min_bound / max_bound = the coordinate-wise min / max of the points; vmin = min_bound - voxel_size * 0.5,
+ *      vmax = max_bound + voxel_size * 0.5; voxel_size * INT_MAX < max_c (vmax_c - vmin_c): M3D_ERR_INVALID_ARG
+ *      "[VoxelDownSample] voxel_size is too small."
+ *   3. voxel of point i, per coordinate: int(floor((p_c - vmin_c) / voxel_size)) -- one subtraction, one IEEE division
+ *      (not a multiplication by a reciprocal: that moves points that lie on voxel faces), floor, int.
+ *   4. per voxel the sums start at +0.0 and the members are added in ascending point index, one rounded fp64 addition
+ *      per coordinate; normals likewise except that a normal with a NaN component is not added (the point still counts);
+ *      colours likewise, none left out.
+ *   5. out = sum / double(count) for point, normal (not re-normalised; the divisor counts the skipped ones) and colour.
+ *   6. ORDER (ours; the reference iterates an unordered_map): voxels in ascending order of their lowest member index.
+ *   7. deviations: a point with a non-finite coordinate is M3D_ERR_NON_FINITE, the message names the lowest such index
+ *      (the reference's int(floor(NaN)) is undefined); a voxel_size of +inf and bounds whose vmin / vmax overflow are
+ *      M3D_ERR_INVALID_ARG (the reference divides inf by inf); n == 0: M3D_OK, *m = 0.
+ * The output equals that restatement bit for bit, in that order.  normals / colors: n x 3 or NULL (then their outputs
+ * are not written and may be NULL).  out_xyz / out_normals / out_colors: capacity n rows; *m = the rows written.
+ * out_first_index (capacity n, may be NULL): the lowest member index of output row j, strictly ascending.  point_to_voxel
+ * (n, may be NULL): the output row of point i (what VoxelDownSampleAndTrace tells).  n > 2^30: M3D_ERR_INVALID_ARG.
+ * On an error *m = 0 and the outputs are unspecified.  stats may be NULL.  Re-entrant: concurrent calls take lanes. */
+#define M3D_VOXEL_PATH_PACKED 1 /* the three voxel indices fit 63 bits together: 64-bit keys in the hash table */
+#define M3D_VOXEL_PATH_WIDE 2   /* any extent the reference accepts (3 x 31 bits): the table holds a member's index */
+typedef struct m3d_voxel_stats {
+    double ms_total;     /* the call, host clock */
+    double ms_upload;    /* the cloud's host-to-device copies, HIP events on the lane's stream */
+    double ms_device;    /* bounds, keys, grouping, ordered sums of every level (incl. the round trips for the bounds and m) */
+    double ms_download;  /* the levels' rows (and trace arrays) device-to-host */
+    uint64_t n_voxels;   /* rows written, all levels */
+    int32_t path;        /* M3D_VOXEL_PATH_* of the last level, 0 = no device work */
+    int32_t sort_passes; /* 8-bit passes of the stable sort, all levels */
+} m3d_voxel_stats;
+int m3d_voxel_down_sample(const double *xyz, const double *normals, const double *colors, size_t n, double voxel_size,
+                          int device, double *out_xyz, double *out_normals, double *out_colors, size_t *out_first_index,
+                          size_t *point_to_voxel, size_t *m, m3d_voxel_stats *stats);
+/* n_levels voxel sizes, every level computed FROM THE ORIGINAL CLOUD (MultiScaleICP's shape, src/pipeline.cpp:937-938,
+ * {v, v/2, v/4}): one upload, the bounds once.  out_xyz[l] .. point_to_voxel[l]: level l's arrays as above (the arrays of
+ * pointers out_normals / out_colors / out_first_index / point_to_voxel may be NULL, as may their entries); m[l] = level
+ * l's rows.  Every level equals the single call at that size bit for bit.  Every voxel size is checked before any
+ * level runs. */
+int m3d_voxel_down_sample_multi(const double *xyz, const double *normals, const double *colors, size_t n,
+                                const double *voxel_sizes, size_t n_levels, int device, double *const *out_xyz,
+                                double *const *out_normals, double *const *out_colors, size_t *const *out_first_index,
+                                size_t *const *point_to_voxel, size_t *m, m3d_voxel_stats *stats);
 
 /* ---- misc3d::segmentation::ProximityExtractor::Segment, src/proximity_extraction.cpp:51-190 ----------------------- */
 /* The clusters are the connected components of the graph with an edge i - j when j is in i's radius neighbourhood

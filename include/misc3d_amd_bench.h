@@ -75,6 +75,11 @@ int m3d_bench_fps_force_path(int path);
  * depend on it. */
 int m3d_bench_knn_force_path(int path);
 
+/* MEASUREMENT / TEST hook (tests/test_gpu_voxel.py): the key path of every later m3d_voxel_down_sample* in the process --
+ * 0 = by the key widths (the default), M3D_VOXEL_PATH_PACKED (where the keys fit 63 bits, else wide), M3D_VOXEL_PATH_WIDE.
+ * The result does not depend on it. */
+int m3d_bench_voxel_force_path(int path);
+
 /* TEST hook (tests/test_proximity.py): the cut-offs m3d_proximity_segment derives on the host for an evaluator
  * (m3d_proximity_fp.hpp) -- out[0] = d2_cut (Distance: dist < t <=> d2 < d2_cut; DistanceNormals: dist >= t <=>
  * d2 >= d2_cut), out[1..4] = lo1, hi1, lo2, hi2 (the angle test accepts dot exactly on [lo1, hi1] u [lo2, hi2]). */

@@ -15,6 +15,7 @@ Drop-in for the reference's python API on this path (module layout of python/py_
     normals  = m3d.features.estimate_normals(pcd, ("hybrid", 0.1, 30), orient_to=(0, 0, 0))   # unorganised clouds
     fpfh     = m3d.features.compute_fpfh_feature(pcd, ("hybrid", 0.25, 100))                  # (33, N), Open3D's Feature.data
     normals, fpfh = m3d.reconstruction.preprocess_fragment(fragment, voxel_size)              # pipeline.cpp:379-401
+    points, normals, colors = m3d.preprocessing.voxel_down_sample(pcd, 0.005)   # Open3D's first call of every example
     index    = m3d.preprocessing.farthest_point_sampling(pcd, 1000)
     roi      = m3d.preprocessing.crop_roi_pointcloud(pcd, (tl_x, tl_y, br_x, br_y), (width, height))
     normals  = m3d.common.estimate_normals(pcd, (848, 480), 3)
@@ -233,7 +234,8 @@ reconstruction = _Reconstruction()
 
 
 class _Preprocessing:
-    """misc3d.preprocessing (python/py_preprocessing.cpp): farthest_point_sampling, crop_roi_pointcloud, project_into_plane"""
+    """misc3d.preprocessing (python/py_preprocessing.cpp): farthest_point_sampling, crop_roi_pointcloud, project_into_plane;
+    and Open3D's voxel_down_sample, the call every example of the reference starts with (+ its multi-level form)"""
 
     _FPS_INFO = ("This method has been added to Open3D official branch and hence it will be deprecated in the future.")
 
@@ -279,6 +281,60 @@ class _Preprocessing:
                 if len(v) == len(pts):
                     setattr(pcd, attr, _o3d.utility.Vector3dVector(v[idx]))
         return pcd
+
+    @staticmethod
+    def _cloud_arrays(points, normals, colors):
+        """points: (N, 3) array or an object with .points (then its .normals / .colors are taken unless given)"""
+        import numpy as _np
+        if normals is None:
+            normals = getattr(points, "normals", None)
+        if colors is None:
+            colors = getattr(points, "colors", None)
+        pts = _xyz(points)
+        attrs = []
+        for a in (normals, colors):
+            if a is not None:
+                a = _np.asarray(a, dtype=_np.float64).reshape(-1, 3)
+                if len(a) != len(pts) or len(a) == 0:   # (Open3D's HasNormals / HasColors)
+                    a = None
+            attrs.append(a)
+        return pts, attrs[0], attrs[1]
+
+    @staticmethod
+    def _voxel_tuple(level, trace):
+        import numpy as _np
+        out = (level["points"], level["normals"], level["colors"])
+        if trace:
+            out += (level["first_index"].astype(_np.int64), level["point_to_voxel"].astype(_np.int64))
+        return out
+
+    @staticmethod
+    def voxel_down_sample(points, voxel_size, normals=None, colors=None, *, trace=False, device=0):
+        """open3d PointCloud.voxel_down_sample(voxel_size) on the device, bit for bit the per-voxel means of the reference
+        (members added in ascending index).  The voxels come in ascending order of their lowest member index (the
+        reference's order is that of an unordered_map).  points: (N, 3) array or an object with .points / .normals /
+        .colors.  Returns (points, normals, colors), each (M, 3) or None; with trace=True also first_index (M,) -- the
+        lowest member of every voxel -- and point_to_voxel (N,) -- the output row of every input point (what
+        voxel_down_sample_and_trace tells), both int64."""
+        from . import capi as _capi
+        pts, nrm, col = _Preprocessing._cloud_arrays(points, normals, colors)
+        try:
+            level = _capi.voxel_down_sample(pts, float(voxel_size), nrm, col, device, trace)
+        except _capi.M3DError as e:
+            raise RuntimeError(str(e)) from e
+        return _Preprocessing._voxel_tuple(level, trace)
+
+    @staticmethod
+    def voxel_down_sample_multi(points, voxel_sizes, normals=None, colors=None, *, trace=False, device=0):
+        """voxel_down_sample at several sizes, every level FROM THE ORIGINAL CLOUD (MultiScaleICP's {v, v/2, v/4},
+        src/pipeline.cpp:937-938) with one upload: a list of voxel_down_sample's tuples, each bit for bit the single call's."""
+        from . import capi as _capi
+        pts, nrm, col = _Preprocessing._cloud_arrays(points, normals, colors)
+        try:
+            levels = _capi.voxel_down_sample_multi(pts, [float(v) for v in voxel_sizes], nrm, col, device, trace)
+        except _capi.M3DError as e:
+            raise RuntimeError(str(e)) from e
+        return [_Preprocessing._voxel_tuple(level, trace) for level in levels]
 
     @staticmethod
     def project_into_plane(pc):

@@ -33,6 +33,7 @@ MODEL_STRIDE = 8
 OK, FALSE = 1, 0
 ERR_PROBABILITY, ERR_TOO_FEW_POINTS, ERR_NO_NORMALS, ERR_SIZE_MISMATCH = -1, -2, -3, -4
 ERR_INVALID_ARG, ERR_DEVICE, ERR_INTERNAL = -5, -6, -7
+ERR_NON_FINITE = -8
 
 
 class M3DError(RuntimeError):
@@ -164,6 +165,12 @@ def lib():
         L.m3d_crop_roi_indices.argtypes = [C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                            C.c_void_p]
         L.m3d_bench_fps_force_path.argtypes = [C.c_int]
+        L.m3d_voxel_down_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.m3d_voxel_down_sample_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                  C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]
+        L.m3d_bench_voxel_force_path.argtypes = [C.c_int]
         L.m3d_proximity_segment.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_double, C.c_void_p,
                                             C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p]
@@ -1095,6 +1102,94 @@ def crop_roi_indices(n, roi, shape):
 def fps_force_path(path: int):
     """measurement / test hook m3d_bench_fps_force_path: 0 = by size, FPS_PATH_SINGLE / _PRUNED / _DENSE"""
     _check(lib().m3d_bench_fps_force_path(int(path)))
+
+
+VOXEL_PATH_PACKED, VOXEL_PATH_WIDE = 1, 2
+
+
+class VoxelStats(C.Structure):
+    """m3d_voxel_stats"""
+    _fields_ = [("ms_total", C.c_double), ("ms_upload", C.c_double), ("ms_device", C.c_double), ("ms_download", C.c_double),
+                ("n_voxels", C.c_uint64), ("path", C.c_int32), ("sort_passes", C.c_int32)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def _voxel_inputs(xyz, normals, colors):
+    xyz = _f64(xyz).reshape(-1, 3)
+    normals = _f64(normals).reshape(-1, 3) if normals is not None else None
+    colors = _f64(colors).reshape(-1, 3) if colors is not None else None
+    for a in (normals, colors):
+        if a is not None and len(a) != len(xyz):
+            raise ValueError("normals / colors must have one row per point")
+    return xyz, normals, colors
+
+
+def _ptr_array(arrays):
+    """a C array of the arrays' addresses (double *const *, size_t *const *), or None when every entry is None"""
+    if all(a is None for a in arrays):
+        return None
+    return (C.c_void_p * len(arrays))(*[_addr(a) for a in arrays])
+
+
+def voxel_down_sample_multi(xyz, voxel_sizes, normals=None, colors=None, device=0, trace=False, stats=False):
+    """m3d_voxel_down_sample_multi: every level from the original cloud -> a list of dicts (points, normals, colors, and
+    with trace=True first_index, point_to_voxel as uint64), and the stats dict when stats=True."""
+    xyz, normals, colors = _voxel_inputs(xyz, normals, colors)
+    sizes = np.ascontiguousarray(voxel_sizes, dtype=np.float64).reshape(-1)
+    n, L = len(xyz), len(sizes)
+    cap = max(n, 1)
+    o_xyz = [np.empty((cap, 3)) for _ in range(L)]
+    o_nrm = [np.empty((cap, 3)) if normals is not None else None for _ in range(L)]
+    o_col = [np.empty((cap, 3)) if colors is not None else None for _ in range(L)]
+    o_first = [np.zeros(cap, dtype=np.uint64) if trace else None for _ in range(L)]
+    o_p2v = [np.zeros(cap, dtype=np.uint64) if trace else None for _ in range(L)]
+    m = np.zeros(max(L, 1), dtype=np.uint64)
+    st = VoxelStats()
+    _check(lib().m3d_voxel_down_sample_multi(_p(xyz), _p(normals), _p(colors), n, _p(sizes), L, device, _ptr_array(o_xyz),
+                                             _ptr_array(o_nrm), _ptr_array(o_col), _ptr_array(o_first), _ptr_array(o_p2v),
+                                             _p(m), C.cast(C.byref(st), C.c_void_p)))
+    levels = []
+    for l in range(L):
+        k = int(m[l])
+        d = {"points": o_xyz[l][:k].copy(), "normals": o_nrm[l][:k].copy() if normals is not None else None,
+             "colors": o_col[l][:k].copy() if colors is not None else None}
+        if trace:
+            d["first_index"] = o_first[l][:k].copy()
+            d["point_to_voxel"] = o_p2v[l][:n].copy()
+        levels.append(d)
+    return (levels, st.asdict()) if stats else levels
+
+
+def voxel_down_sample(xyz, voxel_size, normals=None, colors=None, device=0, trace=False, stats=False):
+    """m3d_voxel_down_sample -> dict(points, normals, colors[, first_index, point_to_voxel]): the per-voxel means in
+    ascending order of the voxels' lowest member index, and the stats dict when stats=True."""
+    xyz, normals, colors = _voxel_inputs(xyz, normals, colors)
+    n = len(xyz)
+    cap = max(n, 1)
+    o_xyz = np.empty((cap, 3))
+    o_nrm = np.empty((cap, 3)) if normals is not None else None
+    o_col = np.empty((cap, 3)) if colors is not None else None
+    o_first = np.zeros(cap, dtype=np.uint64) if trace else None
+    o_p2v = np.zeros(cap, dtype=np.uint64) if trace else None
+    m = C.c_size_t(0)
+    st = VoxelStats()
+    _check(lib().m3d_voxel_down_sample(_p(xyz), _p(normals), _p(colors), n, float(voxel_size), device, _p(o_xyz), _p(o_nrm),
+                                       _p(o_col), _p(o_first), _p(o_p2v), C.cast(C.byref(m), C.c_void_p),
+                                       C.cast(C.byref(st), C.c_void_p)))
+    k = m.value
+    d = {"points": o_xyz[:k].copy(), "normals": o_nrm[:k].copy() if normals is not None else None,
+         "colors": o_col[:k].copy() if colors is not None else None}
+    if trace:
+        d["first_index"] = o_first[:k].copy()
+        d["point_to_voxel"] = o_p2v[:n].copy()
+    return (d, st.asdict()) if stats else d
+
+
+def voxel_force_path(path: int):
+    """measurement / test hook m3d_bench_voxel_force_path: 0 = by the key widths, VOXEL_PATH_PACKED / _WIDE"""
+    _check(lib().m3d_bench_voxel_force_path(int(path)))
 
 
 PROX_DISTANCE, PROX_NORMALS, PROX_DISTANCE_NORMALS = 1, 2, 3

@@ -9,6 +9,7 @@ bench.py); these lines feed DESIGN.md section 6 and check that the full sizes ru
   S1 - S4 ProximityExtractor.segment: the reference example's shape, the raw golden PLY at r = 0.01, 1 M and 10 M synthetic
   K1 - K4 KNearestSearch: 200k x 200k x 33 k=10 batched, 1 000 single-query calls, 1 M x 3 k=30 (grid, tile A/B),
           50k x 33 k=1000 (select)
+  V1 - V3 voxel_down_sample: the 1 M-point bench scene at 0.005 / 0.02 of its extent, and the three-level call
 """
 import json
 import os
@@ -776,3 +777,62 @@ if "F1" in which or ALL:
              ms_device=st["ms_device"], ms_upload=st["ms_upload"], ms_search=st["ms_search"], ms_normals=st["ms_normals"],
              ms_spfh=st["ms_spfh"], ms_fpfh=st["ms_fpfh"], pairs=st["pairs"], pairs_seen=st["pairs_seen"],
              launches=st["launches"], cpu_baseline=cpu)
+
+if any(t in which for t in ("V1", "V2", "V3")) or ALL:
+    # misc3d.preprocessing.voxel_down_sample from host arrays: the 1 M-point scene bench.py fits (synth.plane_cloud_c2) at voxel
+    # sizes 0.005 (V1) and 0.02 (V2) of the scene's largest extent, and the three-level call {v, v/2, v/4} from v = 0.02 (V3).
+    # Median of 25 calls after 5 warm-up calls; the split upload / device / download is m3d_voxel_stats' (HIP events on the
+    # lane's stream); spread = (min, max) of the wall clock.
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from voxel_ref_util import build_ref as voxel_build_ref
+
+    pts = np.ascontiguousarray(synth.plane_cloud_c2(1_000_000, seed=2))
+    scale = float((pts.max(axis=0) - pts.min(axis=0)).max())
+    HOST_LINK_GBS = 64.0   # PCIe 5 x16, one direction, nominal
+
+    def voxel_cpu(sizes):
+        """tests/cpp/voxel_ref.c (gcc -O2 -ffp-contract=off): the reference's algorithm, one thread and a hash map -- x1 core, as
+        the reference runs it; the whole call, the fastest of 3"""
+        if NO_CPU:
+            return None
+        ref = voxel_build_ref(tempfile.mkdtemp())
+        ts = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            for s in sizes:
+                ref(pts, s)
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return {"value": min(ts), "unit": "ms", "cores": 1, "kind": "port", "flags": "-O2 -ffp-contract=off",
+                "note": "x1 core, as the reference runs it (one serial pass over a hash map per level)"}
+
+    for tag, sizes in (("V1", [0.005 * scale]), ("V2", [0.02 * scale]), ("V3", [0.02 * scale, 0.01 * scale, 0.005 * scale])):
+        if not (tag in which or ALL):
+            continue
+        call = (lambda: capi.voxel_down_sample_multi(pts, sizes, stats=True)) if len(sizes) > 1 else \
+               (lambda: capi.voxel_down_sample(pts, sizes[0], stats=True))
+        for _ in range(5):
+            call()
+        runs = []
+        for _ in range(25):
+            t0 = time.perf_counter()
+            _, st = call()
+            runs.append(((time.perf_counter() - t0) * 1e3, st))
+        runs.sort(key=lambda r: r[0])
+        ms, st = runs[len(runs) // 2]
+        med = lambda k: float(np.median([r[1][k] for r in runs]))   # noqa: E731
+        up_bytes, down_bytes = 24.0 * len(pts), 24.0 * st["n_voxels"]
+        emit(f"{tag} voxel_down_sample 1M points, voxel {' / '.join(f'{s / scale:g}' for s in sizes)} of the scene",
+             n=len(pts), voxel_sizes=sizes, voxels=st["n_voxels"], ms=ms, ms_spread=[runs[0][0], runs[-1][0]], runs=len(runs),
+             warmup=5, ms_in_library=med("ms_total"), ms_upload=med("ms_upload"), ms_device=med("ms_device"),
+             ms_download=med("ms_download"), sort_passes=st["sort_passes"], path=st["path"],
+             roofline={"bound": "host link: every byte moves once (24 B per point up, 24 B per voxel down)",
+                       "bytes_up": up_bytes, "bytes_down": down_bytes,
+                       "link_floor_ms": (up_bytes + down_bytes) / (HOST_LINK_GBS * 1e9) * 1e3, "link_peak_GBps": HOST_LINK_GBS,
+                       "achieved_GBps_call": (up_bytes + down_bytes) / (ms * 1e-3) / 1e9,
+                       "hbm_floor_ms": (up_bytes + down_bytes) / (HBM_PEAK_GBS * 1e9) * 1e3,
+                       "device_ms_over_hbm_floor": med("ms_device") / ((up_bytes + down_bytes) / (HBM_PEAK_GBS * 1e9) * 1e3),
+                       "note": "the device part is many small launches over 4-byte arrays (hash insert, scan, 8-bit sort passes, "
+                               "one wave per voxel for the ordered sums) and two round trips (bounds, voxel count), not a "
+                               "streaming kernel: it is not expected near the HBM floor"},
+             cpu_baseline=voxel_cpu(sizes))
