@@ -72,6 +72,39 @@ bool DevBuf::reserve(size_t bytes) {
     lane = ln;
     return true;
 }
+bool CellSort::reserve(size_t n_points, uint32_t ncell) {
+    return cell.reserve(sizeof(uint32_t) * n_points) && start.reserve(sizeof(uint32_t) * ((size_t)ncell + 1)) &&
+           rank.reserve(sizeof(uint32_t) * std::max<size_t>(n_points, 1)) &&
+           sums.reserve(sizeof(uint32_t) * ((size_t)(ncell + 2047) / 2048 + 1)) &&   // one per 2048-cell tile of the scan, + 1
+           total.reserve(16);
+}
+void CellSort::release() {
+    for (DevBuf* b : {&cell, &start, &rank, &sums, &total}) b->release();
+}
+GridDesc radius_grid_desc(const RadiusGridGeom& geom, double r2, double h2_in) {
+    GridDesc g{};
+    g.K = geom.K;
+    g.ox = geom.origin[0];
+    g.oy = geom.origin[1];
+    g.oz = geom.origin[2];
+    g.inv_h = 1.0 / geom.h;
+    g.r2 = r2;
+    g.h2_in = h2_in;
+    g.nx = (uint32_t)geom.dims[0];
+    g.ny = (uint32_t)geom.dims[1];
+    g.nz = (uint32_t)geom.dims[2];
+    return g;
+}
+GridDesc hilbert_sort_desc(const double lo[3], double inv_h, uint32_t bits) {
+    GridDesc g{};
+    g.morton_bits = bits | 0x100u;   // Hilbert order (plain Z-order, bits alone, measured slower: DESIGN.md)
+    g.nx = g.ny = g.nz = 1u << bits;
+    g.ox = lo[0];
+    g.oy = lo[1];
+    g.oz = lo[2];
+    g.inv_h = inv_h;
+    return g;
+}
 void DevBuf::release() {
     if (p) {
         bool parked = false;
@@ -480,8 +513,7 @@ m3d_cloud* m3d_cloud_create_on(m3d::DeviceCtx* ctx, const double* xyz, const dou
     // Hilbert-sorted copy + tile boxes for the culled scoring path.  The bounding box of the finite points comes
     // from the device copy (a host pass over the caller's 10 M-point array took 9 ms, as long as the rest of
     // the upload and sort together)
-    DevBuf &t_cell = ctx->cc_cell, &t_start = ctx->cc_start, &t_fill = ctx->cc_fill, &t_sums = ctx->cc_sums,
-           &t_total = ctx->cc_total, &t_bbox = ctx->cc_bbox;
+    DevBuf& t_bbox = ctx->cc_bbox;
     if (ok) {
         double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
         uint32_t n_finite = 0;
@@ -534,26 +566,12 @@ m3d_cloud* m3d_cloud_create_on(m3d::DeviceCtx* ctx, const double* xyz, const dou
         if (ok && n_finite) {
             double ext = std::max(hi[0] - lo[0], std::max(hi[1] - lo[1], hi[2] - lo[2]));
             if (!std::isfinite(ext)) ext = 0.0;  // absurdly large clouds: one cell, culling degenerates gracefully
-            // about 8 points per cell, at most 2^8 cells per axis
-            uint32_t bits = 1;
-            while (bits < 8 && ((uint64_t)1 << (3 * bits)) * 8 < n_finite) ++bits;
-            GridDesc gs;
-            gs.K = 0;
-            gs.morton_bits = bits | 0x100u;   // Hilbert order (plain Z-order, bits alone, measured slower: DESIGN.md)
-            gs.nx = gs.ny = gs.nz = 1u << bits;
-            gs.ox = lo[0];
-            gs.oy = lo[1];
-            gs.oz = lo[2];
-            gs.inv_h = ext > 0.0 ? (double)(1u << bits) / (ext * (1.0 + 1e-9)) : 0.0;
-            gs.r2 = gs.h2_in = 0.0;
-            const uint32_t ncell = 1u << (3 * bits);
-            ok = t_cell.reserve(sizeof(uint32_t) * n) && t_start.reserve(sizeof(uint32_t) * ((size_t)ncell + 1)) &&
-                 t_fill.reserve(sizeof(uint32_t) * std::max<size_t>(n, 1)) &&   // rank of every point in its cell
-                 t_sums.reserve(sizeof(uint32_t) * ((size_t)(ncell + 2047) / 2048 + 1)) && t_total.reserve(16);
+            const uint32_t bits = sort_grid_bits(n_finite);
+            const GridDesc gs = hilbert_sort_desc(lo, sort_grid_inv_h(ext, bits), bits);
+            ok = ctx->cc_sort.reserve(n, gs.nx * gs.ny * gs.nz);
             if (ok)
-                launch_grid_build(c->view(), gs, t_cell.as<uint32_t>(), t_start.as<uint32_t>(), t_fill.as<uint32_t>(),
-                                  t_sums.as<uint32_t>(), t_total.as<uint32_t>(), c->sx.as<double>(),
-                                  c->sy.as<double>(), c->sz.as<double>(), ctx->stream);
+                launch_grid_build(c->view(), gs, ctx->cc_sort, c->sx.as<double>(), c->sy.as<double>(), c->sz.as<double>(),
+                                  ctx->stream);
         }
         mark(3);
         if (ok && with_sorted_copy) launch_tile_boxes(c->sorted(), c->boxes.as<double>(), ctx->stream);
@@ -617,8 +635,7 @@ void m3d_release_cached(int device) {
         CtxLock lock(ctx);
         (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
-        ctx->cc_stage.release(); ctx->cc_cell.release(); ctx->cc_start.release(); ctx->cc_fill.release();
-        ctx->cc_sums.release(); ctx->cc_total.release(); ctx->cc_bbox.release();
+        ctx->cc_stage.release(); ctx->cc_sort.release(); ctx->cc_bbox.release();
         if (ctx->seg_staging) m3d_host_free(ctx->seg_staging);
         ctx->seg_staging = nullptr;
         ctx->seg_staging_cap = 0;

@@ -11,7 +11,9 @@
 
 #include "../../include/misc3d_amd.h"
 #include "m3d_cull_kernels.hpp"
+#include "m3d_grid_geom.hpp"
 #include "m3d_kernels.hpp"
+#include "m3d_reg_kernels.hpp"
 
 struct m3d_cloud;
 
@@ -49,6 +51,38 @@ struct PinBuf {
         return static_cast<T*>(p);
     }
 };
+
+// A cloud's points counting-sorted by grid cell (launch_grid_build, m3d_reg_kernels.hip): the scratch of the sort, which is also
+// what a search of the grid reads afterwards.  Every site that sorts by cell holds one -- the radius grids (registration's target
+// grid, boundary detection, ProximityExtractor: dimensions from radius_grid_geom) and the Hilbert sorts (m3d_cloud_create, farthest
+// point sampling, registration's source copy: hilbert_sort_desc); the arithmetic of both is in m3d_grid_geom.hpp.
+struct CellSort {
+    DevBuf cell;    // cell of every point
+    DevBuf start;   // ncell + 1: first sorted slot of every cell
+    DevBuf rank;    // rank of every point inside its cell
+    DevBuf sums;    // the scan's tile sums
+    DevBuf total;   // 16 bytes: [0] the points the grid holds (those with three finite coordinates inside it); [1..3] the owner's
+    bool reserve(size_t n_points, uint32_t ncell);   // the ONE place that knows what the kernels expect of the five
+    void release();
+};
+// Row-major cells of a radius grid (radius_grid_geom): squared search radius r2; h2_in, the squared distance below which a
+// neighbour inside the 3x3x3 block is the nearest (registration: (0.999 h)^2; 0 where no kernel reads it)
+GridDesc radius_grid_desc(const RadiusGridGeom& geom, double r2, double h2_in);
+// Hilbert order over (2^bits)^3 cells from the corner lo, inv_h cells per unit length: no search radius, no pad cells
+GridDesc hilbert_sort_desc(const double lo[3], double inv_h, uint32_t bits);
+// launch_grid_build and its two halves on a CellSort reserved for (view.n, the cells of g)
+inline void launch_grid_build(const CloudView& v, const GridDesc& g, CellSort& cs, double* qx, double* qy, double* qz, hipStream_t s,
+                              uint32_t* orig = nullptr, double4* q4 = nullptr) {
+    launch_grid_build(v, g, cs.cell.as<uint32_t>(), cs.start.as<uint32_t>(), cs.rank.as<uint32_t>(), cs.sums.as<uint32_t>(),
+                      cs.total.as<uint32_t>(), qx, qy, qz, s, orig, q4);
+}
+inline void launch_grid_count_scan(const CloudView& v, const GridDesc& g, CellSort& cs, hipStream_t s) {
+    launch_grid_count_scan(v, g, cs.cell.as<uint32_t>(), cs.start.as<uint32_t>(), cs.rank.as<uint32_t>(), cs.sums.as<uint32_t>(),
+                           cs.total.as<uint32_t>(), s);
+}
+inline void launch_grid_scatter(const CloudView& v, const CellSort& cs, double* qx, double* qy, double* qz, hipStream_t s) {
+    launch_grid_scatter(v, cs.cell.as<uint32_t>(), cs.start.as<uint32_t>(), cs.rank.as<uint32_t>(), qx, qy, qz, s);
+}
 
 // One in-flight chunk of hypotheses (two slots: the next chunk is scored while the host replays
 // the previous one).
@@ -104,7 +138,8 @@ struct DeviceCtx {
     const double* last_best_dev = nullptr;   // device address of the last fit's best minimal model (a slot's params or best_params)
     // m3d_cloud_create's upload / sort scratch (a one-shot call -- upload, fit, destroy -- otherwise spends more time
     // in hipMalloc / hipFree than in the fit; the cloud's own buffers come back through DevBuf's free list)
-    DevBuf cc_stage, cc_cell, cc_start, cc_fill, cc_sums, cc_total, cc_bbox;
+    DevBuf cc_stage, cc_bbox;
+    CellSort cc_sort;
     DevBuf pick;               // BestPick: the device's prediction of the winning hypothesis (probability-1 fits)
     PinBuf h_pick;             // BestPickHost mirror (+ at byte 64: inlier total of a compaction started on the prediction)
     bool spec_compaction = false;   // RefineModel's compaction has already been queued on pick->params

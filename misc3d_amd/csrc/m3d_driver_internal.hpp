@@ -1,11 +1,16 @@
 // m3d_driver_internal.hpp -- what the translation units of the host driver share (m3d_device.cpp: errors, lanes, block
 // pools, resident clouds; m3d_fit.cpp: the RANSAC loop; m3d_refine.cpp: RefineModel; m3d_segmentation.cpp:
-// SegmentPlaneIterative; m3d_multi.cpp: one process, several devices; m3d_bench_hooks.cpp).  Not part of any boundary.
+// SegmentPlaneIterative; m3d_multi.cpp: one process, several devices; m3d_bench_hooks.cpp; m3d_preprocessing.cpp, m3d_proximity.cpp,
+// m3d_knn.cpp, m3d_fpfh.cpp, m3d_voxel.cpp: the entry points on top).  Not part of any boundary.  The early-return macros, round_up,
+// now_ms and stream_wait_spin come from m3d_host_util.hpp, which m3d_registration.cpp, m3d_match.cpp,
+// m3d_global_registration.cpp and m3d_normals.hip include on its own; the grid arithmetic from m3d_grid_geom.hpp.
 #pragma once
 #include "m3d_driver.hpp"
 #include "m3d_comm.hpp"
 #include "m3d_config.hpp"
 #include "m3d_fp.hpp"
+#include "m3d_grid_geom.hpp"
+#include "m3d_host_util.hpp"
 #include "m3d_mt19937.hpp"
 #include "m3d_reg_kernels.hpp"
 
@@ -22,34 +27,17 @@
 #include <random>
 #include <thread>
 
-#define HIPCHK(expr)                                                                       \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return m3d::fail(M3D_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-#define RESERVE(buf, bytes)                         \
-    do {                                            \
-        if (!(buf).reserve(bytes)) return M3D_ERR_DEVICE; \
-    } while (0)
-
 namespace m3d {
 
-static inline uint32_t round_up(uint32_t v, uint32_t m) { return (v + m - 1) / m * m; }
 static inline int minimal_sample(int kind) { return kind == M3D_PLANE ? 3 : (kind == M3D_SPHERE ? 4 : 2); }
 static inline int num_params(int kind) { return kind == M3D_CYLINDER ? 7 : 4; }
-static inline double now_ms() {
-    using namespace std::chrono;
-    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
 
 // ---- m3d_device.cpp
 const std::string& last_error_string();
 bool is_library_pinned(const void* p, size_t bytes);   // inside a block m3d_host_alloc handed out?
 void release_buffers(m3d_cloud* c);                    // every device buffer a cloud owns -> its lane's free list
 
-// ---- m3d_fit.cpp
-int stream_wait_spin(DeviceCtx* ctx);
+// ---- m3d_fit.cpp (stream_wait_spin: m3d_host_util.hpp)
 int word_wait_spin(DeviceCtx* ctx, const uint32_t* word /* page-locked */, uint32_t seq);
 int validate_fit_args(int kind, size_t n, bool has_normals, double prob);
 uint64_t resolve_seed(const uint64_t* seed);

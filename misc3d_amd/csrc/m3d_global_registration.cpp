@@ -26,16 +26,11 @@
 #include <vector>
 
 #include "m3d_config.hpp"
-#include "m3d_driver.hpp"
+#include "m3d_host_util.hpp"
 
 using namespace m3d;
 
 namespace {
-
-double now_ms() {
-    using namespace std::chrono;
-    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
 
 // Eigen::MatrixBase::isIdentity(prec) (pipeline.cpp:814): diagonal internal::isApprox(x, 1, prec) = |x - 1| <= min(|x|, 1) prec,
 // off-diagonal internal::isMuchSmallerThan(x, 1, prec) = |x| <= prec.  (oracle: orc_is_identity4)

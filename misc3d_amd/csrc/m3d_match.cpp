@@ -17,40 +17,18 @@
 
 #include "../../include/misc3d_amd_bench.h"
 #include "m3d_config.hpp"
-#include "m3d_driver.hpp"
+#include "m3d_host_util.hpp"
 #include "m3d_reg_kernels.hpp"
-
-namespace m3d {
-int stream_wait_spin(DeviceCtx* ctx);   // (m3d_fit.cpp: the end of the stream's work, polled in page-locked memory)
-}
 
 #pragma clang fp contract(off)
 
 using namespace m3d;
 
-#define HIPCHK(expr)                                                                       \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return fail(M3D_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-#define RESERVE(buf, bytes)                               \
-    do {                                                  \
-        if (!(buf).reserve(bytes)) return M3D_ERR_DEVICE; \
-    } while (0)
-
 namespace {
-
-inline uint32_t round_up(uint32_t v, uint32_t m) { return (v + m - 1) / m * m; }
 
 thread_local unsigned g_match_path = 0;         // m3d_bench_match_last_path's bits
 thread_local uint64_t g_match_fallbacks = 0;   // queries of the CALLING THREAD's last m3d_match_mutual_nn that took the exact fallback
                                                // (thread-local: concurrent calls on different devices used to race on one global)
-
-double now_ms() {
-    using namespace std::chrono;
-    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
 
 }  // namespace
 

@@ -15,8 +15,8 @@
 #include <cstring>
 #include <mutex>
 
-#include "m3d_driver.hpp"
 #include "m3d_eig3.hpp"
+#include "m3d_host_util.hpp"
 
 #pragma clang fp contract(off)
 
@@ -151,13 +151,6 @@ __global__ void nm_normals_k(const double* __restrict__ img, const double* __res
 }  // namespace m3d
 
 using namespace m3d;
-
-#define HIPCHK(expr)                                                                       \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return fail(M3D_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 extern "C" int m3d_normals_from_map(const double* xyz, uint32_t w, uint32_t h, uint32_t k, const double* view_point,
                                     int device, double* normals, double* ms_device) {

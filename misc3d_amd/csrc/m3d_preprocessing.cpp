@@ -18,11 +18,11 @@ std::atomic<int> g_fps_force{0};
 constexpr uint32_t kFpsCrossover = kFpsSingleMaxPoints;
 
 struct FpsBufs {
-    DevBuf aos, out, x, y, z, sx, sy, sz, orig, dist, tiles, wg, state, cell, start, rank, sums, total;
+    DevBuf aos, out, x, y, z, sx, sy, sz, orig, dist, tiles, wg, state;
+    CellSort sort;
     void release() {
-        for (DevBuf* b : {&aos, &out, &x, &y, &z, &sx, &sy, &sz, &orig, &dist, &tiles, &wg, &state, &cell, &start, &rank, &sums,
-                          &total})
-            b->release();
+        for (DevBuf* b : {&aos, &out, &x, &y, &z, &sx, &sy, &sz, &orig, &dist, &tiles, &wg, &state}) b->release();
+        sort.release();
     }
 };
 
@@ -57,30 +57,13 @@ int fps_layout(DeviceCtx* ctx, FpsBufs& B, const double* xyz, uint32_t n, uint32
             RESERVE(B.y, sizeof(double) * n_pad);
             RESERVE(B.z, sizeof(double) * n_pad);
             launch_aos_to_soa(B.aos.as<double>(), B.x.as<double>(), B.y.as<double>(), B.z.as<double>(), n, n_pad, st);
-            // about 8 points per cell, at most 2^8 cells per axis (as m3d_cloud_create's sort)
-            uint32_t bits = 1;
-            while (bits < 8 && ((uint64_t)1 << (3 * bits)) * 8 < n_fin) ++bits;
-            GridDesc gs;
-            gs.K = 0;
-            gs.morton_bits = bits | 0x100u;
-            gs.nx = gs.ny = gs.nz = 1u << bits;
-            gs.ox = lo[0];
-            gs.oy = lo[1];
-            gs.oz = lo[2];
-            gs.inv_h = ext > 0.0 ? (double)(1u << bits) / (ext * (1.0 + 1e-9)) : 0.0;
-            gs.r2 = gs.h2_in = 0.0;
-            const uint32_t ncell = 1u << (3 * bits);
-            RESERVE(B.cell, sizeof(uint32_t) * n);
-            RESERVE(B.start, sizeof(uint32_t) * ((size_t)ncell + 1));
-            RESERVE(B.rank, sizeof(uint32_t) * n);
-            RESERVE(B.sums, sizeof(uint32_t) * ((size_t)(ncell + 2047) / 2048 + 1));
-            RESERVE(B.total, 16);
+            const uint32_t bits = sort_grid_bits(n_fin);   // (the grid of m3d_cloud_create's sort)
+            const GridDesc gs = hilbert_sort_desc(lo, sort_grid_inv_h(ext, bits), bits);
+            if (!B.sort.reserve(n, gs.nx * gs.ny * gs.nz)) return M3D_ERR_DEVICE;
             CloudView v{B.x.as<double>(), B.y.as<double>(), B.z.as<double>(), nullptr, nullptr, nullptr, n, n_pad};
-            launch_grid_build(v, gs, B.cell.as<uint32_t>(), B.start.as<uint32_t>(), B.rank.as<uint32_t>(), B.sums.as<uint32_t>(),
-                              B.total.as<uint32_t>(), B.sx.as<double>(), B.sy.as<double>(), B.sz.as<double>(), st,
-                              B.orig.as<uint32_t>());
+            launch_grid_build(v, gs, B.sort, B.sx.as<double>(), B.sy.as<double>(), B.sz.as<double>(), st, B.orig.as<uint32_t>());
             uint32_t placed = 0;
-            HIPCHK(hipMemcpyAsync(&placed, B.total.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(&placed, B.sort.total.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             HIPCHK(hipGetLastError());
             HIPCHK(hipStreamSynchronize(st));
             if (placed != n_fin) {   // the grid left out a finite point (its cell test rounded): the input order instead

@@ -15,19 +15,18 @@ using namespace m3d;
 namespace {
 
 struct ProxBufs {
-    DevBuf cell_of_point, cell_start, fill, tile_sums, total, qx, qy, qz, cell_orig, snx, sny, snz, parent, size, root, off,
-        idx, nb_d2;
+    CellSort grid;
+    DevBuf qx, qy, qz, cell_orig, snx, sny, snz, parent, size, root, off, idx, nb_d2;
     void release() {
-        for (DevBuf* b : {&cell_of_point, &cell_start, &fill, &tile_sums, &total, &qx, &qy, &qz, &cell_orig, &snx, &sny, &snz,
-                          &parent, &size, &root, &off, &idx, &nb_d2})
-            b->release();
+        grid.release();
+        for (DevBuf* b : {&qx, &qy, &qz, &cell_orig, &snx, &sny, &snz, &parent, &size, &root, &off, &idx, &nb_d2}) b->release();
     }
 };
 
-// The uniform grid of detect_boundary_points' Radius search (build_target_grid with K0 = 1): cell edge 1.001 radius, three
-// pad cells per side, the edge doubled while the dense table would exceed 2^27 cells (a coarser cell still covers the
-// radius, its 3x3x3 block only holds more points).  Points counting-sorted by cell with their original indices
-// (B.cell_orig); B.total[0] = the points the grid holds (those with three finite coordinates).
+// The uniform grid of detect_boundary_points' Radius search (radius_grid_geom with K0 = 1, m3d_grid_geom.hpp): cell edge 1.001
+// radius, three pad cells per side, the edge doubled while the dense table would exceed 2^27 cells (a coarser cell still covers
+// the radius, its 3x3x3 block only holds more points).  Points counting-sorted by cell with their original indices
+// (B.cell_orig); B.grid.total[0] = the points the grid holds (those with three finite coordinates).
 int prox_grid(DeviceCtx* ctx, ProxBufs& B, const m3d_cloud* c, double radius, GridDesc* g_out) {
     double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
     if (c->bb_known)
@@ -35,52 +34,19 @@ int prox_grid(DeviceCtx* ctx, ProxBufs& B, const m3d_cloud* c, double radius, Gr
             lo[k] = c->bb[k];
             hi[k] = c->bb[3 + k];
         }
-    double h = (radius > 0.0 ? radius : 1.0) * 1.001;   // (radius 0: only exact duplicates are neighbours; any cell will do)
-    if (!std::isfinite(h)) return fail(M3D_ERR_INVALID_ARG, "proximity: search radius too large");
-    uint64_t dims[3];
-    for (;;) {
-        bool fits = true;
-        uint64_t cells = 1;
-        for (int k = 0; k < 3; ++k) {
-            const double ext = (hi[k] - lo[k]) / h;
-            if (!(ext < 1e9)) {
-                fits = false;
-                break;
-            }
-            dims[k] = (uint64_t)ext + 1 + 2 * 3;
-            cells *= dims[k];
-            if (cells > ((uint64_t)1 << 27)) fits = false;
-        }
-        if (fits) break;
-        h *= 2.0;
-        if (!std::isfinite(h)) return fail(M3D_ERR_INVALID_ARG, "proximity: the cloud's extent does not allow a grid");
-    }
-    GridDesc g;
-    g.K = 1;
-    g.morton_bits = 0;
-    g.ox = lo[0] - 3 * h;
-    g.oy = lo[1] - 3 * h;
-    g.oz = lo[2] - 3 * h;
-    g.inv_h = 1.0 / h;
-    g.r2 = radius * radius;
-    g.h2_in = 0.0;
-    g.nx = (uint32_t)dims[0];
-    g.ny = (uint32_t)dims[1];
-    g.nz = (uint32_t)dims[2];
-    const uint32_t ncell = g.nx * g.ny * g.nz;
+    const double edge = radius > 0.0 ? radius : 1.0;   // (radius 0: only exact duplicates are neighbours; any cell will do)
+    if (!std::isfinite(edge * 1.001)) return fail(M3D_ERR_INVALID_ARG, "proximity: search radius too large");
+    const RadiusGridGeom geom = radius_grid_geom(lo, hi, edge, 1);
+    if (!std::isfinite(geom.h)) return fail(M3D_ERR_INVALID_ARG, "proximity: the cloud's extent does not allow a grid");
+    const GridDesc g = radius_grid_desc(geom, radius * radius, 0.0);
     const size_t n = c->n;
-    RESERVE(B.cell_of_point, sizeof(uint32_t) * n);
-    RESERVE(B.cell_start, sizeof(uint32_t) * ((size_t)ncell + 1));
-    RESERVE(B.fill, sizeof(uint32_t) * n);
-    RESERVE(B.tile_sums, sizeof(uint32_t) * ((size_t)(ncell + 2047) / 2048 + 1));
-    RESERVE(B.total, 16);
+    if (!B.grid.reserve(n, g.nx * g.ny * g.nz)) return M3D_ERR_DEVICE;
     RESERVE(B.qx, sizeof(double) * n);
     RESERVE(B.qy, sizeof(double) * n);
     RESERVE(B.qz, sizeof(double) * n);
     RESERVE(B.cell_orig, sizeof(uint32_t) * n);
-    launch_grid_build(c->view(), g, B.cell_of_point.as<uint32_t>(), B.cell_start.as<uint32_t>(), B.fill.as<uint32_t>(),
-                      B.tile_sums.as<uint32_t>(), B.total.as<uint32_t>(), B.qx.as<double>(), B.qy.as<double>(),
-                      B.qz.as<double>(), ctx->stream, B.cell_orig.as<uint32_t>());
+    launch_grid_build(c->view(), g, B.grid, B.qx.as<double>(), B.qy.as<double>(), B.qz.as<double>(), ctx->stream,
+                      B.cell_orig.as<uint32_t>());
     HIPCHK(hipGetLastError());
     *g_out = g;
     return M3D_OK;
@@ -186,7 +152,7 @@ int m3d_proximity_segment(const double* xyz, const double* normals, size_t n_nor
         const uint32_t nn = (uint32_t)n;
         HIPCHK(hipEventRecord(ctx->ev0, s));
         if (const int rg = prox_grid(ctx, B, c, radius, &g); rg != M3D_OK) return rg;
-        const uint32_t* n_sorted = B.total.as<uint32_t>();
+        const uint32_t* n_sorted = B.grid.total.as<uint32_t>();
         if (with_normals) {
             RESERVE(B.snx, sizeof(double) * n);
             RESERVE(B.sny, sizeof(double) * n);
@@ -197,7 +163,7 @@ int m3d_proximity_segment(const double* xyz, const double* normals, size_t n_nor
         RESERVE(B.parent, sizeof(uint32_t) * n);
         RESERVE(B.size, sizeof(uint32_t) * n);
         launch_prox_init(B.parent.as<uint32_t>(), B.size.as<uint32_t>(), nn, s);
-        launch_prox_union_grid(g, B.cell_start.as<uint32_t>(), B.qx.as<double>(), B.qy.as<double>(), B.qz.as<double>(),
+        launch_prox_union_grid(g, B.grid.start.as<uint32_t>(), B.qx.as<double>(), B.qy.as<double>(), B.qz.as<double>(),
                                B.cell_orig.as<uint32_t>(), B.snx.as<double>(), B.sny.as<double>(), B.snz.as<double>(), nn,
                                n_sorted, cut, B.parent.as<uint32_t>(), s);
         HIPCHK(hipGetLastError());
@@ -295,8 +261,8 @@ int m3d_radius_neighbors(const double* xyz, size_t n, double radius, int device,
         if (const int rg = prox_grid(ctx, B, c, radius, &g); rg != M3D_OK) return rg;
         RESERVE(B.size, sizeof(uint32_t) * n);
         HIPCHK(hipMemsetAsync(B.size.p, 0, sizeof(uint32_t) * n, s));   // (points outside the grid have no neighbours)
-        launch_prox_nb_count(g, B.cell_start.as<uint32_t>(), B.qx.as<double>(), B.qy.as<double>(), B.qz.as<double>(),
-                             B.cell_orig.as<uint32_t>(), nn, B.total.as<uint32_t>(), B.size.as<uint32_t>(), s);
+        launch_prox_nb_count(g, B.grid.start.as<uint32_t>(), B.qx.as<double>(), B.qy.as<double>(), B.qz.as<double>(),
+                             B.cell_orig.as<uint32_t>(), nn, B.grid.total.as<uint32_t>(), B.size.as<uint32_t>(), s);
         HIPCHK(hipGetLastError());
         std::vector<uint32_t> cnt(n);
         HIPCHK(hipMemcpyAsync(cnt.data(), B.size.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
@@ -308,8 +274,8 @@ int m3d_radius_neighbors(const double* xyz, size_t n, double radius, int device,
         RESERVE(B.idx, sizeof(uint32_t) * std::max<size_t>(offsets[n], 1));
         RESERVE(B.nb_d2, sizeof(double) * std::max<size_t>(offsets[n], 1));
         HIPCHK(hipMemcpyAsync(B.off.p, offsets, sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, s));
-        launch_prox_nb_fill(g, B.cell_start.as<uint32_t>(), B.qx.as<double>(), B.qy.as<double>(), B.qz.as<double>(),
-                            B.cell_orig.as<uint32_t>(), nn, B.total.as<uint32_t>(), B.off.as<uint64_t>(),
+        launch_prox_nb_fill(g, B.grid.start.as<uint32_t>(), B.qx.as<double>(), B.qy.as<double>(), B.qz.as<double>(),
+                            B.cell_orig.as<uint32_t>(), nn, B.grid.total.as<uint32_t>(), B.off.as<uint64_t>(),
                             B.idx.as<uint32_t>(), B.nb_d2.as<double>(), s);
         HIPCHK(hipGetLastError());
         if (offsets[n]) {

@@ -26,37 +26,15 @@
 #include "../../include/misc3d_amd_bench.h"
 #include "m3d_comm.hpp"
 #include "m3d_config.hpp"
-#include "m3d_driver.hpp"
+#include "m3d_host_util.hpp"
 #include "m3d_reg_fp.hpp"
-
-namespace m3d {
-int stream_wait_spin(DeviceCtx* ctx);   // (m3d_fit.cpp: the end of the stream's work, polled in page-locked memory)
-}
 #include "m3d_reg_kernels.hpp"
 
 #pragma clang fp contract(off)
 
 using namespace m3d;
 
-#define HIPCHK(expr)                                                                       \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return fail(M3D_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-#define RESERVE(buf, bytes)                               \
-    do {                                                  \
-        if (!(buf).reserve(bytes)) return M3D_ERR_DEVICE; \
-    } while (0)
-
 namespace {
-
-inline uint32_t round_up(uint32_t v, uint32_t m) { return (v + m - 1) / m * m; }
-
-double now_ms() {
-    using namespace std::chrono;
-    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
 
 // static_cast<int>(std::ceil(v)) as the x86-64 conversion behaves (cvttsd2si -> INT_MIN when out of range)
 int ceil_to_int_x86(double v) {
@@ -66,15 +44,17 @@ int ceil_to_int_x86(double v) {
 }
 
 struct Scratch {  // per-call device buffers (registration calls are rare and large: no caching)
-    DevBuf corr_src, corr_dst, triples, T12, pass, list, Ts, partial, counts, cell_of_point, cell_start, fill,
-        tile_sums, total, qx, qy, qz, best, vals, block_counts, sums, one_T, ratio, partial_sum, sum2,
-        s_cell_of_point, s_cell_start, s_fill, s_tile_sums, sx, sy, sz, keep, nl_start, nl_pts, nl_hdr, nl32, nl_rec, nl32_start, nl32_fallbacks, cell_orig, tile_sph, q4,
+    // the target grid's sort (tgt.total: [0] also the count of launch_compact_vals, [1] launch_nl_count's, [3] the nl32 overflow
+    // word) and the sort behind the source's Hilbert-ordered copy
+    CellSort tgt, src_sort;
+    DevBuf corr_src, corr_dst, triples, T12, pass, list, Ts, partial, counts, qx, qy, qz, best, vals, block_counts, sums, one_T,
+        ratio, partial_sum, sum2, sx, sy, sz, keep, nl_start, nl_pts, nl_hdr, nl32, nl_rec, nl32_start, nl32_fallbacks, cell_orig, tile_sph, q4,
         cc_x, cc_y, cc_z, cc_64, cc_xa, cc_ya, cc_za, cc_R, cc_stats, cc_redo, cc_ring, cc_ring_tmp, cc_pairs;   // the validation's candidate cache (m3d_reg_cache.hip)
     void release() {
-        for (DevBuf* b : {&corr_src, &corr_dst, &triples, &T12, &pass, &list, &Ts, &partial, &counts,
-                          &cell_of_point, &cell_start, &fill, &tile_sums, &total, &qx, &qy, &qz, &best, &vals,
-                          &block_counts, &sums, &one_T, &ratio, &partial_sum, &sum2, &s_cell_of_point,
-                          &s_cell_start, &s_fill, &s_tile_sums, &sx, &sy, &sz, &keep, &nl_start, &nl_pts, &nl_hdr, &nl32, &nl_rec, &nl32_start, &nl32_fallbacks, &cell_orig,
+        tgt.release();
+        src_sort.release();
+        for (DevBuf* b : {&corr_src, &corr_dst, &triples, &T12, &pass, &list, &Ts, &partial, &counts, &qx, &qy, &qz, &best, &vals,
+                          &block_counts, &sums, &one_T, &ratio, &partial_sum, &sum2, &sx, &sy, &sz, &keep, &nl_start, &nl_pts, &nl_hdr, &nl32, &nl_rec, &nl32_start, &nl32_fallbacks, &cell_orig,
                           &tile_sph, &q4, &cc_x, &cc_y, &cc_z, &cc_64, &cc_xa, &cc_ya, &cc_za, &cc_R, &cc_stats, &cc_redo, &cc_ring, &cc_ring_tmp, &cc_pairs})
             b->release();
     }
@@ -102,7 +82,6 @@ int add_neighbour_lists(DeviceCtx* ctx, Scratch& S, GridDesc* gp, size_t n_dst, 
 int build_target_grid(DeviceCtx* ctx, Scratch& S, const CloudView& dst_view, const double* dst, size_t n_dst,
                       double radius, bool with_orig, GridDesc* g_out, int K0 = 4, bool with_nl = true,
                       const double* bbox6 = nullptr) {
-    GridDesc g;
     double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     if (bbox6) {
         for (int k = 0; k < 3; ++k) {
@@ -121,46 +100,10 @@ int build_target_grid(DeviceCtx* ctx, Scratch& S, const CloudView& dst_view, con
     }
     for (int k = 0; k < 3; ++k)
         if (!(lo[k] <= hi[k])) lo[k] = hi[k] = 0.0;
-    int K = K0;
-    double h = radius * 1.001 / K;
-    uint64_t dims[3];
-    for (;;) {
-        bool fits = true;
-        uint64_t cells = 1;
-        for (int k = 0; k < 3; ++k) {
-            const double ext = (hi[k] - lo[k]) / h;
-            if (!(ext < 1e9)) {
-                fits = false;
-                break;
-            }
-            dims[k] = (uint64_t)ext + 1 + 2 * (uint64_t)(2 * K + 1);
-            cells *= dims[k];
-            if (cells > ((uint64_t)1 << 27)) fits = false;
-        }
-        if (fits) break;
-        if (K > 1)
-            K /= 2;
-        h *= 2.0;
-    }
-    g.K = K;
-    g.morton_bits = 0;
-    // 2K+1 pad cells on every side: a query up to one radius (< K cells) outside the bounding box still has its
-    // whole (2K+1)^3 search block inside the table, and anything further out cannot have a neighbour
-    g.ox = lo[0] - (2 * K + 1) * h;
-    g.oy = lo[1] - (2 * K + 1) * h;
-    g.oz = lo[2] - (2 * K + 1) * h;
-    g.inv_h = 1.0 / h;
-    g.r2 = radius * radius;  // radius * radius, KDTreeFlann::SearchHybrid
-    g.h2_in = (0.999 * h) * (0.999 * h);
-    g.nx = (uint32_t)dims[0];
-    g.ny = (uint32_t)dims[1];
-    g.nz = (uint32_t)dims[2];
-    const uint32_t ncell = g.nx * g.ny * g.nz;
-    RESERVE(S.cell_of_point, sizeof(uint32_t) * n_dst);
-    RESERVE(S.cell_start, sizeof(uint32_t) * ((size_t)ncell + 1));
-    RESERVE(S.fill, sizeof(uint32_t) * std::max<size_t>(dst_view.n, 1));   // rank of every point in its cell
-    RESERVE(S.tile_sums, sizeof(uint32_t) * ((size_t)(ncell + 2047) / 2048 + 1));
-    RESERVE(S.total, 16);
+    const RadiusGridGeom geom = radius_grid_geom(lo, hi, radius, K0);
+    // r2: radius * radius, KDTreeFlann::SearchHybrid
+    GridDesc g = radius_grid_desc(geom, radius * radius, (0.999 * geom.h) * (0.999 * geom.h));
+    if (!S.tgt.reserve(n_dst, g.nx * g.ny * g.nz)) return M3D_ERR_DEVICE;
     RESERVE(S.qx, sizeof(double) * n_dst);
     RESERVE(S.qy, sizeof(double) * n_dst);
     RESERVE(S.qz, sizeof(double) * n_dst);
@@ -168,9 +111,8 @@ int build_target_grid(DeviceCtx* ctx, Scratch& S, const CloudView& dst_view, con
     uint32_t* orig = with_orig ? S.cell_orig.as<uint32_t>() : nullptr;
     RESERVE(S.q4, sizeof(double4) * std::max<size_t>(n_dst, 1));
     g.q4 = S.q4.as<double4>();
-    launch_grid_build(dst_view, g, S.cell_of_point.as<uint32_t>(), S.cell_start.as<uint32_t>(),
-                      S.fill.as<uint32_t>(), S.tile_sums.as<uint32_t>(), S.total.as<uint32_t>(),
-                      S.qx.as<double>(), S.qy.as<double>(), S.qz.as<double>(), ctx->stream, orig, S.q4.as<double4>());
+    launch_grid_build(dst_view, g, S.tgt, S.qx.as<double>(), S.qy.as<double>(), S.qz.as<double>(), ctx->stream, orig,
+                      S.q4.as<double4>());
     if (with_nl) {
         const int rn = add_neighbour_lists(ctx, S, &g, n_dst, orig);
         if (rn != M3D_OK) return rn;
@@ -186,8 +128,8 @@ int add_neighbour_lists(DeviceCtx* ctx, Scratch& S, GridDesc* gp, size_t n_dst, 
     const uint32_t ncell = g.nx * g.ny * g.nz;
     if (config().reg_neighbour_lists && n_dst <= ((size_t)2 << 20)) {
         RESERVE(S.nl_start, sizeof(uint32_t) * ((size_t)ncell + 1));
-        launch_nl_count(g, S.cell_start.as<uint32_t>(), S.nl_start.as<uint32_t>(), S.tile_sums.as<uint32_t>(),
-                        S.total.as<uint32_t>() + 1, ctx->stream);
+        launch_nl_count(g, S.tgt.start.as<uint32_t>(), S.nl_start.as<uint32_t>(), S.tgt.sums.as<uint32_t>(),
+                        S.tgt.total.as<uint32_t>() + 1, ctx->stream);
         uint32_t entries = 0;
         HIPCHK(hipMemcpyAsync(&entries, S.nl_start.as<uint32_t>() + ncell, sizeof(uint32_t), hipMemcpyDeviceToHost,
                               ctx->stream));
@@ -203,10 +145,10 @@ int add_neighbour_lists(DeviceCtx* ctx, Scratch& S, GridDesc* gp, size_t n_dst, 
         far += (double)std::max(g.nx, std::max(g.ny, g.nz)) / g.inv_h;
         bool screen = sorted && config().reg_fp32_screen != 0 && far * 0x1p-50 <= 0x1p-24 / g.inv_h * 0.01 &&
                       1.0 / g.inv_h > 1e-15 && 1.0 / g.inv_h < 1e15 && entries < (1u << 28);
-        uint32_t* overflow = S.total.as<uint32_t>() + 3;
+        uint32_t* overflow = S.tgt.total.as<uint32_t>() + 3;
         if (screen) {
             RESERVE(S.nl32_start, sizeof(uint32_t) * ((size_t)ncell + 1));
-            launch_nl32_offsets(S.nl_start.as<uint32_t>(), ncell, S.nl32_start.as<uint32_t>(), S.tile_sums.as<uint32_t>(),
+            launch_nl32_offsets(S.nl_start.as<uint32_t>(), ncell, S.nl32_start.as<uint32_t>(), S.tgt.sums.as<uint32_t>(),
                                 overflow, ctx->stream);   // (the word receives the length first, then serves as the flag)
             uint32_t entries32 = 0;
             HIPCHK(hipMemcpyAsync(&entries32, overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -215,7 +157,7 @@ int add_neighbour_lists(DeviceCtx* ctx, Scratch& S, GridDesc* gp, size_t n_dst, 
             RESERVE(S.nl_rec, sizeof(uint4) * (size_t)ncell);
             HIPCHK(hipMemsetAsync(overflow, 0, sizeof(uint32_t), ctx->stream));
         }
-        launch_nl_fill(g, S.cell_start.as<uint32_t>(), S.nl_start.as<uint32_t>(), S.qx.as<double>(),
+        launch_nl_fill(g, S.tgt.start.as<uint32_t>(), S.nl_start.as<uint32_t>(), S.qx.as<double>(),
                        S.qy.as<double>(), S.qz.as<double>(), S.nl_pts.as<double4>(), ctx->stream, orig, sorted,
                        sorted ? S.nl_hdr.as<uint32_t>() : nullptr, screen ? S.nl32.as<uint2>() : nullptr,
                        screen ? S.nl_rec.as<uint4>() : nullptr, overflow, screen ? S.nl32_start.as<uint32_t>() : nullptr);
@@ -249,16 +191,16 @@ int exact_err2(RegCtx& rc, const double* T_dev, uint64_t* count, double* err2) {
     RESERVE(s.best, sizeof(double) * std::max<uint32_t>(n, 1));
     RESERVE(s.vals, sizeof(double) * std::max<uint32_t>(n, 1));
     RESERVE(s.block_counts, sizeof(uint32_t) * ((size_t)nb + 1));
-    RESERVE(s.total, 16);
+    RESERVE(s.tgt.total, 16);
     RESERVE(s.sums, sizeof(double) * 4);
     RESERVE(ctx->h_small, 256);
-    launch_reg_min_d2(rc.src, T_dev, rc.g, s.cell_start.as<uint32_t>(), s.qx.as<double>(), s.qy.as<double>(),
+    launch_reg_min_d2(rc.src, T_dev, rc.g, s.tgt.start.as<uint32_t>(), s.qx.as<double>(), s.qy.as<double>(),
                       s.qz.as<double>(), s.best.as<double>(), ctx->stream);
-    launch_compact_vals(s.best.as<double>(), n, rc.g.r2, s.block_counts.as<uint32_t>(), s.total.as<uint32_t>(),
+    launch_compact_vals(s.best.as<double>(), n, rc.g.r2, s.block_counts.as<uint32_t>(), s.tgt.total.as<uint32_t>(),
                         s.vals.as<double>(), ctx->stream);
-    launch_serial_sum(s.vals.as<double>(), s.total.as<uint32_t>(), s.sums.as<double>(), ctx->stream);
+    launch_serial_sum(s.vals.as<double>(), s.tgt.total.as<uint32_t>(), s.sums.as<double>(), ctx->stream);
     uint8_t* h = ctx->h_small.as<uint8_t>();
-    HIPCHK(hipMemcpyAsync(h, s.total.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(h, s.tgt.total.p, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(h + 8, s.sums.p, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipGetLastError());
     if (const int wr = stream_wait_spin(ctx); wr != M3D_OK) return wr;   // (results in page-locked memory: a polled word instead of the runtime's wait, which wakes 10-20 us late)
@@ -280,7 +222,7 @@ int tree_err2(RegCtx& rc, const double* T_dev, uint64_t* count, double* err2) {
     RESERVE(s.sums, sizeof(double) * 32);
     RESERVE(s.partial_sum, sizeof(double) * 256 * 16);
     RESERVE(ctx->h_small, 256);
-    launch_reg_min_d2(rc.src, T_dev, rc.g, s.cell_start.as<uint32_t>(), s.qx.as<double>(), s.qy.as<double>(),
+    launch_reg_min_d2(rc.src, T_dev, rc.g, s.tgt.start.as<uint32_t>(), s.qx.as<double>(), s.qy.as<double>(),
                       s.qz.as<double>(), s.best.as<double>(), ctx->stream);
     launch_icp_err(s.best.as<double>(), n, rc.g.r2, s.partial_sum.as<double>(), s.sums.as<double>() + 24, ctx->stream);
     uint8_t* h = ctx->h_small.as<uint8_t>();
@@ -485,7 +427,6 @@ int m3d_reg::setup(const double* src, const double* dst, const size_t* corr_src,
             ext = std::max(ext, shi[k] - slo[k]);
         }
         if (ext > 0.0 && std::isfinite(ext)) {
-            GridDesc gs;
             // Hilbert order over 128^3 cells: the 64 points of a wave form a compact patch, so the lanes probe the same few
             // target cells
             // (round 5: 64^3 / 128^3 / 256^3 / 512^3 cells: the forced C4 run 142.3 / 138.5 / 136.8 / 139.0 ms -- and with the source
@@ -493,23 +434,9 @@ int m3d_reg::setup(const double* src, const double* dst, const size_t* corr_src,
             //  among a wave's lanes is not what the validation kernel's time goes with; profiles/r05_reg_validate_findings.txt)
             const uint32_t fbits = 7u;
             const double hs = ext / 127.0;
-            gs.K = 0;
-            gs.morton_bits = fbits | 0x100u;
-            gs.ox = slo[0];
-            gs.oy = slo[1];
-            gs.oz = slo[2];
-            gs.inv_h = 1.0 / hs;
-            gs.r2 = gs.h2_in = 0.0;
-            const uint32_t side = 1u << fbits;
-            gs.nx = gs.ny = gs.nz = side;
-            const uint32_t ncs = gs.nx * gs.ny * gs.nz;
-            RESERVE(S.s_cell_of_point, sizeof(uint32_t) * n_src);
-            RESERVE(S.s_cell_start, sizeof(uint32_t) * ((size_t)ncs + 1));
-            RESERVE(S.s_fill, sizeof(uint32_t) * std::max<size_t>(R.src.n, 1));   // rank of every point in its cell
-            RESERVE(S.s_tile_sums, sizeof(uint32_t) * ((size_t)(ncs + 2047) / 2048 + 1));
-            launch_grid_count_scan(R.src, gs, S.s_cell_of_point.as<uint32_t>(), S.s_cell_start.as<uint32_t>(),
-                                   S.s_fill.as<uint32_t>(), S.s_tile_sums.as<uint32_t>(), S.total.as<uint32_t>() + 2,
-                                   ctx->stream);
+            const GridDesc gs = hilbert_sort_desc(slo, 1.0 / hs, fbits);
+            if (!S.src_sort.reserve(n_src, gs.nx * gs.ny * gs.nz)) return M3D_ERR_DEVICE;
+            launch_grid_count_scan(R.src, gs, S.src_sort, ctx->stream);
             const uint32_t np = R.src.n_pad;
             RESERVE(S.sx, sizeof(double) * np);
             RESERVE(S.sy, sizeof(double) * np);
@@ -517,8 +444,7 @@ int m3d_reg::setup(const double* src, const double* dst, const size_t* corr_src,
             launch_fill_nan(S.sx.as<double>(), np, ctx->stream);
             launch_fill_nan(S.sy.as<double>(), np, ctx->stream);
             launch_fill_nan(S.sz.as<double>(), np, ctx->stream);
-            launch_grid_scatter(R.src, S.s_cell_of_point.as<uint32_t>(), S.s_cell_start.as<uint32_t>(),
-                                S.s_fill.as<uint32_t>(), S.sx.as<double>(), S.sy.as<double>(), S.sz.as<double>(), ctx->stream);
+            launch_grid_scatter(R.src, S.src_sort, S.sx.as<double>(), S.sy.as<double>(), S.sz.as<double>(), ctx->stream);
             src_sorted.x = S.sx.as<double>();
             src_sorted.y = S.sy.as<double>();
             src_sorted.z = S.sz.as<double>();
@@ -653,13 +579,13 @@ int m3d_reg::ensure_cache(uint32_t s_pad) {
         const size_t ncell = (size_t)g.nx * g.ny * g.nz;
         RESERVE(S.cc_ring, ncell);
         RESERVE(S.cc_ring_tmp, 2 * ncell);
-        launch_reg_rings(g, S.cell_start.as<uint32_t>(), S.cc_ring.as<uint8_t>(), S.cc_ring_tmp.as<uint8_t>(), g.K + 1, ctx->stream);
+        launch_reg_rings(g, S.tgt.start.as<uint32_t>(), S.cc_ring.as<uint8_t>(), S.cc_ring_tmp.as<uint8_t>(), g.K + 1, ctx->stream);
         S.cc_ring_tmp.release();
         cache.ring = S.cc_ring.as<uint8_t>();
         g.ring = cache.ring;     // the walk's outer search looks them up as well (nearest_d2)
         R.g = g;
     }
-    launch_reg_cache_build(src_sorted, best_T_dev, g, S.cell_start.as<uint32_t>(), S.qx.as<double>(), S.qy.as<double>(),
+    launch_reg_cache_build(src_sorted, best_T_dev, g, S.tgt.start.as<uint32_t>(), S.qx.as<double>(), S.qy.as<double>(),
                            S.qz.as<double>(), cache, ctx->stream);
     cache_valid = true;
     cache_ref_index = best_index;
@@ -701,7 +627,7 @@ int m3d_reg::validate(size_t s_begin, size_t s_end, uint32_t* counts_out, double
             if (rcache != M3D_OK) return rcache;
         }
         // bound-and-prune against the best of EARLIER chunks (m3d_config.reg_prune = 0 switches it off)
-        const uint32_t rows = launch_reg_validate(src_sorted, Ts, s_pad, g, S.cell_start.as<uint32_t>(),
+        const uint32_t rows = launch_reg_validate(src_sorted, Ts, s_pad, g, S.tgt.start.as<uint32_t>(),
                             S.qx.as<double>(), S.qy.as<double>(), S.qz.as<double>(),
                             S.partial.as<uint32_t>(), S.partial_sum.as<double>(), S.sum2.as<double>(),
                             reg_prune ? best_cnt : 0u, (uint32_t)n_src, S.keep.as<uint8_t>(), ctx->stream, best_sum2, ns,
@@ -1239,7 +1165,7 @@ int m3d_registration_icp(const double* src, size_t n_src, const double* dst, siz
             RESERVE(d2, sizeof(double) * n);
             RESERVE(S.vals, sizeof(double) * n);
             RESERVE(S.block_counts, sizeof(uint32_t) * ((size_t)nb + 1));
-            RESERVE(S.total, 16);
+            RESERVE(S.tgt.total, 16);
             RESERVE(S.sums, sizeof(double) * 32);
             RESERVE(S.partial_sum, sizeof(double) * 256 * 16);
             RESERVE(S.one_T, sizeof(double) * kRegTStride);
@@ -1266,7 +1192,7 @@ int m3d_registration_icp(const double* src, size_t n_src, const double* dst, siz
             double hs[18];   // sums of the correspondence set for umeyama (filled by result())
             // GetRegistrationResultAndCorrespondences: nearest target point within the radius, count + error2
             auto result = [&]() -> int {
-                launch_icp_nn(px, py, pz, n, g, S.cell_start.as<uint32_t>(), S.qx.as<double>(), S.qy.as<double>(),
+                launch_icp_nn(px, py, pz, n, g, S.tgt.start.as<uint32_t>(), S.qx.as<double>(), S.qy.as<double>(),
                               S.qz.as<double>(), S.cell_orig.as<uint32_t>(), nn.as<uint32_t>(), d2.as<double>(),
                               ctx->stream);
                 launch_icp_err(d2.as<double>(), n, g.r2, S.partial_sum.as<double>(), S.sums.as<double>() + 24, ctx->stream);
@@ -1421,21 +1347,22 @@ int m3d::information_matrix_on(DeviceCtx* ctx, m3d_cloud* csrc, m3d_cloud* cdst,
             RESERVE(S.sums, sizeof(double) * 32);
             RESERVE(S.partial_sum, sizeof(double) * 256 * 16);
             RESERVE(S.one_T, sizeof(double) * kRegTStride);
-            RESERVE(S.block_counts, sizeof(uint32_t) * ((size_t)(n + 2047) / 2048 + 1));
-            RESERVE(S.total, 16);
+            const uint32_t nb = (n + 2047) / 2048;
+            RESERVE(S.block_counts, sizeof(uint32_t) * ((size_t)nb + 1));
+            RESERVE(S.tgt.total, 16);
             RESERVE(S.vals, sizeof(double) * n);
             RESERVE(ctx->h_small, 512);
             HIPCHK(hipMemcpyAsync(S.one_T.p, T, sizeof(double) * 12, hipMemcpyHostToDevice, ctx->stream));
             launch_icp_transform(sv.x, sv.y, sv.z, n, S.one_T.as<double>(), mx.as<double>(), my.as<double>(),
                                  mz.as<double>(), ctx->stream);
-            launch_icp_nn(mx.as<double>(), my.as<double>(), mz.as<double>(), n, g, G.cell_start.as<uint32_t>(),
+            launch_icp_nn(mx.as<double>(), my.as<double>(), mz.as<double>(), n, g, G.tgt.start.as<uint32_t>(),
                           G.qx.as<double>(), G.qy.as<double>(), G.qz.as<double>(), G.cell_orig.as<uint32_t>(),
                           nn.as<uint32_t>(), d2.as<double>(), ctx->stream);
-            launch_compact_vals(d2.as<double>(), n, g.r2, S.block_counts.as<uint32_t>(), S.total.as<uint32_t>(),
+            launch_compact_vals(d2.as<double>(), n, g.r2, S.block_counts.as<uint32_t>(), S.tgt.total.as<uint32_t>(),
                                 S.vals.as<double>(), ctx->stream);   // only for the count
             launch_info_sums(n, dv, nn.as<uint32_t>(), S.partial_sum.as<double>(), S.sums.as<double>(), ctx->stream);
             uint8_t* h = ctx->h_small.as<uint8_t>();
-            HIPCHK(hipMemcpyAsync(h, S.total.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipMemcpyAsync(h, S.tgt.total.p, 4, hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(hipMemcpyAsync(h + 8, S.sums.p, sizeof(double) * 9, hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(hipGetLastError());
             if (const int wr = stream_wait_spin(ctx); wr != M3D_OK) return wr;
@@ -1522,9 +1449,9 @@ int m3d_detect_boundary_points(const double* xyz, const double* normals, size_t 
             if (rg != M3D_OK) return rg;
             RESERVE(flags, (size_t)v.n + 8);
             HIPCHK(hipMemsetAsync(flags.p, 0, (size_t)v.n + 8, ctx->stream));
-            launch_boundary(v, g, S.cell_start.as<uint32_t>(), S.qx.as<double>(), S.qy.as<double>(), S.qz.as<double>(),
+            launch_boundary(v, g, S.tgt.start.as<uint32_t>(), S.qx.as<double>(), S.qy.as<double>(), S.qz.as<double>(),
                             S.cell_orig.as<uint32_t>(), search, max_nn, angle_threshold_deg, flags.as<uint8_t>(),
-                            flags.as<uint8_t>() + v.n, ctx->stream, S.total.as<uint32_t>());
+                            flags.as<uint8_t>() + v.n, ctx->stream, S.tgt.total.as<uint32_t>());
             std::vector<uint8_t> hf((size_t)v.n + 8);
             HIPCHK(hipMemcpyAsync(hf.data(), flags.p, hf.size(), hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(hipGetLastError());

@@ -87,3 +87,15 @@ def test_candidate_cache_certificates_hold_on_the_host():
     for target in ("test_reg_cache_inflate_r", "test_reg_cache_no_slack"):
         r = subprocess.run([os.path.join(cpp, "_build", target), "300"], capture_output=True, text=True, timeout=300)
         assert r.returncode != 0 and "violations 0" not in r.stdout, (target, r.stdout)
+
+
+def test_grid_geometry_is_pinned_on_the_host():
+    """tests/cpp/test_grid_geom.cpp compiles misc3d_amd/csrc/m3d_grid_geom.hpp -- the arithmetic every cell-sorted grid is built
+    from -- with g++ and compares radius_grid_geom's K, cell edge, dimensions and origin with == against rows worked out by
+    hand from its definition (K kept, K halved and the cell doubled, a single point), checks
+    that an extent no finite cell holds returns with a non-finite edge instead of spinning, and sort_grid_bits /
+    sort_grid_inv_h of the Hilbert sorts at every step."""
+    cpp = os.path.join(ROOT, "tests", "cpp")
+    subprocess.run(["make", "-C", cpp, "_build/test_grid_geom"], check=True, capture_output=True)
+    r = subprocess.run([os.path.join(cpp, "_build", "test_grid_geom")], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and r.stdout.rstrip().endswith("OK") and "FAILED" not in r.stdout, r.stdout + r.stderr
