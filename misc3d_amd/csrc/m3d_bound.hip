@@ -34,23 +34,11 @@
 #include "m3d_config.hpp"
 #include "m3d_eig3.hpp"
 #include "m3d_fp.hpp"
+#include "m3d_wave.hpp"
 
 #pragma clang fp contract(off)
 
 namespace m3d {
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_min(double v) {
-    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
-    return v;
-}
 
 constexpr int kFrameLevels = 12;   // residual levels of the candidate search: factor 2 each, from extent / 2^11 to extent
 
@@ -148,7 +136,7 @@ __global__ __launch_bounds__(64) void tile_frames_k(const double* __restrict__ s
         }
     }
     uint32_t key = (cand_ok && found) ? ((lev_s << 16) | ((1023u - min(cnt_s, 1023u)) << 6) | (uint32_t)lane) : 0xFFFFFFFFu;
-    for (int off = 32; off > 0; off >>= 1) key = min(key, (uint32_t)__shfl_xor((int)key, off, 64));
+    key = wave_min(key);
     double e[3] = {0.0, 0.0, 1.0}, c[3] = {bc[0], bc[1], bc[2]}, band = INFINITY;
     if (key != 0xFFFFFFFFu) {   // (wave-uniform)
         const int kb = (int)(key & 63u);
@@ -226,12 +214,7 @@ __global__ __launch_bounds__(64) void tile_frames_k(const double* __restrict__ s
     __syncthreads();
     {   // cum[k] = points with bin < k, k = 0 .. kBoundBins + 2
         const uint32_t h0 = hist[2 * lane], h1 = hist[2 * lane + 1];
-        uint32_t incl = h0 + h1;
-        const uint32_t own = incl;
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t t = (uint32_t)__shfl_up((int)incl, off, 64);
-            if (lane >= off) incl += t;
-        }
+        const uint32_t own = h0 + h1, incl = wave_incl_scan(own, lane);
         const uint32_t excl = incl - own;
         cm[2 * lane] = (uint16_t)excl;
         cm[2 * lane + 1] = (uint16_t)(excl + h0);

@@ -36,6 +36,7 @@
 #include "m3d_config.hpp"
 #include "m3d_fp.hpp"
 #include "m3d_tile_count.hpp"
+#include "m3d_wave.hpp"
 
 #pragma clang fp contract(off)
 
@@ -648,20 +649,20 @@ __global__ __launch_bounds__(64) void lead_fold_keep_k(const uint32_t* __restric
         if (ok && c) key = max(key, ((unsigned long long)c << 32) | (0xFFFFFFFFu - h));
         if (ok && c) key2 = max(key2, ((unsigned long long)c << 32) | h);
     }
-    for (int off = 32; off > 0; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off, 64));
+    v = wave_max(v);
     if (blockIdx.x == 0 && threadIdx.x == 0 && v) atomicMax(best_count, v);
     if (zero && blockIdx.x == 0) {   // block-uniform: what the pair counters hold now is the lead pass' share (m3d_stats.pairs_lead)
         uint32_t* __restrict__ pair_rep = zero + (size_t)kCountReplicas * rep_stride;
         uint32_t p = 0;
         for (int r = threadIdx.x; r < kPairMain; r += 64) p += pair_rep[r];
-        for (int off = 32; off > 0; off >>= 1) p += (uint32_t)__shfl_xor((int)p, off, 64);
+        p = wave_sum(p);
         if (threadIdx.x == 0) pair_rep[kPairLead] = p;
     }
     if (pick_key && blockIdx.x == 0) {   // block-uniform
-        for (int off = 32; off > 0; off >>= 1) key = max(key, (unsigned long long)__shfl_xor((long long)key, off, 64));
+        key = wave_max(key);
         if (threadIdx.x == 0 && key) atomicMax(pick_key, key);
         if (pick_key2) {
-            for (int off = 32; off > 0; off >>= 1) key2 = max(key2, (unsigned long long)__shfl_xor((long long)key2, off, 64));
+            key2 = wave_max(key2);
             if (threadIdx.x == 0 && key2) atomicMax(pick_key2, key2);
         }
     }
@@ -1025,12 +1026,7 @@ __device__ __forceinline__ void score_screen_body(const double* __restrict__ sx,
     } else {
         if (wave == 0) {   // lane l expands its own word behind the words before it (ascending ids)
             const uint32_t pc = (uint32_t)__popcll(mm);
-            uint32_t incl = pc;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t t = (uint32_t)__shfl_up((int)incl, off, 64);
-                if (lane >= off) incl += t;
-            }
+            const uint32_t incl = wave_incl_scan(pc, lane);
             if (lane == 63) s_total = incl;
             uint32_t at = incl - pc;
             unsigned long long w = mm;
@@ -1306,7 +1302,7 @@ __global__ void sum_replicas_k(const uint32_t* __restrict__ counts_rep, uint32_t
     }
     if (best_count) {   // wave-uniform
         uint32_t v = ok ? c : 0u;
-        for (int off = 32; off > 0; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off, 64));
+        v = wave_max(v);
         if ((threadIdx.x & 63) == 0 && v) atomicMax(best_count, v);
     }
     if (!pf.pick) return;   // (kernel argument: uniform)
@@ -1315,11 +1311,11 @@ __global__ void sum_replicas_k(const uint32_t* __restrict__ counts_rep, uint32_t
     __shared__ uint32_t s_last, s_take, s_idx, s_tie;
     {
         unsigned long long key = (ok && c) ? (((unsigned long long)c << 32) | (0xFFFFFFFFu - h)) : 0ull;
-        for (int off = 32; off > 0; off >>= 1) key = max(key, (unsigned long long)__shfl_xor((long long)key, off, 64));
+        key = wave_max(key);
         if ((threadIdx.x & 63) == 0 && key) atomicMax(pf.key, key);
         if (pf.key2) {   // (kernel argument: uniform) the HIGHEST index among the best counts: differs from the lowest = a tie
             unsigned long long key2 = (ok && c) ? (((unsigned long long)c << 32) | h) : 0ull;
-            for (int off = 32; off > 0; off >>= 1) key2 = max(key2, (unsigned long long)__shfl_xor((long long)key2, off, 64));
+            key2 = wave_max(key2);
             if ((threadIdx.x & 63) == 0 && key2) atomicMax(pf.key2, key2);
         }
     }
@@ -1665,7 +1661,7 @@ __global__ void count_bits_k(const unsigned long long* __restrict__ masks, const
     const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
     unsigned long long c = 0;
     if (i < (size_t)n_tiles * n_groups) c = (unsigned long long)__popcll(masks[i] & keep[i % n_groups]);
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(total, c);
 }
 void launch_count_bits(const unsigned long long* masks, const unsigned long long* keep, uint32_t n_tiles,

@@ -13,6 +13,7 @@
 
 #include "m3d_fpfh.hpp"
 #include "m3d_fpfh_fp.hpp"
+#include "m3d_wave.hpp"
 
 #pragma clang fp contract(off)
 
@@ -50,8 +51,7 @@ __global__ __launch_bounds__(256) void fpfh_count_k(const double* __restrict__ l
         cnt[t] = m;
     }
     unsigned long long s = m;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor((unsigned long long)s, off, 64);
+    s = wave_sum(s);
     if ((threadIdx.x & 63) == 0 && s) atomicAdd(pairs, s);
 }
 

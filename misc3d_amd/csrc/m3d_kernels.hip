@@ -24,6 +24,7 @@
 #include "m3d_poison.hpp"
 
 #include "m3d_fp.hpp"
+#include "m3d_wave.hpp"
 
 #pragma clang fp contract(off)
 
@@ -740,7 +741,7 @@ __global__ __launch_bounds__(256) void compact_write_k(
         } else {
             for (uint32_t i = threadIdx.x; i < tile; i += 256u) part += slots[i];
         }
-        for (int off = 32; off > 0; off >>= 1) part += (uint32_t)__shfl_xor((int)part, off, 64);
+        part = wave_sum(part);
         if (lane == 0) wsum[wave] = part;
         __syncthreads();
         row_base = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
@@ -815,7 +816,7 @@ __global__ __launch_bounds__(256) void compact_mask_tail_k(const uint32_t* __res
         if (counts_host) counts_host[i] = v;
         part += v;
     }
-    for (int off = 32; off > 0; off >>= 1) part += (uint32_t)__shfl_xor((int)part, off, 64);
+    part = wave_sum(part);
     if (lane == 0) wsum[wave] = part;
     if (tail.moment_partial) fold_moment_partials(tail);   // (ends with a barrier)
     else __syncthreads();

@@ -20,6 +20,7 @@
 
 #include "m3d_fp.hpp"
 #include "m3d_match_scan.hpp"
+#include "m3d_wave.hpp"
 
 #pragma clang fp contract(off)
 
@@ -166,7 +167,7 @@ __global__ __launch_bounds__(256) void nn64_verify_k(const double* __restrict__ 
         if (pm == -INFINITY) fallback = true;
         m = fminf(m, pm);
     }
-    for (int off = 4; off > 0; off >>= 1) m = fminf(m, __shfl_xor(m, off, 64));
+    m = wave_min<8>(m);
     const float win = m + (2.0f * (e_coeff * (qn2[i] + max_dn2) + e_abs) * 1.000001f + 1e-30f);
     if (!(win < INFINITY) && m < INFINITY) fallback = true;
     for (uint32_t s = sub; s < splits; s += 8)
@@ -485,7 +486,7 @@ __global__ __launch_bounds__(256) void mutual_count_k(const uint32_t* __restrict
     __shared__ uint32_t wsum[4];
     uint32_t j[kMutualPerThread];
     uint32_t c = __popc(mutual_flags(nn_ab, nn_ba, na, nb, blockIdx.x * kMutualPerBlock + threadIdx.x * kMutualPerThread, j));
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+    c = wave_sum(c);
     if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) block_count[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
@@ -522,11 +523,7 @@ __global__ __launch_bounds__(256) void mutual_write_k(const uint32_t* __restrict
     const uint32_t i0 = blockIdx.x * kMutualPerBlock + threadIdx.x * kMutualPerThread;
     const uint32_t bits = mutual_flags(nn_ab, nn_ba, na, nb, i0, j);
     const uint32_t c = __popc(bits), lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t incl = c;   // inclusive prefix over the wave's lanes
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t v = __shfl_up(incl, off, 64);
-        if ((int)lane >= off) incl += v;
-    }
+    const uint32_t incl = wave_incl_scan(c, (int)lane);
     if (lane == 63u) wsum[wave] = incl;
     __syncthreads();
     uint32_t at = block_offset[blockIdx.x] + incl - c;
@@ -778,7 +775,7 @@ __global__ __launch_bounds__(256) void nn64_verify_rev_k(const double* __restric
     const uint2* __restrict__ my = cand + (size_t)j * kRevCap;
     float m = INFINITY;
     for (uint32_t t = sub; t < c; t += 8) m = fminf(m, __uint_as_float(my[t].y));
-    for (int off = 4; off > 0; off >>= 1) m = fminf(m, __shfl_xor(m, off, 64));
+    m = wave_min<8>(m);
     const float win = m + (2.0f * (kMfmaECoeff * (qn2[j] + *max_dn2_p) + kMfmaEAbs) * 1.000001f + 1e-30f);
     double bd = INFINITY;
     uint32_t bi = 0xFFFFFFFFu;

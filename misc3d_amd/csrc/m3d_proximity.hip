@@ -14,6 +14,7 @@
 // with plain loads.
 #include <hip/hip_runtime.h>
 
+#include "m3d_grid_cell.hpp"
 #include "m3d_proximity.hpp"
 
 #pragma clang fp contract(off)
@@ -51,18 +52,6 @@ __device__ __forceinline__ void prox_unite(uint32_t* parent, uint32_t a, uint32_
     }
 }
 
-// the grid cell of a point (m3d_reg_kernels.hip's cell_of): false for NaN / outside [lo_pad, n - lo_pad)
-__device__ __forceinline__ bool prox_cell(const GridDesc& g, double x, double y, double z, int* ix, int* iy, int* iz) {
-    const double fx = (x - g.ox) * g.inv_h, fy = (y - g.oy) * g.inv_h, fz = (z - g.oz) * g.inv_h;
-    if (!(fx >= 1.0 && fx < (double)(g.nx - 1) && fy >= 1.0 && fy < (double)(g.ny - 1) && fz >= 1.0 &&
-          fz < (double)(g.nz - 1)))
-        return false;
-    *ix = (int)fx;
-    *iy = (int)fy;
-    *iz = (int)fz;
-    return true;
-}
-
 // visit(u, d2) for every grid slot u of the 3x3x3 block around sorted point t whose d2 is within the radius (t included)
 template <class F>
 __device__ __forceinline__ void prox_scan_block(const GridDesc& g, const uint32_t* __restrict__ cell_start,
@@ -70,11 +59,11 @@ __device__ __forceinline__ void prox_scan_block(const GridDesc& g, const uint32_
                                                 const double* __restrict__ qz, uint32_t t, F visit) {
     const double px = qx[t], py = qy[t], pz = qz[t];
     int ix, iy, iz;
-    if (!prox_cell(g, px, py, pz, &ix, &iy, &iz)) return;
+    if (!grid_cell(g, px, py, pz, 1, &ix, &iy, &iz)) return;
     for (int dz = -1; dz <= 1; ++dz)
         for (int dy = -1; dy <= 1; ++dy) {
-            const uint32_t row = ((uint32_t)(iz + dz) * g.ny + (uint32_t)(iy + dy)) * g.nx + (uint32_t)ix;
-            const uint32_t b = cell_start[row - 1], e = cell_start[row + 2];
+            uint32_t b, e;
+            grid_row_span(cell_start, grid_cell_id(g, ix, iy + dy, iz + dz), -1, 1, &b, &e);
             for (uint32_t u = b; u < e; ++u) {
                 const double d2 = prox_d2(px - qx[u], py - qy[u], pz - qz[u]);
                 if (prox_in_radius(d2, g.r2)) visit(u, d2);

@@ -42,8 +42,10 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "m3d_grid_cell.hpp"
 #include "m3d_reg_cache_fp.hpp"
 #include "m3d_reg_kernels.hpp"
+#include "m3d_wave.hpp"
 
 namespace m3d {
 
@@ -54,18 +56,6 @@ constexpr int kTiers = kRegCacheTiers;
 constexpr int kSlots = kTierK * kTiers;     // <= 128: the slot rides in seven mantissa bits
 static_assert(kSlots <= 128 && kSlots % 2 == 0 && kTierK % 2 == 0, "slot packing");
 // (every ring lives in registers: kSlots candidates in 3 kSlots VGPRs)
-
-__device__ __forceinline__ bool cache_cell_of(const GridDesc& g, double x, double y, double z, int lo_pad, int* ix, int* iy,
-                                              int* iz) {   // (m3d_reg_kernels.hip: cell_of)
-    const double fx = (x - g.ox) * g.inv_h, fy = (y - g.oy) * g.inv_h, fz = (z - g.oz) * g.inv_h;
-    if (!(fx >= (double)lo_pad && fx < (double)(g.nx - lo_pad) && fy >= (double)lo_pad && fy < (double)(g.ny - lo_pad) &&
-          fz >= (double)lo_pad && fz < (double)(g.nz - lo_pad)))
-        return false;
-    *ix = (int)fx;
-    *iy = (int)fy;
-    *iz = (int)fz;
-    return true;
-}
 
 // The target points of the (2B+1)^3 block around cell (ix, iy, iz), clipped to the table, dealt over the 64 lanes of ONE
 // wave: f(active, index into qx / qy / qz) is called by all lanes together (it may ballot).  A block is (2B+1)^2 x-rows
@@ -88,11 +78,7 @@ __device__ __forceinline__ void for_block_items(const GridDesc& g, const uint32_
             }
         }
         const uint32_t cnt = e - b;
-        uint32_t incl = cnt;
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t v = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += v;
-        }
+        const uint32_t incl = wave_incl_scan(cnt, lane);
         const uint32_t total = __shfl(incl, 63, 64);
         const uint32_t excl = incl - cnt;
         for (uint32_t t0 = 0; t0 < total; t0 += 64) {
@@ -196,7 +182,7 @@ __global__ __launch_bounds__(256) void reg_cache_build_k(const double* __restric
     if (fabs(px) < INFINITY && fabs(py) < INFINITY && fabs(pz) < INFINITY) {   // (NaN fails the comparisons; wave-uniform)
         int ix, iy, iz;
         const int K = g.K;
-        if (!cache_cell_of(g, px, py, pz, K, &ix, &iy, &iz)) {
+        if (!grid_cell(g, px, py, pz, K, &ix, &iy, &iz)) {
             // at least K + 1 cells outside the target's bounding box on some axis (the table carries 2K + 1 pad cells per side)
             for (int t = 0; t < kTiers; ++t) R[t] = (double)(K + 1) * h * (1.0 - 1e-5);
         } else {
@@ -441,7 +427,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                     if (!exact) {
                         int ix, iy, iz;
                         uint32_t rho = 255u;   // outside the table: 2K + 1 pad cells and more from every target point
-                        if (cache_cell_of(g, px, py, pz, 0, &ix, &iy, &iz))
+                        if (grid_cell(g, px, py, pz, 0, &ix, &iy, &iz))
                             rho = c.ring[((size_t)(uint32_t)iz * g.ny + (uint32_t)iy) * g.nx + (uint32_t)ix];
                         if (px != px || py != py || pz != pz) rho = 0u;   // (a NaN pose says nothing)
                         if (rho >= (uint32_t)g.K + 1u) {
@@ -459,7 +445,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                 fail = __ballot(!exact) != 0ull ? 1u : 0u;
                 cnt = (uint32_t)__popcll(__ballot(f));
                 sum = f ? (exact ? d2 : (double)lb2) : 0.0;
-                for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+                sum = wave_sum(sum);
             }
             acc = ((uint32_t)lane == ss) ? cnt : acc;
             acc_sum = ((uint32_t)lane == ss) ? sum : acc_sum;

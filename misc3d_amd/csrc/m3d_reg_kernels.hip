@@ -15,8 +15,10 @@
 #include <algorithm>
 #include <climits>
 
-#include "m3d_reg_fp.hpp"
 #include "m3d_eig3.hpp"
+#include "m3d_grid_cell.hpp"
+#include "m3d_reg_fp.hpp"
+#include "m3d_wave.hpp"
 
 #pragma clang fp contract(off)
 
@@ -77,37 +79,6 @@ void launch_gather_T(const double* T12, const uint32_t* list, uint32_t n, uint32
 // ------------------------------------------------------------------------------------------------
 // uniform grid over the target cloud (counting sort by cell)
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool cell_of(const GridDesc& g, double x, double y, double z, int lo_pad,
-                                        int* ix, int* iy, int* iz) {
-    const double fx = (x - g.ox) * g.inv_h, fy = (y - g.oy) * g.inv_h, fz = (z - g.oz) * g.inv_h;
-    // valid query cells are [lo_pad, n - 1 - lo_pad] (the table carries 2K+1 pad cells per side, so this admits
-    // every query within K cells of the bounding box); NaN fails every comparison
-    if (!(fx >= (double)lo_pad && fx < (double)(g.nx - lo_pad) && fy >= (double)lo_pad &&
-          fy < (double)(g.ny - lo_pad) && fz >= (double)lo_pad && fz < (double)(g.nz - lo_pad)))
-        return false;
-    *ix = (int)fx;
-    *iy = (int)fy;
-    *iz = (int)fz;
-    return true;
-}
-
-// cell_of + the position inside the cell as a fraction of its edge (the scaled coordinate's own fractional part: what
-// (int) dropped), for the fp32 offsets of sorted_walk32
-__device__ __forceinline__ bool cell_of_frac(const GridDesc& g, double x, double y, double z, int lo_pad, int* ix, int* iy,
-                                             int* iz, double* frx, double* fry, double* frz) {
-    const double fx = (x - g.ox) * g.inv_h, fy = (y - g.oy) * g.inv_h, fz = (z - g.oz) * g.inv_h;
-    if (!(fx >= (double)lo_pad && fx < (double)(g.nx - lo_pad) && fy >= (double)lo_pad &&
-          fy < (double)(g.ny - lo_pad) && fz >= (double)lo_pad && fz < (double)(g.nz - lo_pad)))
-        return false;
-    *ix = (int)fx;
-    *iy = (int)fy;
-    *iz = (int)fz;
-    *frx = fx - (double)*ix;   // (exact: fx >= 1 here, and both share their leading bits)
-    *fry = fy - (double)*iy;
-    *frz = fz - (double)*iz;
-    return true;
-}
-
 // hist[cell] counts the points of a cell; rank[i] = how many points of its cell had arrived before point i
 // (the value the counting add returns): the scatter then needs no second round of atomics.
 __global__ void grid_count_k(CloudView dst, GridDesc g, uint32_t* __restrict__ cell_of_point,
@@ -116,7 +87,7 @@ __global__ void grid_count_k(CloudView dst, GridDesc g, uint32_t* __restrict__ c
     if (i >= dst.n) return;
     int ix, iy, iz;
     uint32_t cid = 0xFFFFFFFFu;  // points with NaN/inf coordinates are left out of the grid
-    if (cell_of(g, dst.x[i], dst.y[i], dst.z[i], 0, &ix, &iy, &iz)) {
+    if (grid_cell(g, dst.x[i], dst.y[i], dst.z[i], 0, &ix, &iy, &iz)) {
         if (g.morton_bits) {  // Z-order cell id: consecutive cells form compact cubes
             auto spread = [](uint32_t v) {  // 10 bits -> every third bit
                 v = (v | (v << 16)) & 0x030000FFu;
@@ -163,7 +134,7 @@ __global__ void grid_count_k(CloudView dst, GridDesc g, uint32_t* __restrict__ c
                 cid = spread(X0) | (spread(X1) << 1) | (spread(X2) << 2);
             }
         } else {
-            cid = ((uint32_t)iz * g.ny + (uint32_t)iy) * g.nx + (uint32_t)ix;
+            cid = grid_cell_id(g, ix, iy, iz);
         }
         rank[i] = atomicAdd(&hist[cid], 1u);
     }
@@ -182,12 +153,7 @@ __global__ __launch_bounds__(256) void tile_scan_k(uint32_t* __restrict__ v, uin
         e[k] = base + k < n ? v[base + k] : 0u;
         s += e[k];
     }
-    // wave inclusive scan of s
-    uint32_t incl = s;
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
+    const uint32_t incl = wave_incl_scan(s, lane);
     if (lane == 63) wsum[wave] = incl;
     __syncthreads();
     uint32_t woff = 0;
@@ -293,8 +259,9 @@ __global__ void nl_count_k(GridDesc g, const uint32_t* __restrict__ cell_start, 
     if (ix >= 1 && ix + 1 < g.nx && iy >= 1 && iy + 1 < g.ny && iz >= 1 && iz + 1 < g.nz)
         for (int dz = -1; dz <= 1; ++dz)
             for (int dy = -1; dy <= 1; ++dy) {
-                const uint32_t row = ((iz + dz) * g.ny + (iy + dy)) * g.nx + ix;
-                cnt += cell_start[row + 2] - cell_start[row - 1];
+                uint32_t b, e;
+                grid_row_span(cell_start, grid_cell_id(g, (int)ix, (int)iy + dy, (int)iz + dz), -1, 1, &b, &e);
+                cnt += e - b;
             }
     nl_start[c] = cnt;
 }
@@ -309,8 +276,8 @@ __global__ void nl_fill_k(GridDesc g, const uint32_t* __restrict__ cell_start, u
     const uint32_t ix = c % g.nx, iy = (c / g.nx) % g.ny, iz = c / (g.nx * g.ny);
     for (int dz = -1; dz <= 1; ++dz)
         for (int dy = -1; dy <= 1; ++dy) {
-            const uint32_t row = ((iz + dz) * g.ny + (iy + dy)) * g.nx + ix;
-            const uint32_t b = cell_start[row - 1], e = cell_start[row + 2];
+            uint32_t b, e;
+            grid_row_span(cell_start, grid_cell_id(g, (int)ix, (int)iy + dy, (int)iz + dz), -1, 1, &b, &e);
             for (uint32_t k = b; k < e; ++k)
                 nl_pts[pos++] = make_double4(qx[k], qy[k], qz[k], orig ? (double)orig[k] : 0.0);
         }
@@ -493,7 +460,7 @@ void launch_nl_fill(const GridDesc& g, const uint32_t* cell_start, const uint32_
 // assignment, see axis_gap).
 __device__ __forceinline__ double axis_gap(int d, double f, double h) {
     // query at fraction f in [0,1) of its cell; cells at offset d span [d, d+1) in the same units.
-    // Slack 1e-6 cell edges: cell_of evaluates (x - o) * inv_h with two roundings, relative error < 3 * 2^-53
+    // Slack 1e-6 cell edges: grid_cell evaluates (x - o) * inv_h with two roundings, relative error < 3 * 2^-53
     // of a value below 2^27, i.e. below 5e-8 edges, for the query and for the stored point alike.
     const double g = d > 0 ? (double)d - f : (d < 0 ? f - (double)(d + 1) : 0.0);
     const double gs = g - 1e-6;
@@ -754,23 +721,23 @@ __device__ __forceinline__ double nearest_d2(const GridDesc& g, const uint32_t* 
     double best = INFINITY;
     if (SCREEN) {
         double frx, fry, frz;
-        if (!cell_of_frac(g, px, py, pz, g.K, &ix, &iy, &iz, &frx, &fry, &frz)) {
+        if (!grid_cell_frac(g, px, py, pz, g.K, &ix, &iy, &iz, &frx, &fry, &frz)) {
 #ifdef M3D_REG_TRIP_STATS
             if (g.nl32_fallbacks) atomicAdd(g.nl32_fallbacks + 41, 1ull);
 #endif
             return best;
         }
-        const uint32_t cell = ((uint32_t)iz * g.ny + (uint32_t)iy) * g.nx + (uint32_t)ix;
+        const uint32_t cell = grid_cell_id(g, ix, iy, iz);
         best = sorted_walk32(g, cell, frx, fry, frz, px, py, pz);
-    } else if (!cell_of(g, px, py, pz, g.K, &ix, &iy, &iz)) {
+    } else if (!grid_cell(g, px, py, pz, g.K, &ix, &iy, &iz)) {
         return best;
     } else if (g.nl_start && g.nl_sorted) {
-        const uint32_t cell = ((uint32_t)iz * g.ny + (uint32_t)iy) * g.nx + (uint32_t)ix;
+        const uint32_t cell = grid_cell_id(g, ix, iy, iz);
         best = sorted_walk64(g, cell, px, py, pz);
     } else if (g.nl_start) {
         // the 3x3x3 block of this cell as ONE contiguous list (nl_fill_k): two dependent loads instead of
         // nine row ranges + nine gathers; 4 candidates per trip, the tail repeats the last one (min is idempotent)
-        const uint32_t cell = ((uint32_t)iz * g.ny + (uint32_t)iy) * g.nx + (uint32_t)ix;
+        const uint32_t cell = grid_cell_id(g, ix, iy, iz);
         const uint32_t b = g.nl_start[cell], e = g.nl_start[cell + 1];
         if (b < e) {
             // software pipeline: the loads of trip t+1 are in flight while trip t is evaluated
@@ -947,7 +914,7 @@ __global__ __launch_bounds__(256) void reg_validate_k(const double* __restrict__
                     cnt += (uint32_t)__popcll(__ballot(f));
                     sum += f ? d2 : 0.0;
                 }
-                for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+                sum = wave_sum(sum);
             }
             acc = ((uint32_t)lane == ss) ? cnt : acc;
             acc_sum = ((uint32_t)lane == ss) ? sum : acc_sum;
@@ -1014,7 +981,7 @@ __global__ __launch_bounds__(256) void reg_validate_pairs_k(const double* __rest
             const bool f = d2 < g.r2;
             cnt = (uint32_t)__popcll(__ballot(f));
             sum = f ? d2 : 0.0;
-            for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+            sum = wave_sum(sum);
         }
         if (lane == 0) {
             red[wave] = cnt;
@@ -1383,10 +1350,10 @@ __device__ __forceinline__ void nearest_idx(const GridDesc& g, const uint32_t* _
     uint32_t bo = 0xFFFFFFFFu;
     *d2_out = best;
     *idx_out = bo;
-    if (!cell_of(g, px, py, pz, g.K, &ix, &iy, &iz)) return;
+    if (!grid_cell(g, px, py, pz, g.K, &ix, &iy, &iz)) return;
     bool need_scan = true;
     if (g.nl_start) {
-        const uint32_t cell = ((uint32_t)iz * g.ny + (uint32_t)iy) * g.nx + (uint32_t)ix;
+        const uint32_t cell = grid_cell_id(g, ix, iy, iz);
         const uint32_t b = g.nl_start[cell], e = g.nl_start[cell + 1];
         for (uint32_t c = b; c < e; ++c) {
             const double4 q = g.nl_pts[c];
@@ -1627,7 +1594,7 @@ __global__ __launch_bounds__(64) void boundary_k(CloudView c, GridDesc g, const 
     const uint32_t i = cell_orig[t_sorted];
     const double px = qx[t_sorted], py = qy[t_sorted], pz = qz[t_sorted];
     int ix, iy, iz;
-    if (!cell_of(g, px, py, pz, g.K, &ix, &iy, &iz)) return;
+    if (!grid_cell(g, px, py, pz, g.K, &ix, &iy, &iz)) return;
     __shared__ double s_nd[LDS32 ? 32 * 64 : 1];
     __shared__ uint32_t s_ni[LDS32 ? 32 * 64 : 1];
     double nd_l[LDS32 ? 1 : kBoundaryMaxNb];

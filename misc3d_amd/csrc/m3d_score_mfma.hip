@@ -40,6 +40,7 @@
 #include "m3d_config.hpp"
 #include "m3d_fp.hpp"
 #include "m3d_tile_count.hpp"
+#include "m3d_wave.hpp"
 
 #pragma clang fp contract(off)
 
@@ -215,12 +216,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
     // ---- wave 0: the surviving hypotheses' ids (relative to g0), ascending: lane l expands its own word behind the words before it
     if (wave == 0) {
         const uint32_t pc = (uint32_t)__popcll(mm);
-        uint32_t incl = pc;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t t = (uint32_t)__shfl_up((int)incl, off, 64);
-            if (lane >= off) incl += t;
-        }
+        const uint32_t incl = wave_incl_scan(pc, lane);
         if (lane == 63) s_total = incl;
         uint32_t at = incl - pc;
         unsigned long long w = mm;

@@ -99,3 +99,16 @@ def test_grid_geometry_is_pinned_on_the_host():
     subprocess.run(["make", "-C", cpp, "_build/test_grid_geom"], check=True, capture_output=True)
     r = subprocess.run([os.path.join(cpp, "_build", "test_grid_geom")], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and r.stdout.rstrip().endswith("OK") and "FAILED" not in r.stdout, r.stdout + r.stderr
+
+
+def test_grid_cell_lookup_is_pinned_on_the_host():
+    """tests/cpp/test_grid_cell.cpp compiles misc3d_amd/csrc/m3d_grid_cell.hpp -- the cell lookup grid_count_k assigns the points
+    with and every grid search finds them with -- with g++ and compares grid_cell / grid_cell_frac with == (return value, indices,
+    fractions) against the expression the kernels carried before, on a million random points per descriptor (NaN, +-inf) and on
+    the cell faces around lo_pad and n - lo_pad with their neighbouring doubles; checks the padding contract of radius_grid_geom
+    (every point of the box has a cell, every query within one edge of it has one with lo_pad = K and its (2K + 1)^2 x-row spans
+    stay inside the table) for K kept, K halved, the cell doubled and a single point; and grid_cell_id / grid_row_span by hand."""
+    cpp = os.path.join(ROOT, "tests", "cpp")
+    subprocess.run(["make", "-C", cpp, "_build/test_grid_cell"], check=True, capture_output=True)
+    r = subprocess.run([os.path.join(cpp, "_build", "test_grid_cell")], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and r.stdout.rstrip().endswith("OK") and "FAILED" not in r.stdout, r.stdout + r.stderr
