@@ -565,12 +565,69 @@ int m3d_registration_icp(const double *src, size_t n_src, const double *dst, siz
                          double relative_fitness, double relative_rmse, int device, double T[16],
                          m3d_icp_stats *stats, int64_t *correspondences);
 
+/* ---- point-to-plane ICP: LocalRefineMethod::Point2PlaneICP of MultiScaleICP, src/pipeline.cpp:949-955 ------------- */
+/* RegistrationICP(source, target, max_correspondence_distance, init, TransformationEstimationPointToPlane(),
+ * ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration)).  The arguments of m3d_registration_icp plus
+ * dst_normals (n_dst x 3, used as given: not normalised).  The outer loop, stats and correspondences are those of
+ * m3d_registration_icp; only ComputeTransformation differs.
+ * [RECALL] Open3D 0.15.1 TransformationEstimationPointToPlane::ComputeTransformation, restated (tests/cpp/icp_ref.c is the
+ * checker), over the correspondence set (i, j = nn[i]) with the moving point s as currently transformed:
+ *   1. dst_normals == NULL: M3D_ERR_INVALID_ARG "TransformationEstimationPointToPlane and
+ *      TransformationEstimationColoredICP require pre-computed normal vectors for target PointCloud."
+ *      max_correspondence_distance <= 0 or NaN: M3D_ERR_INVALID_ARG "Invalid max_correspondence_distance." (checked first).
+ *   2. r = (s - t_j) . n_j; J = [s x n_j, n_j] (6 values), cross = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0).
+ *   3. JTJ = sum J J^T (21 distinct sums), JTr = sum J r (6 sums); the loss is L2 (weight 1).
+ *   4. an empty correspondence set: the update is the identity.
+ *   5. det(JTJ) (partial-pivot LU) not finite or |det| < 1e-6: the update is the identity (SolveLinearSystemPSD's check).
+ *   6. otherwise x = LDLT(JTJ).solve(-JTr) and update = [Rz(x2) Ry(x1) Rx(x0) | x3, x4, x5] (TransformVector6dToMatrix4d).
+ *   7. fitness and inlier_rmse are the Euclidean ones of GetRegistrationResultAndCorrespondences (nearest target point within
+ *      the distance, lowest index on exact ties); the point-to-plane r^2 does not feed the stop rule.
+ *   8. ORDER (ours): the sums are tree sums of a fixed shape -- equal bits from run to run -- not the serial sums of a
+ *      one-thread loop: poses agree with the restatement to 1e-9, correspondence sets and iteration counts exactly on
+ *      well-conditioned inputs.
+ * Device ("Multi-scale ICP"): one fused launch per iteration (update, search, gather, 30 sums) and one small
+ * launch that adds the workgroups' records; the 6 x 6 solve is the host's (misc3d_amd/csrc/m3d_icp_fp.hpp). */
+int m3d_registration_icp_plane(const double *src, size_t n_src, const double *dst, const double *dst_normals, size_t n_dst,
+                               double max_correspondence_distance, const double *T_init, int max_iteration,
+                               double relative_fitness, double relative_rmse, int device, double T[16],
+                               m3d_icp_stats *stats, int64_t *correspondences);
+
 /* open3d::pipelines::registration::GetInformationMatrixFromPointClouds(source, target, max_dist, T): the
  * acceptance test of ReconstructionPipeline::GlobalRegistration, src/pipeline.cpp:818-824.
  * info: 6 x 6 row-major; info[35] == *n_correspondences (may be NULL). */
 int m3d_information_matrix(const double *src, size_t n_src, const double *dst, size_t n_dst,
                            double max_correspondence_distance, const double *T, int device, double info[36],
                            uint64_t *n_correspondences);
+
+/* ---- ReconstructionPipeline::MultiScaleICP, src/pipeline.cpp:927-982 -------------------------------------------------
+ * What RegisterFragmentPair (:754-763: {voxel}, {50}) and RefineFragmentPair (:686-697: {v, v/2, v/4}, {50, 30, 15}) call.
+ * Per level l: both clouds down-sampled with voxel_sizes[l] FROM THE ORIGINAL CLOUDS by the voxel contract above (target
+ * normals are the per-voxel means, not re-normalised), then ICP with ICPConvergenceCriteria(1e-6, 1e-6, max_iters[l]) seeded
+ * with the previous level's pose (level 0: T_init, NULL = identity) and max_correspondence_distance at every level (the
+ * reference passes config.voxel_size * 1.4, :936).  After the last level info = GetInformationMatrixFromPointClouds(src, dst,
+ * voxel_sizes[last] * 1.4, T) on the original clouds (:975-979).  The result equals m3d_voxel_down_sample_multi,
+ * m3d_registration_icp / m3d_registration_icp_plane and m3d_information_matrix chained by the caller, bit for bit.
+ * method: PipelineConfig::LocalRefineMethod.  src_normals: n_src x 3 or NULL (not read by methods 0 and 1).
+ * T: 4 x 4 row-major, info: 6 x 6 row-major.  levels: n_levels records or NULL.
+ * M3D_ERR_INVALID_ARG, all before any device work: n_levels == 0 (the reference returns an uninitialised matrix); method 2
+ * or 3 (not accelerated: the message says so) or any other value; method 1 without dst_normals (rule 1 above); a voxel
+ * size the voxel contract's rule 1 rejects, whatever its level; max_correspondence_distance <= 0; 2^30 points or more.
+ * The whole call runs on one lane of the device.  Re-entrant: concurrent calls take lanes. */
+#define M3D_REFINE_POINT2POINT_ICP 0
+#define M3D_REFINE_POINT2PLANE_ICP 1
+#define M3D_REFINE_COLORED_ICP 2      /* not accelerated */
+#define M3D_REFINE_GENERALIZED_ICP 3  /* not accelerated */
+typedef struct m3d_multi_scale_icp_level {
+    uint64_t n_src, n_dst;   /* rows of the level's down-sampled clouds */
+    m3d_icp_stats icp;       /* the level's ICP */
+    double ms_down_sample;   /* both clouds' level, host clock (level 0 carries the two uploads and the bounds) */
+    double ms_icp;           /* the level's ICP call: upload of the level, grid, iterations */
+    double ms_information;   /* the information matrix (last level only) */
+} m3d_multi_scale_icp_level;
+int m3d_multi_scale_icp(const double *src, const double *src_normals, size_t n_src, const double *dst,
+                        const double *dst_normals, size_t n_dst, const double *voxel_sizes, const int *max_iters,
+                        size_t n_levels, double max_correspondence_distance, int method, const double *T_init, int device,
+                        double T[16], double info[36], m3d_multi_scale_icp_level *levels);
 
 /* ---- ReconstructionPipeline::GlobalRegistration (Ransac method), src/pipeline.cpp:790-828, and its caller's shape: one
  * std::thread per fragment pair, src/pipeline.cpp:428-439 ----------------------------------------------

@@ -21,6 +21,8 @@ Drop-in for the reference's python API on this path (module layout of python/py_
     normals  = m3d.common.estimate_normals(pcd, (848, 480), 3)
     ok, T, info = m3d.reconstruction.global_registration(frag_s, frag_t, fpfh_s, fpfh_t, voxel_size)   # pipeline.cpp:790-828
     results  = m3d.reconstruction.register_fragment_pairs(fragments, fpfhs, voxel_size=voxel_size)     # pipeline.cpp:428-439
+    T, info  = m3d.reconstruction.fragment_odometry(frag_s, frag_t, voxel_size, init)                  # pipeline.cpp:754-763
+    T, info  = m3d.reconstruction.refine_fragment_pair(frag_s, frag_t, voxel_size, edge_pose)          # pipeline.cpp:686-697
 
 Layout (only what the path needs):
   csrc/      HIP kernels, host driver, C ABI            -> lib/libmisc3d_amd.so
@@ -33,6 +35,8 @@ There is no CPU fallback: the native libraries must be built (python __graft_ent
 compute call needs a HIP device.
 """
 __version__ = "0.1.0"
+
+import enum as _enum
 
 try:
     from . import _py_misc3d as _ext
@@ -55,18 +59,31 @@ Error, Warning, Info, Debug = (VerbosityLevel.Error, VerbosityLevel.Warning, Ver
 
 
 def registration_icp(source, target, max_correspondence_distance, init=None, max_iteration=30,
-                     relative_fitness=1e-6, relative_rmse=1e-6, device=0):
-    """Point-to-point ICP = open3d.pipelines.registration.registration_icp(source, target,
-    max_correspondence_distance, init, TransformationEstimationPointToPoint(), ICPConvergenceCriteria(...)),
-    which the reference's examples run on the pose of compute_transformation_ransac
-    (examples/cpp/transform_estimation.cpp:82-86).  source / target: (N, 3) arrays or objects with `.points`.
+                     relative_fitness=1e-6, relative_rmse=1e-6, device=0, estimation="point_to_point"):
+    """ICP = open3d.pipelines.registration.registration_icp(source, target, max_correspondence_distance, init,
+    estimation, ICPConvergenceCriteria(...)).  estimation="point_to_point" (the default):
+    TransformationEstimationPointToPoint(), which the reference's examples run on the pose of compute_transformation_ransac
+    (examples/cpp/transform_estimation.cpp:82-86); source / target: (N, 3) arrays or objects with `.points`.
+    estimation="point_to_plane": TransformationEstimationPointToPlane(), MultiScaleICP's Point2PlaneICP
+    (src/pipeline.cpp:949-955); the target then carries normals: a (points, normals) tuple or an object with .points /
+    .normals (RuntimeError without them).
     Returns (4x4 pose, dict(fitness, inlier_rmse, correspondences, iterations, converged))."""
     import numpy as _np
 
     from . import capi as _capi
-    pts = [_np.asarray(getattr(c, "points", c), dtype=_np.float64).reshape(-1, 3) for c in (source, target)]
-    return _capi.registration_icp(pts[0], pts[1], max_correspondence_distance, init, max_iteration,
-                                  relative_fitness, relative_rmse, device)
+    if estimation == "point_to_point":
+        pts = [_np.asarray(getattr(c, "points", c), dtype=_np.float64).reshape(-1, 3) for c in (source, target)]
+        return _capi.registration_icp(pts[0], pts[1], max_correspondence_distance, init, max_iteration,
+                                      relative_fitness, relative_rmse, device)
+    if estimation != "point_to_plane":
+        raise RuntimeError('[Misc3D Error] estimation: "point_to_point" or "point_to_plane"')
+    src, _ = _points_normals(source)
+    dst, nrm = _points_normals(target)
+    try:
+        return _capi.registration_icp_plane(src, dst, nrm, max_correspondence_distance, init, max_iteration,
+                                            relative_fitness, relative_rmse, device)
+    except _capi.M3DError as e:
+        raise RuntimeError(str(e)) from e
 
 
 def _search_param(param):
@@ -174,10 +191,70 @@ def _feat(f, n):
     return _np.ascontiguousarray(a)
 
 
+class LocalRefineMethod(_enum.IntEnum):
+    """PipelineConfig::LocalRefineMethod (include/misc3d/reconstruction/pipeline_config.h:23-28)"""
+    Point2PointICP = 0
+    Point2PlaneICP = 1
+    ColoredICP = 2        # the reference's default; not accelerated (needs colour gradients)
+    GeneralizedICP = 3    # not accelerated
+
+
+_REFINE_METHODS = {"point_to_point": 0, "point_to_plane": 1, "colored": 2, "generalized": 3}
+
+
+def _refine_method(method):
+    if isinstance(method, str):
+        if method not in _REFINE_METHODS:
+            raise RuntimeError("[Misc3D Error] Unknown local refine method.")
+        return _REFINE_METHODS[method]
+    return int(method)
+
+
 class _Reconstruction:
-    """misc3d.reconstruction, the loop-closure half of ReconstructionPipeline (src/pipeline.cpp): PreProcessFragments
-    (:379-401), GlobalRegistration (:790-828) and the loop over fragment pairs that calls it (:428-439).  Calls release the GIL: Python threads that call
+    """misc3d.reconstruction, the registration half of ReconstructionPipeline (src/pipeline.cpp): PreProcessFragments
+    (:379-401), GlobalRegistration (:790-828), the loop over fragment pairs that calls it (:428-439), and MultiScaleICP (:927-982)
+    with its two callers, fragment odometry (:754-763) and refinement (:686-697).  Calls release the GIL: Python threads that call
     global_registration / fit_* / match_correspondence side by side run side by side on the device (lanes)."""
+
+    LocalRefineMethod = LocalRefineMethod
+
+    @staticmethod
+    def multi_scale_icp(source, target, voxel_sizes, max_iters, max_correspondence_distance, init=None,
+                        method="point_to_plane", *, device=0, stats=False):
+        """ReconstructionPipeline::MultiScaleICP: per level both clouds voxel-down-sampled from the originals, ICP with
+        ICPConvergenceCriteria(1e-6, 1e-6, max_iters[l]) seeded with the previous level's pose; then the information matrix
+        of the original clouds at 1.4 voxel_sizes[-1].  source / target: (N, 3) arrays, (points, normals) tuples or objects
+        with .points / .normals; method: "point_to_point", "point_to_plane" or a LocalRefineMethod (ColoredICP and
+        GeneralizedICP are not accelerated: RuntimeError).  Returns (4x4 pose, 6x6 information), and the per-level stats
+        when stats=True."""
+        from . import capi as _capi
+        src, sn = _points_normals(source)
+        dst, dn = _points_normals(target)
+        try:
+            T, info, levels = _capi.multi_scale_icp(src, dst, voxel_sizes, max_iters, max_correspondence_distance, init,
+                                                    _refine_method(method), dn, sn, device)
+        except _capi.M3DError as e:
+            raise RuntimeError(str(e)) from e
+        return (T, info, levels) if stats else (T, info)
+
+    @staticmethod
+    def refine_fragment_pair(source, target, voxel_size, init=None, method="point_to_plane", *, device=0, stats=False):
+        """RefineFragmentPair's registration (src/pipeline.cpp:686-697): multi_scale_icp with {v, v/2, v/4} -- formed in
+        single precision, as the reference's `const float voxel_size` forms them -- max iterations {50, 30, 15} and
+        max_correspondence_distance = 1.4 voxel_size (the single-precision value, as config_.voxel_size_ is); init: the pose-graph edge's pose."""
+        import numpy as _np
+        v = _np.float32(voxel_size)
+        sizes = [float(v), float(v / _np.float32(2.0)), float(v / _np.float32(4.0))]
+        return _Reconstruction.multi_scale_icp(source, target, sizes, [50, 30, 15], float(v) * 1.4, init, method,
+                                               device=device, stats=stats)
+
+    @staticmethod
+    def fragment_odometry(source, target, voxel_size, init=None, method="point_to_plane", *, device=0, stats=False):
+        """RegisterFragmentPair for ADJACENT fragments (src/pipeline.cpp:754-763): multi_scale_icp with {v} (in single
+        precision), {50} and max_correspondence_distance = 1.4 voxel_size; init: the pose from the fragment pose graph."""
+        import numpy as _np
+        v = float(_np.float32(voxel_size))
+        return _Reconstruction.multi_scale_icp(source, target, [v], [50], v * 1.4, init, method, device=device, stats=stats)
 
     @staticmethod
     def global_registration(source, target, feature_source, feature_target, voxel_size, max_iter=100000,
@@ -212,7 +289,7 @@ class _Reconstruction:
         """BuildPoseGraphForScene's loop closures: every (s, t) of `pairs` through global_registration, dealt to `devices`,
         `inflight` pairs at a time per device.  Default pairs: all s < t with t > s + 1 -- the reference sends ADJACENT fragments
         (t == s + 1) to the multi-scale ICP odometry seeded from the fragment pose graph, never to GlobalRegistration
-        (src/pipeline.cpp:752-764); pass `pairs` explicitly to register those here as well.
+        (src/pipeline.cpp:752-764): that is fragment_odometry; pass `pairs` explicitly to register those here as well.
         features=None: the descriptors are computed first, fragment by fragment, with preprocess_fragment(voxel_size).
         Returns [(s, t, success, pose, information), ...]."""
         from . import capi as _capi

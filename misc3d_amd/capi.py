@@ -155,6 +155,12 @@ def lib():
         L.m3d_reg_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.m3d_registration_icp.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p, C.c_int,
                                            C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.m3d_registration_icp_plane.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double,
+                                                 C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]
+        L.m3d_multi_scale_icp.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                          C.c_void_p, C.c_size_t, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]
         L.m3d_normals_from_map.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int,
                                            C.c_void_p, C.c_void_p]
         L.m3d_information_matrix.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p, C.c_int,
@@ -1043,6 +1049,65 @@ def registration_icp(src, dst, max_correspondence_distance, init=None, max_itera
     if want_correspondences:
         return T.reshape(4, 4), st.asdict(), corr[: len(src)]
     return T.reshape(4, 4), st.asdict()
+
+
+def registration_icp_plane(src, dst, dst_normals, max_correspondence_distance, init=None, max_iteration=30,
+                           relative_fitness=1e-6, relative_rmse=1e-6, device=0, want_correspondences=False):
+    """m3d_registration_icp_plane: registration_icp with TransformationEstimationPointToPlane() and the target's normals
+    (None: the library's error) -> (T, stats[, correspondences])."""
+    src = _f64(src).reshape(-1, 3)
+    dst = _f64(dst).reshape(-1, 3)
+    nrm = _f64(dst_normals).reshape(-1, 3) if dst_normals is not None else None
+    if nrm is not None and len(nrm) != len(dst):
+        raise ValueError("dst_normals must have one row per target point")
+    Ti = _f64(init).reshape(16).copy() if init is not None else None
+    T = np.zeros(16)
+    st = IcpStats()
+    corr = np.zeros(max(len(src), 1), dtype=np.int64) if want_correspondences else None
+    _check(lib().m3d_registration_icp_plane(_p(src), len(src), _p(dst), _p(nrm), len(dst), max_correspondence_distance,
+                                            _p(Ti), max_iteration, relative_fitness, relative_rmse, device, _p(T),
+                                            C.cast(C.byref(st), C.c_void_p), _p(corr)))
+    if want_correspondences:
+        return T.reshape(4, 4), st.asdict(), corr[: len(src)]
+    return T.reshape(4, 4), st.asdict()
+
+
+REFINE_POINT2POINT_ICP, REFINE_POINT2PLANE_ICP, REFINE_COLORED_ICP, REFINE_GENERALIZED_ICP = 0, 1, 2, 3
+
+
+class MultiScaleIcpLevel(C.Structure):
+    """m3d_multi_scale_icp_level"""
+    _fields_ = [("n_src", C.c_uint64), ("n_dst", C.c_uint64), ("icp", IcpStats), ("ms_down_sample", C.c_double),
+                ("ms_icp", C.c_double), ("ms_information", C.c_double)]
+
+    def asdict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "icp"}
+        d["icp"] = self.icp.asdict()
+        return d
+
+
+def multi_scale_icp(src, dst, voxel_sizes, max_iters, max_correspondence_distance, init=None,
+                    method=REFINE_POINT2PLANE_ICP, dst_normals=None, src_normals=None, device=0):
+    """m3d_multi_scale_icp: ReconstructionPipeline::MultiScaleICP -> (T (4, 4), information (6, 6), [per-level stats])."""
+    src = _f64(src).reshape(-1, 3)
+    dst = _f64(dst).reshape(-1, 3)
+    dn = _f64(dst_normals).reshape(-1, 3) if dst_normals is not None else None
+    sn = _f64(src_normals).reshape(-1, 3) if src_normals is not None else None
+    if (dn is not None and len(dn) != len(dst)) or (sn is not None and len(sn) != len(src)):
+        raise ValueError("normals must have one row per point")
+    sizes = np.ascontiguousarray(voxel_sizes, dtype=np.float64).reshape(-1)
+    iters = np.ascontiguousarray(max_iters, dtype=np.int32).reshape(-1)
+    if len(sizes) != len(iters):
+        raise ValueError("voxel_sizes and max_iters differ in length")
+    L = len(sizes)
+    Ti = _f64(init).reshape(16).copy() if init is not None else None
+    T = np.zeros(16)
+    info = np.zeros(36)
+    lv = (MultiScaleIcpLevel * max(L, 1))()
+    _check(lib().m3d_multi_scale_icp(_p(src), _p(sn), len(src), _p(dst), _p(dn), len(dst), _p(sizes) if L else None,
+                                     _p(iters) if L else None, L, float(max_correspondence_distance), int(method), _p(Ti),
+                                     device, _p(T), _p(info), C.cast(lv, C.c_void_p)))
+    return T.reshape(4, 4), info.reshape(6, 6), [lv[l].asdict() for l in range(L)]
 
 
 SEARCH_KNN, SEARCH_RADIUS, SEARCH_HYBRID = 0, 1, 2

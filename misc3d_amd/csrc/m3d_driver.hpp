@@ -220,6 +220,21 @@ int information_matrix_on(DeviceCtx* ctx, m3d_cloud* csrc, m3d_cloud* cdst, cons
                           double max_correspondence_distance, const double* T, double* info, uint64_t* n_correspondences,
                           m3d_reg* session = nullptr);
 void reg_session_release(m3d_reg* q);   // ... of a session handed out through session_out (the caller holds the lane)
+// m3d_registration_icp / m3d_registration_icp_plane; held != null: on that lane, which the caller holds (m3d_multi_scale_icp),
+// else the call takes a lane of `device` itself
+int registration_icp_on(DeviceCtx* held, const double* src, size_t n_src, const double* dst, size_t n_dst,
+                        double max_correspondence_distance, const double* T_init, int max_iteration, double relative_fitness,
+                        double relative_rmse, int device, double* T_out, m3d_icp_stats* stats, int64_t* correspondences);
+int registration_icp_plane_on(DeviceCtx* held, const double* src, size_t n_src, const double* dst, const double* dst_normals,
+                              size_t n_dst, double max_correspondence_distance, const double* T_init, int max_iteration,
+                              double relative_fitness, double relative_rmse, int device, double* T_out, m3d_icp_stats* stats,
+                              int64_t* correspondences);
+// m3d_voxel.cpp: the levels of m3d_voxel_down_sample_multi (points and normals) on a lane the caller holds, into host arrays of
+// n rows each; level_ms (may be null): host clock per level, the upload and the bounds counted with level 0.  voxel_sizes_check:
+// rule 1 of the voxel contract for every size (M3D_ERR_INVALID_ARG + its message)
+int voxel_levels_on(DeviceCtx* ctx, const double* xyz, const double* normals, size_t n, const double* voxel_sizes, size_t n_levels,
+                    double* const* out_xyz, double* const* out_normals, size_t* m, double* level_ms);
+int voxel_sizes_check(const double* voxel_sizes, size_t n_levels);
 
 void dev_pool_trim(int device);
 int logical_device_count();           // what m3d_device_count returns: max(physical devices, m3d_config.device_aliases)

@@ -1548,6 +1548,98 @@ void launch_icp_transform(const double* ix, const double* iy, const double* iz, 
     if (n) icp_transform_k<<<(n + 255) / 256, 256, 0, s>>>(ix, iy, iz, n, T_dev, ox, oy, oz);
 }
 
+// Point-to-plane ICP (m3d_registration_icp_plane): ONE launch per iteration.  One moving point per thread, at every size
+// (n < 2^31 -> at most 2^23 workgroups; no thread ever takes a second point).  The thread
+//   1. applies the pending update T (12 doubles, null = none) with icp_transform_k's expression and stores the point (in place
+//      from the second iteration on; the first reads the source cloud);
+//   2. searches its nearest target point (nearest_idx: lowest original index on exact ties) and stores nn[i];
+//   3. for a correspondence (d2 < r^2) gathers t_j and n_j and forms r = (s - t_j) . n_j, J = [s x n_j, n_j];
+//   4. contributes the record of m3d_icp_fp.hpp: count, d2, the 21 products of J J^T, the 6 of J r, r^2 (zeros otherwise).
+// The 30 values are summed over the wave by m3d::wave_sum (xor butterfly, order fixed), the four waves' sums meet in LDS and
+// wave 0 adds them in wave order: one record per workgroup.  icp_plane_final_k then sums the workgroups' records, value k in
+// workgroup k: lane l adds the records l, l + 64, ... in ascending order, wave_sum adds the lanes.  No atomics: the result is a
+// fixed function of (points, update, grid) -- the same bits from run to run, whatever else the device runs.
+__global__ __launch_bounds__(256) void icp_plane_iter_k(const double* __restrict__ ix, const double* __restrict__ iy,
+                                                         const double* __restrict__ iz, uint32_t n,
+                                                         const double* __restrict__ T, double* __restrict__ px,
+                                                         double* __restrict__ py, double* __restrict__ pz, GridDesc g,
+                                                         const uint32_t* __restrict__ cell_start,
+                                                         const double* __restrict__ qx, const double* __restrict__ qy,
+                                                         const double* __restrict__ qz,
+                                                         const uint32_t* __restrict__ cell_orig, CloudView dst,
+                                                         uint32_t* __restrict__ nn, double* __restrict__ partial) {
+    __shared__ double sm[4][kIcpPlaneRecord];
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    double v[kIcpPlaneRecord];
+    for (int k = 0; k < kIcpPlaneRecord; ++k) v[k] = 0.0;
+    if (i < n) {
+        double x = ix[i], y = iy[i], z = iz[i];
+        if (T) {
+            double t[12];
+            for (int k = 0; k < 12; ++k) t[k] = T[k];
+            const double tx = ((t[0] * x + t[1] * y) + t[2] * z) + t[3];
+            const double ty = ((t[4] * x + t[5] * y) + t[6] * z) + t[7];
+            const double tz = ((t[8] * x + t[9] * y) + t[10] * z) + t[11];
+            x = tx;
+            y = ty;
+            z = tz;
+        }
+        px[i] = x;
+        py[i] = y;
+        pz[i] = z;
+        double best;
+        uint32_t bo;
+        nearest_idx(g, cell_start, qx, qy, qz, cell_orig, x, y, z, &best, &bo);
+        const bool ok = best < g.r2;
+        nn[i] = ok ? bo : 0xFFFFFFFFu;
+        if (ok) {
+            const double ax = dst.nx[bo], ay = dst.ny[bo], az = dst.nz[bo];
+            const double ex = x - dst.x[bo], ey = y - dst.y[bo], ez = z - dst.z[bo];
+            const double r = (ex * ax + ey * ay) + ez * az;
+            // s x n, SURVEY.md 8a-note (iii)
+            const double J[6] = {y * az - z * ay, z * ax - x * az, x * ay - y * ax, ax, ay, az};
+            v[0] = 1.0;
+            v[1] = best;
+            int k = 2;
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int b = a; b < 6; ++b) v[k++] = J[a] * J[b];
+#pragma unroll
+            for (int a = 0; a < 6; ++a) v[23 + a] = J[a] * r;
+            v[29] = r * r;
+        }
+    }
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < kIcpPlaneRecord; ++k) {
+        const double s = wave_sum(v[k]);
+        if (lane == 0) sm[wave][k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < (uint32_t)kIcpPlaneRecord) {
+        const uint32_t k = threadIdx.x;
+        partial[(size_t)blockIdx.x * kIcpPlaneStride + k] = ((sm[0][k] + sm[1][k]) + sm[2][k]) + sm[3][k];
+    }
+}
+__global__ __launch_bounds__(64) void icp_plane_final_k(const double* __restrict__ partial, uint32_t n_blocks,
+                                                         double* __restrict__ out) {
+    const uint32_t k = blockIdx.x;
+    double a = 0.0;
+    for (uint32_t b = threadIdx.x; b < n_blocks; b += 64u) a += partial[(size_t)b * kIcpPlaneStride + k];
+    a = wave_sum(a);
+    if (threadIdx.x == 0) out[k] = a;
+}
+void launch_icp_plane_iter(const double* ix, const double* iy, const double* iz, uint32_t n, const double* T_dev, double* px,
+                           double* py, double* pz, const GridDesc& g, const uint32_t* cell_start, const double* qx,
+                           const double* qy, const double* qz, const uint32_t* cell_orig, const CloudView& dst, uint32_t* nn,
+                           double* partial, double* out, hipStream_t s) {
+    const uint32_t nb = icp_plane_blocks(n);
+    icp_plane_iter_k<<<nb, 256, 0, s>>>(ix, iy, iz, n, T_dev, px, py, pz, g, cell_start, qx, qy, qz, cell_orig, dst, nn,
+                                        partial);
+    icp_plane_final_k<<<kIcpPlaneRecord, 64, 0, s>>>(partial, nb, out);
+}
+
 // ------------------------------------------------------------------------------------------------
 // DetectBoundaryPoints (src/boundary_detection.cpp:21-113), one thread per point
 // ------------------------------------------------------------------------------------------------

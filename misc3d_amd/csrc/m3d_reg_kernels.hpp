@@ -152,6 +152,16 @@ void launch_info_sums(uint32_t n, const CloudView& dst, const uint32_t* nn, doub
                       hipStream_t s);
 void launch_icp_transform(const double* ix, const double* iy, const double* iz, uint32_t n, const double* T_dev,
                           double* ox, double* oy, double* oz, hipStream_t s);
+// Point-to-plane ICP's iteration (icp_plane_iter_k + icp_plane_final_k): the pending update T_dev (12 doubles, null = none) applied
+// to (ix, iy, iz) -> (px, py, pz), nn[i], and out[0 .. kIcpPlaneRecord) = the record of m3d_icp_fp.hpp.  partial: kIcpPlaneStride
+// doubles per workgroup of 256 points (icp_plane_blocks(n) of them).  dst needs its normals.
+constexpr int kIcpPlaneRecord = 30;
+constexpr int kIcpPlaneStride = 32;
+inline uint32_t icp_plane_blocks(uint32_t n) { return n ? (n + 255u) / 256u : 1u; }
+void launch_icp_plane_iter(const double* ix, const double* iy, const double* iz, uint32_t n, const double* T_dev, double* px,
+                           double* py, double* pz, const GridDesc& g, const uint32_t* cell_start, const double* qx,
+                           const double* qy, const double* qz, const uint32_t* cell_orig, const CloudView& dst, uint32_t* nn,
+                           double* partial, double* out, hipStream_t s);
 void launch_kabsch_sums(const double* src, const double* dst, uint32_t n, double* partial, double* sums,
                         hipStream_t s);
 void launch_nn(const double* q, uint32_t nq, const double* db, uint32_t ndb, int dim, uint32_t splits,

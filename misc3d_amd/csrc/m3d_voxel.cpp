@@ -7,6 +7,7 @@
 
 #include <atomic>
 #include <climits>
+#include <optional>
 
 using namespace m3d;
 
@@ -86,9 +87,14 @@ struct LevelOut {
     size_t *first_index, *point_to_voxel;
 };
 
+// held: the lane of a caller that already holds one (m3d::voxel_levels_on), else the call takes a lane of `device`.
+// level_ms (may be null): host clock of every level, the upload and the bounds counted with level 0
 int voxel_impl(const double* xyz, const double* normals, const double* colors, size_t n, const double* voxel_sizes,
-               size_t n_levels, int device, const LevelOut* outs, size_t* m_out, m3d_voxel_stats* stats) {
+               size_t n_levels, int device, const LevelOut* outs, size_t* m_out, m3d_voxel_stats* stats,
+               DeviceCtx* held = nullptr, double* level_ms = nullptr) {
     const double t0 = now_ms();
+    if (level_ms)
+        for (size_t l = 0; l < n_levels; ++l) level_ms[l] = 0.0;
     if (stats) *stats = m3d_voxel_stats{};
     if (!m_out || (n_levels && (!voxel_sizes || !outs))) return fail(M3D_ERR_INVALID_ARG, "invalid argument");
     for (size_t l = 0; l < n_levels; ++l) m_out[l] = 0;
@@ -104,8 +110,9 @@ int voxel_impl(const double* xyz, const double* normals, const double* colors, s
             return fail(M3D_ERR_INVALID_ARG, "invalid argument");
     if (n > kVoxelMaxPoints) return fail(M3D_ERR_INVALID_ARG, "too many points");
     const int force = g_voxel_force.load();
-    LaneLock lane(device);
-    DeviceCtx* ctx = lane.ctx;
+    std::optional<LaneLock> lane;
+    if (!held) lane.emplace(device);
+    DeviceCtx* ctx = held ? held : lane->ctx;
     if (!ctx) return M3D_ERR_DEVICE;
     VoxelBufs B;
     TimingEvents ev;
@@ -168,6 +175,7 @@ int voxel_impl(const double* xyz, const double* normals, const double* colors, s
         RESERVE(B.counts, sizeof(uint32_t) * n_counts);
         RESERVE(B.offs, sizeof(uint32_t) * (n + 1));
         std::vector<uint32_t> hf, hp;   // the trace on its way to the caller's size_t arrays
+        double t_level = t0;
         for (size_t l = 0; l < n_levels; ++l) {
             const bool wide = wides[l] != 0;
             path = wide ? M3D_VOXEL_PATH_WIDE : M3D_VOXEL_PATH_PACKED;
@@ -244,6 +252,11 @@ int voxel_impl(const double* xyz, const double* normals, const double* colors, s
             HIPCHK(hipEventElapsedTime(&ms, ev.e[3], ev.e[4]));
             ms_down += ms;
             m_out[l] = m;
+            if (level_ms) {
+                const double t = now_ms();
+                level_ms[l] = t - t_level;
+                t_level = t;
+            }
             voxels += m;
             passes_total += (int)passes;
         }
@@ -266,6 +279,21 @@ int voxel_impl(const double* xyz, const double* normals, const double* colors, s
 }
 
 }  // namespace
+
+// n_levels levels of one cloud on a lane the caller holds (m3d_multi_scale_icp): m3d_voxel_down_sample_multi without colours
+// and trace arrays, the levels' rows in the caller's host arrays
+int m3d::voxel_levels_on(DeviceCtx* ctx, const double* xyz, const double* normals, size_t n, const double* voxel_sizes,
+                         size_t n_levels, double* const* out_xyz, double* const* out_normals, size_t* m, double* level_ms) {
+    std::vector<LevelOut> outs(n_levels);
+    for (size_t l = 0; l < n_levels; ++l)
+        outs[l] = LevelOut{out_xyz[l], out_normals ? out_normals[l] : nullptr, nullptr, nullptr, nullptr};
+    return voxel_impl(xyz, normals, nullptr, n, voxel_sizes, n_levels, ctx->logical, outs.data(), m, nullptr, ctx, level_ms);
+}
+int m3d::voxel_sizes_check(const double* voxel_sizes, size_t n_levels) {
+    for (size_t l = 0; l < n_levels; ++l)
+        if (!voxel_size_ok(voxel_sizes[l])) return voxel_size_error(voxel_sizes[l]);
+    return M3D_OK;
+}
 
 extern "C" {
 

@@ -10,6 +10,8 @@ bench.py); these lines feed DESIGN.md section 6 and check that the full sizes ru
   K1 - K4 KNearestSearch: 200k x 200k x 33 k=10 batched, 1 000 single-query calls, 1 M x 3 k=30 (grid, tile A/B),
           50k x 33 k=1000 (select)
   V1 - V3 voxel_down_sample: the 1 M-point bench scene at 0.005 / 0.02 of its extent, and the three-level call
+  I1 registration_icp_plane against registration_icp at the C4 ICP shape (200k x 200k, 0.02), alternating in one process
+  I2 refine_fragment_pair ({v, v/2, v/4}, {50, 30, 15}) on 50 000-point fragments, with its per-level split
 """
 import json
 import os
@@ -836,3 +838,74 @@ if any(t in which for t in ("V1", "V2", "V3")) or ALL:
                                "one wave per voxel for the ordered sums) and two round trips (bounds, voxel count), not a "
                                "streaming kernel: it is not expected near the HBM floor"},
              cpu_baseline=voxel_cpu(sizes))
+
+if "I1" in which or "I2" in which or ALL:
+    # point-to-plane ICP and the multi-scale driver ("Multi-scale ICP").  The pair is the C4 shape -- the six
+    # patches of synth.registration_pair_c4 -- with analytic normals (tests/icp_ref_util.icp_pair: synth has none).
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import icp_ref_util as icp_util
+    import misc3d_amd as m3d
+
+    if "I1" in which or ALL:
+        # I1: both estimators from the same process, alternating.  A whole call (30 iterations allowed, the default criteria), and
+        # the time of ONE iteration = (call with 40 iterations - call with 10) / 30 with both relative criteria at 0 so that
+        # every iteration runs: set-up (two uploads, the target grid and its neighbour lists) cancels.
+        n = 200_000
+        p = icp_util.icp_pair(n, seed=5, sigma=0.002)
+        init = icp_util.offset_pose(p["T"], 0.3, (0.003, -0.002, 0.002))
+
+        def plane(it, rel):
+            return capi.registration_icp_plane(p["src"], p["dst"], p["dst_normals"], 0.02, init, it, rel, rel)
+
+        def point(it, rel):
+            return capi.registration_icp(p["src"], p["dst"], 0.02, init, it, rel, rel)
+        for fn in (plane, point):
+            fn(30, 1e-6)
+        rows = {"plane": {}, "point": {}}
+        for rep in range(7):
+            for name, fn in (("plane", plane), ("point", point)):
+                for key, it, rel in (("call", 30, 1e-6), ("it10", 10, 0.0), ("it40", 40, 0.0)):
+                    t0 = time.perf_counter()
+                    T, st = fn(it, rel)
+                    rows[name].setdefault(key, []).append(((time.perf_counter() - t0) * 1e3, st, T))
+        out = {}
+        for name in rows:
+            med = {k: sorted(v, key=lambda r: r[0])[len(v) // 2] for k, v in rows[name].items()}
+            assert med["it10"][1]["iterations"] == 10 and med["it40"][1]["iterations"] == 40
+            out[name] = {"ms_call": med["call"][0], "ms_call_spread": [min(r[0] for r in rows[name]["call"]), max(r[0] for r in rows[name]["call"])],
+                         "iterations": med["call"][1]["iterations"], "fitness": med["call"][1]["fitness"],
+                         "rmse": med["call"][1]["inlier_rmse"], "pose_err": float(np.abs(med["call"][2] - p["T"]).max()),
+                         "ms_10_iterations": med["it10"][0], "ms_40_iterations": med["it40"][0],
+                         "us_per_iteration": (med["it40"][0] - med["it10"][0]) / 30.0 * 1e3}
+        emit("I1 registration_icp_plane vs registration_icp, 200k x 200k, 0.02 (alternating, medians of 7)", n=n,
+             point_to_plane=out["plane"], point_to_point=out["point"],
+             launches_per_iteration={"point_to_plane": "2 (+ the completion word's)", "point_to_point": "5 + 3 final reductions (+ the completion word's)"},
+             roofline={"bound": "latency: an iteration is a dependent chain of short launches, one 240-byte copy and one host wait",
+                       "us_per_iteration_plane": out["plane"]["us_per_iteration"], "us_per_iteration_point": out["point"]["us_per_iteration"]},
+             cpu_baseline=None)
+
+    if "I2" in which or ALL:
+        n = 50_000
+        p = icp_util.icp_pair(n, seed=6, sigma=0.001)
+        v = 0.02
+        init = icp_util.offset_pose(p["T"], 1.0, (0.008, -0.005, 0.006))
+        tgt = (p["dst"], p["dst_normals"])
+        for method in ("point_to_plane", "point_to_point"):
+            for _ in range(3):
+                m3d.reconstruction.refine_fragment_pair(p["src"], tgt, v, init, method)
+            runs = []
+            for _ in range(15):
+                t0 = time.perf_counter()
+                T, info, lv = m3d.reconstruction.refine_fragment_pair(p["src"], tgt, v, init, method, stats=True)
+                runs.append(((time.perf_counter() - t0) * 1e3, lv, T, info))
+            runs.sort(key=lambda r: r[0])
+            ms, lv, T, info = runs[len(runs) // 2]
+            med = lambda l, k: float(np.median([r[1][l][k] for r in runs]))   # noqa: E731
+            emit(f"I2 refine_fragment_pair 50k-point fragments, voxel {v}, {method} (median of 15)", n=n, voxel=v, ms=ms,
+                 ms_spread=[runs[0][0], runs[-1][0]], pose_err=float(np.abs(T - p["T"]).max()), info_55=float(info[5, 5]),
+                 levels=[{"n_src": l["n_src"], "n_dst": l["n_dst"], "iterations": l["icp"]["iterations"],
+                          "fitness": l["icp"]["fitness"], "ms_down_sample": med(i, "ms_down_sample"), "ms_icp": med(i, "ms_icp"),
+                          "ms_information": med(i, "ms_information")} for i, l in enumerate(lv)],
+                 roofline={"bound": "latency + host link: three levels through host arrays (download of every level, upload into the "
+                                    "ICP call), a grid per level, then one pass over the original clouds"},
+                 cpu_baseline=None)
