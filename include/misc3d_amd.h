@@ -40,7 +40,8 @@ extern "C" {
 #define M3D_ERR_INVALID_ARG (-5) /* null pointer / out-of-range index / N >= 2^31 */
 #define M3D_ERR_DEVICE (-6) /* no HIP device, HIP runtime error, or out of device memory */
 #define M3D_ERR_INTERNAL (-7) /* self-check failed (counts from the scoring kernel and the refine pass disagree) */
-#define M3D_ERR_NON_FINITE (-8) /* m3d_voxel_down_sample: a point with a non-finite coordinate (the reference's int(floor(..)) is undefined) */
+#define M3D_ERR_NON_FINITE (-8) /* m3d_voxel_down_sample: a point with a non-finite coordinate (the reference's int(floor(..)) is undefined);
+                                   m3d_raycast_pinhole: a vertex that is not finite in single precision under its pose */
 
 enum m3d_model_kind { M3D_PLANE = 0, M3D_SPHERE = 1, M3D_CYLINDER = 2 };
 
@@ -693,6 +694,73 @@ typedef struct m3d_pair_result {
 int m3d_register_fragment_pairs(const m3d_fragment_view *frags, size_t n_frags, int dim, m3d_pair_result *pairs,
                                 size_t n_pairs, double voxel_size, int max_iter, double edge_length_threshold,
                                 double confidence, const int *devices, int n_dev, int inflight);
+
+/* ---- pose_estimation::RayCastRenderer, src/ray_cast_renderer.cpp ------------------------------------------------------
+ * Depth, instance and primitive maps of a list of posed triangle meshes seen by a pinhole camera at the origin looking
+ * along +z: what RayCastRenderer::CastRays computes through Open3D's RaycastingScene (Embree, CPU only).  Bit parity with
+ * Embree is not a goal (it promises no order among equal hits and no operation order); the contract below is ours, follows
+ * the reference wherever the reference is visible, and is checked bit for bit against tests/cpp/raycast_ref.c.  Facts about
+ * Open3D marked [RECALL] are from memory of 0.15.  The arithmetic of rules 1-4 is misc3d_amd/csrc/m3d_raycast_fp.hpp.
+ *   1. CAMERA.  width W, height H, fx, fy, cx, cy (fp64).  The ray of pixel (x, y), row-major index y W + x, starts at
+ *      (0, 0, 0) with direction d = (fp32(((x + 0.5) - cx) / fx), fp32(((y + 0.5) - cy) / fy), 1.0f): computed in fp64, rounded
+ *      once, NOT normalised, so a hit's t is its z-depth ([RECALL] CreateRaysPinhole; app/label_maker/mixed/helper.py:145 and
+ *      GetPointCloud's rays[:, 3:] * t_hit rely on it).
+ *   2. SCENE.  Mesh g (geometry id g = its position in the list, [RECALL] AddTriangles returns ids in order) has fp64
+ *      vertices, triangles as three int32 vertex indices, and a row-major 4 x 4 fp64 pose T whose last row is not read.  A
+ *      vertex becomes fp32(((T[r][0] x + T[r][1] y) + T[r][2] z) + T[r][3]) per row r: fp64, every operation rounded
+ *      separately (no contraction), rounded once to fp32.  From there on everything is fp32 with every operation rounded
+ *      separately, division and square root correctly rounded and subnormals kept (hipcc's defaults for gfx950; the library
+ *      is built with -ffp-contract=off).  A transformed vertex that is not finite in fp32: M3D_ERR_NON_FINITE (the message
+ *      names the vertex and the frame), the outputs are then unspecified.
+ *   3. ONE (RAY, TRIANGLE) PAIR.  Moeller-Trumbore in this order: e1 = v1 - v0, e2 = v2 - v0, p = d x e2, det = e1 . p,
+ *      s = -v0, u = (s . p) / det, q = s x e1, v = (d . q) / det, t = (e2 . q) / det, with a x b = (a1 b2 - a2 b1,
+ *      a2 b0 - a0 b2, a0 b1 - a1 b0) and a . b = (a0 b0 + a1 b1) + a2 b2.  A hit needs det != 0, u >= 0, v >= 0,
+ *      u + v <= 1 and 0 < t < +inf; both faces are hit; NaN fails every comparison.  It needs in addition, with the box of
+ *      the triangle (coordinate-wise min / max of its three fp32 vertices): slab(ray, box) = [a, b] non-empty (a <= b) and
+ *      t >= lower(box) = a - 2^-16 b.  slab: per axis with d != 0 the values lo (1 / d) and hi (1 / d), the smaller-side one
+ *      near, the other far (by the sign of d); a = the maximum of the near values and 0, b = the minimum of the far values and
+ *      +inf, a NaN product (0 x inf) constraining nothing; an axis with d == 0 fails the box unless lo <= 0 <= hi.  Rounding is
+ *      monotone and min / max of fp32 values are exact, so for boxes A inside B the slab of B contains the slab of A and
+ *      lower(B) <= lower(A) in floating point: a traversal that skips a node whose slab fails or whose lower exceeds the
+ *      best t so far loses no hit and no tie.  The clause rejects no Moeller-Trumbore hit of the reference's example scene
+ *      (DESIGN.md "Ray casting").
+ *   4. ONE RAY.  The hit with the smallest t wins; on equal t the lowest geometry id, then the lowest primitive id (the
+ *      triangle's index within its mesh): the answer depends on neither the hierarchy nor the traversal order.  Outputs per
+ *      pixel: t_hit (fp32, +inf on a miss), geometry_ids and primitive_ids (uint32, 0xFFFFFFFF on a miss, [RECALL] Open3D's
+ *      INVALID_ID), primitive_normals (3 x fp32): c = (v1 - v0) x (v2 - v0) of the transformed triangle, l2 = c . c, the
+ *      normal c / sqrt(l2) per component, not flipped towards the ray; (0, 0, 0) on a miss and when l2 is 0 or not finite.
+ *   5. ERRORS, all decided before any device work.  n_meshes == 0: no error, the call returns M3D_FALSE and
+ *      m3d_last_error() is "No mesh is provided." (:67-69: a warning, CastRays returns false).  n_meshes != n_poses:
+ *      M3D_ERR_SIZE_MISMATCH "The number of meshes and poses are not matched." (:71).  M3D_ERR_INVALID_ARG: a vertex index
+ *      outside [0, n_vertices); a non-finite vertex, pose entry or intrinsic; width or height < 1; fx or fy == 0; a corner
+ *      pixel's direction not finite in fp32; 2^31 triangles or pixels, 2^32 vertices or 2^32 - 1 meshes, or more.  A mesh with
+ *      zero triangles is legal and keeps its id.  Without a device: M3D_ERR_DEVICE; there is no CPU path.
+ * poses: n_frames x n_poses row-major 4 x 4 matrices, frame-major -- the label makers' shape (app/label_maker/real/
+ * generate_labels.py:153-177: the same meshes at new poses, frame after frame): the meshes are uploaded once and the frames run
+ * back to back on one stream.  Outputs are laid out [frame][pixel] (n_frames x H x W entries, x 3 for the normals); any of
+ * the four may be NULL.  n_frames == 0: M3D_OK, nothing written.  stats may be NULL.  Re-entrant: concurrent calls take
+ * lanes of the device. */
+typedef struct m3d_raycast_mesh {
+    const double *vertices;   /* n_vertices x 3 */
+    size_t n_vertices;
+    const int32_t *triangles; /* n_triangles x 3 vertex indices */
+    size_t n_triangles;
+} m3d_raycast_mesh;
+typedef struct m3d_raycast_stats {
+    double ms_total;       /* host clock, entry to return */
+    double ms_upload;      /* HIP events: the meshes and the poses to the device */
+    double ms_build;       /* ... transform, sort, hierarchy, all frames */
+    double ms_traverse;    /* ... the traversal, all frames */
+    double ms_download;    /* ... the maps to the host */
+    uint64_t n_triangles;  /* of the list */
+    uint64_t n_nodes;      /* of one frame's hierarchy: 2 n_triangles - 1 */
+    uint64_t n_rays;       /* n_frames x H x W */
+    uint64_t pair_tests;   /* rule-3 tests run, all frames (n_rays x n_triangles without the hierarchy) */
+    uint64_t nodes_visited; /* internal nodes visited, all frames */
+} m3d_raycast_stats;
+int m3d_raycast_pinhole(const m3d_raycast_mesh *meshes, size_t n_meshes, const double *poses, size_t n_poses, size_t n_frames,
+                        int width, int height, double fx, double fy, double cx, double cy, int device, float *t_hit,
+                        uint32_t *geometry_ids, uint32_t *primitive_ids, float *primitive_normals, m3d_raycast_stats *stats);
 
 /* ---- registration::ANNMatcher::Match, src/correspondence_matching.cpp:52-84 ------------------- */
 /* feat_*: Eigen MatrixXd dim x N column-major = N descriptors of dim contiguous doubles.

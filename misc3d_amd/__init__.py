@@ -23,6 +23,8 @@ Drop-in for the reference's python API on this path (module layout of python/py_
     results  = m3d.reconstruction.register_fragment_pairs(fragments, fpfhs, voxel_size=voxel_size)     # pipeline.cpp:428-439
     T, info  = m3d.reconstruction.fragment_odometry(frag_s, frag_t, voxel_size, init)                  # pipeline.cpp:754-763
     T, info  = m3d.reconstruction.refine_fragment_pair(frag_s, frag_t, voxel_size, edge_pose)          # pipeline.cpp:686-697
+    renderer = m3d.pose_estimation.RayCastRenderer(intrinsic); renderer.cast_rays([mesh, mesh], [pose, pose2])
+    depth    = renderer.get_depth_map().numpy(); instance = renderer.get_instance_map().numpy()        # ray_cast_renderer.cpp
 
 Layout (only what the path needs):
   csrc/      HIP kernels, host driver, C ABI            -> lib/libmisc3d_amd.so
@@ -425,11 +427,147 @@ class _Preprocessing:
 preprocessing = _Preprocessing()
 
 
+_MAP_ARRAY = None
+
+
+def _map_array(a):
+    """`a` as an ndarray subclass whose .numpy() returns the array itself, so that the reference's
+    `renderer.get_depth_map().numpy()` (an open3d.core.Tensor there) runs unchanged"""
+    global _MAP_ARRAY
+    if _MAP_ARRAY is None:
+        import numpy as _np
+
+        class MapArray(_np.ndarray):
+            def numpy(self):
+                return self
+        _MAP_ARRAY = MapArray
+    return a.view(_MAP_ARRAY)
+
+
+def _log_warning(msg):
+    if int(get_verbosity_level()) >= int(VerbosityLevel.Warning):
+        print(f"[Misc3D WARNING] {msg}")
+
+
+class RayCastRenderer:
+    """misc3d.pose_estimation.RayCastRenderer (src/ray_cast_renderer.cpp; python/py_pose_estimation.cpp:111-118) on the
+    device: depth, instance and primitive maps of posed triangle meshes seen by a pinhole camera at the origin.
+    intrinsic: an open3d PinholeCameraIntrinsic (anything with .width, .height and .intrinsic_matrix) or a
+    (width, height, fx, fy, cx, cy) tuple.  A hit's depth is its z (the rays are not normalised); among equal depths the
+    lowest geometry id, then the lowest triangle index wins; the poses are applied in double precision."""
+
+    def __init__(self, intrinsic, *, device=0):
+        import numpy as _np
+        if hasattr(intrinsic, "intrinsic_matrix"):
+            K = _np.asarray(intrinsic.intrinsic_matrix, dtype=_np.float64).reshape(3, 3)
+            cam = (int(intrinsic.width), int(intrinsic.height), K[0, 0], K[1, 1], K[0, 2], K[1, 2])
+        else:
+            w, h, fx, fy, cx, cy = intrinsic
+            cam = (int(w), int(h), float(fx), float(fy), float(cx), float(cy))
+        self._cam = cam
+        self._device = device
+        self._res = None
+        self._n = 0
+
+    @staticmethod
+    def _mesh(m):
+        if isinstance(m, tuple) and len(m) == 2:
+            return m
+        return (m.vertices, m.triangles)
+
+    def _cast(self, mesh_list, pose_lists, device):
+        from . import capi as _capi
+        try:
+            return _capi.raycast_pinhole([self._mesh(m) for m in mesh_list], pose_lists, self._cam,
+                                         self._device if device is None else device)
+        except _capi.M3DError as e:
+            raise RuntimeError(str(e)) from e
+
+    def cast_rays(self, mesh_list, pose_list, *, device=None):
+        """CastRays: True, or False (after the reference's warning) when mesh_list is empty."""
+        mesh_list, pose_list = list(mesh_list), list(pose_list)
+        if not mesh_list:
+            _log_warning("No mesh is provided.")
+            return False
+        res = self._cast(mesh_list, [pose_list], device)
+        self._res = {k: v[0] for k, v in res.items()}
+        self._n = len(mesh_list)
+        return True
+
+    def cast_rays_batch(self, mesh_list, pose_lists, *, device=None):
+        """The same meshes at F lists of poses (the label makers' loop), uploaded once: a dict of (F, H, W) arrays t_hit,
+        geometry_ids, primitive_ids and (F, H, W, 3) normals, each frame bit for bit what cast_rays gives.  The getters
+        keep describing the last cast_rays call."""
+        mesh_list = list(mesh_list)
+        if not mesh_list:
+            _log_warning("No mesh is provided.")
+            return None
+        return self._cast(mesh_list, [list(pl) for pl in pose_lists], device)
+
+    def _result(self):
+        if self._res is None:
+            _log_warning("No ray cast result is available.")
+        return self._res
+
+    def get_depth_map(self):
+        """(H, W) float32 t_hit, +inf where nothing is hit; an empty array before the first cast"""
+        import numpy as _np
+        r = self._result()
+        return _map_array(r["t_hit"] if r else _np.zeros(0, _np.float32))
+
+    def get_instance_map(self):
+        """(H, W) uint32 geometry ids (positions in mesh_list), 0xFFFFFFFF where nothing is hit"""
+        import numpy as _np
+        r = self._result()
+        return _map_array(r["geometry_ids"] if r else _np.zeros(0, _np.uint32))
+
+    def get_primitive_ids(self):
+        import numpy as _np
+        r = self._result()
+        return r["primitive_ids"] if r else _np.zeros(0, _np.uint32)
+
+    def get_normal_map(self):
+        import numpy as _np
+        r = self._result()
+        return r["normals"] if r else _np.zeros((0, 3), _np.float32)
+
+    def _cloud(self, mask):
+        import numpy as _np
+        W, H, fx, fy, cx, cy = self._cam
+        d = _np.empty((H, W, 3), _np.float32)
+        d[..., 0] = (((_np.arange(W, dtype=_np.float64) + 0.5) - cx) / fx).astype(_np.float32)[None, :]
+        d[..., 1] = (((_np.arange(H, dtype=_np.float64) + 0.5) - cy) / fy).astype(_np.float32)[:, None]
+        d[..., 2] = 1.0
+        pts = d[mask] * self._res["t_hit"][mask][:, None]   # fp32, as the reference's tensors
+        return pts.astype(_np.float64), self._res["normals"][mask].astype(_np.float64)
+
+    def get_point_cloud(self):
+        """(points, normals) of the pixels that hit something, in ascending pixel order: rays * t_hit and the primitive normals"""
+        import numpy as _np
+        if self._result() is None:
+            return _np.zeros((0, 3)), _np.zeros((0, 3))
+        return self._cloud(_np.isfinite(self._res["t_hit"]))
+
+    def get_instance_point_cloud(self):
+        """one (points, normals) per mesh of the last cast: the pixels whose geometry id is that mesh's"""
+        if self._result() is None:
+            return []
+        return [self._cloud(self._res["geometry_ids"] == i) for i in range(self._n)]
+
+
+class _PoseEstimation:
+    """misc3d.pose_estimation (python/py_pose_estimation.cpp): RayCastRenderer.  PPFEstimator is not part of this build."""
+    RayCastRenderer = RayCastRenderer
+
+
+pose_estimation = _PoseEstimation()
+
+
 def registration_session(*args, **kwargs):
     """capi.RegSession: compute_transformation_ransac cut into begin_chunk / validate / replay, the unit
     misc3d_amd.distributed.registration_ransac_sharded shards over ranks."""
     from . import capi as _capi
     return _capi.RegSession(*args, **kwargs)
 
-__all__ = ["common", "registration", "segmentation", "features", "preprocessing", "reconstruction", "registration_icp", "registration_session", "VerbosityLevel", "set_verbosity_level",
+__all__ = ["common", "registration", "segmentation", "features", "preprocessing", "reconstruction", "pose_estimation", "registration_icp", "registration_session", "VerbosityLevel", "set_verbosity_level",
            "get_verbosity_level", "device_count"]

@@ -177,6 +177,9 @@ def lib():
                                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p]
         L.m3d_bench_voxel_force_path.argtypes = [C.c_int]
+        L.m3d_raycast_pinhole.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_double,
+                                          C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]
         L.m3d_proximity_segment.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_double, C.c_void_p,
                                             C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p]
@@ -1250,6 +1253,54 @@ def voxel_down_sample(xyz, voxel_size, normals=None, colors=None, device=0, trac
         d["first_index"] = o_first[:k].copy()
         d["point_to_voxel"] = o_p2v[:n].copy()
     return (d, st.asdict()) if stats else d
+
+
+class RaycastMesh(C.Structure):
+    """m3d_raycast_mesh"""
+    _fields_ = [("vertices", C.c_void_p), ("n_vertices", C.c_size_t), ("triangles", C.c_void_p), ("n_triangles", C.c_size_t)]
+
+
+class RaycastStats(C.Structure):
+    """m3d_raycast_stats"""
+    _fields_ = [("ms_total", C.c_double), ("ms_upload", C.c_double), ("ms_build", C.c_double), ("ms_traverse", C.c_double),
+                ("ms_download", C.c_double), ("n_triangles", C.c_uint64), ("n_nodes", C.c_uint64), ("n_rays", C.c_uint64),
+                ("pair_tests", C.c_uint64), ("nodes_visited", C.c_uint64)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def raycast_pinhole(meshes, pose_lists, camera, device=0, stats=False, outputs=("t_hit", "geometry_ids", "primitive_ids", "normals")):
+    """m3d_raycast_pinhole.  meshes: a list of (vertices (n, 3), triangles (m, 3)); pose_lists: F lists of one 4 x 4 pose per
+    mesh; camera: (W, H, fx, fy, cx, cy).  -> None when the list of meshes is empty (the call's M3D_FALSE), else a dict of
+    the asked-for maps, (F, H, W) each ((F, H, W, 3) the normals), and the stats dict when stats=True."""
+    W, H, fx, fy, cx, cy = camera
+    W, H = int(W), int(H)
+    keep = [(np.ascontiguousarray(v, dtype=np.float64).reshape(-1, 3), np.ascontiguousarray(f, dtype=np.int32).reshape(-1, 3))
+            for v, f in meshes]
+    arr = (RaycastMesh * max(len(keep), 1))()
+    for k, (v, f) in enumerate(keep):
+        arr[k] = RaycastMesh(v.ctypes.data, len(v), f.ctypes.data, len(f))
+    frames = [[np.asarray(T, dtype=np.float64).reshape(4, 4) for T in pl] for pl in pose_lists]
+    n_poses = len(frames[0]) if frames else len(keep)
+    if any(len(fr) != n_poses for fr in frames):
+        raise ValueError("every frame needs the same number of poses")
+    poses = np.ascontiguousarray(np.array(frames, dtype=np.float64).reshape(len(frames), n_poses, 4, 4))
+    F = len(frames)
+    shape = (F, max(H, 0), max(W, 0))
+    out = {"t_hit": np.empty(shape, np.float32) if "t_hit" in outputs else None,
+           "geometry_ids": np.empty(shape, np.uint32) if "geometry_ids" in outputs else None,
+           "primitive_ids": np.empty(shape, np.uint32) if "primitive_ids" in outputs else None,
+           "normals": np.empty(shape + (3,), np.float32) if "normals" in outputs else None}
+    st = RaycastStats()
+    rc = _check(lib().m3d_raycast_pinhole(C.cast(arr, C.c_void_p), len(keep), _p(poses) if poses.size else None, n_poses, F, W, H,
+                                          float(fx), float(fy), float(cx), float(cy), device, _p(out["t_hit"]),
+                                          _p(out["geometry_ids"]), _p(out["primitive_ids"]), _p(out["normals"]),
+                                          C.cast(C.byref(st), C.c_void_p)))
+    if rc == FALSE:
+        return (None, st.asdict()) if stats else None
+    res = {k: v for k, v in out.items() if v is not None}
+    return (res, st.asdict()) if stats else res
 
 
 def voxel_force_path(path: int):

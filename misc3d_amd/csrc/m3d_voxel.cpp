@@ -207,16 +207,9 @@ int voxel_impl(const double* xyz, const double* normals, const double* colors, s
                     RESERVE(B.v1, sizeof(uint32_t) * n);
                 }
             }
-            for (uint32_t p = 0; p < passes; ++p) {
-                uint32_t* ko = (p & 1 ? B.k1 : B.k0).as<uint32_t>();
-                uint32_t* vo = (p & 1 ? B.v1 : B.v0).as<uint32_t>();
-                launch_voxel_sort_count(keys, nn, 8 * p, B.counts.as<uint32_t>(), st);
-                launch_scan_exclusive(B.counts.as<uint32_t>(), B.counts.as<uint32_t>(), n_counts, B.scan.as<uint32_t>(),
-                                      B.total.as<uint32_t>(), st);
-                launch_voxel_sort_scatter(keys, vals, nn, 8 * p, B.counts.as<uint32_t>(), ko, vo, st);
-                keys = ko;
-                vals = vo;
-            }
+            launch_radix_sort_pairs(keys, vals, nn, passes, B.k0.as<uint32_t>(), B.v0.as<uint32_t>(), B.k1.as<uint32_t>(),
+                                    B.v1.as<uint32_t>(), B.counts.as<uint32_t>(), B.scan.as<uint32_t>(), B.total.as<uint32_t>(),
+                                    &keys, &vals, st);
             launch_voxel_offsets(keys, nn, m, B.offs.as<uint32_t>(), st);
             // the ordered sums
             const size_t out_bytes = sizeof(double) * 3 * m;

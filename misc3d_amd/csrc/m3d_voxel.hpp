@@ -6,13 +6,12 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "m3d_radix_sort.hpp"   // the exclusive scan and the stable sort (their kernels are in m3d_voxel.hip)
+
 namespace m3d {
 
 constexpr uint32_t kVoxelNone = 0xFFFFFFFFu;
 constexpr uint32_t kVoxelBoundsBlocks = 1024;   // partial records of the bounds reduction
-constexpr uint32_t kVoxelScanTile = 2048;       // elements one workgroup of the scan handles
-constexpr uint32_t kVoxelSortRadix = 256;       // 8 bits per pass of the stable sort
-constexpr uint32_t kVoxelSortMaxBlocks = 8192;
 
 struct VoxelBounds {   // what the bounds reduction leaves on the device (one 64-byte block)
     double lo[3], hi[3];       // coordinate-wise min / max over the points with three finite coordinates
@@ -25,11 +24,6 @@ struct VoxelGrid {   // a level's grid, computed on the host from the bounds (m3
     double voxel_size;
     uint32_t bits[3];   // packed keys: bit widths of the three voxel indices (their sum <= 63); unused for wide keys
 };
-
-// elements of the scratch scan_exclusive needs for n elements
-size_t voxel_scan_scratch(size_t n);
-// out[i] = in[0] + ... + in[i - 1], *total_dev = the sum of all (in == out allowed); uint32 arithmetic
-void launch_scan_exclusive(const uint32_t* in, uint32_t* out, size_t n, uint32_t* scratch, uint32_t* total_dev, hipStream_t st);
 
 // partial: kVoxelBoundsBlocks records of scratch
 void launch_voxel_bounds(const double* xyz, uint32_t n, VoxelBounds* partial, VoxelBounds* out, hipStream_t st);
@@ -49,14 +43,6 @@ void launch_voxel_flags(uint32_t n, const uint32_t* slot_of, const uint32_t* fir
 // the first members
 void launch_voxel_ids(uint32_t n, const uint32_t* slot_of, const uint32_t* first, const uint32_t* rank, uint32_t* vid,
                       uint32_t* first_index, hipStream_t st);
-
-// the stable sort's geometry for n elements: elements per workgroup (a multiple of 64) and workgroups
-void voxel_sort_shape(uint32_t n, uint32_t* tile, uint32_t* blocks);
-// one pass over the digit (key >> shift) & 255: counts[digit * blocks + block]
-void launch_voxel_sort_count(const uint32_t* keys, uint32_t n, uint32_t shift, uint32_t* counts, hipStream_t st);
-// ... counts scanned exclusively: a stable scatter of (keys, vals) (vals_in == nullptr: vals = 0 .. n - 1)
-void launch_voxel_sort_scatter(const uint32_t* keys_in, const uint32_t* vals_in, uint32_t n, uint32_t shift,
-                               const uint32_t* counts, uint32_t* keys_out, uint32_t* vals_out, hipStream_t st);
 
 // sorted_keys ascending: offsets[j] = the first position of voxel j, offsets[m] = n
 void launch_voxel_offsets(const uint32_t* sorted_keys, uint32_t n, uint32_t m, uint32_t* offsets, hipStream_t st);

@@ -12,6 +12,8 @@ bench.py); these lines feed DESIGN.md section 6 and check that the full sizes ru
   V1 - V3 voxel_down_sample: the 1 M-point bench scene at 0.005 / 0.02 of its extent, and the three-level call
   I1 registration_icp_plane against registration_icp at the C4 ICP shape (200k x 200k, 0.02), alternating in one process
   I2 refine_fragment_pair ({v, v/2, v/4}, {50, 30, 15}) on 50 000-point fragments, with its per-level split
+  R1 - R3 RayCastRenderer: the reference example (640 x 480, obj.ply at its two poses), 1920 x 1080 with 64 instances, and a
+          100-frame batch of the example
 """
 import json
 import os
@@ -909,3 +911,70 @@ if "I1" in which or "I2" in which or ALL:
                  roofline={"bound": "latency + host link: three levels through host arrays (download of every level, upload into the "
                                     "ICP call), a grid per level, then one pass over the original clouds"},
                  cpu_baseline=None)
+
+if any(t in which for t in ("R1", "R2", "R3")) or ALL:
+    # pose_estimation.RayCastRenderer ("Ray casting") through the C ABI, host arrays in and out.  The mesh is
+    # the reference example's obj.ply (tests/golden/raycast_obj.npz, 11 678 triangles) scaled by 0.001.  Median of 15 calls after
+    # 3 warm-up calls; the split is m3d_raycast_stats' (HIP events on the lane's stream); pruning = rule-3 pair tests run over
+    # rays x triangles.  cpu_baseline = the plain-C BRUTE FORCE over every pair (tests/cpp/raycast_ref.c) under OpenMP on 16
+    # threads -- NOT Embree, which the reference uses and which is not in the image.
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import raycast_ref_util as ray_util
+
+    mesh, ex_poses, ex_cam = ray_util.golden_obj(1)
+
+    def ray_line(tag, name, meshes, frames, cam, reps=15, baseline=False):
+        for _ in range(3):
+            capi.raycast_pinhole(meshes, frames, cam)
+        runs = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            res, st = capi.raycast_pinhole(meshes, frames, cam, stats=True)
+            runs.append(((time.perf_counter() - t0) * 1e3, st))
+        runs.sort(key=lambda r: r[0])
+        ms, st = runs[len(runs) // 2]
+        med = lambda k: float(np.median([r[1][k] for r in runs]))   # noqa: E731
+        cpu, extra = None, {}
+        if baseline and not NO_CPU:
+            os.environ.setdefault("OMP_NUM_THREADS", "16")
+            ref = ray_util.build_ref(tempfile.mkdtemp(), openmp=True)
+            t0 = time.perf_counter()
+            exp = ref(meshes, frames[0], cam)
+            cpu = {"value": (time.perf_counter() - t0) * 1e3, "unit": "ms", "kind": "brute force, not Embree",
+                   "what": "tests/cpp/raycast_ref.c: every (ray, triangle) pair, gcc -O2 -ffp-contract=off -fopenmp, 16 threads"}
+            extra = {"equal_to_brute_force_bit_for_bit": bool(ray_util.same({k: v[0] for k, v in res.items()}, exp)),
+                     "clause": exp["counts"]}
+        emit(f"{tag} {name}", width=cam[0], height=cam[1], meshes=len(meshes), frames=len(frames), triangles=st["n_triangles"],
+             nodes=st["n_nodes"], rays=st["n_rays"], ms=ms, ms_spread=[runs[0][0], runs[-1][0]], runs=reps, warmup=3,
+             ms_per_frame=ms / len(frames), ms_in_library=med("ms_total"), ms_upload=med("ms_upload"), ms_build=med("ms_build"),
+             ms_traverse=med("ms_traverse"), ms_download=med("ms_download"), pair_tests=st["pair_tests"],
+             nodes_visited=st["nodes_visited"], pair_tests_per_ray=st["pair_tests"] / st["n_rays"],
+             nodes_visited_per_ray=st["nodes_visited"] / st["n_rays"],
+             pruning=st["pair_tests"] / (float(st["n_rays"]) * max(st["n_triangles"], 1)),
+             rays_per_second_traversal=st["n_rays"] / (med("ms_traverse") * 1e-3),
+             roofline={"bound": "latency and divergence: a ray walks ~tens of dependent 64-byte node reads, the lanes of a wave "
+                                "diverge below the first levels; neither the HBM nor the VALU peak is a meaningful ceiling here",
+                       "share_of_peak": "not measured"},
+             cpu_baseline=cpu, **extra)
+
+    if "R1" in which or ALL:
+        ray_line("R1", "ray cast, the reference example: 640 x 480, obj.ply at its two poses", [mesh, mesh], [list(ex_poses)], ex_cam,
+                 baseline=True)
+    if "R2" in which or ALL:
+        # 64 instances on an 8 x 8 lattice that fills a 1920 x 1080 view of the example's focal length x 3
+        cam = (1920, 1080, ex_cam[2] * 3, ex_cam[3] * 3, 959.5, 539.5)
+        poses = []
+        for k in range(64):
+            T = ex_poses[k % 2].copy()
+            T[:3, 3] = ((k % 8 - 3.5) * 0.085, (k // 8 - 3.5) * 0.047, 1.0 + 0.01 * (k % 5))
+            poses.append(T)
+        ray_line("R2", "ray cast, 1920 x 1080, 64 instances of obj.ply", [mesh] * 64, [poses], cam)
+    if "R3" in which or ALL:
+        frames = []
+        for f in range(100):
+            a, b = ex_poses[0].copy(), ex_poses[1].copy()
+            a[0, 3] += 0.001 * f
+            b[1, 3] -= 0.001 * f
+            frames.append([a, b])
+        ray_line("R3", "ray cast, a 100-frame batch of the reference example (one call)", [mesh, mesh], frames, ex_cam, reps=7)
