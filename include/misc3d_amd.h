@@ -291,7 +291,9 @@ int m3d_normals_from_map(const double *xyz, uint32_t w, uint32_t h, uint32_t k, 
  * (max_nn <= 128; radius ignored), 1 = KDTreeSearchParamRadius (radius), 2 = KDTreeSearchParamHybrid (radius,
  * max_nn <= 128) -- the python default is Hybrid(0.01, 30),
  * python/py_features.cpp:19.  angle_threshold in degrees (default 90).  indices: capacity n, written in
- * ascending order (the reference's order depends on thread timing); *k = their number. */
+ * ascending order (the reference's order depends on thread timing); *k = their number.  Only the DIRECTION of a
+ * normal matters, not its length or sign (the reference's basis has |u| = |n|, so there a normal that is not a unit
+ * vector distorts the angles); a point whose normal has length zero or not finite (in double) is never flagged. */
 int m3d_detect_boundary_points(const double *xyz, const double *normals, size_t n, int search, double radius,
                                int max_nn, double angle_threshold_deg, int device, size_t *indices, size_t *k);
 

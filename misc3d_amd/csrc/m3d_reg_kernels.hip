@@ -1644,8 +1644,11 @@ void launch_icp_plane_iter(const double* ix, const double* iy, const double* iz,
 // DetectBoundaryPoints (src/boundary_detection.cpp:21-113), one thread per point
 // ------------------------------------------------------------------------------------------------
 // Eigen's generic unitOrthogonal on (n, 0) + cross3 ([RECALL], same restatement as the oracle); the boundary
-// decision does not depend on the basis (angular gaps are invariant), only its roundings do.
-__device__ __forceinline__ void tangent_basis(const double* n, double* u, double* v) {
+// decision does not depend on the basis (angular gaps are invariant), only its roundings do.  false: the normal gives no
+// direction (its length, in double, is zero or not finite) -- such a point is never flagged, whatever the threshold.
+__device__ __forceinline__ bool tangent_basis(const double* n, double* u, double* v) {
+    const double len = sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+    if (!(len > 0.0 && isfinite(len))) return false;
     const double a[4] = {fabs(n[0]), fabs(n[1]), fabs(n[2]), 0.0};
     int maxi = 0;
     for (int i = 1; i < 4; ++i)
@@ -1661,9 +1664,14 @@ __device__ __forceinline__ void tangent_basis(const double* n, double* u, double
     v[0] = p[0];
     v[1] = p[1];
     v[2] = p[2];
-    u[0] = n[1] * v[2] - n[2] * v[1];
-    u[1] = n[2] * v[0] - n[0] * v[2];
-    u[2] = n[0] * v[1] - n[1] * v[0];
+    // [DEVIATION] u = (n x v) / |n|: the reference's u = n x v has the normal's length while v is a unit vector, so with a
+    // normal that is not a unit vector the angles are stretched along u and the decision depends on the normal's
+    // magnitude and on the basis; dividing makes (u, v) orthonormal, and with a unit normal the two agree to rounding
+    // (bit for bit where the computed length is exactly 1)
+    u[0] = (n[1] * v[2] - n[2] * v[1]) / len;
+    u[1] = (n[2] * v[0] - n[0] * v[2]) / len;
+    u[2] = (n[0] * v[1] - n[1] * v[0]) / len;
+    return true;
 }
 
 // Neighbourhood = KDTreeFlann::Search with Radius (all d2 <= r^2), Hybrid (the max_nn nearest with d2 < r^2) or KNN
@@ -1813,7 +1821,7 @@ __global__ __launch_bounds__(64) void boundary_k(CloudView c, GridDesc g, const 
         j3x3_smallest_eigvec(Cm, nrm);
     }
     double u[3], v[3];
-    tangent_basis(nrm, u, v);
+    if (!tangent_basis(nrm, u, v)) return;
     // angles of the neighbours in the tangent plane (:33-41), kept sorted as they come
     // (the angles go where the distances were: those are not needed any more)
     int na = 0;

@@ -36,7 +36,10 @@ static int dbl_cmp(const void *a, const void *b) {
 }
 
 /* Eigen generic unitOrthogonal on (n0, n1, n2, 0) + cross3: v = unitOrthogonal(n), u = n x v ([RECALL]) */
-static void tangent_basis(const double *n, double *u, double *v) {
+/* 0: the normal gives no direction (its length, in double, is zero or not finite) -- such a point is never flagged */
+static int tangent_basis(const double *n, double *u, double *v) {
+    const double len = sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+    if (!(len > 0.0 && isfinite(len))) return 0;
     const double a[4] = {fabs(n[0]), fabs(n[1]), fabs(n[2]), 0.0};
     int maxi = 0;
     for (int i = 1; i < 4; ++i)
@@ -52,9 +55,14 @@ static void tangent_basis(const double *n, double *u, double *v) {
     v[0] = p[0];
     v[1] = p[1];
     v[2] = p[2];
-    u[0] = n[1] * v[2] - n[2] * v[1];
-    u[1] = n[2] * v[0] - n[0] * v[2];
-    u[2] = n[0] * v[1] - n[1] * v[0];
+    /* [DEVIATION] u = (n x v) / |n|: the reference's u = n x v has the normal's length while v is a unit vector, so with
+     * a normal that is not a unit vector the angles are stretched along u and the decision depends on the normal's
+     * magnitude and on the basis; dividing makes (u, v) orthonormal, and with a unit normal the two agree to rounding
+     * (bit for bit where the computed length is exactly 1) */
+    u[0] = (n[1] * v[2] - n[2] * v[1]) / len;
+    u[1] = (n[2] * v[0] - n[0] * v[2]) / len;
+    u[2] = (n[0] * v[1] - n[1] * v[0]) / len;
+    return 1;
 }
 
 /* search: 0 = KNN (the max_nn nearest, no radius), 1 = Radius (all points with d2 <= r^2), 2 = Hybrid (the max_nn
@@ -113,7 +121,7 @@ size_t orc_detect_boundary_points(const double *xyz, const double *normals, size
             orc_j3x3_smallest_eigvec(Cm, nrm);
         }
         double u[3], v[3];
-        tangent_basis(nrm, u, v);
+        if (!tangent_basis(nrm, u, v)) continue;
         size_t na = 0;
         for (size_t t = 0; t < m; ++t) {
             const double *p = xyz + 3 * nb[t].idx;

@@ -75,3 +75,128 @@ def test_python_api_estimate_normals(capi):
     assert np.array_equal(np.nan_to_num(np.asarray(c.normals)), np.nan_to_num(capi.normals_from_map(xyz, w, h, 5)))
     with pytest.raises(RuntimeError, match="not equal to given point map size"):
         m3d.common.estimate_normals(xyz, (w + 1, h), 3)
+
+
+# ------------------------------------------------------------------------------------------------
+# every compiled box-sum variant at its seams: the ring's tail, the 64-row block edge, the generic kernel's 256-row edge
+# ------------------------------------------------------------------------------------------------
+RING_DEPTH = {1: 8, 2: 8, 3: 8, 4: 6, 5: 4, 6: 4, 7: 4}      # nm_box_sum_k<K, DEPTH>; every other k: the generic kernel
+HEIGHTS = (1, 2, 63, 64, 65, 130)
+
+
+def _bitwise(capi, orc, xyz, w, h, k, vp=(0.1, -0.2, -0.5)):
+    """NaN masks equal, every normal that is finite in the oracle bit-equal -> (got, ref)"""
+    got = capi.normals_from_map(xyz, w, h, k, vp)
+    ref = orc.normals_from_map(xyz, w, h, k, vp)
+    assert np.array_equal(np.isnan(got), np.isnan(ref)), (w, h, k)
+    ok = np.isfinite(ref).all(axis=1)
+    assert np.array_equal(got[ok].view(np.uint64), ref[ok].view(np.uint64)), (w, h, k)
+    return got, ref
+
+
+def _sizes(k):
+    d = RING_DEPTH.get(k, 8)
+    widths = sorted({1, 2, 3, d - 1, d, d + 1, d + 2, 2 * d, 2 * d + 1, 2 * d + 3})
+    sizes = [(w, h) for w in widths for h in (2, 65)] + [(w, h) for w in (3, 2 * d + 1) for h in HEIGHTS]
+    sizes += [(w, 3) for w in range(1, 2 * d + 4)]               # every remainder of (w - 1) mod DEPTH, twice over
+    return sorted(set(sizes))
+
+
+@pytest.mark.parametrize("k", [1, 2, 3, 4, 5, 6, 7, 8])
+def test_normals_every_variant_at_its_seams(capi, orc, k):
+    sizes = _sizes(k)
+    assert any(k >= w for w, _ in sizes) and any(k >= h for _, h in sizes)
+    for w, h in sizes:
+        got, _ = _bitwise(capi, orc, _depth_map(w, h, seed=1000 * k + 10 * w + h, holes=0.05 if w * h > 8 else 0.0), w, h, k)
+        assert w * h <= 8 or np.isfinite(got).any()
+
+
+@pytest.mark.parametrize("k", [8, 12])
+@pytest.mark.parametrize("h", [255, 256, 257])
+def test_normals_generic_kernel_block_edge(capi, orc, k, h):
+    for w in (1, 5, 19):
+        _bitwise(capi, orc, _depth_map(w, h, seed=k + h + w), w, h, k)
+
+
+def _stress_maps(w, h):
+    """inputs that stress the recurrence rather than the surface"""
+    maps = {}
+    base = _depth_map(w, h, seed=77, holes=0.02)
+    maps["offset"] = base + np.array([1e3, -2e3, 5e2])           # E[x^2] - E[x]^2 cancels: covariances negative in the last bits
+    u, v = np.meshgrid(np.arange(w), np.arange(h))
+    maps["binary-plane"] = np.stack([u / 64.0, v / 64.0, np.ones((h, w))], -1).reshape(-1, 3)   # exact sums, zero off-diagonals
+    cols = base.reshape(h, w, 3).copy()
+    cols[:, ::3] = np.nan
+    maps["nan-columns"] = cols.reshape(-1, 3)
+    rows = base.reshape(h, w, 3).copy()
+    rows[1::4] = np.nan
+    maps["nan-rows"] = rows.reshape(-1, 3)
+    frame = base.reshape(h, w, 3).copy()
+    frame[[0, -1]] = np.nan
+    frame[:, [0, -1]] = np.nan
+    maps["nan-frame"] = frame.reshape(-1, 3)
+    corners = np.full((h, w, 3), np.nan)
+    for r in (0, h - 1):
+        for c in (0, w - 1):
+            corners[r, c] = base.reshape(h, w, 3)[r, c]
+    corners[0, 0] = _depth_map(w, h, seed=78, holes=0.0)[0]       # valid whatever base's holes are
+    maps["corners"] = corners.reshape(-1, 3)
+    return maps
+
+
+@pytest.mark.parametrize("k", [1, 4, 5, 8])
+def test_normals_stress_inputs(capi, orc, k):
+    w, h = 23, 67
+    for name, xyz in _stress_maps(w, h).items():
+        got, _ = _bitwise(capi, orc, xyz, w, h, k)
+        assert np.isfinite(got).any(), name
+        if name == "binary-plane":
+            # an exact plane z = 1: the covariance is off by a few ulp of 1 (1 / count is rounded), the in-plane variances
+            # are >= (1/128)^2, so the normal tilts by <= ~1e-11 and |n_z| falls short of 1 by its square
+            assert np.isfinite(got).all() and (np.abs(got[:, 2]) >= 1 - 1e-12).all()
+    row = _depth_map(37, 1, seed=79, holes=0.1)                   # a single valid row
+    _bitwise(capi, orc, row, 37, 1, k)
+
+
+@pytest.mark.parametrize("k", [2, 4, 7, 9])
+def test_normals_nonfinite_values_that_pass_validity(capi, orc, k):
+    """validity looks at z only: x = NaN with a finite z, and z = +Inf, poison the running sums of their rows from that
+    column on.  The NaN mask is the oracle's, and every normal the oracle has finite is bit-equal."""
+    w, h = 29, 66
+    xyz = _depth_map(w, h, seed=80, holes=0.0).reshape(h, w, 3)
+    xyz[5, 11, 0] = np.nan
+    xyz[40, 3, 2] = np.inf
+    xyz[64, 20, 1] = -np.inf
+    got, ref = _bitwise(capi, orc, xyz.reshape(-1, 3), w, h, k)
+    fin = np.isfinite(ref).all(axis=1).reshape(h, w)
+    assert fin[20:30].all()                                      # rows out of the windows' reach are untouched
+    assert not fin[5, 11:].any() and fin[5 + k + 1:40 - k - 1].any()
+
+
+def test_normals_orientation(capi, orc):
+    w, h, k = 31, 20, 3
+    xyz = _depth_map(w, h, seed=81, holes=0.02)
+    valid = ~np.isnan(xyz[:, 2])
+    at = np.flatnonzero(valid)[137]
+    for vp in ((0.0, 0.0, 0.0), (0.1, -0.2, -0.5), (0.0, 0.0, 5.0), (3.0, 1.0, 1.05), tuple(xyz[at])):
+        got, _ = _bitwise(capi, orc, xyz, w, h, k, vp)
+        ok = np.isfinite(got).all(axis=1)
+        assert np.array_equal(ok, valid)
+        assert (np.einsum("ij,ij->i", np.asarray(vp) - xyz[ok], got[ok]) >= 0).all()
+    front = capi.normals_from_map(xyz, w, h, k, (0.0, 0.0, 0.0))
+    behind = capi.normals_from_map(xyz, w, h, k, (0.0, 0.0, 5.0))
+    assert np.array_equal(front[valid], -behind[valid])           # the two sides of the surface
+    # (the view point ON a valid pixel, the last of the loop: dd == 0 there, no flip -- the bit comparison with the oracle
+    # is what holds the kernel to it)
+
+
+def test_normals_limits(capi, orc):
+    """k <= 4096 is accepted, 4097 is not.  k = 4096 itself needs 20 images of 8194^2 doubles (10.7 GB) on the device and
+    as much in the oracle, so the generic kernel is run at the largest k whose 20 images stay under 256 MB:
+    20 * 8 * (2 + 2k)^2 <= 2^28 -> k = 646"""
+    k = 646
+    assert 160 * (2 + 2 * k) ** 2 <= 1 << 28 < 160 * (2 + 2 * (k + 1)) ** 2
+    xyz = _depth_map(2, 2, seed=82, holes=0.0)
+    _bitwise(capi, orc, xyz, 2, 2, k)
+    with pytest.raises(capi.M3DError):
+        capi.normals_from_map(xyz, 2, 2, 4097)
