@@ -171,7 +171,19 @@ int m3d_cloud_score_shard(m3d_cloud *cloud, m3d_sampler *sampler, double thresho
 int m3d_cloud_exact_error(m3d_cloud *cloud, int kind, double threshold, const double *model,
                           uint64_t *count, double *error);
 /* RefineModel (ransac.h:534-549) for a given pre-refinement model: inlier indices (ascending) and
- * GeneralFit applied in place to params.  Return 1/0 = GeneralFit's return. */
+ * GeneralFit applied in place to params.  Return 1/0 = GeneralFit's return.
+ *
+ * REFINED PARAMETERS, the accuracy contract of every entry point that returns them (m3d_fit_plane / m3d_fit_sphere,
+ * m3d_cloud_fit, m3d_cloud_fit_batch, m3d_cloud_refine*, m3d_segment_plane_iterative*).  The reference answer is EXACT: for a
+ * plane the closed form of ransac.h:164-211 (centred moment sums, the three determinants, the branch by the largest, the
+ * `norm < 1e-8` failure) evaluated in rational arithmetic on the fit's own inliers; for a sphere the least-squares solution of
+ * [2x 2y 2z 1] w = |p|^2 on them.  With err = the largest absolute difference of the four parameters,
+ *     err <= max(32 err(fp64 restatement of the reference), F),   F = 16 * 2^-53 * max(1, max |inlier coordinate|, max |parameter|).
+ * Where the exact closed form fails (fewer than 3 / 4 inliers, norm < 1e-8) the return is 0 and params is the best minimal model,
+ * bit for bit.  A plane whose two largest determinants agree to 1e-9 is undecided: rounding picks the branch, and the result is
+ * held to the nearer of the two branches' exact values, up to the sign of (a, b, c, d).  The sums are taken about a point
+ * among the inliers -- a sample point of the winning hypothesis, or the inliers' mean -- never about a sphere's centre, which
+ * lies a radius away from a cap of inliers (tests/test_gpu_generalfit.py, tests/test_generalfit.py). */
 int m3d_cloud_refine(m3d_cloud *cloud, int kind, double threshold, double *params,
                      size_t *inliers, size_t *n_inliers);
 /* Same, when the caller already knows the inlier count of `params` from the scoring pass (the record of the best

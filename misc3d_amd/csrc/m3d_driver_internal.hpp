@@ -57,7 +57,6 @@ int approx_error_pair(DeviceCtx* ctx, const CloudView& v, int kind, double thr, 
                              const double* model_b, uint64_t* count_a, double* error_a, uint64_t* count_b, double* error_b);
 int approx_error(DeviceCtx* ctx, const CloudView& v, int kind, double thr,
                         const double* model_dev, uint64_t* count, double* error);
-bool plane_from_moments(const double* mean, const double* s, double* out);
 int refine_slot(const DeviceCtx* ctx);
 double* h_best_at(DeviceCtx* ctx);
 uint8_t* h_total_at(DeviceCtx* ctx);

@@ -19,6 +19,7 @@
 //
 // There is no CPU fallback: every entry point needs a HIP device.
 #include "m3d_driver_internal.hpp"
+#include "m3d_generalfit_fp.hpp"
 
 #pragma clang fp contract(off)
 

@@ -203,6 +203,12 @@ __global__ __launch_bounds__(64) void minimal_fit_k(CloudView c, const uint32_t*
             }
             ok = sphere_minimal_fit(p, par);
             if (ok) {
+                // spare slots of the PARAMETER record, as for the plane: the provisional centre of RefineModel's fused moment
+                // sums -- the centroid of the four sample points, which lies among the inliers (each sample point is one) and
+                // IS their mean when they are the only inliers; not the model's centre (see compact_count_k)
+                par[4] = ((p[0] + p[3]) + (p[6] + p[9])) * 0.25;
+                par[5] = ((p[1] + p[4]) + (p[7] + p[10])) * 0.25;
+                par[6] = ((p[2] + p[5]) + (p[8] + p[11])) * 0.25;
                 rec[0] = par[0];
                 rec[1] = par[1];
                 rec[2] = par[2];
@@ -429,11 +435,13 @@ __device__ __forceinline__ double ref_distance(const double* m, double x, double
 }
 
 // SUMS (RefineModel of a plane / sphere fit): the same pass also accumulates, over the INLIERS, the raw moments
-// GeneralFit needs about a provisional centre c0 taken from the model record (plane: the hypothesis' first sample
-// point, slots 4..6; sphere: the minimal model's centre) -- s = p - c0:
+// GeneralFit needs about a provisional centre c0 taken from the model record (slots 4..6: the plane hypothesis' first
+// sample point, the centroid of the sphere hypothesis' four) -- s = p - c0:
 //   [0..2] sum s   [3..8] sum s s^T (xx,xy,xz,yy,yz,zz)   [9..11] sum s |s|^2 (sphere)
 // one 16-double partial per workgroup (fixed tree: deterministic); scan_blocks_k folds the partials.  c0 lies
-// among the inliers, so the shift to the true mean (host, moments_about_mean) cancels at most a few bits.  This
+// among the inliers (a sample point is an inlier of its own minimal model), so the shift to the true mean (host, moments_about_mean,
+// m3d_generalfit_fp.hpp) cancels at most a few bits -- a sphere's minimal CENTRE would not do: it lies a radius away
+// from a cap of inliers, and the shift would cancel by (radius / extent)^3.  This
 // replaces two gather passes over the inlier list (ransac.h:170-188, 302-316 read the points once more).
 template <int KIND, bool SUMS>
 __global__ __launch_bounds__(256) void compact_count_k(CloudView c, const double* __restrict__ model,
@@ -455,7 +463,7 @@ __global__ __launch_bounds__(256) void compact_count_k(CloudView c, const double
     constexpr int NV = KIND == 1 ? 12 : 9;
     double acc[NV];
     for (int k = 0; k < NV; ++k) acc[k] = 0.0;
-    const double c0x = KIND == 0 ? m[4] : m[0], c0y = KIND == 0 ? m[5] : m[1], c0z = KIND == 0 ? m[6] : m[2];
+    const double c0x = m[4], c0y = m[5], c0z = m[6];
     for (int r = 0; r < kCompactTile / 256; ++r) {
         const uint32_t i = base + r * 256 + threadIdx.x;
         bool f = false;
@@ -661,8 +669,7 @@ __global__ __launch_bounds__(256) void compact_write_k(
     constexpr int NV = SUMS ? (KIND == 1 ? 12 : 9) : 1;
     double acc[NV];
     for (int k = 0; k < NV; ++k) acc[k] = 0.0;
-    const double c0x = SUMS ? (KIND == 0 ? m[4] : m[0]) : 0.0, c0y = SUMS ? (KIND == 0 ? m[5] : m[1]) : 0.0,
-                 c0z = SUMS ? (KIND == 0 ? m[6] : m[2]) : 0.0;
+    const double c0x = SUMS ? m[4] : 0.0, c0y = SUMS ? m[5] : 0.0, c0z = SUMS ? m[6] : 0.0;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const uint32_t i = base + r * 256 + threadIdx.x;
@@ -1124,32 +1131,6 @@ void launch_general_fit_sums(const CloudView& c, const uint64_t* idx, uint32_t n
                              double* out_host, hipStream_t s) {
     sum_xyz_k<<<kSumBlocks, 256, 0, s>>>(c, idx, n_idx, partial_dev);
     sum_moments_k<<<kSumBlocks, 256, 0, s>>>(c, idx, n_idx, partial_dev, out_host);
-}
-
-// Raw moments about the provisional centre c0 (compact_count_k<.., true> + scan_blocks_k) -> mean and centred moments.
-// With s = p - c0, m = (sum s) / n, r = s - m, q = |r|^2:
-//   sum r r^T = sum s s^T - n m m^T
-//   sum q     = trace of that
-//   sum r q   = sum s|s|^2 - 2 (sum s s^T) m + m (2 n |m|^2 - trace(sum s s^T))
-// c0 is an inlier (plane) / the minimal centre (sphere), so |m| is at most the inliers' extent and the subtractions
-// lose a few bits at worst.
-void moments_about_mean(const double* mo, const double c0[3], double n, double mean[3], double centred[10]) {
-    const double m[3] = {mo[0] / n, mo[1] / n, mo[2] / n};
-    for (int k = 0; k < 3; ++k) mean[k] = c0[k] + m[k];
-    const double S[6] = {mo[3], mo[4], mo[5], mo[6], mo[7], mo[8]};   // xx xy xz yy yz zz
-    centred[0] = S[0] - n * m[0] * m[0];
-    centred[1] = S[1] - n * m[0] * m[1];
-    centred[2] = S[2] - n * m[0] * m[2];
-    centred[3] = S[3] - n * m[1] * m[1];
-    centred[4] = S[4] - n * m[1] * m[2];
-    centred[5] = S[5] - n * m[2] * m[2];
-    const double trS = (S[0] + S[3]) + S[5];
-    const double mm = (m[0] * m[0] + m[1] * m[1]) + m[2] * m[2];
-    const double Sm[3] = {(S[0] * m[0] + S[1] * m[1]) + S[2] * m[2], (S[1] * m[0] + S[3] * m[1]) + S[4] * m[2],
-                          (S[2] * m[0] + S[4] * m[1]) + S[5] * m[2]};
-    const double f = 2.0 * n * mm - trS;
-    for (int k = 0; k < 3; ++k) centred[6 + k] = (mo[9 + k] - 2.0 * Sm[k]) + m[k] * f;
-    centred[9] = (centred[0] + centred[3]) + centred[5];
 }
 
 // sums[0..2] = sum of x, y, z; sums[4..13] = the ten centred moments: the last level of the fixed tree, on the host,

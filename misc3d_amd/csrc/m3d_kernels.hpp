@@ -145,11 +145,10 @@ void launch_compact(int kind, const CloudView& c, const double* model, double th
                     uint32_t* ready_word = nullptr /* the mask form: page-locked word that receives done_seq as soon as the mask and
                                                       the tile counts are in host memory, ahead of the moments and the total */);
 // moment_out layout: [0..2] sum s, [3..8] sum s s^T (xx,xy,xz,yy,yz,zz), [9..11] sum s |s|^2 (sphere), [12] inlier count;
-// s = p - c0, c0 = model[4..6] (plane: the hypothesis' first sample point) or model[0..2] (sphere: the minimal centre).
+// s = p - c0, c0 = model[4..6]: the plane hypothesis' first sample point, the centroid of the sphere hypothesis' four (minimal_fit_k).
+// moments_about_mean (m3d_generalfit_fp.hpp) turns them into what the closed forms take: mean[3] and the ten centred
+// moments (xx,xy,xz,yy,yz,zz, sum r q (3), sum q with q = |r|^2, r = p - mean) -- the same quantities sum_moments_k produces
 constexpr int kFusedMomentDoubles = 16;
-// raw moments about c0 -> what the closed forms take: mean[3] and the ten centred moments (xx,xy,xz,yy,yz,zz, sum r q
-// (3), sum q with q = |r|^2, r = p - mean) -- the same quantities sum_moments_k produces
-void moments_about_mean(const double* moment_out, const double c0[3], double n, double mean[3], double centred[10]);
 
 // serial-order sum of `n[0]` doubles (EvaluateModel's `error += distance`, ransac.h:637)
 void launch_serial_sum(const double* v, const uint32_t* n, double* out, hipStream_t s);

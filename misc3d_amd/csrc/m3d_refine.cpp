@@ -2,6 +2,7 @@
 // fitness ties (ransac.h:595-596, 632-650): the ordered inlier list (compact_count_k + scan_blocks_k + compact_write_k, straight
 // into the caller's page-locked buffer), GeneralFit from the fused moments, the serial-order sum on demand.
 #include "m3d_driver_internal.hpp"
+#include "m3d_generalfit_fp.hpp"
 #include "m3d_mask_expand.hpp"
 
 #include <condition_variable>
@@ -216,76 +217,7 @@ int approx_error(DeviceCtx* ctx, const CloudView& v, int kind, double thr,
     return approx_error_pair(ctx, v, kind, thr, model_dev, nullptr, count, error, nullptr, nullptr);
 }
 
-// ------------------------------------------------------------------------------------------------
-// GeneralFit closed forms (host; the sums come from sum_*_k)
-// ------------------------------------------------------------------------------------------------
-// PlaneEstimator::GeneralFit, ransac.h:190-211
-bool plane_from_moments(const double* mean, const double* s, double* out) {
-    const double xx = s[0], xy = s[1], xz = s[2], yy = s[3], yz = s[4], zz = s[5];
-    const double det_x = yy * zz - yz * yz;
-    const double det_y = xx * zz - xz * xz;
-    const double det_z = xx * yy - xy * xy;
-    double a, b, c;
-    if (det_x > det_y && det_x > det_z) {
-        a = det_x;
-        b = xz * yz - xy * zz;
-        c = xy * yz - xz * yy;
-    } else if (det_y > det_z) {
-        a = xz * yz - xy * zz;
-        b = det_y;
-        c = xy * xz - yz * xx;
-    } else {
-        a = xy * yz - xz * yy;
-        b = xy * xz - yz * xx;
-        c = det_z;
-    }
-    const double norm = std::sqrt((a * a + b * b) + c * c);
-    if (norm < 1.0e-8) return false;
-    a /= norm;
-    b /= norm;
-    c /= norm;
-    out[0] = a;
-    out[1] = b;
-    out[2] = c;
-    out[3] = -((a * mean[0] + b * mean[1]) + c * mean[2]);
-    return true;
-}
-
-// SphereEstimator::GeneralFit, ransac.h:296-330: least squares of [2x 2y 2z 1] w = x^2+y^2+z^2.
-// The reference's bdcSvd(FullU) needs an N_inl x N_inl matrix (its own TODO, ransac.h:318-319);
-// here the same least-squares problem is solved from the CENTRED normal equations
-//   4 S c' = 2 sum(p' q),  w3' = sum(q)/n,  q = |p'|^2,  p' = p - mean,
-// then centre = mean + c', r = sqrt(|c'|^2 + w3').  Same minimiser, parameters agree to ~1e-12.
-static bool sphere_from_moments(const double* mean, const double* s, double n, double* out) {
-    double A[3][4] = {{4 * s[0], 4 * s[1], 4 * s[2], 2 * s[6]},
-                      {4 * s[1], 4 * s[3], 4 * s[4], 2 * s[7]},
-                      {4 * s[2], 4 * s[4], 4 * s[5], 2 * s[8]}};
-    for (int col = 0; col < 3; ++col) {  // Gaussian elimination, partial pivoting
-        int piv = col;
-        for (int r = col + 1; r < 3; ++r)
-            if (std::fabs(A[r][col]) > std::fabs(A[piv][col])) piv = r;
-        if (piv != col)
-            for (int k = 0; k < 4; ++k) std::swap(A[piv][k], A[col][k]);
-        if (A[col][col] == 0.0) continue;
-        for (int r = col + 1; r < 3; ++r) {
-            const double f = A[r][col] / A[col][col];
-            for (int k = col; k < 4; ++k) A[r][k] -= f * A[col][k];
-        }
-    }
-    double c[3];
-    for (int r = 2; r >= 0; --r) {
-        double acc = A[r][3];
-        for (int k = r + 1; k < 3; ++k) acc -= A[r][k] * c[k];
-        c[r] = A[r][r] != 0.0 ? acc / A[r][r] : 0.0;
-    }
-    const double w3 = s[9] / n;
-    out[0] = mean[0] + c[0];
-    out[1] = mean[1] + c[1];
-    out[2] = mean[2] + c[2];
-    out[3] = std::sqrt(((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]) + w3);
-    return true;
-}
-
+// (GeneralFit's closed forms -- moments_about_mean, plane_from_moments, sphere_from_moments: m3d_generalfit_fp.hpp)
 
 // RefineModel, ransac.h:534-549.  flag_view: cloud the distances are evaluated on; gather_view +
 // orig: when the flags are computed on a compacted cloud (segmentation) the inlier list holds
@@ -476,10 +408,10 @@ int refine(DeviceCtx* ctx, const CloudView& flag_view, const CloudView& gather_v
                 double sums[14];
                 double mean[3];
                 if (have_moments) {
-                    // raw moments about the record's provisional centre -> mean + centred moments (m3d_kernels.hip)
+                    // raw moments about the record's provisional centre (slots 4..6: a point among the samples) -> mean +
+                    // centred moments (m3d_generalfit_fp.hpp)
                     const double* rec = lazy_in;
-                    const double c0[3] = {kind == M3D_PLANE ? rec[4] : rec[0], kind == M3D_PLANE ? rec[5] : rec[1],
-                                          kind == M3D_PLANE ? rec[6] : rec[2]};
+                    const double c0[3] = {rec[4], rec[5], rec[6]};
                     moments_about_mean(h_moments_at(ctx), c0, (double)ni_e, mean, sums + 4);
                 } else {
                     general_fit_sums_finish(ctx->h_sums.as<double>(), sums);

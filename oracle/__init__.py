@@ -201,6 +201,7 @@ class FitResult:
     iterations: int
     best_index: int
     trace: dict | None = None
+    general_fit_ok: int = 1      # RefineModel's return value (0: GeneralFit failed, params is the best minimal model)
 
 
 def fit(kind, xyz, normals=None, thr=0.01, max_iter=1000, prob=0.9999, seed=0, trace=False, lookahead=1) -> FitResult:
@@ -230,7 +231,7 @@ def fit(kind, xyz, normals=None, thr=0.01, max_iter=1000, prob=0.9999, seed=0, t
     else:
         ret = lib().orc_fit(*args)
     return FitResult(ret, params, inl[: ni.value].copy(), st.fitness, st.inlier_rmse, int(st.count),
-                     int(st.iterations), int(st.best_index), tr_arrays)
+                     int(st.iterations), int(st.best_index), tr_arrays, int(st.general_fit_ok))
 
 
 def refine(kind, xyz, thr, model):
