@@ -65,17 +65,21 @@ struct CloudView {
     const double* xyz = nullptr;      // n x 3
     const double* normals = nullptr;  // n x 3 or null
     size_t n = 0;
+    const double* colors = nullptr;   // n x 3 (RGB) or null: read by coloured ICP only
     CloudView() = default;
     CloudView(const double* p, const double* nrm, size_t count) : xyz(p), normals(nrm), n(count) {}
+    CloudView(const double* p, const double* nrm, const double* rgb, size_t count) : xyz(p), normals(nrm), n(count), colors(rgb) {}
     CloudView(const PointCloud& pc)  // NOLINT: implicit by design
         : xyz(pc.points_.empty() ? nullptr : pc.points_[0].data()),
           normals(pc.HasNormals() ? pc.normals_[0].data() : nullptr),
-          n(pc.points_.size()) {}
+          n(pc.points_.size()),
+          colors(pc.HasColors() ? pc.colors_[0].data() : nullptr) {}
 #ifdef MISC3D_WITH_OPEN3D
     CloudView(const open3d::geometry::PointCloud& pc)  // NOLINT: Eigen::Vector3d is 24-byte POD
         : xyz(pc.points_.empty() ? nullptr : pc.points_[0].data()),
           normals(pc.HasNormals() ? pc.normals_[0].data() : nullptr),
-          n(pc.points_.size()) {}
+          n(pc.points_.size()),
+          colors(pc.HasColors() ? pc.colors_[0].data() : nullptr) {}
 #endif
 };
 

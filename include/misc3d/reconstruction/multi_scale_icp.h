@@ -1,7 +1,8 @@
 // misc3d/reconstruction/multi_scale_icp.h -- the local-refinement stage of misc3d::reconstruction::ReconstructionPipeline
 // over the C ABI: MultiScaleICP (src/pipeline.cpp:927-982) and its two callers' registration step, RefineFragmentPair
-// (:686-697) and the odometry case of RegisterFragmentPair (:754-763).  Point2PointICP and Point2PlaneICP are accelerated;
-// ColoredICP (the reference's default: needs colour gradients) and GeneralizedICP are refused with an error.
+// (:686-697) and the odometry case of RegisterFragmentPair (:754-763).  Point2PointICP and Point2PlaneICP are accelerated, and
+// so is ColoredICP (the reference's default) when both clouds carry colours (CloudView::colors); ColoredICP without colours and
+// GeneralizedICP are refused with an error.
 #pragma once
 #include <array>
 #include <tuple>
@@ -26,10 +27,11 @@ struct MultiScaleICPOption {
     double voxel_size = 0.01;   // PipelineConfig::voxel_size_ (a float there); max_dis = 1.4 voxel_size at every level (:936)
     LocalRefineMethod method = LocalRefineMethod::Point2PlaneICP;
     int device = 0;
+    double lambda_geometric = 0.968;   // TransformationEstimationForColoredICP's (ColoredICP only)
 };
 
 // std::tuple<Eigen::Matrix4d, Eigen::Matrix6d> ReconstructionPipeline::MultiScaleICP(src, dst, voxel_size, max_iter, init_trans).
-// dst needs normals for Point2PlaneICP.  levels (optional): one record per level.
+// dst needs normals for Point2PlaneICP and ColoredICP; ColoredICP runs when both views carry colours.  levels (optional): one record per level.
 inline std::tuple<Matrix4d, Matrix6d> MultiScaleICP(const CloudView& src, const CloudView& dst,
                                                    const std::vector<float>& voxel_size, const std::vector<int>& max_iter,
                                                    const Matrix4d& init_trans, const MultiScaleICPOption& opt = {},
@@ -39,6 +41,13 @@ inline std::tuple<Matrix4d, Matrix6d> MultiScaleICP(const CloudView& src, const 
     if (levels) levels->assign(sizes.size(), m3d_multi_scale_icp_level{});
     Matrix4d pose;
     Matrix6d info;
+    if (opt.method == LocalRefineMethod::ColoredICP && src.colors && dst.colors) {
+        CheckStatus(m3d_multi_scale_icp_colored(src.xyz, src.normals, src.colors, src.n, dst.xyz, dst.normals, dst.colors, dst.n,
+                                                sizes.data(), max_iter.data(), sizes.size(), (double)(float)opt.voxel_size * 1.4,
+                                                opt.lambda_geometric, init_trans.data(), opt.device, pose.data(), info.data(),
+                                                levels && !levels->empty() ? levels->data() : nullptr));
+        return std::make_tuple(pose, info);
+    }
     CheckStatus(m3d_multi_scale_icp(src.xyz, src.normals, src.n, dst.xyz, dst.normals, dst.n, sizes.data(), max_iter.data(),
                                     sizes.size(), (double)(float)opt.voxel_size * 1.4, (int)opt.method, init_trans.data(),
                                     opt.device, pose.data(), info.data(), levels && !levels->empty() ? levels->data() : nullptr));

@@ -88,6 +88,23 @@ def registration_icp(source, target, max_correspondence_distance, init=None, max
         raise RuntimeError(str(e)) from e
 
 
+def registration_colored_icp(source, target, max_correspondence_distance, init=None, lambda_geometric=0.968, max_iteration=30,
+                             relative_fitness=1e-6, relative_rmse=1e-6, device=0):
+    """open3d.pipelines.registration.registration_colored_icp(source, target, max_correspondence_distance, init,
+    TransformationEstimationForColoredICP(lambda_geometric), ICPConvergenceCriteria(...)): MultiScaleICP's ColoredICP, the
+    reference's default (src/pipeline.cpp:956-962).  source / target: (points, normals, colors) tuples or objects with
+    .points / .normals / .colors; the source needs colours, the target normals and colours (RuntimeError without them).
+    Returns (4x4 pose, dict(fitness, inlier_rmse, correspondences, iterations, converged)), as registration_icp does."""
+    from . import capi as _capi
+    src, _, sc = _points_normals_colors(source)
+    dst, nrm, dc = _points_normals_colors(target)
+    try:
+        return _capi.registration_icp_colored(src, sc, dst, nrm, dc, max_correspondence_distance, init, lambda_geometric,
+                                              max_iteration, relative_fitness, relative_rmse, device)
+    except _capi.M3DError as e:
+        raise RuntimeError(str(e)) from e
+
+
 def _search_param(param):
     """An open3d KDTreeSearchParamHybrid / KDTreeSearchParamRadius / KDTreeSearchParamKNN (anything with .radius and
     optionally .max_nn, or with .knn), or a tuple ("hybrid", radius, max_nn) / ("radius", radius) / ("knn", k)
@@ -123,6 +140,23 @@ def _points_normals(pc):
         if len(nrm) != len(pts) or len(nrm) == 0:
             nrm = None
     return pts, nrm
+
+
+def _points_normals_colors(pc):
+    """_points_normals, and a (points, normals, colors) tuple or an object's .colors -> (points, normals, colors); an entry
+    that is missing, empty or of another length is None"""
+    import numpy as _np
+    if isinstance(pc, tuple) and len(pc) == 3 and _np.ndim(pc[0]) == 2:   # (three bare points stay an array of points)
+        pts, nrm = _points_normals((pc[0], pc[1]))
+        col = pc[2]
+    else:
+        pts, nrm = _points_normals(pc)
+        col = None if isinstance(pc, tuple) else getattr(pc, "colors", None)
+    if col is not None:
+        col = _np.asarray(col, dtype=_np.float64).reshape(-1, 3)
+        if len(col) != len(pts) or len(col) == 0:
+            col = None
+    return pts, nrm, col
 
 
 class _Features:
@@ -197,7 +231,7 @@ class LocalRefineMethod(_enum.IntEnum):
     """PipelineConfig::LocalRefineMethod (include/misc3d/reconstruction/pipeline_config.h:23-28)"""
     Point2PointICP = 0
     Point2PlaneICP = 1
-    ColoredICP = 2        # the reference's default; not accelerated (needs colour gradients)
+    ColoredICP = 2        # the reference's default; accelerated when both clouds carry colours (m3d_multi_scale_icp_colored)
     GeneralizedICP = 3    # not accelerated
 
 
@@ -222,25 +256,32 @@ class _Reconstruction:
 
     @staticmethod
     def multi_scale_icp(source, target, voxel_sizes, max_iters, max_correspondence_distance, init=None,
-                        method="point_to_plane", *, device=0, stats=False):
+                        method="point_to_plane", *, device=0, stats=False, lambda_geometric=0.968):
         """ReconstructionPipeline::MultiScaleICP: per level both clouds voxel-down-sampled from the originals, ICP with
         ICPConvergenceCriteria(1e-6, 1e-6, max_iters[l]) seeded with the previous level's pose; then the information matrix
         of the original clouds at 1.4 voxel_sizes[-1].  source / target: (N, 3) arrays, (points, normals) tuples or objects
-        with .points / .normals; method: "point_to_point", "point_to_plane" or a LocalRefineMethod (ColoredICP and
-        GeneralizedICP are not accelerated: RuntimeError).  Returns (4x4 pose, 6x6 information), and the per-level stats
-        when stats=True."""
+        with .points / .normals; method: "point_to_point", "point_to_plane", "colored" or a LocalRefineMethod.  ColoredICP
+        runs when both clouds carry colours ((points, normals, colors) tuples or objects with .colors), with
+        lambda_geometric; without colours it is refused as before, as GeneralizedICP always is ("not accelerated":
+        RuntimeError).  Returns (4x4 pose, 6x6 information), and the per-level stats when stats=True."""
         from . import capi as _capi
-        src, sn = _points_normals(source)
-        dst, dn = _points_normals(target)
+        src, sn, sc = _points_normals_colors(source)
+        dst, dn, dc = _points_normals_colors(target)
+        m = _refine_method(method)
         try:
-            T, info, levels = _capi.multi_scale_icp(src, dst, voxel_sizes, max_iters, max_correspondence_distance, init,
-                                                    _refine_method(method), dn, sn, device)
+            if m == _capi.REFINE_COLORED_ICP and sc is not None and dc is not None:
+                T, info, levels = _capi.multi_scale_icp_colored(src, sc, dst, dn, dc, voxel_sizes, max_iters,
+                                                                max_correspondence_distance, init, lambda_geometric, sn, device)
+            else:
+                T, info, levels = _capi.multi_scale_icp(src, dst, voxel_sizes, max_iters, max_correspondence_distance, init,
+                                                        m, dn, sn, device)
         except _capi.M3DError as e:
             raise RuntimeError(str(e)) from e
         return (T, info, levels) if stats else (T, info)
 
     @staticmethod
-    def refine_fragment_pair(source, target, voxel_size, init=None, method="point_to_plane", *, device=0, stats=False):
+    def refine_fragment_pair(source, target, voxel_size, init=None, method="point_to_plane", *, device=0, stats=False,
+                             lambda_geometric=0.968):
         """RefineFragmentPair's registration (src/pipeline.cpp:686-697): multi_scale_icp with {v, v/2, v/4} -- formed in
         single precision, as the reference's `const float voxel_size` forms them -- max iterations {50, 30, 15} and
         max_correspondence_distance = 1.4 voxel_size (the single-precision value, as config_.voxel_size_ is); init: the pose-graph edge's pose."""
@@ -248,15 +289,17 @@ class _Reconstruction:
         v = _np.float32(voxel_size)
         sizes = [float(v), float(v / _np.float32(2.0)), float(v / _np.float32(4.0))]
         return _Reconstruction.multi_scale_icp(source, target, sizes, [50, 30, 15], float(v) * 1.4, init, method,
-                                               device=device, stats=stats)
+                                               device=device, stats=stats, lambda_geometric=lambda_geometric)
 
     @staticmethod
-    def fragment_odometry(source, target, voxel_size, init=None, method="point_to_plane", *, device=0, stats=False):
+    def fragment_odometry(source, target, voxel_size, init=None, method="point_to_plane", *, device=0, stats=False,
+                          lambda_geometric=0.968):
         """RegisterFragmentPair for ADJACENT fragments (src/pipeline.cpp:754-763): multi_scale_icp with {v} (in single
         precision), {50} and max_correspondence_distance = 1.4 voxel_size; init: the pose from the fragment pose graph."""
         import numpy as _np
         v = float(_np.float32(voxel_size))
-        return _Reconstruction.multi_scale_icp(source, target, [v], [50], v * 1.4, init, method, device=device, stats=stats)
+        return _Reconstruction.multi_scale_icp(source, target, [v], [50], v * 1.4, init, method, device=device, stats=stats,
+                                               lambda_geometric=lambda_geometric)
 
     @staticmethod
     def global_registration(source, target, feature_source, feature_target, voxel_size, max_iter=100000,
@@ -569,5 +612,5 @@ def registration_session(*args, **kwargs):
     from . import capi as _capi
     return _capi.RegSession(*args, **kwargs)
 
-__all__ = ["common", "registration", "segmentation", "features", "preprocessing", "reconstruction", "pose_estimation", "registration_icp", "registration_session", "VerbosityLevel", "set_verbosity_level",
+__all__ = ["common", "registration", "segmentation", "features", "preprocessing", "reconstruction", "pose_estimation", "registration_icp", "registration_colored_icp", "registration_session", "VerbosityLevel", "set_verbosity_level",
            "get_verbosity_level", "device_count"]

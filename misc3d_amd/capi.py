@@ -161,6 +161,13 @@ def lib():
         L.m3d_multi_scale_icp.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                           C.c_void_p, C.c_size_t, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                           C.c_void_p, C.c_void_p]
+        L.m3d_color_gradient.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_int, C.c_int, C.c_void_p]
+        L.m3d_registration_icp_colored.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_size_t, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_double,
+                                                   C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.m3d_multi_scale_icp_colored.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double,
+                                                  C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.m3d_normals_from_map.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int,
                                            C.c_void_p, C.c_void_p]
         L.m3d_information_matrix.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p, C.c_int,
@@ -1075,6 +1082,49 @@ def registration_icp_plane(src, dst, dst_normals, max_correspondence_distance, i
     return T.reshape(4, 4), st.asdict()
 
 
+def _rows(a, like, what):
+    """an optional n x 3 array with one row per row of `like`"""
+    if a is None:
+        return None
+    a = _f64(a).reshape(-1, 3)
+    if len(a) != len(like):
+        raise ValueError(what + " must have one row per point")
+    return a
+
+
+def color_gradient(dst, dst_normals, dst_colors, radius, max_nn=30, device=0):
+    """m3d_color_gradient: the per-point colour gradients of coloured ICP (InitializePointCloudForColoredICP) over the Hybrid
+    (radius, max_nn) neighbourhoods -> (n, 3)."""
+    dst = _f64(dst).reshape(-1, 3)
+    nrm, col = _rows(dst_normals, dst, "dst_normals"), _rows(dst_colors, dst, "dst_colors")
+    out = np.zeros((max(len(dst), 1), 3))
+    _check(lib().m3d_color_gradient(_p(dst), _p(nrm), _p(col), len(dst), float(radius), int(max_nn), device, _p(out)))
+    return out[: len(dst)]
+
+
+def registration_icp_colored(src, src_colors, dst, dst_normals, dst_colors, max_correspondence_distance, init=None,
+                             lambda_geometric=0.968, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6, device=0,
+                             want_correspondences=False):
+    """m3d_registration_icp_colored: registration_colored_icp(source, target, max_correspondence_distance, init,
+    TransformationEstimationForColoredICP(lambda_geometric), ICPConvergenceCriteria(...)) -> (T, stats[, correspondences]).
+    Missing normals or colours (None): the library's error."""
+    src = _f64(src).reshape(-1, 3)
+    dst = _f64(dst).reshape(-1, 3)
+    sc = _rows(src_colors, src, "src_colors")
+    nrm, dc = _rows(dst_normals, dst, "dst_normals"), _rows(dst_colors, dst, "dst_colors")
+    Ti = _f64(init).reshape(16).copy() if init is not None else None
+    T = np.zeros(16)
+    st = IcpStats()
+    corr = np.zeros(max(len(src), 1), dtype=np.int64) if want_correspondences else None
+    _check(lib().m3d_registration_icp_colored(_p(src), _p(sc), len(src), _p(dst), _p(nrm), _p(dc), len(dst),
+                                              max_correspondence_distance, lambda_geometric, _p(Ti), max_iteration,
+                                              relative_fitness, relative_rmse, device, _p(T), C.cast(C.byref(st), C.c_void_p),
+                                              _p(corr)))
+    if want_correspondences:
+        return T.reshape(4, 4), st.asdict(), corr[: len(src)]
+    return T.reshape(4, 4), st.asdict()
+
+
 REFINE_POINT2POINT_ICP, REFINE_POINT2PLANE_ICP, REFINE_COLORED_ICP, REFINE_GENERALIZED_ICP = 0, 1, 2, 3
 
 
@@ -1110,6 +1160,30 @@ def multi_scale_icp(src, dst, voxel_sizes, max_iters, max_correspondence_distanc
     _check(lib().m3d_multi_scale_icp(_p(src), _p(sn), len(src), _p(dst), _p(dn), len(dst), _p(sizes) if L else None,
                                      _p(iters) if L else None, L, float(max_correspondence_distance), int(method), _p(Ti),
                                      device, _p(T), _p(info), C.cast(lv, C.c_void_p)))
+    return T.reshape(4, 4), info.reshape(6, 6), [lv[l].asdict() for l in range(L)]
+
+
+def multi_scale_icp_colored(src, src_colors, dst, dst_normals, dst_colors, voxel_sizes, max_iters, max_correspondence_distance,
+                            init=None, lambda_geometric=0.968, src_normals=None, device=0):
+    """m3d_multi_scale_icp_colored: MultiScaleICP with LocalRefineMethod::ColoredICP -> (T (4, 4), information (6, 6),
+    [per-level stats])."""
+    src = _f64(src).reshape(-1, 3)
+    dst = _f64(dst).reshape(-1, 3)
+    sc, sn = _rows(src_colors, src, "src_colors"), _rows(src_normals, src, "src_normals")
+    dn, dc = _rows(dst_normals, dst, "dst_normals"), _rows(dst_colors, dst, "dst_colors")
+    sizes = np.ascontiguousarray(voxel_sizes, dtype=np.float64).reshape(-1)
+    iters = np.ascontiguousarray(max_iters, dtype=np.int32).reshape(-1)
+    if len(sizes) != len(iters):
+        raise ValueError("voxel_sizes and max_iters differ in length")
+    L = len(sizes)
+    Ti = _f64(init).reshape(16).copy() if init is not None else None
+    T = np.zeros(16)
+    info = np.zeros(36)
+    lv = (MultiScaleIcpLevel * max(L, 1))()
+    _check(lib().m3d_multi_scale_icp_colored(_p(src), _p(sn), _p(sc), len(src), _p(dst), _p(dn), _p(dc), len(dst),
+                                             _p(sizes) if L else None, _p(iters) if L else None, L,
+                                             float(max_correspondence_distance), float(lambda_geometric), _p(Ti), device, _p(T),
+                                             _p(info), C.cast(lv, C.c_void_p)))
     return T.reshape(4, 4), info.reshape(6, 6), [lv[l].asdict() for l in range(L)]
 
 

@@ -229,11 +229,18 @@ int registration_icp_plane_on(DeviceCtx* held, const double* src, size_t n_src, 
                               size_t n_dst, double max_correspondence_distance, const double* T_init, int max_iteration,
                               double relative_fitness, double relative_rmse, int device, double* T_out, m3d_icp_stats* stats,
                               int64_t* correspondences);
+// m3d_registration_icp_colored, the same way (m3d_multi_scale_icp_colored holds the lane)
+int registration_icp_colored_on(DeviceCtx* held, const double* src, const double* src_colors, size_t n_src, const double* dst,
+                                const double* dst_normals, const double* dst_colors, size_t n_dst,
+                                double max_correspondence_distance, double lambda_geometric, const double* T_init,
+                                int max_iteration, double relative_fitness, double relative_rmse, int device, double* T_out,
+                                m3d_icp_stats* stats, int64_t* correspondences);
 // m3d_voxel.cpp: the levels of m3d_voxel_down_sample_multi (points and normals) on a lane the caller holds, into host arrays of
 // n rows each; level_ms (may be null): host clock per level, the upload and the bounds counted with level 0.  voxel_sizes_check:
 // rule 1 of the voxel contract for every size (M3D_ERR_INVALID_ARG + its message)
 int voxel_levels_on(DeviceCtx* ctx, const double* xyz, const double* normals, size_t n, const double* voxel_sizes, size_t n_levels,
-                    double* const* out_xyz, double* const* out_normals, size_t* m, double* level_ms);
+                    double* const* out_xyz, double* const* out_normals, size_t* m, double* level_ms,
+                    const double* colors = nullptr, double* const* out_colors = nullptr /* the levels' colour means too */);
 int voxel_sizes_check(const double* voxel_sizes, size_t n_levels);
 
 void dev_pool_trim(int device);

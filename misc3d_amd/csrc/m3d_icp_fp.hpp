@@ -1,5 +1,5 @@
-// m3d_icp_fp.hpp -- the host arithmetic of point-to-plane ICP's ComputeTransformation (m3d_registration_icp_plane): from the 30
-// sums of an iteration to its 4 x 4 update.  Plain C++, no HIP: the library and the stand-alone check
+// m3d_icp_fp.hpp -- the host arithmetic of point-to-plane and coloured ICP's ComputeTransformation (m3d_registration_icp_plane,
+// m3d_registration_icp_colored): from the 30 sums of an iteration to its 4 x 4 update; and the 3 x 3 solve of the colour gradient.  Plain C++, no HIP: the library and the stand-alone check
 // tests/cpp/test_icp_solve.cpp compile the same text (build with -ffp-contract=off).
 //
 // [RECALL] Open3D 0.15.1 TransformationEstimationPointToPlane::ComputeTransformation ->
@@ -12,6 +12,12 @@
 #pragma once
 #include <cmath>
 #include <cstring>
+
+#if defined(__HIPCC__)
+#define M3D_ICP_HD __host__ __device__
+#else
+#define M3D_ICP_HD
+#endif
 
 namespace m3d {
 
@@ -53,56 +59,66 @@ inline double icp_det6(const double* A) {
     return det;
 }
 
-// x = A.ldlt().solve(b) for a symmetric 6 x 6 A: P A P^T = L D L^T with the largest remaining |diagonal| as the pivot of
+// x = A.ldlt().solve(b) for a symmetric N x N A: P A P^T = L D L^T with the largest remaining |diagonal| as the pivot of
 // every step (Eigen's LDLT), then the two triangular solves; a zero pivot's component of the solution is 0, as Eigen's.
-inline void icp_ldlt_solve6(const double* A, const double* b, double* x) {
-    double M[36];   // below the diagonal: L, column by column as the steps finish; the rest: what is left to factor
-    std::memcpy(M, A, sizeof(M));
-    int perm[6];
-    double D[6];
-    for (int k = 0; k < 6; ++k) perm[k] = k;
-    for (int k = 0; k < 6; ++k) {
+// One text for both sizes: 6 (the pose, on the host) and 3 (the colour gradient, in color_gradient_k and on the host).
+template <int N>
+M3D_ICP_HD inline void icp_ldlt_solve(const double* A, const double* b, double* x) {
+    double M[N * N];   // below the diagonal: L, column by column as the steps finish; the rest: what is left to factor
+    for (int k = 0; k < N * N; ++k) M[k] = A[k];
+    int perm[N];
+    double D[N];
+    for (int k = 0; k < N; ++k) perm[k] = k;
+    for (int k = 0; k < N; ++k) {
         int p = k;
-        double best = std::fabs(M[6 * k + k]);
-        for (int i = k + 1; i < 6; ++i) {
-            const double v = std::fabs(M[6 * i + i]);
+        double best = std::fabs(M[N * k + k]);
+        for (int i = k + 1; i < N; ++i) {
+            const double v = std::fabs(M[N * i + i]);
             if (v > best) {
                 best = v;
                 p = i;
             }
         }
-        if (p != k) {
-            for (int j = 0; j < 6; ++j) {   // rows k, p (the finished columns of L with them)
-                const double t = M[6 * k + j];
-                M[6 * k + j] = M[6 * p + j];
-                M[6 * p + j] = t;
+        for (int q = k + 1; q < N; ++q) {   // (q == p found by a loop over constants: on the device M stays in registers)
+            if (q != p) continue;
+            for (int j = 0; j < N; ++j) {   // rows k, p (the finished columns of L with them)
+                const double t = M[N * k + j];
+                M[N * k + j] = M[N * q + j];
+                M[N * q + j] = t;
             }
-            for (int i = 0; i < 6; ++i) {   // columns k, p
-                const double t = M[6 * i + k];
-                M[6 * i + k] = M[6 * i + p];
-                M[6 * i + p] = t;
+            for (int i = 0; i < N; ++i) {   // columns k, p
+                const double t = M[N * i + k];
+                M[N * i + k] = M[N * i + q];
+                M[N * i + q] = t;
             }
             const int t = perm[k];
-            perm[k] = perm[p];
-            perm[p] = t;
+            perm[k] = perm[q];
+            perm[q] = t;
         }
-        const double d = M[6 * k + k];
+        const double d = M[N * k + k];
         D[k] = d;
-        for (int i = k + 1; i < 6; ++i) {
-            const double l = d != 0.0 ? M[6 * i + k] / d : 0.0;
-            for (int j = k + 1; j < 6; ++j) M[6 * i + j] -= l * M[6 * k + j];
-            M[6 * i + k] = l;
+        for (int i = k + 1; i < N; ++i) {
+            const double l = d != 0.0 ? M[N * i + k] / d : 0.0;
+            for (int j = k + 1; j < N; ++j) M[N * i + j] -= l * M[N * k + j];
+            M[N * i + k] = l;
         }
     }
-    double y[6];
-    for (int i = 0; i < 6; ++i) y[i] = b[perm[i]];
-    for (int i = 0; i < 6; ++i)   // L z = y
-        for (int j = 0; j < i; ++j) y[i] -= M[6 * i + j] * y[j];
-    for (int i = 0; i < 6; ++i) y[i] = D[i] != 0.0 ? y[i] / D[i] : 0.0;
-    for (int i = 5; i >= 0; --i)   // L^T v = w
-        for (int j = i + 1; j < 6; ++j) y[i] -= M[6 * j + i] * y[j];
-    for (int i = 0; i < 6; ++i) x[perm[i]] = y[i];
+    double y[N];
+    for (int i = 0; i < N; ++i)
+        for (int j = 0; j < N; ++j)
+            if (perm[i] == j) y[i] = b[j];
+    for (int i = 0; i < N; ++i)   // L z = y
+        for (int j = 0; j < i; ++j) y[i] -= M[N * i + j] * y[j];
+    for (int i = 0; i < N; ++i) y[i] = D[i] != 0.0 ? y[i] / D[i] : 0.0;
+    for (int i = N - 1; i >= 0; --i)   // L^T v = w
+        for (int j = i + 1; j < N; ++j) y[i] -= M[N * j + i] * y[j];
+    for (int i = 0; i < N; ++i)
+        for (int j = 0; j < N; ++j)
+            if (perm[i] == j) x[j] = y[i];
 }
+inline void icp_ldlt_solve6(const double* A, const double* b, double* x) { icp_ldlt_solve<6>(A, b, x); }
+// the colour gradient's solve (rule G7 of m3d_color_gradient): no determinant check, the result stored as it comes
+M3D_ICP_HD inline void icp_ldlt_solve3(const double* A, const double* b, double* x) { icp_ldlt_solve<3>(A, b, x); }
 
 inline void icp_identity4(double* T) {
     for (int k = 0; k < 16; ++k) T[k] = (k % 5 == 0) ? 1.0 : 0.0;

@@ -4,7 +4,7 @@
 //   reference, per level                                      here
 //   ----------------------------------------------            -------------------------------------------------------------
 //   src.VoxelDownSample(v[l]), dst.VoxelDownSample(v[l])      voxel_levels_on: one upload per cloud, every level from the original
-//   RegistrationICP(.., max_dis, current, method, criteria)   registration_icp_on / registration_icp_plane_on
+//   RegistrationICP(.., max_dis, current, method, criteria)   registration_icp_on / registration_icp_plane_on / registration_icp_colored_on
 //   GetInformationMatrixFromPointClouds (last level)          information_matrix_on on the original clouds
 //
 // The whole call holds ONE lane.  The levels travel through host arrays between the down-sampling and the ICP (the ICP
@@ -19,11 +19,18 @@
 
 using namespace m3d;
 
-extern "C" int m3d_multi_scale_icp(const double* src, const double* src_normals, size_t n_src, const double* dst,
-                                   const double* dst_normals, size_t n_dst, const double* voxel_sizes, const int* max_iters,
-                                   size_t n_levels, double max_correspondence_distance, int method, const double* T_init,
-                                   int device, double* T, double* info, m3d_multi_scale_icp_level* levels) {
-    (void)src_normals;   // (neither accelerated estimator reads the source's normals)
+namespace {
+
+// the colour arguments of m3d_multi_scale_icp_colored (null: one of the colourless methods)
+struct ColourArgs {
+    const double *src_colors, *dst_colors;
+    double lambda_geometric;
+};
+
+int multi_scale_impl(const double* src, size_t n_src, const double* dst, const double* dst_normals, size_t n_dst,
+                     const double* voxel_sizes, const int* max_iters, size_t n_levels, double max_correspondence_distance,
+                     int method, const ColourArgs* colour, const double* T_init, int device, double* T, double* info,
+                     m3d_multi_scale_icp_level* levels) {
     if (!T || !info || (!src && n_src) || (!dst && n_dst) || (n_levels && (!voxel_sizes || !max_iters)))
         return fail(M3D_ERR_INVALID_ARG, "invalid argument");
     static const double I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -33,15 +40,20 @@ extern "C" int m3d_multi_scale_icp(const double* src, const double* src_normals,
         for (size_t l = 0; l < n_levels; ++l) std::memset(&levels[l], 0, sizeof(levels[l]));
     if (n_levels == 0)   // (the reference returns an uninitialised information matrix)
         return fail(M3D_ERR_INVALID_ARG, "MultiScaleICP: no levels (voxel_sizes is empty).");
-    if (method == M3D_REFINE_COLORED_ICP || method == M3D_REFINE_GENERALIZED_ICP)
+    if (!colour && (method == M3D_REFINE_COLORED_ICP || method == M3D_REFINE_GENERALIZED_ICP))
         return fail(M3D_ERR_INVALID_ARG, "MultiScaleICP: ColoredICP and GeneralizedICP are not accelerated; use "
                                          "Point2PointICP (0) or Point2PlaneICP (1).");
-    if (method != M3D_REFINE_POINT2POINT_ICP && method != M3D_REFINE_POINT2PLANE_ICP)
+    if (!colour && method != M3D_REFINE_POINT2POINT_ICP && method != M3D_REFINE_POINT2PLANE_ICP)
         return fail(M3D_ERR_INVALID_ARG, "Unknown local refine method.");
-    if (method == M3D_REFINE_POINT2PLANE_ICP && !dst_normals)
+    if (method != M3D_REFINE_POINT2POINT_ICP && !dst_normals)
         return fail(M3D_ERR_INVALID_ARG,
                     "TransformationEstimationPointToPlane and TransformationEstimationColoredICP require pre-computed normal "
                     "vectors for target PointCloud.");
+    if (colour && (!colour->src_colors || !colour->dst_colors))
+        return fail(M3D_ERR_INVALID_ARG, "TransformationEstimationForColoredICP requires colors for the source and the target "
+                                         "PointCloud.");
+    if (colour && !(colour->lambda_geometric >= 0.0 && colour->lambda_geometric <= 1.0))
+        return fail(M3D_ERR_INVALID_ARG, "lambda_geometric must be in [0, 1].");
     if (const int rv = voxel_sizes_check(voxel_sizes, n_levels); rv != M3D_OK) return rv;
     if (!(max_correspondence_distance > 0.0)) return fail(M3D_ERR_INVALID_ARG, "Invalid max_correspondence_distance.");
     if (n_src >= ((size_t)1 << 30) || n_dst >= ((size_t)1 << 30)) return fail(M3D_ERR_INVALID_ARG, "too many points");
@@ -49,10 +61,10 @@ extern "C" int m3d_multi_scale_icp(const double* src, const double* src_normals,
     LaneLock lane(device);
     DeviceCtx* ctx = lane.ctx;
     if (!ctx) return M3D_ERR_DEVICE;
-    const bool plane = method == M3D_REFINE_POINT2PLANE_ICP;
+    const bool plane = method != M3D_REFINE_POINT2POINT_ICP;   // (the target's normals travel with its levels)
     // ---- every level of both clouds: one upload each
-    std::vector<std::vector<double>> s_xyz(n_levels), d_xyz(n_levels), d_nrm(n_levels);
-    std::vector<double*> ps(n_levels), pd(n_levels), pn(n_levels);
+    std::vector<std::vector<double>> s_xyz(n_levels), d_xyz(n_levels), d_nrm(n_levels), s_col(n_levels), d_col(n_levels);
+    std::vector<double*> ps(n_levels), pd(n_levels), pn(n_levels), pcs(n_levels, nullptr), pcd(n_levels, nullptr);
     for (size_t l = 0; l < n_levels; ++l) {
         s_xyz[l].resize(3 * std::max<size_t>(n_src, 1));
         d_xyz[l].resize(3 * std::max<size_t>(n_dst, 1));
@@ -60,13 +72,21 @@ extern "C" int m3d_multi_scale_icp(const double* src, const double* src_normals,
         ps[l] = s_xyz[l].data();
         pd[l] = d_xyz[l].data();
         pn[l] = plane ? d_nrm[l].data() : nullptr;
+        if (colour) {
+            s_col[l].resize(3 * std::max<size_t>(n_src, 1));
+            d_col[l].resize(3 * std::max<size_t>(n_dst, 1));
+            pcs[l] = s_col[l].data();
+            pcd[l] = d_col[l].data();
+        }
     }
     std::vector<size_t> ms(n_levels, 0), md(n_levels, 0);
     std::vector<double> t_s(n_levels, 0.0), t_d(n_levels, 0.0);
-    int rc = voxel_levels_on(ctx, src, nullptr, n_src, voxel_sizes, n_levels, ps.data(), nullptr, ms.data(), t_s.data());
+    int rc = voxel_levels_on(ctx, src, nullptr, n_src, voxel_sizes, n_levels, ps.data(), nullptr, ms.data(), t_s.data(),
+                             colour ? colour->src_colors : nullptr, colour ? pcs.data() : nullptr);
     if (rc != M3D_OK) return rc;
     rc = voxel_levels_on(ctx, dst, plane ? dst_normals : nullptr, n_dst, voxel_sizes, n_levels, pd.data(),
-                         plane ? pn.data() : nullptr, md.data(), t_d.data());
+                         plane ? pn.data() : nullptr, md.data(), t_d.data(), colour ? colour->dst_colors : nullptr,
+                         colour ? pcd.data() : nullptr);
     if (rc != M3D_OK) return rc;
     // ---- the levels, each seeded with the pose of the one before
     double current[16];
@@ -75,7 +95,11 @@ extern "C" int m3d_multi_scale_icp(const double* src, const double* src_normals,
         m3d_icp_stats st;
         double next[16];
         const double t0 = now_ms();
-        if (plane)
+        if (colour)
+            rc = registration_icp_colored_on(ctx, ps[l], pcs[l], ms[l], pd[l], pn[l], pcd[l], md[l], max_correspondence_distance,
+                                             colour->lambda_geometric, current, max_iters[l], 1e-6, 1e-6, device, next, &st,
+                                             nullptr);
+        else if (plane)
             rc = registration_icp_plane_on(ctx, ps[l], ms[l], pd[l], pn[l], md[l], max_correspondence_distance, current,
                                            max_iters[l], 1e-6, 1e-6, device, next, &st, nullptr);
         else
@@ -109,4 +133,27 @@ extern "C" int m3d_multi_scale_icp(const double* src, const double* src_normals,
     if (levels) levels[n_levels - 1].ms_information = now_ms() - t1;
     std::memcpy(T, current, sizeof(current));
     return M3D_OK;
+}
+
+}  // namespace
+
+extern "C" int m3d_multi_scale_icp(const double* src, const double* src_normals, size_t n_src, const double* dst,
+                                   const double* dst_normals, size_t n_dst, const double* voxel_sizes, const int* max_iters,
+                                   size_t n_levels, double max_correspondence_distance, int method, const double* T_init,
+                                   int device, double* T, double* info, m3d_multi_scale_icp_level* levels) {
+    (void)src_normals;   // (no accelerated estimator reads the source's normals)
+    return multi_scale_impl(src, n_src, dst, dst_normals, n_dst, voxel_sizes, max_iters, n_levels, max_correspondence_distance,
+                            method, nullptr, T_init, device, T, info, levels);
+}
+
+// LocalRefineMethod::ColoredICP (src/pipeline.cpp:956-962): the levels carry the per-voxel colour means of both clouds
+extern "C" int m3d_multi_scale_icp_colored(const double* src, const double* src_normals, const double* src_colors, size_t n_src,
+                                           const double* dst, const double* dst_normals, const double* dst_colors, size_t n_dst,
+                                           const double* voxel_sizes, const int* max_iters, size_t n_levels,
+                                           double max_correspondence_distance, double lambda_geometric, const double* T_init,
+                                           int device, double* T, double* info, m3d_multi_scale_icp_level* levels) {
+    (void)src_normals;
+    const ColourArgs colour{src_colors, dst_colors, lambda_geometric};
+    return multi_scale_impl(src, n_src, dst, dst_normals, n_dst, voxel_sizes, max_iters, n_levels, max_correspondence_distance,
+                            M3D_REFINE_COLORED_ICP, &colour, T_init, device, T, info, levels);
 }

@@ -1640,6 +1640,101 @@ void launch_icp_plane_iter(const double* ix, const double* iy, const double* iz,
     icp_plane_final_k<<<kIcpPlaneRecord, 64, 0, s>>>(partial, nb, out);
 }
 
+// Coloured ICP (m3d_registration_icp_colored): the colour twin of icp_plane_iter_k, ONE launch per iteration, one moving point per
+// thread at every size.  Steps 1 and 2 are the plane kernel's (the pending update, the search, nn[i]); for a correspondence the
+// thread gathers t_j, n_j, the colour gradient g_j (grad: n_dst x 3 rows) and the intensity It_j, takes its own intensity Is_i
+// (it does not move with the pose), and forms the two rows of rules C3 and C4 of include/misc3d_amd.h:
+//   e = (s - t) . n          r0 = sg e                 J0 = sg [s x n, n]
+//   q = (s - e n) - t        I0 = g . q + It           m = -(g^T (I - n n^T))       r1 = sp (Is - I0)      J1 = sp [s x m, m]
+// and contributes count, d2, the 21 products J0a J0b + J1a J1b, the 6 values J0a r0 + J1a r1 and r0 r0 + r1 r1: the record of
+// m3d_icp_fp.hpp, reduced exactly as the plane kernel's (wave_sum, the four waves in LDS in wave order, one record per
+// workgroup, icp_plane_final_k over the workgroups).  No atomics.
+__global__ __launch_bounds__(256) void icp_colored_iter_k(const double* __restrict__ ix, const double* __restrict__ iy,
+                                                           const double* __restrict__ iz, uint32_t n,
+                                                           const double* __restrict__ T, double* __restrict__ px,
+                                                           double* __restrict__ py, double* __restrict__ pz, GridDesc g,
+                                                           const uint32_t* __restrict__ cell_start,
+                                                           const double* __restrict__ qx, const double* __restrict__ qy,
+                                                           const double* __restrict__ qz,
+                                                           const uint32_t* __restrict__ cell_orig, CloudView dst,
+                                                           const double* __restrict__ grad, const double* __restrict__ it_dst,
+                                                           const double* __restrict__ is_src, double sg, double sp,
+                                                           uint32_t* __restrict__ nn, double* __restrict__ partial) {
+    __shared__ double sm[4][kIcpPlaneRecord];
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    double v[kIcpPlaneRecord];
+    for (int k = 0; k < kIcpPlaneRecord; ++k) v[k] = 0.0;
+    if (i < n) {
+        double x = ix[i], y = iy[i], z = iz[i];
+        if (T) {
+            double t[12];
+            for (int k = 0; k < 12; ++k) t[k] = T[k];
+            const double tx = ((t[0] * x + t[1] * y) + t[2] * z) + t[3];
+            const double ty = ((t[4] * x + t[5] * y) + t[6] * z) + t[7];
+            const double tz = ((t[8] * x + t[9] * y) + t[10] * z) + t[11];
+            x = tx;
+            y = ty;
+            z = tz;
+        }
+        px[i] = x;
+        py[i] = y;
+        pz[i] = z;
+        double best;
+        uint32_t bo;
+        nearest_idx(g, cell_start, qx, qy, qz, cell_orig, x, y, z, &best, &bo);
+        const bool ok = best < g.r2;
+        nn[i] = ok ? bo : 0xFFFFFFFFu;
+        if (ok) {
+            const double ax = dst.nx[bo], ay = dst.ny[bo], az = dst.nz[bo];
+            const double tx = dst.x[bo], ty = dst.y[bo], tz = dst.z[bo];
+            const double g0 = grad[3 * (size_t)bo], g1 = grad[3 * (size_t)bo + 1], g2 = grad[3 * (size_t)bo + 2];
+            const double e = ((x - tx) * ax + (y - ty) * ay) + (z - tz) * az;
+            const double r0 = sg * e;
+            const double q0 = (x - e * ax) - tx, q1 = (y - e * ay) - ty, q2 = (z - e * az) - tz;
+            const double i0 = ((g0 * q0 + g1 * q1) + g2 * q2) + it_dst[bo];
+            const double r1 = sp * (is_src[i] - i0);
+            // m = -(g^T (I - n n^T)), the nine entries written out
+            const double m0 = -((g0 * (1.0 - ax * ax) + g1 * (-(ay * ax))) + g2 * (-(az * ax)));
+            const double m1 = -((g0 * (-(ax * ay)) + g1 * (1.0 - ay * ay)) + g2 * (-(az * ay)));
+            const double m2 = -((g0 * (-(ax * az)) + g1 * (-(ay * az))) + g2 * (1.0 - az * az));
+            // s x n and s x m, associated as in icp_plane_iter_k
+            const double J0[6] = {sg * (y * az - z * ay), sg * (z * ax - x * az), sg * (x * ay - y * ax), sg * ax, sg * ay, sg * az};
+            const double J1[6] = {sp * (y * m2 - z * m1), sp * (z * m0 - x * m2), sp * (x * m1 - y * m0), sp * m0, sp * m1, sp * m2};
+            v[0] = 1.0;
+            v[1] = best;
+            int k = 2;
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int b = a; b < 6; ++b) v[k++] = J0[a] * J0[b] + J1[a] * J1[b];
+#pragma unroll
+            for (int a = 0; a < 6; ++a) v[23 + a] = J0[a] * r0 + J1[a] * r1;
+            v[29] = r0 * r0 + r1 * r1;
+        }
+    }
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < kIcpPlaneRecord; ++k) {
+        const double s = wave_sum(v[k]);
+        if (lane == 0) sm[wave][k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < (uint32_t)kIcpPlaneRecord) {
+        const uint32_t k = threadIdx.x;
+        partial[(size_t)blockIdx.x * kIcpPlaneStride + k] = ((sm[0][k] + sm[1][k]) + sm[2][k]) + sm[3][k];
+    }
+}
+void launch_icp_colored_iter(const double* ix, const double* iy, const double* iz, uint32_t n, const double* T_dev, double* px,
+                             double* py, double* pz, const GridDesc& g, const uint32_t* cell_start, const double* qx,
+                             const double* qy, const double* qz, const uint32_t* cell_orig, const CloudView& dst,
+                             const double* grad, const double* it_dst, const double* is_src, double sg, double sp, uint32_t* nn,
+                             double* partial, double* out, hipStream_t s) {
+    const uint32_t nb = icp_plane_blocks(n);
+    icp_colored_iter_k<<<nb, 256, 0, s>>>(ix, iy, iz, n, T_dev, px, py, pz, g, cell_start, qx, qy, qz, cell_orig, dst, grad,
+                                          it_dst, is_src, sg, sp, nn, partial);
+    icp_plane_final_k<<<kIcpPlaneRecord, 64, 0, s>>>(partial, nb, out);
+}
+
 // ------------------------------------------------------------------------------------------------
 // DetectBoundaryPoints (src/boundary_detection.cpp:21-113), one thread per point
 // ------------------------------------------------------------------------------------------------

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/misc3d_amd_bench.h"
+#include "m3d_colored_icp.hpp"
 #include "m3d_comm.hpp"
 #include "m3d_config.hpp"
 #include "m3d_host_util.hpp"
@@ -1436,6 +1437,171 @@ extern "C" int m3d_registration_icp_plane(const double* src, size_t n_src, const
                                           double* T_out, m3d_icp_stats* stats, int64_t* correspondences) {
     return registration_icp_plane_on(nullptr, src, n_src, dst, dst_normals, n_dst, max_correspondence_distance, T_init,
                                      max_iteration, relative_fitness, relative_rmse, device, T_out, stats, correspondences);
+}
+
+// Coloured ICP: the RegistrationICP loop of the plane call with TransformationEstimationForColoredICP (the contract:
+// include/misc3d_amd.h, rules G1 - G7 and C1 - C6).  Before the loop: the target's colour gradients and intensities
+// (color_gradient_on: Hybrid(2 max_correspondence_distance, 30)) and the source's intensities, all resident for the call.  An
+// iteration is launch_icp_colored_iter, one copy of the record and one polled wait; icp_plane_update solves the record.
+int m3d::registration_icp_colored_on(DeviceCtx* held, const double* src, const double* src_colors, size_t n_src, const double* dst,
+                                     const double* dst_normals, const double* dst_colors, size_t n_dst,
+                                     double max_correspondence_distance, double lambda_geometric, const double* T_init,
+                                     int max_iteration, double relative_fitness, double relative_rmse, int device, double* T_out,
+                                     m3d_icp_stats* stats, int64_t* correspondences) {
+    const double t_begin = now_ms();
+    if (!T_out || (!src && n_src) || (!dst && n_dst)) return fail(M3D_ERR_INVALID_ARG, "invalid argument");
+    static const double I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    double T[16];
+    std::memcpy(T, T_init ? T_init : I4, sizeof(T));
+    std::memcpy(T_out, T, sizeof(T));
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (!(max_correspondence_distance > 0.0))   // Open3D: LogError("Invalid max_correspondence_distance.")
+        return fail(M3D_ERR_INVALID_ARG, "Invalid max_correspondence_distance.");
+    if (!dst_normals)
+        return fail(M3D_ERR_INVALID_ARG,
+                    "TransformationEstimationPointToPlane and TransformationEstimationColoredICP require pre-computed normal "
+                    "vectors for target PointCloud.");
+    if (!src_colors || !dst_colors)
+        return fail(M3D_ERR_INVALID_ARG, "TransformationEstimationForColoredICP requires colors for the source and the target "
+                                         "PointCloud.");
+    if (!(lambda_geometric >= 0.0 && lambda_geometric <= 1.0))
+        return fail(M3D_ERR_INVALID_ARG, "lambda_geometric must be in [0, 1].");
+    if (n_src >= ((size_t)1 << 31) || n_dst >= ((size_t)1 << 31)) return fail(M3D_ERR_INVALID_ARG, "too many points");
+    if (n_src == 0 || n_dst == 0) {   // no correspondences: every update is the identity, fitness 0
+        if (correspondences)
+            for (size_t i = 0; i < n_src; ++i) correspondences[i] = -1;
+        if (stats) {
+            stats->iterations = max_iteration > 0 ? 1 : 0;   // the first repeat already meets both criteria
+            stats->converged = max_iteration > 0;
+        }
+        return M3D_OK;
+    }
+    const double sg = std::sqrt(lambda_geometric), sp = std::sqrt(1.0 - lambda_geometric);
+    std::optional<LaneLock> lane;
+    if (!held) lane.emplace(device);
+    DeviceCtx* ctx = held ? held : lane->ctx;
+    if (!ctx) return M3D_ERR_DEVICE;
+    DevBuf grad, it_dst, is_src, col_src;
+    if (const int rgr = color_gradient_on(ctx, dst, dst_normals, dst_colors, n_dst, 2.0 * max_correspondence_distance, 30, grad,
+                                          it_dst, nullptr);
+        rgr != M3D_OK) {
+        grad.release();
+        it_dst.release();
+        return rgr;
+    }
+    m3d_cloud* csrc = m3d_cloud_create_on(ctx, src, nullptr, n_src, 0);
+    m3d_cloud* cdst = csrc ? m3d_cloud_create_on(ctx, dst, dst_normals, n_dst, 0) : nullptr;
+    if (!csrc || !cdst) {
+        if (csrc) m3d_cloud_destroy_on(csrc);
+        grad.release();
+        it_dst.release();
+        return M3D_ERR_DEVICE;
+    }
+    Scratch S;
+    DevBuf mx, my, mz, nn;
+    int rc;
+    {
+        rc = [&]() -> int {
+            HIPCHK(hipSetDevice(ctx->device));
+            const CloudView sv = csrc->view(), dv = cdst->view();
+            const uint32_t n = sv.n;
+            GridDesc g;
+            const int rg = build_target_grid(ctx, S, dv, dst, n_dst, max_correspondence_distance, true, &g);
+            if (rg != M3D_OK) return rg;
+            RESERVE(mx, sizeof(double) * n);
+            RESERVE(my, sizeof(double) * n);
+            RESERVE(mz, sizeof(double) * n);
+            RESERVE(nn, sizeof(uint32_t) * n);
+            RESERVE(col_src, sizeof(double) * 3 * n_src);
+            RESERVE(is_src, sizeof(double) * n_src);
+            RESERVE(S.sums, sizeof(double) * kIcpPlaneStride);
+            RESERVE(S.partial_sum, sizeof(double) * kIcpPlaneStride * (size_t)icp_plane_blocks(n));
+            RESERVE(S.one_T, sizeof(double) * kRegTStride);
+            RESERVE(ctx->h_small, 512);
+            HIPCHK(hipMemcpyAsync(col_src.p, src_colors, sizeof(double) * 3 * n_src, hipMemcpyHostToDevice, ctx->stream));
+            launch_color_intensity(col_src.as<double>(), n, is_src.as<double>(), ctx->stream);
+            double* px = mx.as<double>();
+            double* py = my.as<double>();
+            double* pz = mz.as<double>();
+            double hs[kIcpPlaneSums];   // the record of the last iteration
+            uint64_t cnt = 0;
+            double e2 = 0.0;
+            auto iterate = [&](bool first, const double* update) -> int {
+                if (update) HIPCHK(hipMemcpyAsync(S.one_T.p, update, sizeof(double) * 12, hipMemcpyHostToDevice, ctx->stream));
+                launch_icp_colored_iter(first ? sv.x : px, first ? sv.y : py, first ? sv.z : pz, n,
+                                        update ? S.one_T.as<double>() : nullptr, px, py, pz, g, S.tgt.start.as<uint32_t>(),
+                                        S.qx.as<double>(), S.qy.as<double>(), S.qz.as<double>(), S.cell_orig.as<uint32_t>(), dv,
+                                        grad.as<double>(), it_dst.as<double>(), is_src.as<double>(), sg, sp, nn.as<uint32_t>(),
+                                        S.partial_sum.as<double>(), S.sums.as<double>(), ctx->stream);
+                uint8_t* h = ctx->h_small.as<uint8_t>();
+                HIPCHK(hipMemcpyAsync(h, S.sums.p, sizeof(hs), hipMemcpyDeviceToHost, ctx->stream));
+                HIPCHK(hipGetLastError());
+                if (const int wr = stream_wait_spin(ctx); wr != M3D_OK) return wr;   // (an iteration's one wait: polled)
+                std::memcpy(hs, h, sizeof(hs));
+                cnt = (uint64_t)hs[0];
+                e2 = hs[1];
+                return M3D_OK;
+            };
+            // pcd = source; if (!init.isIdentity()) pcd.Transform(init)
+            int r = iterate(true, std::memcmp(T, I4, sizeof(T)) != 0 ? T : nullptr);
+            if (r != M3D_OK) return r;
+            double fit = (double)cnt / (double)n_src;
+            double rm = cnt ? std::sqrt(e2 / (double)cnt) : 0.0;
+            int it = 0;
+            bool converged = false;
+            for (; it < max_iteration; ++it) {
+                double U[16];
+                icp_plane_update(hs, U);   // ComputeTransformation: the record has the plane call's layout
+                double Tn[16];
+                for (int rr = 0; rr < 4; ++rr)
+                    for (int cc = 0; cc < 4; ++cc)
+                        Tn[4 * rr + cc] = ((U[4 * rr] * T[cc] + U[4 * rr + 1] * T[4 + cc]) + U[4 * rr + 2] * T[8 + cc]) +
+                                          U[4 * rr + 3] * T[12 + cc];
+                std::memcpy(T, Tn, sizeof(T));
+                const double fit0 = fit, rm0 = rm;
+                r = iterate(false, U);   // pcd.Transform(update), the next result
+                if (r != M3D_OK) return r;
+                fit = (double)cnt / (double)n_src;
+                rm = cnt ? std::sqrt(e2 / (double)cnt) : 0.0;
+                if (std::fabs(fit0 - fit) < relative_fitness && std::fabs(rm0 - rm) < relative_rmse) {
+                    ++it;
+                    converged = true;
+                    break;
+                }
+            }
+            std::memcpy(T_out, T, sizeof(T));
+            if (correspondences) {
+                std::vector<uint32_t> hn(n);
+                HIPCHK(hipMemcpy(hn.data(), nn.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+                for (uint32_t i = 0; i < n; ++i) correspondences[i] = hn[i] == 0xFFFFFFFFu ? -1 : (int64_t)hn[i];
+            }
+            if (stats) {
+                stats->fitness = fit;
+                stats->inlier_rmse = rm;
+                stats->correspondences = cnt;
+                stats->iterations = it;
+                stats->converged = converged ? 1 : 0;
+            }
+            return M3D_OK;
+        }();
+        (void)hipStreamSynchronize(ctx->stream);
+        S.release();
+        for (DevBuf* b : {&mx, &my, &mz, &nn, &grad, &it_dst, &is_src, &col_src}) b->release();
+    }
+    m3d_cloud_destroy_on(csrc);
+    m3d_cloud_destroy_on(cdst);
+    if (stats) stats->ms_total = now_ms() - t_begin;
+    return rc;
+}
+
+extern "C" int m3d_registration_icp_colored(const double* src, const double* src_colors, size_t n_src, const double* dst,
+                                            const double* dst_normals, const double* dst_colors, size_t n_dst,
+                                            double max_correspondence_distance, double lambda_geometric, const double* T_init,
+                                            int max_iteration, double relative_fitness, double relative_rmse, int device,
+                                            double* T_out, m3d_icp_stats* stats, int64_t* correspondences) {
+    return registration_icp_colored_on(nullptr, src, src_colors, n_src, dst, dst_normals, dst_colors, n_dst,
+                                       max_correspondence_distance, lambda_geometric, T_init, max_iteration, relative_fitness,
+                                       relative_rmse, device, T_out, stats, correspondences);
 }
 
 extern "C" {

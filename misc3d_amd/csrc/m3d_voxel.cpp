@@ -273,14 +273,15 @@ int voxel_impl(const double* xyz, const double* normals, const double* colors, s
 
 }  // namespace
 
-// n_levels levels of one cloud on a lane the caller holds (m3d_multi_scale_icp): m3d_voxel_down_sample_multi without colours
-// and trace arrays, the levels' rows in the caller's host arrays
+// n_levels levels of one cloud on a lane the caller holds (m3d_multi_scale_icp): m3d_voxel_down_sample_multi without
+// trace arrays (colours only for the coloured call), the levels' rows in the caller's host arrays
 int m3d::voxel_levels_on(DeviceCtx* ctx, const double* xyz, const double* normals, size_t n, const double* voxel_sizes,
-                         size_t n_levels, double* const* out_xyz, double* const* out_normals, size_t* m, double* level_ms) {
+                         size_t n_levels, double* const* out_xyz, double* const* out_normals, size_t* m, double* level_ms,
+                         const double* colors, double* const* out_colors) {
     std::vector<LevelOut> outs(n_levels);
     for (size_t l = 0; l < n_levels; ++l)
-        outs[l] = LevelOut{out_xyz[l], out_normals ? out_normals[l] : nullptr, nullptr, nullptr, nullptr};
-    return voxel_impl(xyz, normals, nullptr, n, voxel_sizes, n_levels, ctx->logical, outs.data(), m, nullptr, ctx, level_ms);
+        outs[l] = LevelOut{out_xyz[l], out_normals ? out_normals[l] : nullptr, out_colors ? out_colors[l] : nullptr, nullptr, nullptr};
+    return voxel_impl(xyz, normals, colors, n, voxel_sizes, n_levels, ctx->logical, outs.data(), m, nullptr, ctx, level_ms);
 }
 int m3d::voxel_sizes_check(const double* voxel_sizes, size_t n_levels) {
     for (size_t l = 0; l < n_levels; ++l)

@@ -11,7 +11,8 @@ bench.py); these lines feed DESIGN.md section 6 and check that the full sizes ru
           50k x 33 k=1000 (select)
   V1 - V3 voxel_down_sample: the 1 M-point bench scene at 0.005 / 0.02 of its extent, and the three-level call
   I1 registration_icp_plane against registration_icp at the C4 ICP shape (200k x 200k, 0.02), alternating in one process
-  I2 refine_fragment_pair ({v, v/2, v/4}, {50, 30, 15}) on 50 000-point fragments, with its per-level split
+  I2 refine_fragment_pair ({v, v/2, v/4}, {50, 30, 15}) on 50 000-point fragments, with its per-level split (point-to-plane,
+     point-to-point and coloured)
   R1 - R3 RayCastRenderer: the reference example (640 x 480, obj.ply at its two poses), 1920 x 1080 with 64 instances, and a
           100-frame batch of the example
 """
@@ -892,13 +893,17 @@ if "I1" in which or "I2" in which or ALL:
         v = 0.02
         init = icp_util.offset_pose(p["T"], 1.0, (0.008, -0.005, 0.006))
         tgt = (p["dst"], p["dst_normals"])
-        for method in ("point_to_plane", "point_to_point"):
+        # the coloured line: the same pair with the smooth colour field of the coloured-ICP tests on both clouds
+        import colored_icp_ref_util as colored_util
+        sc, dc = colored_util.colors_of(p)
+        for method in ("point_to_plane", "point_to_point", "colored"):
+            src_m, tgt_m = ((p["src"], None, sc), (p["dst"], p["dst_normals"], dc)) if method == "colored" else (p["src"], tgt)
             for _ in range(3):
-                m3d.reconstruction.refine_fragment_pair(p["src"], tgt, v, init, method)
+                m3d.reconstruction.refine_fragment_pair(src_m, tgt_m, v, init, method)
             runs = []
             for _ in range(15):
                 t0 = time.perf_counter()
-                T, info, lv = m3d.reconstruction.refine_fragment_pair(p["src"], tgt, v, init, method, stats=True)
+                T, info, lv = m3d.reconstruction.refine_fragment_pair(src_m, tgt_m, v, init, method, stats=True)
                 runs.append(((time.perf_counter() - t0) * 1e3, lv, T, info))
             runs.sort(key=lambda r: r[0])
             ms, lv, T, info = runs[len(runs) // 2]
