@@ -220,8 +220,16 @@ int information_matrix_on(DeviceCtx* ctx, m3d_cloud* csrc, m3d_cloud* cdst, cons
                           double max_correspondence_distance, const double* T, double* info, uint64_t* n_correspondences,
                           m3d_reg* session = nullptr);
 void reg_session_release(m3d_reg* q);   // ... of a session handed out through session_out (the caller holds the lane)
-// m3d_registration_icp / m3d_registration_icp_plane; held != null: on that lane, which the caller holds (m3d_multi_scale_icp),
-// else the call takes a lane of `device` itself
+// Open3D's messages for the arguments of RegistrationICP and its estimators: the ICP entry points and m3d_multi_scale_icp,
+// which checks the same arguments before its first level, report the same text
+inline constexpr char kIcpInvalidDistance[] = "Invalid max_correspondence_distance.";
+inline constexpr char kIcpNeedsNormals[] =
+    "TransformationEstimationPointToPlane and TransformationEstimationColoredICP require pre-computed normal vectors for target "
+    "PointCloud.";
+inline constexpr char kIcpNeedsColors[] = "TransformationEstimationForColoredICP requires colors for the source and the target PointCloud.";
+inline constexpr char kIcpBadLambda[] = "lambda_geometric must be in [0, 1].";
+// m3d_registration_icp / m3d_registration_icp_plane: the three estimators of the one RegistrationICP loop (m3d_registration.cpp);
+// held != null: on that lane, which the caller holds (m3d_multi_scale_icp), else the call takes a lane of `device` itself
 int registration_icp_on(DeviceCtx* held, const double* src, size_t n_src, const double* dst, size_t n_dst,
                         double max_correspondence_distance, const double* T_init, int max_iteration, double relative_fitness,
                         double relative_rmse, int device, double* T_out, m3d_icp_stats* stats, int64_t* correspondences);

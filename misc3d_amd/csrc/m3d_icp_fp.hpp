@@ -1,6 +1,8 @@
-// m3d_icp_fp.hpp -- the host arithmetic of point-to-plane and coloured ICP's ComputeTransformation (m3d_registration_icp_plane,
-// m3d_registration_icp_colored): from the 30 sums of an iteration to its 4 x 4 update; and the 3 x 3 solve of the colour gradient.  Plain C++, no HIP: the library and the stand-alone check
-// tests/cpp/test_icp_solve.cpp compile the same text (build with -ffp-contract=off).
+// m3d_icp_fp.hpp -- the host arithmetic of the RegistrationICP loop (icp_loop, m3d_registration.cpp): the compose step every
+// estimator shares (icp_compose4), and ComputeTransformation of the two estimators that reduce an iteration to a record
+// (m3d_registration_icp_plane, m3d_registration_icp_colored): from the 30 sums to the 4 x 4 update; and the 3 x 3 solve of the
+// colour gradient.  Plain C++, no HIP: the library and the stand-alone check tests/cpp/test_icp_solve.cpp compile the same text
+// (build with -ffp-contract=off).
 //
 // [RECALL] Open3D 0.15.1 TransformationEstimationPointToPlane::ComputeTransformation ->
 // SolveJacobianSystemAndObtainExtrinsicMatrix(JTJ, JTr) -> SolveLinearSystemPSD(JTJ, -JTr, check_det = true) ->
@@ -122,6 +124,16 @@ M3D_ICP_HD inline void icp_ldlt_solve3(const double* A, const double* b, double*
 
 inline void icp_identity4(double* T) {
     for (int k = 0; k < 16; ++k) T[k] = (k % 5 == 0) ? 1.0 : 0.0;
+}
+
+// transformation = update * transformation of the RegistrationICP loop: T = U T, 4 x 4 row-major, every entry associated as
+// ((U0 T0 + U1 T4) + U2 T8) + U3 T12
+inline void icp_compose4(const double* U, double* T) {
+    double Tn[16];
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c)
+            Tn[4 * r + c] = ((U[4 * r] * T[c] + U[4 * r + 1] * T[4 + c]) + U[4 * r + 2] * T[8 + c]) + U[4 * r + 3] * T[12 + c];
+    std::memcpy(T, Tn, sizeof(Tn));
 }
 
 // TransformVector6dToMatrix4d: rotation Rz(x[2]) Ry(x[1]) Rx(x[0]), translation (x[3], x[4], x[5]).  T: 4 x 4 row-major.

@@ -45,17 +45,12 @@ int multi_scale_impl(const double* src, size_t n_src, const double* dst, const d
                                          "Point2PointICP (0) or Point2PlaneICP (1).");
     if (!colour && method != M3D_REFINE_POINT2POINT_ICP && method != M3D_REFINE_POINT2PLANE_ICP)
         return fail(M3D_ERR_INVALID_ARG, "Unknown local refine method.");
-    if (method != M3D_REFINE_POINT2POINT_ICP && !dst_normals)
-        return fail(M3D_ERR_INVALID_ARG,
-                    "TransformationEstimationPointToPlane and TransformationEstimationColoredICP require pre-computed normal "
-                    "vectors for target PointCloud.");
-    if (colour && (!colour->src_colors || !colour->dst_colors))
-        return fail(M3D_ERR_INVALID_ARG, "TransformationEstimationForColoredICP requires colors for the source and the target "
-                                         "PointCloud.");
+    if (method != M3D_REFINE_POINT2POINT_ICP && !dst_normals) return fail(M3D_ERR_INVALID_ARG, kIcpNeedsNormals);
+    if (colour && (!colour->src_colors || !colour->dst_colors)) return fail(M3D_ERR_INVALID_ARG, kIcpNeedsColors);
     if (colour && !(colour->lambda_geometric >= 0.0 && colour->lambda_geometric <= 1.0))
-        return fail(M3D_ERR_INVALID_ARG, "lambda_geometric must be in [0, 1].");
+        return fail(M3D_ERR_INVALID_ARG, kIcpBadLambda);
     if (const int rv = voxel_sizes_check(voxel_sizes, n_levels); rv != M3D_OK) return rv;
-    if (!(max_correspondence_distance > 0.0)) return fail(M3D_ERR_INVALID_ARG, "Invalid max_correspondence_distance.");
+    if (!(max_correspondence_distance > 0.0)) return fail(M3D_ERR_INVALID_ARG, kIcpInvalidDistance);
     if (n_src >= ((size_t)1 << 30) || n_dst >= ((size_t)1 << 30)) return fail(M3D_ERR_INVALID_ARG, "too many points");
 
     LaneLock lane(device);

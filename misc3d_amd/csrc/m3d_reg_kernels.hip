@@ -24,6 +24,16 @@
 
 namespace m3d {
 
+// PointCloud::Transform of one point: T = the first three rows of the 4 x 4 matrix, row-major (12 doubles, all loaded before
+// the point moves: in place is fine).  Every kernel of this file that moves a point by a pose does it through this text: the
+// validation of a hypothesis, the inlier ratio, launch_icp_transform and the ICP iteration kernels.
+__device__ __forceinline__ double3 move_point(const double* __restrict__ T, double x, double y, double z) {
+    double t[12];
+    for (int k = 0; k < 12; ++k) t[k] = T[k];
+    return make_double3(((t[0] * x + t[1] * y) + t[2] * z) + t[3], ((t[4] * x + t[5] * y) + t[6] * z) + t[7],
+                        ((t[8] * x + t[9] * y) + t[10] * z) + t[11]);
+}
+
 // ------------------------------------------------------------------------------------------------
 // K8  3-point Kabsch + checkers, one thread per hypothesis
 // ------------------------------------------------------------------------------------------------
@@ -974,10 +984,8 @@ __global__ __launch_bounds__(256) void reg_validate_pairs_k(const double* __rest
         uint32_t cnt = 0;
         double sum = 0.0;
         if (t[0] == t[0]) {
-            const double px = ((t[0] * x + t[1] * y) + t[2] * z) + t[3];
-            const double py = ((t[4] * x + t[5] * y) + t[6] * z) + t[7];
-            const double pz = ((t[8] * x + t[9] * y) + t[10] * z) + t[11];
-            const double d2 = nearest_d2<SCREEN>(g, cell_start, qx, qy, qz, px, py, pz);
+            const double3 p3 = move_point(t, x, y, z);
+            const double d2 = nearest_d2<SCREEN>(g, cell_start, qx, qy, qz, p3.x, p3.y, p3.z);
             const bool f = d2 < g.r2;
             cnt = (uint32_t)__popcll(__ballot(f));
             sum = f ? d2 : 0.0;
@@ -1170,13 +1178,8 @@ __global__ void reg_min_d2_k(CloudView src, const double* __restrict__ T, GridDe
                              double* __restrict__ best) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= src.n) return;
-    double t[12];
-    for (int k = 0; k < 12; ++k) t[k] = T[k];
-    const double x = src.x[i], y = src.y[i], z = src.z[i];
-    const double px = ((t[0] * x + t[1] * y) + t[2] * z) + t[3];
-    const double py = ((t[4] * x + t[5] * y) + t[6] * z) + t[7];
-    const double pz = ((t[8] * x + t[9] * y) + t[10] * z) + t[11];
-    best[i] = nearest_d2(g, cell_start, qx, qy, qz, px, py, pz);
+    const double3 p = move_point(T, src.x[i], src.y[i], src.z[i]);
+    best[i] = nearest_d2(g, cell_start, qx, qy, qz, p.x, p.y, p.z);
 }
 void launch_reg_min_d2(const CloudView& src, const double* T, const GridDesc& g, const uint32_t* cell_start,
                        const double* qx, const double* qy, const double* qz, double* best, hipStream_t s) {
@@ -1241,14 +1244,9 @@ __global__ void corr_ratio_k(CloudView src, CloudView dst, const uint32_t* __res
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     bool f = false;
     if (i < m) {
-        double t[12];
-        for (int k = 0; k < 12; ++k) t[k] = T[k];
         const uint32_t si = corr_src[i], di = corr_dst[i];
-        const double x = src.x[si], y = src.y[si], z = src.z[si];
-        const double px = ((t[0] * x + t[1] * y) + t[2] * z) + t[3];
-        const double py = ((t[4] * x + t[5] * y) + t[6] * z) + t[7];
-        const double pz = ((t[8] * x + t[9] * y) + t[10] * z) + t[11];
-        const double ddx = px - dst.x[di], ddy = py - dst.y[di], ddz = pz - dst.z[di];
+        const double3 p = move_point(T, src.x[si], src.y[si], src.z[si]);
+        const double ddx = p.x - dst.x[di], ddy = p.y - dst.y[di], ddz = p.z - dst.z[di];
         f = ((ddx * ddx + ddy * ddy) + ddz * ddz) < r2;
     }
     const uint32_t c = (uint32_t)__popcll(__ballot(f));
@@ -1536,80 +1534,60 @@ __global__ void icp_transform_k(const double* __restrict__ ix, const double* __r
                                 double* __restrict__ ox, double* __restrict__ oy, double* __restrict__ oz) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    double t[12];
-    for (int k = 0; k < 12; ++k) t[k] = T[k];
-    const double x = ix[i], y = iy[i], z = iz[i];
-    ox[i] = ((t[0] * x + t[1] * y) + t[2] * z) + t[3];
-    oy[i] = ((t[4] * x + t[5] * y) + t[6] * z) + t[7];
-    oz[i] = ((t[8] * x + t[9] * y) + t[10] * z) + t[11];
+    const double3 p = move_point(T, ix[i], iy[i], iz[i]);
+    ox[i] = p.x;
+    oy[i] = p.y;
+    oz[i] = p.z;
 }
 void launch_icp_transform(const double* ix, const double* iy, const double* iz, uint32_t n, const double* T_dev,
                           double* ox, double* oy, double* oz, hipStream_t s) {
     if (n) icp_transform_k<<<(n + 255) / 256, 256, 0, s>>>(ix, iy, iz, n, T_dev, ox, oy, oz);
 }
 
-// Point-to-plane ICP (m3d_registration_icp_plane): ONE launch per iteration.  One moving point per thread, at every size
-// (n < 2^31 -> at most 2^23 workgroups; no thread ever takes a second point).  The thread
-//   1. applies the pending update T (12 doubles, null = none) with icp_transform_k's expression and stores the point (in place
-//      from the second iteration on; the first reads the source cloud);
-//   2. searches its nearest target point (nearest_idx: lowest original index on exact ties) and stores nn[i];
-//   3. for a correspondence (d2 < r^2) gathers t_j and n_j and forms r = (s - t_j) . n_j, J = [s x n_j, n_j];
-//   4. contributes the record of m3d_icp_fp.hpp: count, d2, the 21 products of J J^T, the 6 of J r, r^2 (zeros otherwise).
-// The 30 values are summed over the wave by m3d::wave_sum (xor butterfly, order fixed), the four waves' sums meet in LDS and
-// wave 0 adds them in wave order: one record per workgroup.  icp_plane_final_k then sums the workgroups' records, value k in
-// workgroup k: lane l adds the records l, l + 64, ... in ascending order, wave_sum adds the lanes.  No atomics: the result is a
-// fixed function of (points, update, grid) -- the same bits from run to run, whatever else the device runs.
-__global__ __launch_bounds__(256) void icp_plane_iter_k(const double* __restrict__ ix, const double* __restrict__ iy,
-                                                         const double* __restrict__ iz, uint32_t n,
-                                                         const double* __restrict__ T, double* __restrict__ px,
-                                                         double* __restrict__ py, double* __restrict__ pz, GridDesc g,
-                                                         const uint32_t* __restrict__ cell_start,
-                                                         const double* __restrict__ qx, const double* __restrict__ qy,
-                                                         const double* __restrict__ qz,
-                                                         const uint32_t* __restrict__ cell_orig, CloudView dst,
-                                                         uint32_t* __restrict__ nn, double* __restrict__ partial) {
+// The iteration kernels of point-to-plane and coloured ICP (m3d_registration_icp_plane, m3d_registration_icp_colored): ONE
+// launch per iteration, one moving point per thread at every size (n < 2^31 -> at most 2^23 workgroups; no thread ever takes
+// a second point).  Both kernels are the same frame around their own rows:
+//   icp_move_and_match   1. applies the pending update T (12 doubles, null = none) and stores the point (in place from the
+//                           second iteration on; the first reads the source cloud);
+//                        2. searches its nearest target point (nearest_idx: lowest original index on exact ties), stores nn[i];
+//   the kernel's body    3. for a correspondence (d2 < r^2) forms the residual and Jacobian rows of its estimator and from them
+//                           the thread's record of m3d_icp_fp.hpp: count, d2, the 21 products of JTJ, the 6 of JTr, r^2 (zeros
+//                           otherwise);
+//   icp_record_reduce    4. sums the 30 values over the wave by m3d::wave_sum (xor butterfly, order fixed); the four waves' sums
+//                           meet in LDS and wave 0 adds them in wave order: one record per workgroup.
+// icp_plane_final_k then sums the workgroups' records, value k in workgroup k: lane l adds the records l, l + 64, ... in
+// ascending order, wave_sum adds the lanes.  No atomics: the result is a fixed function of (points, update, grid) -- the same
+// bits from run to run, whatever else the device runs -- and the ONE order of these sums is what relates the estimators.
+struct IcpMatch {
+    double x, y, z;   // the moved point
+    double d2;        // squared distance to the nearest target point
+    uint32_t j;       // that point's original index
+    bool ok;          // a correspondence: the thread has a point and d2 < r^2
+};
+__device__ __forceinline__ IcpMatch icp_move_and_match(uint32_t i, const double* __restrict__ ix, const double* __restrict__ iy,
+                                                       const double* __restrict__ iz, uint32_t n, const double* __restrict__ T,
+                                                       double* __restrict__ px, double* __restrict__ py, double* __restrict__ pz,
+                                                       const GridDesc& g, const uint32_t* __restrict__ cell_start,
+                                                       const double* __restrict__ qx, const double* __restrict__ qy,
+                                                       const double* __restrict__ qz, const uint32_t* __restrict__ cell_orig,
+                                                       uint32_t* __restrict__ nn) {
+    IcpMatch m = {0.0, 0.0, 0.0, 0.0, 0xFFFFFFFFu, false};
+    if (i >= n) return m;
+    double3 p = make_double3(ix[i], iy[i], iz[i]);
+    if (T) p = move_point(T, p.x, p.y, p.z);
+    px[i] = p.x;
+    py[i] = p.y;
+    pz[i] = p.z;
+    nearest_idx(g, cell_start, qx, qy, qz, cell_orig, p.x, p.y, p.z, &m.d2, &m.j);
+    m.x = p.x;
+    m.y = p.y;
+    m.z = p.z;
+    m.ok = m.d2 < g.r2;
+    nn[i] = m.ok ? m.j : 0xFFFFFFFFu;
+    return m;
+}
+__device__ __forceinline__ void icp_record_reduce(const double (&v)[kIcpPlaneRecord], double* __restrict__ partial) {
     __shared__ double sm[4][kIcpPlaneRecord];
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    double v[kIcpPlaneRecord];
-    for (int k = 0; k < kIcpPlaneRecord; ++k) v[k] = 0.0;
-    if (i < n) {
-        double x = ix[i], y = iy[i], z = iz[i];
-        if (T) {
-            double t[12];
-            for (int k = 0; k < 12; ++k) t[k] = T[k];
-            const double tx = ((t[0] * x + t[1] * y) + t[2] * z) + t[3];
-            const double ty = ((t[4] * x + t[5] * y) + t[6] * z) + t[7];
-            const double tz = ((t[8] * x + t[9] * y) + t[10] * z) + t[11];
-            x = tx;
-            y = ty;
-            z = tz;
-        }
-        px[i] = x;
-        py[i] = y;
-        pz[i] = z;
-        double best;
-        uint32_t bo;
-        nearest_idx(g, cell_start, qx, qy, qz, cell_orig, x, y, z, &best, &bo);
-        const bool ok = best < g.r2;
-        nn[i] = ok ? bo : 0xFFFFFFFFu;
-        if (ok) {
-            const double ax = dst.nx[bo], ay = dst.ny[bo], az = dst.nz[bo];
-            const double ex = x - dst.x[bo], ey = y - dst.y[bo], ez = z - dst.z[bo];
-            const double r = (ex * ax + ey * ay) + ez * az;
-            // s x n, SURVEY.md 8a-note (iii)
-            const double J[6] = {y * az - z * ay, z * ax - x * az, x * ay - y * ax, ax, ay, az};
-            v[0] = 1.0;
-            v[1] = best;
-            int k = 2;
-#pragma unroll
-            for (int a = 0; a < 6; ++a)
-#pragma unroll
-                for (int b = a; b < 6; ++b) v[k++] = J[a] * J[b];
-#pragma unroll
-            for (int a = 0; a < 6; ++a) v[23 + a] = J[a] * r;
-            v[29] = r * r;
-        }
-    }
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < kIcpPlaneRecord; ++k) {
@@ -1621,6 +1599,41 @@ __global__ __launch_bounds__(256) void icp_plane_iter_k(const double* __restrict
         const uint32_t k = threadIdx.x;
         partial[(size_t)blockIdx.x * kIcpPlaneStride + k] = ((sm[0][k] + sm[1][k]) + sm[2][k]) + sm[3][k];
     }
+}
+
+// Point-to-plane: r = (s - t_j) . n_j, J = [s x n_j, n_j]
+__global__ __launch_bounds__(256) void icp_plane_iter_k(const double* __restrict__ ix, const double* __restrict__ iy,
+                                                         const double* __restrict__ iz, uint32_t n,
+                                                         const double* __restrict__ T, double* __restrict__ px,
+                                                         double* __restrict__ py, double* __restrict__ pz, GridDesc g,
+                                                         const uint32_t* __restrict__ cell_start,
+                                                         const double* __restrict__ qx, const double* __restrict__ qy,
+                                                         const double* __restrict__ qz,
+                                                         const uint32_t* __restrict__ cell_orig, CloudView dst,
+                                                         uint32_t* __restrict__ nn, double* __restrict__ partial) {
+    double v[kIcpPlaneRecord];
+    for (int k = 0; k < kIcpPlaneRecord; ++k) v[k] = 0.0;
+    const IcpMatch m = icp_move_and_match(blockIdx.x * 256u + threadIdx.x, ix, iy, iz, n, T, px, py, pz, g, cell_start, qx, qy, qz,
+                                          cell_orig, nn);
+    if (m.ok) {
+        const double x = m.x, y = m.y, z = m.z;
+        const double ax = dst.nx[m.j], ay = dst.ny[m.j], az = dst.nz[m.j];
+        const double ex = x - dst.x[m.j], ey = y - dst.y[m.j], ez = z - dst.z[m.j];
+        const double r = (ex * ax + ey * ay) + ez * az;
+        // s x n, SURVEY.md 8a-note (iii)
+        const double J[6] = {y * az - z * ay, z * ax - x * az, x * ay - y * ax, ax, ay, az};
+        v[0] = 1.0;
+        v[1] = m.d2;
+        int k = 2;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = a; b < 6; ++b) v[k++] = J[a] * J[b];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) v[23 + a] = J[a] * r;
+        v[29] = r * r;
+    }
+    icp_record_reduce(v, partial);
 }
 __global__ __launch_bounds__(64) void icp_plane_final_k(const double* __restrict__ partial, uint32_t n_blocks,
                                                          double* __restrict__ out) {
@@ -1640,15 +1653,12 @@ void launch_icp_plane_iter(const double* ix, const double* iy, const double* iz,
     icp_plane_final_k<<<kIcpPlaneRecord, 64, 0, s>>>(partial, nb, out);
 }
 
-// Coloured ICP (m3d_registration_icp_colored): the colour twin of icp_plane_iter_k, ONE launch per iteration, one moving point per
-// thread at every size.  Steps 1 and 2 are the plane kernel's (the pending update, the search, nn[i]); for a correspondence the
-// thread gathers t_j, n_j, the colour gradient g_j (grad: n_dst x 3 rows) and the intensity It_j, takes its own intensity Is_i
-// (it does not move with the pose), and forms the two rows of rules C3 and C4 of include/misc3d_amd.h:
+// Coloured: for a correspondence the thread gathers t_j, n_j, the colour gradient g_j (grad: n_dst x 3 rows) and the intensity
+// It_j, takes its own intensity Is_i (it does not move with the pose), and forms the two rows of rules C3 and C4 of
+// include/misc3d_amd.h:
 //   e = (s - t) . n          r0 = sg e                 J0 = sg [s x n, n]
 //   q = (s - e n) - t        I0 = g . q + It           m = -(g^T (I - n n^T))       r1 = sp (Is - I0)      J1 = sp [s x m, m]
-// and contributes count, d2, the 21 products J0a J0b + J1a J1b, the 6 values J0a r0 + J1a r1 and r0 r0 + r1 r1: the record of
-// m3d_icp_fp.hpp, reduced exactly as the plane kernel's (wave_sum, the four waves in LDS in wave order, one record per
-// workgroup, icp_plane_final_k over the workgroups).  No atomics.
+// and contributes count, d2, the 21 products J0a J0b + J1a J1b, the 6 values J0a r0 + J1a r1 and r0 r0 + r1 r1.
 __global__ __launch_bounds__(256) void icp_colored_iter_k(const double* __restrict__ ix, const double* __restrict__ iy,
                                                            const double* __restrict__ iz, uint32_t n,
                                                            const double* __restrict__ T, double* __restrict__ px,
@@ -1660,69 +1670,40 @@ __global__ __launch_bounds__(256) void icp_colored_iter_k(const double* __restri
                                                            const double* __restrict__ grad, const double* __restrict__ it_dst,
                                                            const double* __restrict__ is_src, double sg, double sp,
                                                            uint32_t* __restrict__ nn, double* __restrict__ partial) {
-    __shared__ double sm[4][kIcpPlaneRecord];
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     double v[kIcpPlaneRecord];
     for (int k = 0; k < kIcpPlaneRecord; ++k) v[k] = 0.0;
-    if (i < n) {
-        double x = ix[i], y = iy[i], z = iz[i];
-        if (T) {
-            double t[12];
-            for (int k = 0; k < 12; ++k) t[k] = T[k];
-            const double tx = ((t[0] * x + t[1] * y) + t[2] * z) + t[3];
-            const double ty = ((t[4] * x + t[5] * y) + t[6] * z) + t[7];
-            const double tz = ((t[8] * x + t[9] * y) + t[10] * z) + t[11];
-            x = tx;
-            y = ty;
-            z = tz;
-        }
-        px[i] = x;
-        py[i] = y;
-        pz[i] = z;
-        double best;
-        uint32_t bo;
-        nearest_idx(g, cell_start, qx, qy, qz, cell_orig, x, y, z, &best, &bo);
-        const bool ok = best < g.r2;
-        nn[i] = ok ? bo : 0xFFFFFFFFu;
-        if (ok) {
-            const double ax = dst.nx[bo], ay = dst.ny[bo], az = dst.nz[bo];
-            const double tx = dst.x[bo], ty = dst.y[bo], tz = dst.z[bo];
-            const double g0 = grad[3 * (size_t)bo], g1 = grad[3 * (size_t)bo + 1], g2 = grad[3 * (size_t)bo + 2];
-            const double e = ((x - tx) * ax + (y - ty) * ay) + (z - tz) * az;
-            const double r0 = sg * e;
-            const double q0 = (x - e * ax) - tx, q1 = (y - e * ay) - ty, q2 = (z - e * az) - tz;
-            const double i0 = ((g0 * q0 + g1 * q1) + g2 * q2) + it_dst[bo];
-            const double r1 = sp * (is_src[i] - i0);
-            // m = -(g^T (I - n n^T)), the nine entries written out
-            const double m0 = -((g0 * (1.0 - ax * ax) + g1 * (-(ay * ax))) + g2 * (-(az * ax)));
-            const double m1 = -((g0 * (-(ax * ay)) + g1 * (1.0 - ay * ay)) + g2 * (-(az * ay)));
-            const double m2 = -((g0 * (-(ax * az)) + g1 * (-(ay * az))) + g2 * (1.0 - az * az));
-            // s x n and s x m, associated as in icp_plane_iter_k
-            const double J0[6] = {sg * (y * az - z * ay), sg * (z * ax - x * az), sg * (x * ay - y * ax), sg * ax, sg * ay, sg * az};
-            const double J1[6] = {sp * (y * m2 - z * m1), sp * (z * m0 - x * m2), sp * (x * m1 - y * m0), sp * m0, sp * m1, sp * m2};
-            v[0] = 1.0;
-            v[1] = best;
-            int k = 2;
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const IcpMatch m = icp_move_and_match(i, ix, iy, iz, n, T, px, py, pz, g, cell_start, qx, qy, qz, cell_orig, nn);
+    if (m.ok) {
+        const double x = m.x, y = m.y, z = m.z;
+        const uint32_t bo = m.j;
+        const double ax = dst.nx[bo], ay = dst.ny[bo], az = dst.nz[bo];
+        const double tx = dst.x[bo], ty = dst.y[bo], tz = dst.z[bo];
+        const double g0 = grad[3 * (size_t)bo], g1 = grad[3 * (size_t)bo + 1], g2 = grad[3 * (size_t)bo + 2];
+        const double e = ((x - tx) * ax + (y - ty) * ay) + (z - tz) * az;
+        const double r0 = sg * e;
+        const double q0 = (x - e * ax) - tx, q1 = (y - e * ay) - ty, q2 = (z - e * az) - tz;
+        const double i0 = ((g0 * q0 + g1 * q1) + g2 * q2) + it_dst[bo];
+        const double r1 = sp * (is_src[i] - i0);
+        // m = -(g^T (I - n n^T)), the nine entries written out
+        const double m0 = -((g0 * (1.0 - ax * ax) + g1 * (-(ay * ax))) + g2 * (-(az * ax)));
+        const double m1 = -((g0 * (-(ax * ay)) + g1 * (1.0 - ay * ay)) + g2 * (-(az * ay)));
+        const double m2 = -((g0 * (-(ax * az)) + g1 * (-(ay * az))) + g2 * (1.0 - az * az));
+        // s x n and s x m, associated as in icp_plane_iter_k
+        const double J0[6] = {sg * (y * az - z * ay), sg * (z * ax - x * az), sg * (x * ay - y * ax), sg * ax, sg * ay, sg * az};
+        const double J1[6] = {sp * (y * m2 - z * m1), sp * (z * m0 - x * m2), sp * (x * m1 - y * m0), sp * m0, sp * m1, sp * m2};
+        v[0] = 1.0;
+        v[1] = m.d2;
+        int k = 2;
 #pragma unroll
-            for (int a = 0; a < 6; ++a)
+        for (int a = 0; a < 6; ++a)
 #pragma unroll
-                for (int b = a; b < 6; ++b) v[k++] = J0[a] * J0[b] + J1[a] * J1[b];
+            for (int b = a; b < 6; ++b) v[k++] = J0[a] * J0[b] + J1[a] * J1[b];
 #pragma unroll
-            for (int a = 0; a < 6; ++a) v[23 + a] = J0[a] * r0 + J1[a] * r1;
-            v[29] = r0 * r0 + r1 * r1;
-        }
+        for (int a = 0; a < 6; ++a) v[23 + a] = J0[a] * r0 + J1[a] * r1;
+        v[29] = r0 * r0 + r1 * r1;
     }
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < kIcpPlaneRecord; ++k) {
-        const double s = wave_sum(v[k]);
-        if (lane == 0) sm[wave][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < (uint32_t)kIcpPlaneRecord) {
-        const uint32_t k = threadIdx.x;
-        partial[(size_t)blockIdx.x * kIcpPlaneStride + k] = ((sm[0][k] + sm[1][k]) + sm[2][k]) + sm[3][k];
-    }
+    icp_record_reduce(v, partial);
 }
 void launch_icp_colored_iter(const double* ix, const double* iy, const double* iz, uint32_t n, const double* T_dev, double* px,
                              double* py, double* pz, const GridDesc& g, const uint32_t* cell_start, const double* qx,

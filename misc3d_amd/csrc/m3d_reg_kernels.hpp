@@ -152,7 +152,9 @@ void launch_info_sums(uint32_t n, const CloudView& dst, const uint32_t* nn, doub
                       hipStream_t s);
 void launch_icp_transform(const double* ix, const double* iy, const double* iz, uint32_t n, const double* T_dev,
                           double* ox, double* oy, double* oz, hipStream_t s);
-// Point-to-plane ICP's iteration (icp_plane_iter_k + icp_plane_final_k): the pending update T_dev (12 doubles, null = none) applied
+// The iteration of the two ICP estimators that reduce to a record (the host's icp_record_loop): one frame in the kernel file --
+// the pending update, the store of the moved point, the search, nn[i]; the record's reduction -- around each estimator's rows.
+// Point-to-plane ICP's (icp_plane_iter_k + icp_plane_final_k): the pending update T_dev (12 doubles, null = none) applied
 // to (ix, iy, iz) -> (px, py, pz), nn[i], and out[0 .. kIcpPlaneRecord) = the record of m3d_icp_fp.hpp.  partial: kIcpPlaneStride
 // doubles per workgroup of 256 points (icp_plane_blocks(n) of them).  dst needs its normals.
 constexpr int kIcpPlaneRecord = 30;

@@ -4,6 +4,8 @@
 //   m3d_registration_ransac  registration::RANSACSolver::Solve        src/transform_estimation.cpp:124-164
 //                            (= Open3D 0.15.1 RegistrationRANSACBasedOnCorrespondence)
 //   (m3d_match_mutual_nn -- registration::ANNMatcher::Match, src/correspondence_matching.cpp:52-84 -- lives in m3d_match.cpp)
+//   m3d_registration_icp[_plane|_colored]   Open3D RegistrationICP: one call frame, one loop, three estimators ("RegistrationICP" below)
+//   m3d_information_matrix, m3d_detect_boundary_points   GetInformationMatrixFromPointClouds, DetectBoundaryPoints
 //
 // Sequential (one-thread) semantics of the Open3D loop with an explicit seed: iteration `itr` draws
 // three correspondences from std::uniform_int_distribution<int>(0, M-1) on std::mt19937 iff
@@ -1110,12 +1112,321 @@ int m3d_registration_ransac_sharded(const double* src, size_t n_src, const doubl
     return rc;
 }
 
+}  // extern "C"
 
-// Point-to-point ICP: Open3D RegistrationICP with TransformationEstimationPointToPoint, which both registration
-// examples of the reference run on the RANSAC pose (examples/cpp/transform_estimation.cpp:82-86); SURVEY.md 8(f)
-// N1.  [RECALL] of the Open3D 0.15.1 loop: oracle/misc3d_oracle_reg.c orc_registration_icp.  Reuses the
-// registration path's target grid (+ original indices), the serial-order error sum, the Kabsch sums and the
-// K3x3 umeyama assembly.  The moving cloud is transformed in place every iteration, as Open3D does.
+// ------------------------------------------------------------------------------------------------
+// RegistrationICP: one call (icp_call), one loop (icp_loop) and three estimators.  Both registration examples of the reference
+// run it on the RANSAC pose (examples/cpp/transform_estimation.cpp:82-86), the pipeline runs it per level
+// (m3d_multi_scale_icp.cpp).  [RECALL] of the Open3D 0.15.1 loop: oracle/misc3d_oracle_reg.c orc_registration_icp.
+//   icp_call   the argument checks and the result of an empty cloud (icp_prologue); what a call holds (IcpFrame): lane, clouds,
+//              the registration path's target grid with original indices, the moving cloud (transformed in place every
+//              iteration, as Open3D does), the estimator's own buffers; the ONE path that releases it
+//   icp_loop   result, update, compose, next result, the two-criteria convergence test, the outputs
+// An estimator is its own argument check, its reservations and two callables: iterate(first, update) moves the cloud by the
+// pending update, searches the correspondences and leaves their count and error in the frame; compute_update(U) is
+// ComputeTransformation on what iterate left behind.  Point-to-point: transform, search, error sum, Kabsch sums and one polled
+// wait, the K3x3 umeyama assembly.  Point-to-plane and coloured (icp_record_loop; they differ in the launch): one launch -- the
+// pending update, the search, the 30 sums -- one copy of the record and one polled wait; the 6 x 6 solve of m3d_icp_fp.hpp.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+struct IcpArgs {   // the arguments every estimator's entry point has
+    const double *src, *dst, *T_init;
+    size_t n_src, n_dst;
+    double max_correspondence_distance, relative_fitness, relative_rmse;
+    int max_iteration, device;
+    double* T_out;
+    m3d_icp_stats* stats;
+    int64_t* correspondences;
+};
+
+struct IcpFrame {   // what a call holds
+    const double t_begin = now_ms();
+    double T[16];                   // the pose so far
+    std::optional<LaneLock> lane;   // the call's own, unless the caller holds one
+    DeviceCtx* ctx = nullptr;
+    m3d_cloud *csrc = nullptr, *cdst = nullptr;
+    CloudView sv, dv;
+    uint32_t n = 0;   // moving points
+    Scratch S;
+    GridDesc g;
+    DevBuf mx, my, mz, nn;                            // the moving cloud and its correspondences (original target indices)
+    double *px = nullptr, *py = nullptr, *pz = nullptr;   // ... = mx, my, mz
+    DevBuf extra[4];    // the estimator's own: d2 (point-to-point); grad, it_dst, is_src, col_src (coloured)
+    uint64_t cnt = 0;   // the last result: correspondences and the sum of their squared distances
+    double e2 = 0.0;
+};
+
+// -> true: go on with T = the initial pose (T_out has it too, the stats are zero); false: the call is over, *rc its return
+// value.  estimator_error: the message of the estimator's own argument check (null: passed), reported where Open3D reports it
+bool icp_prologue(const IcpArgs& a, const char* estimator_error, double* T, int* rc) {
+    auto refuse = [&](const char* message) { *rc = fail(M3D_ERR_INVALID_ARG, message); return false; };
+    *rc = M3D_OK;
+    if (!a.T_out || (!a.src && a.n_src) || (!a.dst && a.n_dst)) return refuse("invalid argument");
+    if (a.T_init) std::memcpy(T, a.T_init, sizeof(double) * 16);
+    else icp_identity4(T);
+    std::memcpy(a.T_out, T, sizeof(double) * 16);
+    if (a.stats) std::memset(a.stats, 0, sizeof(*a.stats));
+    if (!(a.max_correspondence_distance > 0.0)) return refuse(kIcpInvalidDistance);   // Open3D: LogError
+    if (estimator_error) return refuse(estimator_error);
+    if (a.n_src >= ((size_t)1 << 31) || a.n_dst >= ((size_t)1 << 31)) return refuse("too many points");
+    if (a.n_src == 0 || a.n_dst == 0) {   // no correspondences: every update is the identity, fitness 0
+        if (a.correspondences)
+            for (size_t i = 0; i < a.n_src; ++i) a.correspondences[i] = -1;
+        if (a.stats) {
+            a.stats->iterations = a.max_iteration > 0 ? 1 : 0;   // the first repeat already meets both criteria
+            a.stats->converged = a.max_iteration > 0;
+        }
+        return false;
+    }
+    return true;
+}
+
+// A call from its checks to its release.  before_upload(f): what the estimator makes resident ahead of the clouds (into
+// f.extra); body(f): its reservations and its icp_loop, on the frame's grid and moving buffers.  held != null: the caller's lane.
+template <class BeforeUpload, class Body>
+int icp_call(DeviceCtx* held, const IcpArgs& a, const char* estimator_error, const double* dst_normals,
+             BeforeUpload&& before_upload, Body&& body) {
+    IcpFrame f;
+    int rc;
+    if (!icp_prologue(a, estimator_error, f.T, &rc)) return rc;
+    if (!held) f.lane.emplace(a.device);
+    DeviceCtx* ctx = f.ctx = held ? held : f.lane->ctx;
+    if (!ctx) return M3D_ERR_DEVICE;
+    rc = before_upload(f);
+    if (rc == M3D_OK) {
+        f.csrc = m3d_cloud_create_on(ctx, a.src, nullptr, a.n_src, 0);
+        f.cdst = f.csrc ? m3d_cloud_create_on(ctx, a.dst, dst_normals, a.n_dst, 0) : nullptr;
+        if (f.csrc && !f.cdst) m3d_cloud_destroy_on(f.csrc);
+        if (!f.cdst) rc = M3D_ERR_DEVICE;
+    }
+    if (rc != M3D_OK) {
+        for (DevBuf& b : f.extra) b.release();
+        return rc;
+    }
+    rc = [&]() -> int {
+        HIPCHK(hipSetDevice(ctx->device));
+        f.sv = f.csrc->view();
+        f.dv = f.cdst->view();
+        f.n = f.sv.n;
+        const int rg = build_target_grid(ctx, f.S, f.dv, a.dst, a.n_dst, a.max_correspondence_distance, true, &f.g);
+        if (rg != M3D_OK) return rg;
+        RESERVE(f.mx, sizeof(double) * f.n);
+        RESERVE(f.my, sizeof(double) * f.n);
+        RESERVE(f.mz, sizeof(double) * f.n);
+        RESERVE(f.nn, sizeof(uint32_t) * f.n);
+        f.px = f.mx.as<double>();
+        f.py = f.my.as<double>();
+        f.pz = f.mz.as<double>();
+        return body(f);
+    }();
+    (void)hipStreamSynchronize(ctx->stream);
+    f.S.release();
+    for (DevBuf* b : {&f.mx, &f.my, &f.mz, &f.nn, &f.extra[0], &f.extra[1], &f.extra[2], &f.extra[3]}) b->release();
+    m3d_cloud_destroy_on(f.csrc);
+    m3d_cloud_destroy_on(f.cdst);
+    if (a.stats) a.stats->ms_total = now_ms() - f.t_begin;
+    return rc;
+}
+int icp_nothing_before_upload(IcpFrame&) { return M3D_OK; }
+
+template <class Iterate, class Update>
+int icp_loop(IcpFrame& f, const IcpArgs& a, Iterate&& iterate, Update&& compute_update) {
+    double fit = 0.0, rm = 0.0;
+    auto score = [&]() {
+        fit = (double)f.cnt / (double)a.n_src;
+        rm = f.cnt ? std::sqrt(f.e2 / (double)f.cnt) : 0.0;
+    };
+    double I4[16];
+    icp_identity4(I4);
+    // pcd = source; if (!init.isIdentity()) pcd.Transform(init)
+    int r = iterate(true, std::memcmp(f.T, I4, sizeof(I4)) != 0 ? f.T : nullptr);
+    if (r != M3D_OK) return r;
+    score();
+    int it = 0;
+    bool converged = false;
+    for (; it < a.max_iteration; ++it) {
+        double U[16];
+        compute_update(U);      // ComputeTransformation
+        icp_compose4(U, f.T);   // transformation = update * transformation
+        const double fit0 = fit, rm0 = rm;
+        r = iterate(false, U);   // pcd.Transform(update), the next result
+        if (r != M3D_OK) return r;
+        score();
+        if (std::fabs(fit0 - fit) < a.relative_fitness && std::fabs(rm0 - rm) < a.relative_rmse) {
+            ++it;
+            converged = true;
+            break;
+        }
+    }
+    std::memcpy(a.T_out, f.T, sizeof(f.T));
+    if (a.correspondences) {
+        std::vector<uint32_t> hn(f.n);
+        HIPCHK(hipMemcpy(hn.data(), f.nn.p, sizeof(uint32_t) * f.n, hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < f.n; ++i) a.correspondences[i] = hn[i] == 0xFFFFFFFFu ? -1 : (int64_t)hn[i];
+    }
+    if (a.stats) {
+        a.stats->fitness = fit;
+        a.stats->inlier_rmse = rm;
+        a.stats->correspondences = f.cnt;
+        a.stats->iterations = it;
+        a.stats->converged = converged ? 1 : 0;
+    }
+    return M3D_OK;
+}
+
+// The loop of the two estimators whose iteration is one launch that leaves the record of m3d_icp_fp.hpp:
+// launch(ix, iy, iz, T_dev) is launch_icp_plane_iter or launch_icp_colored_iter on the frame's buffers.
+static_assert(kIcpPlaneRecord == kIcpPlaneSums, "the kernels' record is the one m3d_icp_fp.hpp reads");
+template <class Launch>
+int icp_record_loop(IcpFrame& f, const IcpArgs& a, Launch&& launch) {
+    DeviceCtx* ctx = f.ctx;
+    Scratch& S = f.S;
+    RESERVE(S.sums, sizeof(double) * kIcpPlaneStride);
+    RESERVE(S.partial_sum, sizeof(double) * kIcpPlaneStride * (size_t)icp_plane_blocks(f.n));
+    RESERVE(S.one_T, sizeof(double) * kRegTStride);
+    RESERVE(ctx->h_small, 512);
+    double hs[kIcpPlaneSums];   // the record of the last iteration
+    // Transform(update) of the moving cloud + GetRegistrationResultAndCorrespondences + the sums of the NEXT
+    // ComputeTransformation.  update == null: the source cloud as it is (an identity init)
+    auto iterate = [&](bool first, const double* update) -> int {
+        if (update) HIPCHK(hipMemcpyAsync(S.one_T.p, update, sizeof(double) * 12, hipMemcpyHostToDevice, ctx->stream));
+        launch(first ? f.sv.x : f.px, first ? f.sv.y : f.py, first ? f.sv.z : f.pz, update ? S.one_T.as<double>() : nullptr);
+        uint8_t* h = ctx->h_small.as<uint8_t>();
+        HIPCHK(hipMemcpyAsync(h, S.sums.p, sizeof(hs), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipGetLastError());
+        if (const int wr = stream_wait_spin(ctx); wr != M3D_OK) return wr;   // (an iteration's one wait: polled)
+        std::memcpy(hs, h, sizeof(hs));
+        f.cnt = (uint64_t)hs[0];
+        f.e2 = hs[1];
+        return M3D_OK;
+    };
+    return icp_loop(f, a, iterate, [&](double* U) { icp_plane_update(hs, U); });
+}
+
+}  // namespace
+
+// TransformationEstimationPointToPoint
+int m3d::registration_icp_on(DeviceCtx* held, const double* src, size_t n_src, const double* dst, size_t n_dst,
+                             double max_correspondence_distance, const double* T_init, int max_iteration,
+                             double relative_fitness, double relative_rmse, int device, double* T_out,
+                             m3d_icp_stats* stats, int64_t* correspondences) {
+    const IcpArgs a{src, dst, T_init, n_src, n_dst, max_correspondence_distance, relative_fitness, relative_rmse, max_iteration,
+                    device, T_out, stats, correspondences};
+    return icp_call(held, a, nullptr, nullptr, icp_nothing_before_upload, [&](IcpFrame& f) -> int {
+        DeviceCtx* ctx = f.ctx;
+        Scratch& S = f.S;
+        const uint32_t n = f.n;
+        DevBuf& d2 = f.extra[0];
+        RESERVE(d2, sizeof(double) * n);
+        RESERVE(S.vals, sizeof(double) * n);
+        RESERVE(S.block_counts, sizeof(uint32_t) * ((size_t)((n + 2047) / 2048) + 1));
+        RESERVE(S.tgt.total, 16);
+        RESERVE(S.sums, sizeof(double) * 32);
+        RESERVE(S.partial_sum, sizeof(double) * 256 * 16);
+        RESERVE(S.one_T, sizeof(double) * kRegTStride);
+        RESERVE(ctx->h_small, 512);
+        double hs[18];   // sums of the correspondence set for umeyama
+        auto iterate = [&](bool first, const double* update) -> int {
+            if (update) {
+                HIPCHK(hipMemcpyAsync(S.one_T.p, update, sizeof(double) * 12, hipMemcpyHostToDevice, ctx->stream));
+                launch_icp_transform(first ? f.sv.x : f.px, first ? f.sv.y : f.py, first ? f.sv.z : f.pz, n, S.one_T.as<double>(),
+                                     f.px, f.py, f.pz, ctx->stream);
+            } else {
+                HIPCHK(hipMemcpyAsync(f.px, f.sv.x, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream));
+                HIPCHK(hipMemcpyAsync(f.py, f.sv.y, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream));
+                HIPCHK(hipMemcpyAsync(f.pz, f.sv.z, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream));
+            }
+            // GetRegistrationResultAndCorrespondences: nearest target point within the radius, count + error2
+            launch_icp_nn(f.px, f.py, f.pz, n, f.g, S.tgt.start.as<uint32_t>(), S.qx.as<double>(), S.qy.as<double>(),
+                          S.qz.as<double>(), S.cell_orig.as<uint32_t>(), f.nn.as<uint32_t>(), d2.as<double>(), ctx->stream);
+            launch_icp_err(d2.as<double>(), n, f.g.r2, S.partial_sum.as<double>(), S.sums.as<double>() + 24, ctx->stream);
+            // the sums of the NEXT ComputeTransformation are queued behind it at once (they read the count from
+            // the device): one host wait per iteration instead of two; after the last iteration they go unused
+            launch_icp_sums(f.px, f.py, f.pz, n, f.dv, f.nn.as<uint32_t>(), S.sums.as<double>() + 25, S.partial_sum.as<double>(),
+                            S.sums.as<double>(), ctx->stream);
+            uint8_t* h = ctx->h_small.as<uint8_t>();
+            HIPCHK(hipMemcpyAsync(h, S.sums.as<double>() + 24, 16, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipMemcpyAsync(h + 32, S.sums.p, sizeof(hs), hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipGetLastError());
+            if (const int wr = stream_wait_spin(ctx); wr != M3D_OK) return wr;   // (an iteration's one wait: polled, see corr_inlier_ratio)
+            double es[2];
+            std::memcpy(es, h, 16);
+            std::memcpy(hs, h + 32, sizeof(hs));
+            f.e2 = es[0];
+            f.cnt = (uint32_t)es[1];
+            return M3D_OK;
+        };
+        // ComputeTransformation: Eigen::umeyama over the correspondence set, no scaling
+        auto compute_update = [&](double* U) {
+            icp_identity4(U);
+            if (!f.cnt) return;
+            const double one_over_n = 1.0 / (double)f.cnt;
+            double ms[3], md[3], sig[9];
+            for (int k = 0; k < 3; ++k) {
+                ms[k] = hs[k] * one_over_n;
+                md[k] = hs[3 + k] * one_over_n;
+            }
+            for (int k = 0; k < 9; ++k) sig[k] = hs[6 + k] * one_over_n;
+            const double src_var = ((hs[15] + hs[16]) + hs[17]) * one_over_n;
+            umeyama_assemble(ms, md, sig, src_var, false, U);
+        };
+        return icp_loop(f, a, iterate, compute_update);
+    });
+}
+
+// TransformationEstimationPointToPlane (the contract: include/misc3d_amd.h)
+int m3d::registration_icp_plane_on(DeviceCtx* held, const double* src, size_t n_src, const double* dst, const double* dst_normals,
+                                   size_t n_dst, double max_correspondence_distance, const double* T_init, int max_iteration,
+                                   double relative_fitness, double relative_rmse, int device, double* T_out,
+                                   m3d_icp_stats* stats, int64_t* correspondences) {
+    const IcpArgs a{src, dst, T_init, n_src, n_dst, max_correspondence_distance, relative_fitness, relative_rmse, max_iteration,
+                    device, T_out, stats, correspondences};
+    return icp_call(held, a, !dst_normals ? kIcpNeedsNormals : nullptr, dst_normals, icp_nothing_before_upload, [&](IcpFrame& f) {
+        Scratch& S = f.S;
+        return icp_record_loop(f, a, [&](const double* ix, const double* iy, const double* iz, const double* T_dev) {
+            launch_icp_plane_iter(ix, iy, iz, f.n, T_dev, f.px, f.py, f.pz, f.g, S.tgt.start.as<uint32_t>(), S.qx.as<double>(),
+                                  S.qy.as<double>(), S.qz.as<double>(), S.cell_orig.as<uint32_t>(), f.dv, f.nn.as<uint32_t>(),
+                                  S.partial_sum.as<double>(), S.sums.as<double>(), f.ctx->stream);
+        });
+    });
+}
+
+// TransformationEstimationForColoredICP (the contract: include/misc3d_amd.h, rules G1 - G7 and C1 - C6).  Before the loop: the
+// target's colour gradients and intensities (color_gradient_on: Hybrid(2 max_correspondence_distance, 30)) and the source's
+// intensities, all resident for the call.  The record has the plane call's layout: the same solve.
+int m3d::registration_icp_colored_on(DeviceCtx* held, const double* src, const double* src_colors, size_t n_src, const double* dst,
+                                     const double* dst_normals, const double* dst_colors, size_t n_dst,
+                                     double max_correspondence_distance, double lambda_geometric, const double* T_init,
+                                     int max_iteration, double relative_fitness, double relative_rmse, int device, double* T_out,
+                                     m3d_icp_stats* stats, int64_t* correspondences) {
+    const IcpArgs a{src, dst, T_init, n_src, n_dst, max_correspondence_distance, relative_fitness, relative_rmse, max_iteration,
+                    device, T_out, stats, correspondences};
+    const char* bad = !dst_normals ? kIcpNeedsNormals : (!src_colors || !dst_colors) ? kIcpNeedsColors : nullptr;
+    if (!bad && !(lambda_geometric >= 0.0 && lambda_geometric <= 1.0)) bad = kIcpBadLambda;
+    auto gradients = [&](IcpFrame& f) {   // grad = extra[0], it_dst = extra[1]
+        return color_gradient_on(f.ctx, dst, dst_normals, dst_colors, n_dst, 2.0 * max_correspondence_distance, 30, f.extra[0],
+                                 f.extra[1], nullptr);
+    };
+    return icp_call(held, a, bad, dst_normals, gradients, [&](IcpFrame& f) -> int {
+        Scratch& S = f.S;
+        DevBuf &grad = f.extra[0], &it_dst = f.extra[1], &is_src = f.extra[2], &col_src = f.extra[3];
+        const double sg = std::sqrt(lambda_geometric), sp = std::sqrt(1.0 - lambda_geometric);
+        RESERVE(col_src, sizeof(double) * 3 * n_src);
+        RESERVE(is_src, sizeof(double) * n_src);
+        HIPCHK(hipMemcpyAsync(col_src.p, src_colors, sizeof(double) * 3 * n_src, hipMemcpyHostToDevice, f.ctx->stream));
+        launch_color_intensity(col_src.as<double>(), f.n, is_src.as<double>(), f.ctx->stream);
+        return icp_record_loop(f, a, [&](const double* ix, const double* iy, const double* iz, const double* T_dev) {
+            launch_icp_colored_iter(ix, iy, iz, f.n, T_dev, f.px, f.py, f.pz, f.g, S.tgt.start.as<uint32_t>(), S.qx.as<double>(),
+                                    S.qy.as<double>(), S.qz.as<double>(), S.cell_orig.as<uint32_t>(), f.dv, grad.as<double>(),
+                                    it_dst.as<double>(), is_src.as<double>(), sg, sp, f.nn.as<uint32_t>(),
+                                    S.partial_sum.as<double>(), S.sums.as<double>(), f.ctx->stream);
+        });
+    });
+}
+
+extern "C" {
+
 int m3d_registration_icp(const double* src, size_t n_src, const double* dst, size_t n_dst,
                          double max_correspondence_distance, const double* T_init, int max_iteration,
                          double relative_fitness, double relative_rmse, int device, double* T_out,
@@ -1123,488 +1434,25 @@ int m3d_registration_icp(const double* src, size_t n_src, const double* dst, siz
     return registration_icp_on(nullptr, src, n_src, dst, n_dst, max_correspondence_distance, T_init, max_iteration,
                                relative_fitness, relative_rmse, device, T_out, stats, correspondences);
 }
-}  // extern "C"
 
-int m3d::registration_icp_on(DeviceCtx* held, const double* src, size_t n_src, const double* dst, size_t n_dst,
-                             double max_correspondence_distance, const double* T_init, int max_iteration,
-                             double relative_fitness, double relative_rmse, int device, double* T_out,
-                             m3d_icp_stats* stats, int64_t* correspondences) {
-    const double t_begin = now_ms();
-    if (!T_out || (!src && n_src) || (!dst && n_dst)) return fail(M3D_ERR_INVALID_ARG, "invalid argument");
-    static const double I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    double T[16];
-    std::memcpy(T, T_init ? T_init : I4, sizeof(T));
-    std::memcpy(T_out, T, sizeof(T));
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if (!(max_correspondence_distance > 0.0))   // Open3D: LogError("Invalid max_correspondence_distance.")
-        return fail(M3D_ERR_INVALID_ARG, "Invalid max_correspondence_distance.");
-    if (n_src >= ((size_t)1 << 31) || n_dst >= ((size_t)1 << 31)) return fail(M3D_ERR_INVALID_ARG, "too many points");
-    if (n_src == 0 || n_dst == 0) {   // no correspondences: every update is the identity, fitness 0
-        if (correspondences)
-            for (size_t i = 0; i < n_src; ++i) correspondences[i] = -1;
-        if (stats) {
-            stats->iterations = max_iteration > 0 ? 1 : 0;   // the first repeat already meets both criteria
-            stats->converged = max_iteration > 0;
-        }
-        return M3D_OK;
-    }
-    std::optional<LaneLock> lane;
-    if (!held) lane.emplace(device);
-    DeviceCtx* ctx = held ? held : lane->ctx;
-    if (!ctx) return M3D_ERR_DEVICE;
-    m3d_cloud* csrc = m3d_cloud_create_on(ctx, src, nullptr, n_src, 0);
-    if (!csrc) return M3D_ERR_DEVICE;
-    m3d_cloud* cdst = m3d_cloud_create_on(ctx, dst, nullptr, n_dst, 0);
-    if (!cdst) {
-        m3d_cloud_destroy_on(csrc);
-        return M3D_ERR_DEVICE;
-    }
-    Scratch S;
-    DevBuf mx, my, mz, nn, d2;
-    int rc;
-    {
-        rc = [&]() -> int {
-            HIPCHK(hipSetDevice(ctx->device));
-            const CloudView sv = csrc->view(), dv = cdst->view();
-            const uint32_t n = sv.n;
-            GridDesc g;
-            const int rg = build_target_grid(ctx, S, dv, dst, n_dst, max_correspondence_distance, true, &g);
-            if (rg != M3D_OK) return rg;
-            const uint32_t nb = (n + 2047) / 2048;
-            RESERVE(mx, sizeof(double) * n);
-            RESERVE(my, sizeof(double) * n);
-            RESERVE(mz, sizeof(double) * n);
-            RESERVE(nn, sizeof(uint32_t) * n);
-            RESERVE(d2, sizeof(double) * n);
-            RESERVE(S.vals, sizeof(double) * n);
-            RESERVE(S.block_counts, sizeof(uint32_t) * ((size_t)nb + 1));
-            RESERVE(S.tgt.total, 16);
-            RESERVE(S.sums, sizeof(double) * 32);
-            RESERVE(S.partial_sum, sizeof(double) * 256 * 16);
-            RESERVE(S.one_T, sizeof(double) * kRegTStride);
-            RESERVE(ctx->h_small, 512);
-            double* px = mx.as<double>();
-            double* py = my.as<double>();
-            double* pz = mz.as<double>();
-            auto upload_T = [&](const double* M) -> int {
-                HIPCHK(hipMemcpyAsync(S.one_T.p, M, sizeof(double) * 12, hipMemcpyHostToDevice, ctx->stream));
-                return M3D_OK;
-            };
-            // pcd = source; if (!init.isIdentity()) pcd.Transform(init)
-            if (std::memcmp(T, I4, sizeof(T)) != 0) {
-                const int r = upload_T(T);
-                if (r != M3D_OK) return r;
-                launch_icp_transform(sv.x, sv.y, sv.z, n, S.one_T.as<double>(), px, py, pz, ctx->stream);
-            } else {
-                HIPCHK(hipMemcpyAsync(px, sv.x, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream));
-                HIPCHK(hipMemcpyAsync(py, sv.y, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream));
-                HIPCHK(hipMemcpyAsync(pz, sv.z, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream));
-            }
-            uint64_t cnt = 0;
-            double e2 = 0.0;
-            double hs[18];   // sums of the correspondence set for umeyama (filled by result())
-            // GetRegistrationResultAndCorrespondences: nearest target point within the radius, count + error2
-            auto result = [&]() -> int {
-                launch_icp_nn(px, py, pz, n, g, S.tgt.start.as<uint32_t>(), S.qx.as<double>(), S.qy.as<double>(),
-                              S.qz.as<double>(), S.cell_orig.as<uint32_t>(), nn.as<uint32_t>(), d2.as<double>(),
-                              ctx->stream);
-                launch_icp_err(d2.as<double>(), n, g.r2, S.partial_sum.as<double>(), S.sums.as<double>() + 24, ctx->stream);
-                // the sums of the NEXT ComputeTransformation are queued behind it at once (they read the count from
-                // the device): one host wait per iteration instead of two; after the last iteration they go unused
-                launch_icp_sums(px, py, pz, n, dv, nn.as<uint32_t>(), S.sums.as<double>() + 25,
-                                S.partial_sum.as<double>(), S.sums.as<double>(), ctx->stream);
-                RESERVE(ctx->h_small, 256);
-                uint8_t* h = ctx->h_small.as<uint8_t>();
-                HIPCHK(hipMemcpyAsync(h, S.sums.as<double>() + 24, 16, hipMemcpyDeviceToHost, ctx->stream));
-                HIPCHK(hipMemcpyAsync(h + 32, S.sums.p, sizeof(hs), hipMemcpyDeviceToHost, ctx->stream));
-                HIPCHK(hipGetLastError());
-                if (const int wr = stream_wait_spin(ctx); wr != M3D_OK) return wr;   // (an iteration's one wait: polled, see corr_inlier_ratio)
-                double es[2];
-                std::memcpy(es, h, 16);
-                std::memcpy(hs, h + 32, sizeof(hs));
-                e2 = es[0];
-                const uint32_t c = (uint32_t)es[1];
-                cnt = c;
-                return M3D_OK;
-            };
-            int r = result();
-            if (r != M3D_OK) return r;
-            double fit = (double)cnt / (double)n_src;
-            double rm = cnt ? std::sqrt(e2 / (double)cnt) : 0.0;
-            int it = 0;
-            bool converged = false;
-            for (; it < max_iteration; ++it) {
-                double U[16];
-                std::memcpy(U, I4, sizeof(U));
-                if (cnt) {   // ComputeTransformation: Eigen::umeyama over the correspondence set, no scaling
-                    const double* h = hs;
-                    const double one_over_n = 1.0 / (double)cnt;
-                    double ms[3], md[3], sig[9];
-                    for (int k = 0; k < 3; ++k) {
-                        ms[k] = h[k] * one_over_n;
-                        md[k] = h[3 + k] * one_over_n;
-                    }
-                    for (int k = 0; k < 9; ++k) sig[k] = h[6 + k] * one_over_n;
-                    const double src_var = ((h[15] + h[16]) + h[17]) * one_over_n;
-                    umeyama_assemble(ms, md, sig, src_var, false, U);
-                }
-                // transformation = update * transformation
-                double Tn[16];
-                for (int rr = 0; rr < 4; ++rr)
-                    for (int cc = 0; cc < 4; ++cc)
-                        Tn[4 * rr + cc] = ((U[4 * rr] * T[cc] + U[4 * rr + 1] * T[4 + cc]) + U[4 * rr + 2] * T[8 + cc]) +
-                                          U[4 * rr + 3] * T[12 + cc];
-                std::memcpy(T, Tn, sizeof(T));
-                r = upload_T(U);
-                if (r != M3D_OK) return r;
-                launch_icp_transform(px, py, pz, n, S.one_T.as<double>(), px, py, pz, ctx->stream);   // pcd.Transform(update)
-                const double fit0 = fit, rm0 = rm;
-                r = result();
-                if (r != M3D_OK) return r;
-                fit = (double)cnt / (double)n_src;
-                rm = cnt ? std::sqrt(e2 / (double)cnt) : 0.0;
-                if (std::fabs(fit0 - fit) < relative_fitness && std::fabs(rm0 - rm) < relative_rmse) {
-                    ++it;
-                    converged = true;
-                    break;
-                }
-            }
-            std::memcpy(T_out, T, sizeof(T));
-            if (correspondences) {
-                std::vector<uint32_t> hn(n);
-                HIPCHK(hipMemcpy(hn.data(), nn.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-                for (uint32_t i = 0; i < n; ++i) correspondences[i] = hn[i] == 0xFFFFFFFFu ? -1 : (int64_t)hn[i];
-            }
-            if (stats) {
-                stats->fitness = fit;
-                stats->inlier_rmse = rm;
-                stats->correspondences = cnt;
-                stats->iterations = it;
-                stats->converged = converged ? 1 : 0;
-            }
-            return M3D_OK;
-        }();
-        (void)hipStreamSynchronize(ctx->stream);
-        S.release();
-        mx.release(); my.release(); mz.release(); nn.release(); d2.release();
-    }
-    m3d_cloud_destroy_on(csrc);
-    m3d_cloud_destroy_on(cdst);
-    if (stats) stats->ms_total = now_ms() - t_begin;
-    return rc;
-}
-
-// Point-to-plane ICP: the same RegistrationICP loop with TransformationEstimationPointToPlane (the contract: include/misc3d_amd.h).
-// An iteration is launch_icp_plane_iter -- the pending update, the search, the 30 sums -- one copy of the record to page-locked
-// memory and one polled wait; the 6 x 6 solve is the host's (m3d_icp_fp.hpp).  Shares the target grid with the point-to-point path.
-static_assert(kIcpPlaneRecord == kIcpPlaneSums, "the kernels' record is the one m3d_icp_fp.hpp reads");
-int m3d::registration_icp_plane_on(DeviceCtx* held, const double* src, size_t n_src, const double* dst, const double* dst_normals,
-                                   size_t n_dst, double max_correspondence_distance, const double* T_init, int max_iteration,
-                                   double relative_fitness, double relative_rmse, int device, double* T_out,
-                                   m3d_icp_stats* stats, int64_t* correspondences) {
-    const double t_begin = now_ms();
-    if (!T_out || (!src && n_src) || (!dst && n_dst)) return fail(M3D_ERR_INVALID_ARG, "invalid argument");
-    static const double I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    double T[16];
-    std::memcpy(T, T_init ? T_init : I4, sizeof(T));
-    std::memcpy(T_out, T, sizeof(T));
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if (!(max_correspondence_distance > 0.0))   // Open3D: LogError("Invalid max_correspondence_distance.")
-        return fail(M3D_ERR_INVALID_ARG, "Invalid max_correspondence_distance.");
-    if (!dst_normals)
-        return fail(M3D_ERR_INVALID_ARG,
-                    "TransformationEstimationPointToPlane and TransformationEstimationColoredICP require pre-computed normal "
-                    "vectors for target PointCloud.");
-    if (n_src >= ((size_t)1 << 31) || n_dst >= ((size_t)1 << 31)) return fail(M3D_ERR_INVALID_ARG, "too many points");
-    if (n_src == 0 || n_dst == 0) {   // no correspondences: every update is the identity, fitness 0
-        if (correspondences)
-            for (size_t i = 0; i < n_src; ++i) correspondences[i] = -1;
-        if (stats) {
-            stats->iterations = max_iteration > 0 ? 1 : 0;   // the first repeat already meets both criteria
-            stats->converged = max_iteration > 0;
-        }
-        return M3D_OK;
-    }
-    std::optional<LaneLock> lane;
-    if (!held) lane.emplace(device);
-    DeviceCtx* ctx = held ? held : lane->ctx;
-    if (!ctx) return M3D_ERR_DEVICE;
-    m3d_cloud* csrc = m3d_cloud_create_on(ctx, src, nullptr, n_src, 0);
-    if (!csrc) return M3D_ERR_DEVICE;
-    m3d_cloud* cdst = m3d_cloud_create_on(ctx, dst, dst_normals, n_dst, 0);
-    if (!cdst) {
-        m3d_cloud_destroy_on(csrc);
-        return M3D_ERR_DEVICE;
-    }
-    Scratch S;
-    DevBuf mx, my, mz, nn;
-    int rc;
-    {
-        rc = [&]() -> int {
-            HIPCHK(hipSetDevice(ctx->device));
-            const CloudView sv = csrc->view(), dv = cdst->view();
-            const uint32_t n = sv.n;
-            GridDesc g;
-            const int rg = build_target_grid(ctx, S, dv, dst, n_dst, max_correspondence_distance, true, &g);
-            if (rg != M3D_OK) return rg;
-            RESERVE(mx, sizeof(double) * n);
-            RESERVE(my, sizeof(double) * n);
-            RESERVE(mz, sizeof(double) * n);
-            RESERVE(nn, sizeof(uint32_t) * n);
-            RESERVE(S.sums, sizeof(double) * kIcpPlaneStride);
-            RESERVE(S.partial_sum, sizeof(double) * kIcpPlaneStride * (size_t)icp_plane_blocks(n));
-            RESERVE(S.one_T, sizeof(double) * kRegTStride);
-            RESERVE(ctx->h_small, 512);
-            double* px = mx.as<double>();
-            double* py = my.as<double>();
-            double* pz = mz.as<double>();
-            double hs[kIcpPlaneSums];   // the record of the last iteration
-            uint64_t cnt = 0;
-            double e2 = 0.0;
-            // Transform(update) of the moving cloud + GetRegistrationResultAndCorrespondences + the sums of the NEXT
-            // ComputeTransformation.  update == null: the source cloud as it is (an identity init)
-            auto iterate = [&](bool first, const double* update) -> int {
-                if (update) HIPCHK(hipMemcpyAsync(S.one_T.p, update, sizeof(double) * 12, hipMemcpyHostToDevice, ctx->stream));
-                launch_icp_plane_iter(first ? sv.x : px, first ? sv.y : py, first ? sv.z : pz, n,
-                                      update ? S.one_T.as<double>() : nullptr, px, py, pz, g, S.tgt.start.as<uint32_t>(),
-                                      S.qx.as<double>(), S.qy.as<double>(), S.qz.as<double>(), S.cell_orig.as<uint32_t>(), dv,
-                                      nn.as<uint32_t>(), S.partial_sum.as<double>(), S.sums.as<double>(), ctx->stream);
-                uint8_t* h = ctx->h_small.as<uint8_t>();
-                HIPCHK(hipMemcpyAsync(h, S.sums.p, sizeof(hs), hipMemcpyDeviceToHost, ctx->stream));
-                HIPCHK(hipGetLastError());
-                if (const int wr = stream_wait_spin(ctx); wr != M3D_OK) return wr;   // (an iteration's one wait: polled)
-                std::memcpy(hs, h, sizeof(hs));
-                cnt = (uint64_t)hs[0];
-                e2 = hs[1];
-                return M3D_OK;
-            };
-            // pcd = source; if (!init.isIdentity()) pcd.Transform(init)
-            int r = iterate(true, std::memcmp(T, I4, sizeof(T)) != 0 ? T : nullptr);
-            if (r != M3D_OK) return r;
-            double fit = (double)cnt / (double)n_src;
-            double rm = cnt ? std::sqrt(e2 / (double)cnt) : 0.0;
-            int it = 0;
-            bool converged = false;
-            for (; it < max_iteration; ++it) {
-                double U[16];
-                icp_plane_update(hs, U);   // ComputeTransformation
-                // transformation = update * transformation
-                double Tn[16];
-                for (int rr = 0; rr < 4; ++rr)
-                    for (int cc = 0; cc < 4; ++cc)
-                        Tn[4 * rr + cc] = ((U[4 * rr] * T[cc] + U[4 * rr + 1] * T[4 + cc]) + U[4 * rr + 2] * T[8 + cc]) +
-                                          U[4 * rr + 3] * T[12 + cc];
-                std::memcpy(T, Tn, sizeof(T));
-                const double fit0 = fit, rm0 = rm;
-                r = iterate(false, U);   // pcd.Transform(update), the next result
-                if (r != M3D_OK) return r;
-                fit = (double)cnt / (double)n_src;
-                rm = cnt ? std::sqrt(e2 / (double)cnt) : 0.0;
-                if (std::fabs(fit0 - fit) < relative_fitness && std::fabs(rm0 - rm) < relative_rmse) {
-                    ++it;
-                    converged = true;
-                    break;
-                }
-            }
-            std::memcpy(T_out, T, sizeof(T));
-            if (correspondences) {
-                std::vector<uint32_t> hn(n);
-                HIPCHK(hipMemcpy(hn.data(), nn.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-                for (uint32_t i = 0; i < n; ++i) correspondences[i] = hn[i] == 0xFFFFFFFFu ? -1 : (int64_t)hn[i];
-            }
-            if (stats) {
-                stats->fitness = fit;
-                stats->inlier_rmse = rm;
-                stats->correspondences = cnt;
-                stats->iterations = it;
-                stats->converged = converged ? 1 : 0;
-            }
-            return M3D_OK;
-        }();
-        (void)hipStreamSynchronize(ctx->stream);
-        S.release();
-        mx.release(); my.release(); mz.release(); nn.release();
-    }
-    m3d_cloud_destroy_on(csrc);
-    m3d_cloud_destroy_on(cdst);
-    if (stats) stats->ms_total = now_ms() - t_begin;
-    return rc;
-}
-
-extern "C" int m3d_registration_icp_plane(const double* src, size_t n_src, const double* dst, const double* dst_normals,
-                                          size_t n_dst, double max_correspondence_distance, const double* T_init,
-                                          int max_iteration, double relative_fitness, double relative_rmse, int device,
-                                          double* T_out, m3d_icp_stats* stats, int64_t* correspondences) {
+int m3d_registration_icp_plane(const double* src, size_t n_src, const double* dst, const double* dst_normals, size_t n_dst,
+                               double max_correspondence_distance, const double* T_init, int max_iteration,
+                               double relative_fitness, double relative_rmse, int device, double* T_out, m3d_icp_stats* stats,
+                               int64_t* correspondences) {
     return registration_icp_plane_on(nullptr, src, n_src, dst, dst_normals, n_dst, max_correspondence_distance, T_init,
                                      max_iteration, relative_fitness, relative_rmse, device, T_out, stats, correspondences);
 }
 
-// Coloured ICP: the RegistrationICP loop of the plane call with TransformationEstimationForColoredICP (the contract:
-// include/misc3d_amd.h, rules G1 - G7 and C1 - C6).  Before the loop: the target's colour gradients and intensities
-// (color_gradient_on: Hybrid(2 max_correspondence_distance, 30)) and the source's intensities, all resident for the call.  An
-// iteration is launch_icp_colored_iter, one copy of the record and one polled wait; icp_plane_update solves the record.
-int m3d::registration_icp_colored_on(DeviceCtx* held, const double* src, const double* src_colors, size_t n_src, const double* dst,
-                                     const double* dst_normals, const double* dst_colors, size_t n_dst,
-                                     double max_correspondence_distance, double lambda_geometric, const double* T_init,
-                                     int max_iteration, double relative_fitness, double relative_rmse, int device, double* T_out,
-                                     m3d_icp_stats* stats, int64_t* correspondences) {
-    const double t_begin = now_ms();
-    if (!T_out || (!src && n_src) || (!dst && n_dst)) return fail(M3D_ERR_INVALID_ARG, "invalid argument");
-    static const double I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    double T[16];
-    std::memcpy(T, T_init ? T_init : I4, sizeof(T));
-    std::memcpy(T_out, T, sizeof(T));
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if (!(max_correspondence_distance > 0.0))   // Open3D: LogError("Invalid max_correspondence_distance.")
-        return fail(M3D_ERR_INVALID_ARG, "Invalid max_correspondence_distance.");
-    if (!dst_normals)
-        return fail(M3D_ERR_INVALID_ARG,
-                    "TransformationEstimationPointToPlane and TransformationEstimationColoredICP require pre-computed normal "
-                    "vectors for target PointCloud.");
-    if (!src_colors || !dst_colors)
-        return fail(M3D_ERR_INVALID_ARG, "TransformationEstimationForColoredICP requires colors for the source and the target "
-                                         "PointCloud.");
-    if (!(lambda_geometric >= 0.0 && lambda_geometric <= 1.0))
-        return fail(M3D_ERR_INVALID_ARG, "lambda_geometric must be in [0, 1].");
-    if (n_src >= ((size_t)1 << 31) || n_dst >= ((size_t)1 << 31)) return fail(M3D_ERR_INVALID_ARG, "too many points");
-    if (n_src == 0 || n_dst == 0) {   // no correspondences: every update is the identity, fitness 0
-        if (correspondences)
-            for (size_t i = 0; i < n_src; ++i) correspondences[i] = -1;
-        if (stats) {
-            stats->iterations = max_iteration > 0 ? 1 : 0;   // the first repeat already meets both criteria
-            stats->converged = max_iteration > 0;
-        }
-        return M3D_OK;
-    }
-    const double sg = std::sqrt(lambda_geometric), sp = std::sqrt(1.0 - lambda_geometric);
-    std::optional<LaneLock> lane;
-    if (!held) lane.emplace(device);
-    DeviceCtx* ctx = held ? held : lane->ctx;
-    if (!ctx) return M3D_ERR_DEVICE;
-    DevBuf grad, it_dst, is_src, col_src;
-    if (const int rgr = color_gradient_on(ctx, dst, dst_normals, dst_colors, n_dst, 2.0 * max_correspondence_distance, 30, grad,
-                                          it_dst, nullptr);
-        rgr != M3D_OK) {
-        grad.release();
-        it_dst.release();
-        return rgr;
-    }
-    m3d_cloud* csrc = m3d_cloud_create_on(ctx, src, nullptr, n_src, 0);
-    m3d_cloud* cdst = csrc ? m3d_cloud_create_on(ctx, dst, dst_normals, n_dst, 0) : nullptr;
-    if (!csrc || !cdst) {
-        if (csrc) m3d_cloud_destroy_on(csrc);
-        grad.release();
-        it_dst.release();
-        return M3D_ERR_DEVICE;
-    }
-    Scratch S;
-    DevBuf mx, my, mz, nn;
-    int rc;
-    {
-        rc = [&]() -> int {
-            HIPCHK(hipSetDevice(ctx->device));
-            const CloudView sv = csrc->view(), dv = cdst->view();
-            const uint32_t n = sv.n;
-            GridDesc g;
-            const int rg = build_target_grid(ctx, S, dv, dst, n_dst, max_correspondence_distance, true, &g);
-            if (rg != M3D_OK) return rg;
-            RESERVE(mx, sizeof(double) * n);
-            RESERVE(my, sizeof(double) * n);
-            RESERVE(mz, sizeof(double) * n);
-            RESERVE(nn, sizeof(uint32_t) * n);
-            RESERVE(col_src, sizeof(double) * 3 * n_src);
-            RESERVE(is_src, sizeof(double) * n_src);
-            RESERVE(S.sums, sizeof(double) * kIcpPlaneStride);
-            RESERVE(S.partial_sum, sizeof(double) * kIcpPlaneStride * (size_t)icp_plane_blocks(n));
-            RESERVE(S.one_T, sizeof(double) * kRegTStride);
-            RESERVE(ctx->h_small, 512);
-            HIPCHK(hipMemcpyAsync(col_src.p, src_colors, sizeof(double) * 3 * n_src, hipMemcpyHostToDevice, ctx->stream));
-            launch_color_intensity(col_src.as<double>(), n, is_src.as<double>(), ctx->stream);
-            double* px = mx.as<double>();
-            double* py = my.as<double>();
-            double* pz = mz.as<double>();
-            double hs[kIcpPlaneSums];   // the record of the last iteration
-            uint64_t cnt = 0;
-            double e2 = 0.0;
-            auto iterate = [&](bool first, const double* update) -> int {
-                if (update) HIPCHK(hipMemcpyAsync(S.one_T.p, update, sizeof(double) * 12, hipMemcpyHostToDevice, ctx->stream));
-                launch_icp_colored_iter(first ? sv.x : px, first ? sv.y : py, first ? sv.z : pz, n,
-                                        update ? S.one_T.as<double>() : nullptr, px, py, pz, g, S.tgt.start.as<uint32_t>(),
-                                        S.qx.as<double>(), S.qy.as<double>(), S.qz.as<double>(), S.cell_orig.as<uint32_t>(), dv,
-                                        grad.as<double>(), it_dst.as<double>(), is_src.as<double>(), sg, sp, nn.as<uint32_t>(),
-                                        S.partial_sum.as<double>(), S.sums.as<double>(), ctx->stream);
-                uint8_t* h = ctx->h_small.as<uint8_t>();
-                HIPCHK(hipMemcpyAsync(h, S.sums.p, sizeof(hs), hipMemcpyDeviceToHost, ctx->stream));
-                HIPCHK(hipGetLastError());
-                if (const int wr = stream_wait_spin(ctx); wr != M3D_OK) return wr;   // (an iteration's one wait: polled)
-                std::memcpy(hs, h, sizeof(hs));
-                cnt = (uint64_t)hs[0];
-                e2 = hs[1];
-                return M3D_OK;
-            };
-            // pcd = source; if (!init.isIdentity()) pcd.Transform(init)
-            int r = iterate(true, std::memcmp(T, I4, sizeof(T)) != 0 ? T : nullptr);
-            if (r != M3D_OK) return r;
-            double fit = (double)cnt / (double)n_src;
-            double rm = cnt ? std::sqrt(e2 / (double)cnt) : 0.0;
-            int it = 0;
-            bool converged = false;
-            for (; it < max_iteration; ++it) {
-                double U[16];
-                icp_plane_update(hs, U);   // ComputeTransformation: the record has the plane call's layout
-                double Tn[16];
-                for (int rr = 0; rr < 4; ++rr)
-                    for (int cc = 0; cc < 4; ++cc)
-                        Tn[4 * rr + cc] = ((U[4 * rr] * T[cc] + U[4 * rr + 1] * T[4 + cc]) + U[4 * rr + 2] * T[8 + cc]) +
-                                          U[4 * rr + 3] * T[12 + cc];
-                std::memcpy(T, Tn, sizeof(T));
-                const double fit0 = fit, rm0 = rm;
-                r = iterate(false, U);   // pcd.Transform(update), the next result
-                if (r != M3D_OK) return r;
-                fit = (double)cnt / (double)n_src;
-                rm = cnt ? std::sqrt(e2 / (double)cnt) : 0.0;
-                if (std::fabs(fit0 - fit) < relative_fitness && std::fabs(rm0 - rm) < relative_rmse) {
-                    ++it;
-                    converged = true;
-                    break;
-                }
-            }
-            std::memcpy(T_out, T, sizeof(T));
-            if (correspondences) {
-                std::vector<uint32_t> hn(n);
-                HIPCHK(hipMemcpy(hn.data(), nn.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-                for (uint32_t i = 0; i < n; ++i) correspondences[i] = hn[i] == 0xFFFFFFFFu ? -1 : (int64_t)hn[i];
-            }
-            if (stats) {
-                stats->fitness = fit;
-                stats->inlier_rmse = rm;
-                stats->correspondences = cnt;
-                stats->iterations = it;
-                stats->converged = converged ? 1 : 0;
-            }
-            return M3D_OK;
-        }();
-        (void)hipStreamSynchronize(ctx->stream);
-        S.release();
-        for (DevBuf* b : {&mx, &my, &mz, &nn, &grad, &it_dst, &is_src, &col_src}) b->release();
-    }
-    m3d_cloud_destroy_on(csrc);
-    m3d_cloud_destroy_on(cdst);
-    if (stats) stats->ms_total = now_ms() - t_begin;
-    return rc;
-}
-
-extern "C" int m3d_registration_icp_colored(const double* src, const double* src_colors, size_t n_src, const double* dst,
-                                            const double* dst_normals, const double* dst_colors, size_t n_dst,
-                                            double max_correspondence_distance, double lambda_geometric, const double* T_init,
-                                            int max_iteration, double relative_fitness, double relative_rmse, int device,
-                                            double* T_out, m3d_icp_stats* stats, int64_t* correspondences) {
+int m3d_registration_icp_colored(const double* src, const double* src_colors, size_t n_src, const double* dst,
+                                 const double* dst_normals, const double* dst_colors, size_t n_dst,
+                                 double max_correspondence_distance, double lambda_geometric, const double* T_init,
+                                 int max_iteration, double relative_fitness, double relative_rmse, int device, double* T_out,
+                                 m3d_icp_stats* stats, int64_t* correspondences) {
     return registration_icp_colored_on(nullptr, src, src_colors, n_src, dst, dst_normals, dst_colors, n_dst,
                                        max_correspondence_distance, lambda_geometric, T_init, max_iteration, relative_fitness,
                                        relative_rmse, device, T_out, stats, correspondences);
 }
 
-extern "C" {
 // open3d::pipelines::registration::GetInformationMatrixFromPointClouds(source, target, max_dist, T): what
 // ReconstructionPipeline::GlobalRegistration (src/pipeline.cpp:818-824) uses to accept or reject the RANSAC
 // pose (info(5,5) / min(Ns, Nt) < 0.3 -> reject); SURVEY.md 8(f) N2.  info(5,5) is the correspondence count
@@ -1615,7 +1463,7 @@ int m3d_information_matrix(const double* src, size_t n_src, const double* dst, s
     if (!info || !T || (!src && n_src) || (!dst && n_dst)) return fail(M3D_ERR_INVALID_ARG, "invalid argument");
     for (int k = 0; k < 36; ++k) info[k] = 0.0;
     if (n_correspondences) *n_correspondences = 0;
-    if (!(max_correspondence_distance > 0.0)) return fail(M3D_ERR_INVALID_ARG, "Invalid max_correspondence_distance.");
+    if (!(max_correspondence_distance > 0.0)) return fail(M3D_ERR_INVALID_ARG, kIcpInvalidDistance);
     if (n_src >= ((size_t)1 << 31) || n_dst >= ((size_t)1 << 31)) return fail(M3D_ERR_INVALID_ARG, "too many points");
     if (n_src == 0 || n_dst == 0) return M3D_OK;
     LaneLock lane(device);

@@ -196,11 +196,8 @@ CASES = iu.CASES
 
 
 def sized_case(n_src, max_iteration=3):
-    """the iteration kernel's seams: n_src moving points (the first rows of a pair of n_src + 40), at most 3 iterations"""
-    p = iu.icp_pair(n_src + 40, seed=40 + n_src % 7)
-    c = dict(src=np.ascontiguousarray(p["src"][:n_src]), dst=p["dst"], dst_normals=p["dst_normals"], T=p["T"],
-             max_dist=0.08 if n_src < 1000 else 0.02, init=iu.offset_pose(p["T"], 0.5, (0.004, -0.002, 0.003)),
-             max_iteration=max_iteration)
+    """the coloured twin of iu.sized_case(n_src): the iteration kernel's seams"""
+    c = iu.sized_case(n_src, max_iteration)
     c["src_colors"], c["dst_colors"] = colors_of(c)
     return c
 

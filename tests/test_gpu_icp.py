@@ -2,8 +2,9 @@
 (tests/cpp/icp_ref.c, levels from tests/cpp/voxel_ref.c): iteration counts, correspondence arrays and fitness equal,
 inlier_rmse to rel 1e-9, poses to atol 1e-9 (the project's n-point bar) -- point-to-point through the same
 reference file; run-to-run and thread-to-thread bit equality; the multi-scale call against the reference and, bit for bit,
-against the same levels composed from the public calls; the Python API and the C++ mirror.  tests/test_icp.py guards
-every input used here: the order of the reference's sums decides nothing on it."""
+against the same levels composed from the public calls; the Python API and the C++ mirror; the plane kernel at the
+workgroup seams, against the numpy restatement.  tests/test_icp.py guards every input used here (the seam test its own): the
+order of the reference's sums decides nothing on it."""
 import os
 import subprocess
 import threading
@@ -79,6 +80,24 @@ def test_point_to_plane_matches_the_reference(dev, ref, name):
 def test_point_to_point_matches_the_same_reference(dev, ref, name):
     c = iu.case(name)
     _check(_run(dev, c, False), ref.icp(c["src"], c["dst"], c["max_dist"], c["init"], c["max_iteration"], None))
+
+
+@pytest.mark.parametrize("n", [255, 256, 257, 16385])
+def test_plane_iteration_kernel_workgroup_seams(dev, ref, n):
+    """the workgroup edge (255, 256, 257 moving points) and 65 workgroup records (the 64-stride edge of the final launch) of
+    the frame the plane kernel shares with the coloured one (tests/test_gpu_colored_icp.py runs the same sizes), against the
+    numpy restatement; the input is guarded here: the plain-C restatement agrees with it and, summed in descending order, with
+    itself"""
+    c = iu.sized_case(n)
+    assert c["max_iteration"] <= 3 and len(c["src"]) == n
+    args = (c["src"], c["dst"], c["max_dist"], c["init"], c["max_iteration"], c["dst_normals"])
+    with np.errstate(invalid="ignore"):
+        exp = iu.icp_numpy(*args)
+    up, down = ref.icp(*args, order=1), ref.icp(*args, order=-1)
+    for r in (up, down):
+        assert r["iterations"] == exp["iterations"] and np.array_equal(r["corr"], exp["corr"])
+    assert exp["correspondences"] > 0.9 * n
+    _check(_run(dev, c, True), exp)
 
 
 def test_deterministic_alone_and_from_two_threads(dev):
