@@ -57,6 +57,22 @@ int m3d_bench_last_segment_ms(double out[6]);
 int m3d_bench_reg_checkers(const double *ps, const double *pd, const double *T, double edge_threshold,
                            double distance_threshold);
 
+/* TEST hook (tests/test_gpu_reg_sums.py): the 18 sums m3d_kabsch reads back for n point pairs (n x 3 row-major doubles each),
+ * from the upload, launch and read-back m3d_kabsch itself makes -- out[0..2] / [3..5] = the coordinate sums of src / dst,
+ * out[6 + 3 r + c] = sum (dst_r - mean dst_r)(src_c - mean src_c), out[15..17] = sum (src_k - mean src_k)^2, the means being the
+ * kernels' own (coordinate sum * (1 / n)).  Arguments are checked as m3d_kabsch checks them (n >= 3). */
+int m3d_bench_kabsch_sums(const double *src, const double *dst, size_t n, int device, double out[18]);
+
+/* TEST hook (tests/test_gpu_reg_sums.py): ONE evaluation of the point-to-point ICP step under the pose T (4 x 4 row-major), by
+ * the launches m3d_registration_icp and m3d_information_matrix make on the target grid m3d_registration_icp builds: the source
+ * moved by T, its nearest target points within max_correspondence_distance, then out[0] = the sum of their squared distances,
+ * out[1] = their number, out[2..19] = the 18 sums of the next update over the correspondence set (laid out as in
+ * m3d_bench_kabsch_sums, means = coordinate sum * (1 / out[1])), out[20..28] = the moments of the matched target points
+ * (x y z xx yy zz xy xz yz); corr (may be NULL): n_src entries, the target index of source point i or -1.  An empty cloud:
+ * all zeros, every corr -1. */
+int m3d_bench_icp_sums(const double *src, size_t n_src, const double *dst, size_t n_dst, double max_correspondence_distance,
+                       const double *T, int device, double out[29], int64_t *corr);
+
 /* 1: the library was built with -DM3D_EXPERIMENTAL -- round 4's three refuted variants (score_mfma_k, score_screen4_k,
  * compact_write_k<.., ONE>) are compiled in and m3d_config.score_mfma / score_waves4 / compact_one_pass switch them on;
  * 0 (the product build): those switches are ignored and m3d_bench_mfma_probe returns an error. */

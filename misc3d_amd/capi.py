@@ -141,6 +141,9 @@ def lib():
                                                   C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p]
         L.m3d_kabsch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
+        L.m3d_bench_kabsch_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        L.m3d_bench_icp_sums.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p, C.c_int,
+                                         C.c_void_p, C.c_void_p]
         L.m3d_registration_ransac.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                               C.c_void_p, C.c_size_t, C.c_double, C.c_int, C.c_double, C.c_double,
                                               C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
@@ -1003,6 +1006,32 @@ def kabsch(src, dst, scaling=False, device=0):
     T = np.zeros(16)
     _check(lib().m3d_kabsch(_p(src), _p(dst), len(src), int(bool(scaling)), device, _p(T)))
     return T.reshape(4, 4)
+
+
+def kabsch_sums(src, dst, device=0):
+    """test hook m3d_bench_kabsch_sums -> the 18 sums m3d_kabsch reads back (6 coordinate sums, 9 covariance sums d s^T,
+    3 squared sums of s, the last twelve about the kernels' own means)"""
+    src = _f64(src).reshape(-1, 3)
+    dst = _f64(dst).reshape(-1, 3)
+    if len(src) != len(dst):
+        raise M3DError(ERR_SIZE_MISMATCH, "The number of points pair is not equal.")
+    out = np.zeros(18)
+    _check(lib().m3d_bench_kabsch_sums(_p(src), _p(dst), len(src), device, _p(out)))
+    return out
+
+
+def icp_sums(src, dst, max_correspondence_distance, T, device=0):
+    """test hook m3d_bench_icp_sums: one evaluation of the point-to-point ICP step under T -> (out, corr): out[0] = error sum,
+    out[1] = count, out[2:20] = the 18 sums of the update, out[20:29] = the moments of the matched target points; corr[i] =
+    target index of source point i or -1"""
+    src = _f64(src).reshape(-1, 3)
+    dst = _f64(dst).reshape(-1, 3)
+    Tm = _f64(T).reshape(16).copy()
+    out = np.zeros(29)
+    corr = np.zeros(max(len(src), 1), dtype=np.int64)
+    _check(lib().m3d_bench_icp_sums(_p(src), len(src), _p(dst), len(dst), float(max_correspondence_distance), _p(Tm), device,
+                                    _p(out), _p(corr)))
+    return out, corr[: len(src)]
 
 
 def registration_ransac(src, dst, corr_src, corr_dst, threshold=0.01, max_iter=100000, edge_length_threshold=0.9,

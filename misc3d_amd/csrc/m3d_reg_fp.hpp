@@ -137,6 +137,20 @@ M3D_HD void umeyama_assemble(const double* ms, const double* md, const double* s
     T[15] = 1.0;
 }
 
+// Eigen::umeyama from the 18 sums over n correspondences (launch_kabsch_sums / launch_icp_sums: 6 coordinate sums, 9 covariance
+// sums d s^T and 3 squared sums of s about the means): means, sigma = (1/n) sum d s^T, src_var = (1/n) sum |s|^2.
+M3D_HD void umeyama_from_sums(const double* h, double n, bool with_scaling, double* T) {
+    const double one_over_n = 1.0 / n;
+    double ms[3], md[3], sig[9];
+    for (int k = 0; k < 3; ++k) {
+        ms[k] = h[k] * one_over_n;
+        md[k] = h[3 + k] * one_over_n;
+    }
+    for (int k = 0; k < 9; ++k) sig[k] = h[6 + k] * one_over_n;
+    const double src_var = ((h[15] + h[16]) + h[17]) * one_over_n;
+    umeyama_assemble(ms, md, sig, src_var, with_scaling, T);
+}
+
 // Eigen::umeyama on three correspondences, sums in index order (Open3D
 // TransformationEstimationPointToPoint::ComputeTransformation with ransac_n = 3).
 M3D_HD void umeyama3(const double* ps, const double* pd, double* T) {

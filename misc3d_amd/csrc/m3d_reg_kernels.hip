@@ -1446,8 +1446,9 @@ void launch_icp_err(const double* d2, uint32_t n, double r2, double* partial, do
 }
 
 // Eigen::umeyama sums over the correspondence set (moving point i, target point nn[i]): PASS 0 = the six
-// coordinate sums, PASS 1 = covariance d s^T (9) and |s|^2 (3) about the means.  Order-free tree sums (the
-// n-point Kabsch parity bar is 1e-9).
+// coordinate sums, PASS 1 = covariance d s^T (9) and |s|^2 (3) about the means.  Order-free tree sums: a term passes through
+// at most D = ceil(n / 65536) + 16 additions after its 3 roundings, so |sum - exact| <= (D + 3) 2^-53 sum |t_i| + m |dmean_d|
+// |dmean_s| to first order ("The registration sums and their bound"; held at twice that by tests/test_gpu_reg_sums.py).
 template <int PASS>
 __global__ __launch_bounds__(256) void icp_sums_k(const double* __restrict__ px, const double* __restrict__ py,
                                                    const double* __restrict__ pz, uint32_t n, CloudView dst,

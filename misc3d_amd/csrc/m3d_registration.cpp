@@ -257,12 +257,10 @@ int corr_inlier_ratio(RegCtx& rc, const double* T_dev, double* ratio) {
     return M3D_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int m3d_kabsch(const double* src, const double* dst, size_t n, int scaling, int device, double* T) {
-    if (!T || ((!src || !dst) && n)) return fail(M3D_ERR_INVALID_ARG, "invalid argument");
+// The 18 sums of launch_kabsch_sums for n point pairs in the caller's memory: the checks on (src, dst, n), upload, launch and
+// read-back of m3d_kabsch -- and of m3d_bench_kabsch_sums, which returns them as they are.
+int kabsch_sums_of(const double* src, const double* dst, size_t n, int device, double h[18]) {
+    if ((!src || !dst) && n) return fail(M3D_ERR_INVALID_ARG, "invalid argument");
     if (n < 3)  // CheckValid, transform_estimation.cpp:27-31
         return fail(M3D_ERR_TOO_FEW_POINTS, "The number of points pair is less than 3.");
     if (n >= ((size_t)1 << 31)) return fail(M3D_ERR_INVALID_ARG, "too many points");
@@ -271,7 +269,6 @@ int m3d_kabsch(const double* src, const double* dst, size_t n, int scaling, int 
     if (!ctx) return M3D_ERR_DEVICE;
     HIPCHK(hipSetDevice(ctx->device));
     DevBuf ds, dd, partial, sums;
-    int rc = M3D_OK;
     auto done = [&](int r) {
         ds.release(); dd.release(); partial.release(); sums.release();
         return r;
@@ -290,19 +287,26 @@ int m3d_kabsch(const double* src, const double* dst, size_t n, int scaling, int 
              hipGetLastError() == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
     }
     if (!ok) return done(fail(M3D_ERR_DEVICE, "m3d_kabsch: HIP error"));
+    std::memcpy(h, ctx->h_small.p, sizeof(double) * 18);
+    return done(M3D_OK);
+}
+
+}  // namespace
+
+extern "C" {
+
+int m3d_kabsch(const double* src, const double* dst, size_t n, int scaling, int device, double* T) {
+    if (!T) return fail(M3D_ERR_INVALID_ARG, "invalid argument");
     double h[18];
-    std::memcpy(h, ctx->h_small.p, sizeof(h));
-    // Eigen::umeyama: means, sigma = (1/n) sum d s^T, src_var = (1/n) sum |s|^2
-    const double one_over_n = 1.0 / (double)n;
-    double ms[3], md[3], sig[9];
-    for (int k = 0; k < 3; ++k) {
-        ms[k] = h[k] * one_over_n;
-        md[k] = h[3 + k] * one_over_n;
-    }
-    for (int k = 0; k < 9; ++k) sig[k] = h[6 + k] * one_over_n;
-    const double src_var = ((h[15] + h[16]) + h[17]) * one_over_n;
-    umeyama_assemble(ms, md, sig, src_var, scaling != 0, T);
-    return done(rc);
+    if (const int rc = kabsch_sums_of(src, dst, n, device, h); rc != M3D_OK) return rc;
+    umeyama_from_sums(h, (double)n, scaling != 0, T);
+    return M3D_OK;
+}
+
+// test hook (include/misc3d_amd_bench.h): the sums m3d_kabsch assembles its pose from
+int m3d_bench_kabsch_sums(const double* src, const double* dst, size_t n, int device, double out[18]) {
+    if (!out) return fail(M3D_ERR_INVALID_ARG, "invalid argument");
+    return kabsch_sums_of(src, dst, n, device, out);
 }
 
 }  // extern "C"
@@ -1361,17 +1365,53 @@ int m3d::registration_icp_on(DeviceCtx* held, const double* src, size_t n_src, c
         auto compute_update = [&](double* U) {
             icp_identity4(U);
             if (!f.cnt) return;
-            const double one_over_n = 1.0 / (double)f.cnt;
-            double ms[3], md[3], sig[9];
-            for (int k = 0; k < 3; ++k) {
-                ms[k] = hs[k] * one_over_n;
-                md[k] = hs[3 + k] * one_over_n;
-            }
-            for (int k = 0; k < 9; ++k) sig[k] = hs[6 + k] * one_over_n;
-            const double src_var = ((hs[15] + hs[16]) + hs[17]) * one_over_n;
-            umeyama_assemble(ms, md, sig, src_var, false, U);
+            umeyama_from_sums(hs, (double)f.cnt, false, U);
         };
         return icp_loop(f, a, iterate, compute_update);
+    });
+}
+
+// test hook (include/misc3d_amd_bench.h): one evaluation of the point-to-point step under T -- the call frame, grid and
+// launches of registration_icp_on's iterate, then information_matrix_on's moments of the same correspondence set
+extern "C" int m3d_bench_icp_sums(const double* src, size_t n_src, const double* dst, size_t n_dst,
+                                  double max_correspondence_distance, const double* T, int device, double out[29],
+                                  int64_t* corr) {
+    if (!out || !T) return fail(M3D_ERR_INVALID_ARG, "invalid argument");
+    for (int k = 0; k < 29; ++k) out[k] = 0.0;
+    double T_copy[16];
+    const IcpArgs a{src, dst, T, n_src, n_dst, max_correspondence_distance, 0.0, 0.0, 0, device, T_copy, nullptr, corr};
+    return icp_call(nullptr, a, nullptr, nullptr, icp_nothing_before_upload, [&](IcpFrame& f) -> int {
+        DeviceCtx* ctx = f.ctx;
+        Scratch& S = f.S;
+        const uint32_t n = f.n;
+        DevBuf& d2 = f.extra[0];
+        RESERVE(d2, sizeof(double) * n);
+        RESERVE(S.sums, sizeof(double) * 48);   // [0, 18) the update's sums, [24] error, [25] count, [32, 41) the moments
+        RESERVE(S.partial_sum, sizeof(double) * 256 * 16);
+        RESERVE(S.one_T, sizeof(double) * kRegTStride);
+        RESERVE(ctx->h_small, 512);
+        double* sums = S.sums.as<double>();
+        HIPCHK(hipMemcpyAsync(S.one_T.p, f.T, sizeof(double) * 12, hipMemcpyHostToDevice, ctx->stream));
+        launch_icp_transform(f.sv.x, f.sv.y, f.sv.z, n, S.one_T.as<double>(), f.px, f.py, f.pz, ctx->stream);
+        launch_icp_nn(f.px, f.py, f.pz, n, f.g, S.tgt.start.as<uint32_t>(), S.qx.as<double>(), S.qy.as<double>(),
+                      S.qz.as<double>(), S.cell_orig.as<uint32_t>(), f.nn.as<uint32_t>(), d2.as<double>(), ctx->stream);
+        launch_icp_err(d2.as<double>(), n, f.g.r2, S.partial_sum.as<double>(), sums + 24, ctx->stream);
+        launch_icp_sums(f.px, f.py, f.pz, n, f.dv, f.nn.as<uint32_t>(), sums + 25, S.partial_sum.as<double>(), sums, ctx->stream);
+        launch_info_sums(n, f.dv, f.nn.as<uint32_t>(), S.partial_sum.as<double>(), sums + 32, ctx->stream);
+        double h[41];
+        HIPCHK(hipMemcpyAsync(ctx->h_small.p, S.sums.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        std::memcpy(h, ctx->h_small.p, sizeof(h));
+        std::vector<uint32_t> hn(corr ? n : 0);
+        if (corr) HIPCHK(hipMemcpy(hn.data(), f.nn.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+        out[0] = h[24];
+        out[1] = h[25];
+        for (int k = 0; k < 18; ++k) out[2 + k] = h[k];
+        for (int k = 0; k < 9; ++k) out[20 + k] = h[32 + k];
+        if (corr)
+            for (uint32_t i = 0; i < n; ++i) corr[i] = hn[i] == 0xFFFFFFFFu ? -1 : (int64_t)hn[i];
+        return M3D_OK;
     });
 }
 
