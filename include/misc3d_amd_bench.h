@@ -73,11 +73,6 @@ int m3d_bench_kabsch_sums(const double *src, const double *dst, size_t n, int de
 int m3d_bench_icp_sums(const double *src, size_t n_src, const double *dst, size_t n_dst, double max_correspondence_distance,
                        const double *T, int device, double out[29], int64_t *corr);
 
-/* 1: the library was built with -DM3D_EXPERIMENTAL -- round 4's three refuted variants (score_mfma_k, score_screen4_k,
- * compact_write_k<.., ONE>) are compiled in and m3d_config.score_mfma / score_waves4 / compact_one_pass switch them on;
- * 0 (the product build): those switches are ignored and m3d_bench_mfma_probe returns an error. */
-int m3d_bench_experimental(void);
-
 /* MEASUREMENT / TEST hook (tools/bench_configs.py P1 / P2, tests/test_gpu_fps.py): the device path of every later
  * m3d_farthest_point_sampling in the process -- 0 = by size (the default), M3D_FPS_PATH_SINGLE (n <= 8192),
  * M3D_FPS_PATH_PRUNED, M3D_FPS_PATH_DENSE (the pruned path's steps with no tile skipped: the A/B reference).  The
@@ -111,15 +106,6 @@ int m3d_bench_fpfh_pair_bins(const double *pairs, size_t m, int32_t *bins, doubl
  * later slice did not fit the scale chosen from the first ones and the search was redone whole on the resident matrices,
  * bit 3: the fp32 screen, bit 4: fp64 brute force. */
 unsigned m3d_bench_match_last_path(void);
-
-/* TEST hook (tests/test_gpu_mfma_screen.py): the MFMA screen of the plane scoring (score_mfma_k) on ONE tile -- 512 points
- * xyz (row-major doubles), their box (centre xyz, half extents xyz: every |x - centre| <= half extent), n_h plane records
- * (a, b, c, d, T, 0, 0, 0) -- through the production kernel's own operand builders and the matrix pipe:
- * out_q[h][i] = (u1, u2) = the pipe's T - S and T + S for hypothesis h and point i, unscaled (inside <=> u1 u2 > 0, decided when
- * |u1 u2| >= out_h[h][0]), out_h[h] = (band h on the product, scale Sigma_h, the bound E_p on either u) (h = NaN: the record
- * is not screened), out_off[i] = the fp32 offsets the pipe was fed.  Sizes: out_q n_h x 512 x 2, out_h n_h x 3, out_off 512 x 3. */
-int m3d_bench_mfma_probe(int device, const double *xyz512, const double box[6], double max_abs, const double *records,
-                         size_t n_h, double *out_q, double *out_h, float *out_off);
 
 #ifdef __cplusplus
 }

@@ -33,12 +33,10 @@ void sanitize(m3d_config& c) {
     if (c.score_min_workgroups < 1) c.score_min_workgroups = 8192;
     if (c.dense_workgroups < 1) c.dense_workgroups = 8192;
     if (c.pool_limit_mb < 0) c.pool_limit_mb = 0;
-    if (c.score_mfma_groups < 1 || c.score_mfma_groups > 64) c.score_mfma_groups = 64;
-    if (c.score_waves4_groups < 1 || c.score_waves4_groups > 64) c.score_waves4_groups = 64;
     if (c.score_phases < -1 || c.score_phases == 1 || c.score_phases > 3) c.score_phases = -1;
     if (c.plane_bound < 0 || c.plane_bound > 2) c.plane_bound = 1;
     if (c.cull_fp32 < 0 || c.cull_fp32 > 2) c.cull_fp32 = 1;
-    if (!kExperimentalBuild) c.score_mfma = c.score_waves4 = c.compact_one_pass = 0;   // (not compiled in: m3d_kernels.hpp)
+    c.score_mfma = c.score_mfma_groups = c.score_waves4 = c.score_waves4_groups = c.compact_one_pass = 0;   // (retired slots)
     if (c.lanes < 1 || c.lanes > 8) c.lanes = 4;
     if (c.wait_spin_us < 0) c.wait_spin_us = 500;
     c.prestream = c.prestream != 0;
@@ -73,12 +71,7 @@ void load_env() {
     g_cfg.cull_fp32 = env_is("M3D_CULL_FP32", '0') ? 0 : (env_is("M3D_CULL_FP32", '2') ? 2 : 1);
     g_cfg.reg_fp32_screen = !env_is("M3D_REG_SCREEN", '0');
     g_cfg.sorted_tombstones = !env_is("M3D_TOMBSTONES", '0');
-    g_cfg.score_mfma = env_is("M3D_SCORE_MFMA", '1');
-    g_cfg.score_mfma_groups = (int32_t)env_long("M3D_MFMA_GPB", 64);
-    g_cfg.score_waves4 = env_is("M3D_SCORE_WAVES4", '1');   // C2 0.1059 ms against 0.1020 (one-wave workgroups), C3 equal: off
-    g_cfg.score_waves4_groups = (int32_t)env_long("M3D_WAVES4_GPB", 64);
     g_cfg.score_phases = (int32_t)env_long("M3D_SCORE_PHASES", -1);
-    g_cfg.compact_one_pass = env_is("M3D_COMPACT_ONE_PASS", '1');   // C5 rounds 17.4 against 15.3 ms, C2 step +8 us: off (profiles/r04_compact_one_pass.txt)
     g_cfg.plane_bound = (int32_t)env_long("M3D_PLANE_BOUND", 1);
     g_cfg.lanes = (int32_t)env_long("M3D_LANES", 4);
     g_cfg.wait_spin_us = (int32_t)env_long("M3D_SPIN_US", 500);
@@ -128,12 +121,10 @@ void m3d_get_config(m3d_config* out) {
 }
 int m3d_set_config(const m3d_config* in) {
     if (!in) return m3d::fail(M3D_ERR_INVALID_ARG, "invalid argument");
-    // the three switches of round 4's refuted variants select kernels a product build does not contain (m3d_kernels.hpp): asking
-    // for one is an error, not a silent no-op; their slots stay for the layout of the fields behind them
-    if (!m3d::kExperimentalBuild && (in->score_mfma || in->score_waves4 || in->compact_one_pass))
-        return m3d::fail(M3D_ERR_INVALID_ARG,
-                         "score_mfma / score_waves4 / compact_one_pass: these kernels are compiled with -DM3D_EXPERIMENTAL only "
-                         "(m3d_bench_experimental() == 0)");
+    // the switches of the refuted variants select kernels that were removed: asking for one is an error, not a silent no-op
+    // (VERDICT r5 item 8); their slots stay for the layout of the fields behind them
+    if (in->score_mfma || in->score_waves4 || in->compact_one_pass)
+        return m3d::fail(M3D_ERR_INVALID_ARG, "score_mfma / score_waves4 / compact_one_pass: retired, must be 0 (the variants were removed)");
     m3d::config_store(*in);
     return M3D_OK;
 }

@@ -97,17 +97,6 @@ void launch_score_mask(int kind, const SortedView& s, const double* score, const
                        hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr /* both set: receive the launch's own start / stop
                        times (m3d_stats.ms_score_kernel) */,
                        bool thinned = false /* plane_bound_k has pruned the window: more groups per workgroup */);
-// score_mfma_k (m3d_score_mfma.hip): the same counting with the screen on the matrix pipe -- planes, m3d_config.score_mfma.
-// false: not applicable (another kind, tombstones in the copy, no fp32 tile offsets, switched off), nothing launched;
-// launch_score_mask calls it first.
-bool launch_score_mfma(int kind, const SortedView& s, const double* score, const unsigned long long* masks,
-                       const unsigned long long* keep, uint32_t n_groups, uint32_t* counts_rep, uint32_t rep_stride,
-                       uint32_t* pair_rep, hipStream_t st, uint32_t group_begin, uint32_t group_end, hipEvent_t ev_start,
-                       hipEvent_t ev_stop);
-// test probe of the MFMA screen: one tile (512 x 3 doubles, device), its box (6 doubles, device), n_h plane records ->
-// out_q[n_h][512][2] = (u1, u2) / Sigma_h, out_h[n_h][3] = (h, Sigma_h, E_p), out_off[512][3] = the fp32 offsets
-void launch_mfma_probe(const double* pts, const double* box, double max_abs, const double* recs, uint32_t n_h, double* out_q,
-                       double* out_h, float* out_off, hipStream_t st);
 // cull_lead_k: the box tests of groups [lead_groups, cull_end) and the counting of the leading groups [0, lead_groups) (which
 // run their own box tests) in ONE launch -- the head of a fit's first chunk on one GPU.  keep[0 .. lead_groups) and the
 // counter replicas must be prepared (minimal_fit_k's LeadPrep or keep_mask_k); ub is not written for the leading groups
@@ -122,12 +111,6 @@ bool launch_score_phased(int kind, const SortedView& s, const double* score, con
                          unsigned long long* keep, uint32_t n_groups, uint32_t* counts_rep, uint32_t rep_stride,
                          uint32_t* pair_rep, const uint32_t* ub, const uint32_t* ubp, const uint32_t* best_count, hipStream_t st,
                          uint32_t group_begin, uint32_t group_end, hipEvent_t ev_start, hipEvent_t ev_stop);
-// The chunk's box tests INSIDE its scoring launch (every workgroup tests its tile against its own groups): for chunks that
-// prune nothing (keep all ones).  false: preconditions not met (fp32 box tests / screen off), nothing launched.
-bool launch_score_own_tests(int kind, const SortedView& s, const double* score, const float* cull32, unsigned long long* masks,
-                            const unsigned long long* keep, uint32_t n_groups, uint32_t groups, uint32_t* counts_rep,
-                            uint32_t rep_stride, uint32_t* pair_rep, hipStream_t st, hipEvent_t ev_start = nullptr,
-                            hipEvent_t ev_stop = nullptr);
 // (planes and spheres go through score_screen_k unless m3d_config.score_fp32_screen is 0)
 // The device's prediction of the hypothesis the replay will end with (pick_best_k, m3d_cull_kernels.hip)
 struct BestPick {

@@ -173,7 +173,6 @@ struct DeviceCtx {
     DevBuf moment_partial;     // fused RefineModel: per-workgroup raw moments of the compaction's counting pass
     PinBuf h_moments;          // ... folded (scan_blocks_k), device-visible: kFusedMomentDoubles doubles
     hipEvent_t ev_pre_gate = nullptr;         // recorded on `stream` where a fit starts; pre_stream waits for it (pre_stream_gate)
-    uint32_t compact_epoch = 0;               // launch counter of the compaction scratch (compact_scratch)
     bool compaction_fused = false;            // the compaction in flight carried the moments
     uint64_t* compaction_idx_host = nullptr;  // ... and wrote the index list to this page-locked destination as well
     // ... or, compaction_mask (m3d_config.list_mask): shipped the inliers as a bit mask + per-tile counts instead, which

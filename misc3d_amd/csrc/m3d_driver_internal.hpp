@@ -50,7 +50,7 @@ int cloud_fit_locked(m3d_cloud* c, int kind, double thr, size_t max_iter, double
                      m3d_comm* comm = nullptr);
 
 // ---- m3d_refine.cpp
-int compact_scratch(DeviceCtx* ctx, uint32_t nb, CompactScratch* out);
+int compact_scratch(DeviceCtx* ctx, uint32_t nb, uint32_t** slots);
 int exact_error(DeviceCtx* ctx, const CloudView& v, int kind, double thr,
                        const double* model_dev, uint64_t* count, double* error);
 int approx_error_pair(DeviceCtx* ctx, const CloudView& v, int kind, double thr, const double* model_a,

@@ -402,18 +402,8 @@ static int issue_chunk(DeviceCtx* ctx, ChunkSlot& s, const CloudView& v, const S
                 s.lead_fused = launch_cull_lead(kind, sv, s.score.as<double>(), c32.out, masks, keep, n_groups, ga,
                                                 ctx->counts_rep.as<uint32_t>(), h_pad, pair_rep, ub, g1, ctx->stream, ubp);
             }
-            // nothing to prune and every group prepared by minimal_fit_k: the box tests run inside the scoring launch
-            bool scored_with_own_tests = false;
-            // (Round 6: OFF.  Fusing the box tests into the scoring launch paid in round 3, when cull_tiles32_k was 9 us of dependent
-            //  scalar loads; since round 5's staged records the two launches are the faster way round again -- C5's 165 clutter rounds
-            //  15.1 against 16.1 ms.  And the other direction is closed as well: ALL of a tile's groups in one scoring workgroup
-            //   -- with its own box tests 22.0 ms, behind precomputed masks 21.6 ms: 1528 one-wave workgroups leave
-            //  every wave's chain of dependent loads exposed, 12 228 of them hide it.  profiles/r06_c5_tail_rounds.txt)
-            constexpr bool kScoreWithOwnTests = false;
-            if (kScoreWithOwnTests && all_prepared && c32.out)
-                scored_with_own_tests = launch_score_own_tests(kind, sv, s.score.as<double>(), c32.out, masks, keep, n_groups, g1,
-                                                               ctx->counts_rep.as<uint32_t>(), h_pad, pair_rep, ctx->stream,
-                                                               timing ? s.k0 : nullptr, timing ? s.k1 : nullptr);
+            // (Tried and removed: the chunk's box tests inside the scoring launch, and all of a tile's groups in one scoring
+            //  workgroup -- both slower on C5's clutter rounds, profiles/r06_c5_tail_rounds.txt.)
             // planes with an incumbent and tile frames: a histogram upper bound per touched (tile, hypothesis) pair replaces
             // "512 per touched tile" in the keep rule (m3d_bound.hip).  The keep kernels below hand plane_bound_k the kept
             // hypotheses as a list (its length: word 6 of best_count); ubsum is the slot's phase-counter array, zeroed by
@@ -424,7 +414,7 @@ static int issue_chunk(DeviceCtx* ctx, ChunkSlot& s, const CloudView& v, const S
             // launch costs what it saves; theirs runs when the bound is forced, m3d_config.plane_bound = 2, i.e. in the tests.)
             const bool bound_on = (kind == M3D_CYLINDER || !ubp) && prune && bc && sv.frames && config().plane_bound != 0 &&
                                   (config().plane_bound == 2 || (kind != M3D_SPHERE && bound_pays(sv.n_tiles, comm ? sl_pad : count))) &&
-                                  (use_lead || !new_fit) && !scored_with_own_tests && std::max(g0, ga) < g1;
+                                  (use_lead || !new_fit) && std::max(g0, ga) < g1;
             uint32_t* const ubsum = ubp ? ub + 2 * (size_t)h_pad : ub + h_pad;
             if (bound_on) {
                 const int src = reserve_survivor_scratch(ctx, h_pad);
@@ -437,11 +427,11 @@ static int issue_chunk(DeviceCtx* ctx, ChunkSlot& s, const CloudView& v, const S
             // plane_bound_k reads instead of repeating the tests
             unsigned long long* touched = nullptr;
             bool touched_written = false;
-            if (bound_on && kind == M3D_CYLINDER && c32.out && !s.lead_fused && !scored_with_own_tests && !(ga && g0 >= ga) && g1 - g0 >= 128u) {
+            if (bound_on && kind == M3D_CYLINDER && c32.out && !s.lead_fused && !(ga && g0 >= ga) && g1 - g0 >= 128u) {
                 RESERVE(s.touched, sizeof(uint64_t) * (size_t)((sv.n_tiles + 63u) / 64u) * h_pad);
                 touched = s.touched.as<unsigned long long>();
             }
-            if (!s.lead_fused && !scored_with_own_tests) {
+            if (!s.lead_fused) {
                 if (ga && g0 >= ga)   // (rank > 0: the lead is somebody else's slice)
                     launch_cull_mask(kind, sv, s.score.as<double>(), s.valid.as<uint8_t>(), count, n_groups, masks, ub,
                                      ctx->stream, /*ub_is_zero=*/true, 0, ga, c32.out);
@@ -475,10 +465,10 @@ static int issue_chunk(DeviceCtx* ctx, ChunkSlot& s, const CloudView& v, const S
                                    bound_tickets(ctx), c32.out, ctx->stream, config().plane_bound == 2,
                                    touched_written && g_lo == g0 ? touched : nullptr, h_pad);
             bool phased = false;
-            if (!scored_with_own_tests && ubp)
+            if (ubp)
                 phased = launch_score_phased(kind, sv, s.score.as<double>(), masks, keep, n_groups, ctx->counts_rep.as<uint32_t>(), h_pad,
                                              pair_rep, ub, ubp, bc, ctx->stream, g_lo, g1, timing ? s.k0 : nullptr, timing ? s.k1 : nullptr);
-            if (!scored_with_own_tests && !phased)
+            if (!phased)
                 launch_score_mask(kind, sv, s.score.as<double>(), masks, keep, n_groups, ctx->counts_rep.as<uint32_t>(), h_pad,
                                   pair_rep, ctx->stream, g_lo, g1, timing ? s.k0 : nullptr, timing ? s.k1 : nullptr, bound_on);
             // one launch: fold the counter replicas, tag MinimalFit's return into bit 31, update the incumbent
@@ -626,8 +616,6 @@ static void unpack_slot(ChunkSlot& s) {
     }
 }
 
-// Scratch of launch_compact (m3d_kernels.hpp, CompactScratch): one slot per compaction workgroup, zero when the buffer is
-// (re)allocated and when the epoch counter starts over; every launch gets the next epoch.
 // ------------------------------------------------------------------------------------------------
 // RANSAC::FitModelParallel on a resident view.  Leaves the best minimal model in
 // device memory at ctx->last_best_dev; RefineModel's first kernel forwards it to ctx->h_best (pinned host).

@@ -611,41 +611,24 @@ __device__ __forceinline__ void fold_moment_partials(const CompactTail& tail) {
     }
 }
 
-// ONE = true: the counting pass rides in THIS launch (compact_count_k and its launch tail are gone).  A workgroup classifies
-// its tile, PUBLISHES the count in slots[tile] -- tagged with the launch's epoch (host counter, `tag`), the count in the low 12
-// bits -- and waits for the tagged counts of the tiles below it while it sums them: the tiles of a launch classify at the
-// same time, a tile's wait ends with the slowest of the tiles below it, and nothing a workgroup waits for waits for a higher
-// tile.  The launcher uses this form only while EVERY workgroup of the launch is resident at once (kCompactOnePassMaxTiles),
-// so no assumption about the dispatch order is made.  No ticket either: a same-address atomic per workgroup costs ~30 ns,
-// serialised -- 489 of them cost more than the launch they replace (measured: the first form of this kernel, with a tile
-// ticket and a completion ticket, made the C2 step 28 us SLOWER).  SUMS: a tile's moment partial is written (and released)
-// BEFORE its count, so the last tile, once it has seen every count, folds the partials -- in compact_count_k<.., true>'s
-// order: the same sums.  The output is the two-pass output, position for position.
-// MEASURED (profiles/r04_compact_one_pass.txt): slower than the two launches -- a segmentation round on ~1 M points 101 us
-// against 89, the C2 step +8 us: a published count reaches the other XCDs through memory, and the ~490 workgroups' waits for
-// it cost more than the ~5 us launch boundary.  Compiled with -DM3D_EXPERIMENTAL only (then m3d_config.compact_one_pass switches it on).
-// ONE = false: `slots` holds compact_count_k's raw counts (m3d_config.compact_one_pass = 0, or more tiles than fit the chip).
-template <int KIND, int MODE, bool ONE, bool SUMS>
+// The writing pass: `slots` holds compact_count_k's counts, one per tile of kCompactTile points.  (The two passes as ONE launch --
+// counts published and awaited inside it -- were measured slower and removed: profiles/r04_compact_one_pass.txt.)
+template <int KIND, int MODE>
 __global__ __launch_bounds__(256) void compact_write_k(
     CloudView c, const double* __restrict__ model, double thr, const uint32_t* __restrict__ orig,
-    uint32_t* __restrict__ slots, uint32_t tag, uint64_t* __restrict__ out_idx,
+    uint32_t* __restrict__ slots, uint64_t* __restrict__ out_idx,
     double* __restrict__ out_dist, double* __restrict__ ox, double* __restrict__ oy,
     double* __restrict__ oz, uint32_t* __restrict__ oorig, uint32_t n_pad_cap,
     uint64_t* __restrict__ out_idx_host /* MODE 0 / 4: the caller's page-locked index list, written as well (may be null) */,
-    CompactTail tail, double* __restrict__ model_copy, double* moment_partial) {
-    static_assert(!SUMS || (ONE && KIND != 2 && (MODE == 0 || MODE == 4)), "the moments ride in a one-pass inlier compaction");
-    static_assert(kCompactTile < (1 << 12), "a tile's count shares its slot with the epoch tag");
+    CompactTail tail) {
     __shared__ uint32_t wsum[4];
-    constexpr uint32_t kCountMask = 0xFFFu;
     const uint32_t tile = blockIdx.x;
-    constexpr int NM = ONE ? kModelStride : 7;
+    constexpr int NM = 7;
     double m[NM];
     for (int k = 0; k < NM; ++k) m[k] = model[k];
-    // the model record (8 doubles) also goes where the caller wants a copy (pinned host memory): no copy command
-    if (ONE && model_copy && tile == 0 && threadIdx.x < kModelStride) model_copy[threadIdx.x] = model[threadIdx.x];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // ONE = false: workgroup 0 also folds RefineModel's moment partials
-    if (!ONE && tail.moment_partial && blockIdx.x == 0) fold_moment_partials(tail);   // (workgroup-uniform)
+    // workgroup 0 also folds RefineModel's moment partials
+    if (tail.moment_partial && blockIdx.x == 0) fold_moment_partials(tail);   // (workgroup-uniform)
     const uint32_t base = tile * kCompactTile;
     // All of the workgroup's rows are loaded and classified FIRST (8 rows x 3 coordinates in flight per thread), the
     // per-row wave counts meet in LDS behind ONE barrier, then every row is written.  (A barrier per row serialised
@@ -664,12 +647,6 @@ __global__ __launch_bounds__(256) void compact_write_k(
         pz[r] = in ? c.z[i] : 0.0;
         og[r] = (MODE == 0 || MODE == 2 || MODE == 4) ? (in && orig ? orig[i] : i) : 0u;
     }
-    // SUMS: GeneralFit's raw moments over the inliers (compact_count_k<.., true>: the same expressions, the same per-thread
-    // row order, the same tree)
-    constexpr int NV = SUMS ? (KIND == 1 ? 12 : 9) : 1;
-    double acc[NV];
-    for (int k = 0; k < NV; ++k) acc[k] = 0.0;
-    const double c0x = SUMS ? m[4] : 0.0, c0y = SUMS ? m[5] : 0.0, c0z = SUMS ? m[6] : 0.0;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const uint32_t i = base + r * 256 + threadIdx.x;
@@ -680,24 +657,6 @@ __global__ __launch_bounds__(256) void compact_write_k(
         // f: what modes 0 / 1 / 4 list (the inliers) resp. what modes 2 / 3 keep (the rest); g (mode 4): the rest
         // (mode 3, the sorted copy: its dead points -- x = NaN, poison_plane_inliers_k -- are dropped with the inliers)
         const bool f = MODE == 3 ? (in && !inl && px[r] == px[r]) : (MODE == 2 ? (in && !inl) : inl);
-        if (SUMS && f) {
-            const double sx = px[r] - c0x, sy = py[r] - c0y, sz = pz[r] - c0z;
-            acc[0] += sx;
-            acc[1] += sy;
-            acc[2] += sz;
-            acc[3] += sx * sx;
-            acc[4] += sx * sy;
-            acc[5] += sx * sz;
-            acc[6] += sy * sy;
-            acc[7] += sy * sz;
-            acc[8] += sz * sz;
-            if (KIND == 1) {
-                const double q = (sx * sx + sy * sy) + sz * sz;
-                acc[9] += sx * q;
-                acc[10] += sy * q;
-                acc[11] += sz * q;
-            }
-        }
         bf[r] = __ballot(f);
         if (MODE == 4) bg[r] = __ballot(in && !inl);
         if (lane == 0) {
@@ -710,44 +669,8 @@ __global__ __launch_bounds__(256) void compact_write_k(
     // workgroups at once, against a one-workgroup scan kernel and its launch gap (7 us) between two passes.
     uint32_t row_base;
     {
-        if (SUMS) {   // the tile's moment partial, out before its count
-            __shared__ double sm[NV * 256];
-            block_tree_reduce<NV>(acc, sm);
-            if (threadIdx.x < 12) {
-                moment_partial[(size_t)tile * 16 + threadIdx.x] = (int)threadIdx.x < NV ? sm[threadIdx.x * 256] : 0.0;
-                __threadfence();   // (release / acquire at agent scope around the count: the partials cross L2s, error_sum_k)
-            }
-            __syncthreads();
-        }
-        if (ONE && threadIdx.x == 0) {
-            uint32_t mine = 0;
-#pragma unroll
-            for (int r = 0; r < R; ++r) mine += (wf[r][0] + wf[r][1]) + (wf[r][2] + wf[r][3]);
-            __hip_atomic_store(slots + tile, tag | mine, SUMS ? __ATOMIC_RELEASE : __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
         uint32_t part = 0;
-        if (ONE) {
-            // every thread asks for ALL its slots first (kCompactOnePassMaxTiles / 256 of them), then goes back to the ones
-            // that were not out yet
-            constexpr int kMine = (kCompactOnePassMaxTiles + 255) / 256;
-            uint32_t v[kMine];
-#pragma unroll
-            for (int k = 0; k < kMine; ++k) {
-                const uint32_t i = threadIdx.x + 256u * (uint32_t)k;
-                v[k] = i < tile ? __hip_atomic_load(slots + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : tag;
-            }
-#pragma unroll
-            for (int k = 0; k < kMine; ++k) {
-                const uint32_t i = threadIdx.x + 256u * (uint32_t)k;
-                while ((v[k] & ~kCountMask) != tag) {
-                    __builtin_amdgcn_s_sleep(1);
-                    v[k] = __hip_atomic_load(slots + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                part += v[k] & kCountMask;
-            }
-        } else {
-            for (uint32_t i = threadIdx.x; i < tile; i += 256u) part += slots[i];
-        }
+        for (uint32_t i = threadIdx.x; i < tile; i += 256u) part += slots[i];
         part = wave_sum(part);
         if (lane == 0) wsum[wave] = part;
         __syncthreads();
@@ -798,10 +721,6 @@ __global__ __launch_bounds__(256) void compact_write_k(
             oz[i] = nan;
         }
     }
-    if (SUMS && tile == gridDim.x - 1) {   // (workgroup-uniform) every count has been seen: every partial is out
-        __threadfence();
-        fold_moment_partials(tail);
-    }
 }
 
 // The mask form's second launch (one workgroup): what compact_write_k's workgroup 0 and last tile delivered -- the folded
@@ -839,7 +758,7 @@ template <int KIND>
 static void launch_compact_kind(const CloudView& c, const double* model, double thr, int mode,
                                 const uint32_t* orig, uint64_t* out_idx, double* out_dist,
                                 double* ox, double* oy, double* oz, uint32_t* oorig,
-                                uint32_t n_pad_out, const CompactScratch& scratch, uint32_t* total,
+                                uint32_t n_pad_out, uint32_t* block_counts, uint32_t* total,
                                 hipStream_t s, double* model_copy, double* moment_partial, double* moment_out,
                                 uint64_t* out_idx_host, uint32_t* total_host, const PartitionOut* part,
                                 uint64_t* mask_host, uint32_t* counts_host, uint32_t* done_word, uint32_t done_seq,
@@ -853,10 +772,7 @@ static void launch_compact_kind(const CloudView& c, const double* model, double 
         return;
     }
     const bool sums = moment_partial && moment_out && mode == 0 && KIND != 2;
-    const bool one = kExperimentalBuild && config().compact_one_pass != 0 && nb <= kCompactOnePassMaxTiles && scratch.tag != 0u;
-    uint32_t* block_counts = scratch.slots;
-    const uint32_t tag = scratch.tag;
-    if (mask_host && counts_host && sums && !orig && !part && !one) {
+    if (mask_host && counts_host && sums && !orig && !part) {
         // the mask form: no list is written anywhere -- the host expands the mask (m3d_mask_expand.hpp)
         // (ready_word: the counting launch stores the tile counts itself and the tail announces them before anything else)
         compact_count_k<KIND == 2 ? 0 : KIND, true><<<nb, 256, 0, s>>>(c, model, thr, 0, block_counts, model_copy, moment_partial,
@@ -870,12 +786,10 @@ static void launch_compact_kind(const CloudView& c, const double* model, double 
         compact_mask_tail_k<<<1, 256, 0, s>>>(block_counts, tail, ready_word ? nullptr : counts_host, ready_word, done_word, done_seq);
         return;
     }
-    if (!one) {
-        if (sums)
-            compact_count_k<KIND == 2 ? 0 : KIND, true><<<nb, 256, 0, s>>>(c, model, thr, 0, block_counts, model_copy, moment_partial);
-        else
-            compact_count_k<KIND, false><<<nb, 256, 0, s>>>(c, model, thr, mode == 3 ? 2 : (mode >= 2 ? 1 : 0), block_counts, model_copy, nullptr);
-    }
+    if (sums)
+        compact_count_k<KIND == 2 ? 0 : KIND, true><<<nb, 256, 0, s>>>(c, model, thr, 0, block_counts, model_copy, moment_partial);
+    else
+        compact_count_k<KIND, false><<<nb, 256, 0, s>>>(c, model, thr, mode == 3 ? 2 : (mode >= 2 ? 1 : 0), block_counts, model_copy, nullptr);
     CompactTail tail;
     tail.total = total;
     tail.total_host = total_host;
@@ -884,55 +798,38 @@ static void launch_compact_kind(const CloudView& c, const double* model, double 
     tail.nb = nb;
     const PartitionOut none;
     const PartitionOut& po = part ? *part : none;
-    constexpr int KS = KIND == 2 ? 0 : KIND;   // (the moments are a plane's or a sphere's: `sums` is false for cylinders)
-#define M3D_COMPACT_GO(MODE_, ONE_, SUMS_, K_, ...) \
-    compact_write_k<K_, MODE_, ONE_, SUMS_><<<nb, 256, 0, s>>>(c, model, thr, __VA_ARGS__, tail, model_copy, moment_partial)
-    // the one-launch forms exist in experimental builds only (kExperimentalBuild: the branch is discarded, not instantiated)
-#define M3D_COMPACT_PICK(MODE_, WITH_SUMS_, ...)                                              \
-    do {                                                                                      \
-        if constexpr (kExperimentalBuild) {                                                   \
-            if constexpr (WITH_SUMS_) {                                                       \
-                if (one && sums) {                                                            \
-                    M3D_COMPACT_GO(MODE_, true, true, KS, __VA_ARGS__);                       \
-                    break;                                                                    \
-                }                                                                             \
-            }                                                                                 \
-            if (one) {                                                                        \
-                M3D_COMPACT_GO(MODE_, true, false, KIND, __VA_ARGS__);                        \
-                break;                                                                        \
-            }                                                                                 \
-        }                                                                                     \
-        M3D_COMPACT_GO(MODE_, false, false, KIND, __VA_ARGS__);                               \
-    } while (0)
     if (mode == 0 && part && orig)
-        M3D_COMPACT_PICK(4, true, orig, block_counts, tag, out_idx, nullptr, po.ox, po.oy, po.oz, po.oorig, po.n_pad_cap, out_idx_host);
+        compact_write_k<KIND, 4><<<nb, 256, 0, s>>>(c, model, thr, orig, block_counts, out_idx, nullptr, po.ox, po.oy, po.oz, po.oorig,
+                                                    po.n_pad_cap, out_idx_host, tail);
     else if (mode == 0)
-        M3D_COMPACT_PICK(0, true, orig, block_counts, tag, out_idx, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, out_idx_host);
+        compact_write_k<KIND, 0><<<nb, 256, 0, s>>>(c, model, thr, orig, block_counts, out_idx, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                    0u, out_idx_host, tail);
     else if (mode == 1)
-        M3D_COMPACT_PICK(1, false, orig, block_counts, tag, nullptr, out_dist, nullptr, nullptr, nullptr, nullptr, 0u, nullptr);
+        compact_write_k<KIND, 1><<<nb, 256, 0, s>>>(c, model, thr, orig, block_counts, nullptr, out_dist, nullptr, nullptr, nullptr, nullptr,
+                                                    0u, nullptr, tail);
     else if (mode == 2)
-        M3D_COMPACT_PICK(2, false, orig, block_counts, tag, nullptr, nullptr, ox, oy, oz, oorig, n_pad_out, nullptr);
+        compact_write_k<KIND, 2><<<nb, 256, 0, s>>>(c, model, thr, orig, block_counts, nullptr, nullptr, ox, oy, oz, oorig, n_pad_out,
+                                                    nullptr, tail);
     else
-        M3D_COMPACT_PICK(3, false, nullptr, block_counts, tag, nullptr, nullptr, ox, oy, oz, nullptr, n_pad_out, nullptr);
-#undef M3D_COMPACT_PICK
-#undef M3D_COMPACT_GO
+        compact_write_k<KIND, 3><<<nb, 256, 0, s>>>(c, model, thr, nullptr, block_counts, nullptr, nullptr, ox, oy, oz, nullptr, n_pad_out,
+                                                    nullptr, tail);
 }
 
 void launch_compact(int kind, const CloudView& c, const double* model, double thr, int mode,
                     const uint32_t* orig, uint64_t* out_idx, double* out_dist, double* ox,
                     double* oy, double* oz, uint32_t* oorig, uint32_t n_pad_out,
-                    const CompactScratch& scratch, uint32_t* total, hipStream_t s, double* model_copy,
+                    uint32_t* block_counts, uint32_t* total, hipStream_t s, double* model_copy,
                     double* moment_partial, double* moment_out, uint64_t* out_idx_host, uint32_t* total_host,
                     const PartitionOut* part, uint64_t* mask_host, uint32_t* counts_host, uint32_t* done_word,
                     uint32_t done_seq, uint32_t* ready_word) {
     if (kind == 0)
-        launch_compact_kind<0>(c, model, thr, mode, orig, out_idx, out_dist, ox, oy, oz, oorig, n_pad_out, scratch, total, s,
+        launch_compact_kind<0>(c, model, thr, mode, orig, out_idx, out_dist, ox, oy, oz, oorig, n_pad_out, block_counts, total, s,
                                model_copy, moment_partial, moment_out, out_idx_host, total_host, part, mask_host, counts_host, done_word, done_seq, ready_word);
     else if (kind == 1)
-        launch_compact_kind<1>(c, model, thr, mode, orig, out_idx, out_dist, ox, oy, oz, oorig, n_pad_out, scratch, total, s,
+        launch_compact_kind<1>(c, model, thr, mode, orig, out_idx, out_dist, ox, oy, oz, oorig, n_pad_out, block_counts, total, s,
                                model_copy, moment_partial, moment_out, out_idx_host, total_host, part, mask_host, counts_host, done_word, done_seq, ready_word);
     else
-        launch_compact_kind<2>(c, model, thr, mode, orig, out_idx, out_dist, ox, oy, oz, oorig, n_pad_out, scratch, total, s,
+        launch_compact_kind<2>(c, model, thr, mode, orig, out_idx, out_dist, ox, oy, oz, oorig, n_pad_out, block_counts, total, s,
                                model_copy, nullptr, nullptr, out_idx_host, total_host, part, nullptr, nullptr, nullptr, 0u, nullptr);
 }
 

@@ -13,17 +13,6 @@ constexpr int kScoreBlock = 256;    // threads per scoring workgroup (4 waves)
 constexpr int kScoreTile = kScoreBlock * kScoreP;  // points per scoring workgroup
 constexpr int kCompactTile = 2048;  // points per compaction workgroup
 
-// -DM3D_EXPERIMENTAL (make DEFS=-DM3D_EXPERIMENTAL): the three variants round 4 built, measured and refuted are compiled in
-// and m3d_config.score_mfma / score_waves4 / compact_one_pass switch them on -- score_mfma_k (m3d_score_mfma.hip: the planes'
-// screen on the matrix pipe, profiles/r04_score_mfma.txt), score_screen4_k (four-wave scoring workgroups,
-// profiles/r04_score_waves4.txt), compact_write_k<.., ONE> (the ordered compaction as one launch,
-// profiles/r04_compact_one_pass.txt).  The product library is built without them: the three switches are then ignored.
-#ifdef M3D_EXPERIMENTAL
-constexpr bool kExperimentalBuild = true;
-#else
-constexpr bool kExperimentalBuild = false;
-#endif
-
 // SoA view of a resident cloud.  Arrays are padded to a multiple of kScoreTile with NaN so the
 // scoring kernels need no bounds checks (a NaN coordinate is never an inlier).
 struct CloudView {
@@ -106,17 +95,9 @@ void launch_bbox(const double* x, const double* y, const double* z, uint32_t n, 
 // mode 1: out_dist[k] = distance of the k-th inlier
 // mode 2: stable partition of the NON-inliers into (ox,oy,oz,oorig) (segmentation round)
 // mode 3: the same for coordinates only (the Z-order sorted copy)
-// scratch: one uint32 slot per compaction workgroup (ceil(n / kCompactTile)), ZERO when the buffer is allocated and whenever the
-// owner's epoch counter starts over; tag = the launch's epoch (1 .. 2^20 - 1, a different one for every launch on the buffer) in
-// bits 12..31 -- what the one-pass form marks a published count with (compact_write_k); tag 0: two passes.
+// block_counts: scratch of one uint32 per compaction workgroup (ceil(n / kCompactTile)); the counting pass writes every one of
+// them before the writing pass reads any, so the buffer needs no initial value.
 // total[0] receives the inlier count.
-// The one-pass form needs every workgroup of the launch resident at once: 5 workgroups fit a CU (92 VGPRs, 21 KB of LDS).
-constexpr uint32_t kCompactOnePassMaxTiles = 1024;
-constexpr uint32_t kCompactEpochs = 0xFFFFFu;
-struct CompactScratch {
-    uint32_t* slots = nullptr;
-    uint32_t tag = 0;
-};
 struct PartitionOut {
     double *ox = nullptr, *oy = nullptr, *oz = nullptr;
     uint32_t* oorig = nullptr;
@@ -127,7 +108,7 @@ void launch_gather_points(const CloudView& c, const uint64_t* idx, size_t total,
 void launch_compact(int kind, const CloudView& c, const double* model, double thr, int mode,
                     const uint32_t* orig, uint64_t* out_idx, double* out_dist, double* ox,
                     double* oy, double* oz, uint32_t* oorig, uint32_t n_pad_out,
-                    const CompactScratch& scratch, uint32_t* total, hipStream_t s,
+                    uint32_t* block_counts, uint32_t* total, hipStream_t s,
                     double* model_copy = nullptr /* device-visible (pinned host): receives the 8-double model record */,
                     double* moment_partial = nullptr /* mode 0, plane / sphere: scratch of ceil(n / kCompactTile) x 16 doubles ... */,
                     double* moment_out = nullptr /* ... and kFusedMomentDoubles doubles (device-visible host memory): GeneralFit's raw

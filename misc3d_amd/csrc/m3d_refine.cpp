@@ -148,17 +148,10 @@ private:
 }  // namespace
 
 
-// Scratch of launch_compact (m3d_kernels.hpp, CompactScratch): one slot per compaction workgroup, zero when the buffer is
-// (re)allocated and when the epoch counter starts over; every launch gets the next epoch.
-int compact_scratch(DeviceCtx* ctx, uint32_t nb, CompactScratch* out) {
-    const size_t need = sizeof(uint32_t) * ((size_t)nb + 1);
-    const bool grow = ctx->block_counts.cap < need;
-    if (grow) RESERVE(ctx->block_counts, need);
-    if (ctx->compact_epoch >= kCompactEpochs) ctx->compact_epoch = 0;
-    if (grow || ctx->compact_epoch == 0)
-        HIPCHK(hipMemsetAsync(ctx->block_counts.p, 0, ctx->block_counts.cap, ctx->stream));
-    out->slots = ctx->block_counts.as<uint32_t>();
-    out->tag = ++ctx->compact_epoch << 12;
+// Scratch of launch_compact (m3d_kernels.hpp): one slot per compaction workgroup
+int compact_scratch(DeviceCtx* ctx, uint32_t nb, uint32_t** slots) {
+    RESERVE(ctx->block_counts, sizeof(uint32_t) * ((size_t)nb + 1));
+    *slots = ctx->block_counts.as<uint32_t>();
     return M3D_OK;
 }
 
@@ -167,7 +160,7 @@ int exact_error(DeviceCtx* ctx, const CloudView& v, int kind, double thr,
                        const double* model_dev, uint64_t* count, double* error) {
     const uint32_t nb = (v.n + kCompactTile - 1) / kCompactTile;
     RESERVE(ctx->dist, sizeof(double) * (size_t)std::max<uint32_t>(v.n, 1));
-    CompactScratch scratch;
+    uint32_t* scratch;
     if (const int rc = compact_scratch(ctx, nb, &scratch); rc != M3D_OK) return rc;
     RESERVE(ctx->total, sizeof(uint32_t) * 4);
     RESERVE(ctx->sums, sizeof(double) * 32);
@@ -247,7 +240,7 @@ int issue_refine_compaction(DeviceCtx* ctx, const CloudView& flag_view, const ui
     const uint32_t n = flag_view.n;
     const uint32_t nb = (n + kCompactTile - 1) / kCompactTile;
     RESERVE(ctx->idx, sizeof(uint64_t) * (size_t)std::max<uint32_t>(n, 1));
-    CompactScratch scratch;
+    uint32_t* scratch;
     if (const int rc = compact_scratch(ctx, nb, &scratch); rc != M3D_OK) return rc;
     RESERVE(ctx->total, sizeof(uint32_t) * 4);
     fused = fused && kind != M3D_CYLINDER;

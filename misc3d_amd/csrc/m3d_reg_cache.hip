@@ -29,7 +29,7 @@
 // or an unlisted one (>= t), so it may be an inlier unless min(m1 - E, t^2) already reaches the radius, and adds at least that
 // much to the sum if it is.  The (tile, hypothesis) record then holds an upper bound of the count and a lower bound of the
 // sum and is flagged in `redo`; bound-and-prune is exact on bounds, and the flagged pairs of the hypotheses that survive
-// it are walked by reg_validate_k (launch_reg_validate) -- the final records are the walk's, bit for bit, either way.
+// it are walked by reg_validate_pairs_k (launch_reg_validate) -- the final records are the walk's, bit for bit, either way.
 //
 // Rounding bound.  c_j = fl32(q_j - xa) and u carry a relative 2^-24 each, |c_j|, |u| <= R: every coordinate difference
 // is within e = 2^-22 R of the truth; the three products and two sums add 3 2^-24 s; packing the candidate's slot into

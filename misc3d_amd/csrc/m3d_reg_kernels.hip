@@ -13,6 +13,7 @@
 #include "m3d_reg_kernels.hpp"
 
 #include <algorithm>
+#include <cassert>
 #include <climits>
 
 #include "m3d_eig3.hpp"
@@ -855,8 +856,7 @@ __global__ __launch_bounds__(256) void reg_validate_k(const double* __restrict__
                                                        uint32_t* __restrict__ partial_cnt,
                                                        double* __restrict__ partial_sum, uint32_t res_mask,
                                                        uint32_t n_tiles_total, const uint8_t* __restrict__ keep,
-                                                       uint32_t n_tiles_launch, uint32_t n_split,
-                                                       const uint8_t* __restrict__ redo /* [tile][s_pad] or null: only the flagged pairs (m3d_reg_cache.hip) */) {
+                                                       uint32_t n_tiles_launch, uint32_t n_split) {
     __shared__ uint32_t red[4][64];
     __shared__ double reds[4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -891,10 +891,7 @@ __global__ __launch_bounds__(256) void reg_validate_k(const double* __restrict__
         double acc_sum = 0.0;
         // the 64 keep flags of the block in one load (a byte load + wait per hypothesis stalled the wave for a memory
         // latency each), and the next hypothesis' transformation requested while this one is evaluated
-        unsigned long long keep_mask = keep ? __ballot(keep[sb + (uint32_t)lane] != 0) : ~0ull;
-        const unsigned long long redo_mask = redo ? __ballot(redo[(size_t)tile * s_pad + sb + (uint32_t)lane] != 0) : ~0ull;
-        keep_mask &= redo_mask;
-        if (redo && keep_mask == 0ull) continue;   // (wave-uniform, the same in all four waves: no barrier is skipped by one of them alone)
+        const unsigned long long keep_mask = keep ? __ballot(keep[sb + (uint32_t)lane] != 0) : ~0ull;
         double tn[12];
         {
             const double* __restrict__ T = Ts + (size_t)(sb + ss0) * kRegTStride;
@@ -932,7 +929,7 @@ __global__ __launch_bounds__(256) void reg_validate_k(const double* __restrict__
         red[wave][lane] = acc;
         reds[wave][lane] = acc_sum;
         __syncthreads();
-        if (wave == 0 && (uint32_t)lane >= ss0 && (uint32_t)lane < ss1 && ((redo_mask >> lane) & 1ull)) {
+        if (wave == 0 && (uint32_t)lane >= ss0 && (uint32_t)lane < ss1) {
             partial_cnt[(size_t)tile * s_pad + sb + lane] =
                 (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
             partial_sum[(size_t)tile * s_pad + sb + lane] =
@@ -1102,10 +1099,10 @@ uint32_t launch_reg_validate(const CloudView& src, const double* Ts, uint32_t s_
                                        n_tiles, kp, tiles, cache->redo, s);
             return;
         }
-        const uint8_t* redo = cache ? cache->redo : nullptr;
-        if (cache && cache->pairs) {   // the flagged pairs as a list, one pair per workgroup trip
+        if (cache) {   // the flagged pairs as a list, one pair per workgroup trip
+            assert(cache->pairs && cache->n_pairs);   // (m3d_reg::ensure_cache reserves them with the cache)
             (void)hipMemsetAsync(cache->n_pairs, 0, sizeof(uint32_t), s);
-            redo_pairs_k<<<dim3((s_pad + 255) / 256, tiles), 256, 0, s>>>(redo, kp, s_pad, res_mask, n_tiles, tiles, cache->pairs, cache->n_pairs);
+            redo_pairs_k<<<dim3((s_pad + 255) / 256, tiles), 256, 0, s>>>(cache->redo, kp, s_pad, res_mask, n_tiles, tiles, cache->pairs, cache->n_pairs);
             if (g.nl32 && g.nl_rec && g.nl_sorted && g.nl_start && g.nl_hdr)
                 reg_validate_pairs_k<true><<<8192, 256, 0, s>>>(src.x, src.y, src.z, Ts, s_pad, g, cell_start, qx, qy, qz, partial_cnt, partial_sum,
                                                                cache->pairs, cache->n_pairs);
@@ -1116,10 +1113,10 @@ uint32_t launch_reg_validate(const CloudView& src, const double* Ts, uint32_t s_
         }
         if (g.nl32 && g.nl_rec && g.nl_sorted && g.nl_start && g.nl_hdr)
             reg_validate_k<true><<<slots * 8 * nsplit, 256, 0, s>>>(src.x, src.y, src.z, Ts, s_pad, per_split, g, cell_start, qx, qy,
-                                                                   qz, partial_cnt, partial_sum, res_mask, n_tiles, kp, tiles, nsplit, redo);
+                                                                   qz, partial_cnt, partial_sum, res_mask, n_tiles, kp, tiles, nsplit);
         else
             reg_validate_k<false><<<slots * 8 * nsplit, 256, 0, s>>>(src.x, src.y, src.z, Ts, s_pad, per_split, g, cell_start, qx, qy,
-                                                                    qz, partial_cnt, partial_sum, res_mask, n_tiles, kp, tiles, nsplit, redo);
+                                                                    qz, partial_cnt, partial_sum, res_mask, n_tiles, kp, tiles, nsplit);
     };
     if (best_cnt == 0 || n_tiles < 16) {
         launch(0xFFFFFFFFu, nullptr, false);

@@ -77,7 +77,7 @@ static int cloud_remove_issue(m3d_cloud* c, int kind, double thr, const double* 
     const uint32_t nb = (cur.n + kCompactTile - 1) / kCompactTile;
     const uint32_t snb = (c->n_sorted + kCompactTile - 1) / kCompactTile;
     const uint32_t scap = c->n_tiles0 * kTilePoints;
-    CompactScratch scratch;
+    uint32_t* scratch;
     if (const int rc = compact_scratch(ctx, std::max(nb, snb), &scratch); rc != M3D_OK) return rc;
     RESERVE(ctx->total, 16);
     RESERVE(ctx->h_small, 256);
@@ -122,7 +122,6 @@ static int cloud_remove_issue(m3d_cloud* c, int kind, double thr, const double* 
     sview.nx = sview.ny = sview.nz = nullptr;
     sview.n = c->n_sorted;
     sview.n_pad = w.scur.n_tiles * kTilePoints;
-    if (const int rc = compact_scratch(ctx, std::max(nb, snb), &scratch); rc != M3D_OK) return rc;   // (a launch of its own: the next epoch)
     launch_compact(kind, sview, model_dev, thr, 3, nullptr, nullptr, nullptr, w.sbx[w.spp].as<double>(),
                    w.sby[w.spp].as<double>(), w.sbz[w.spp].as<double>(), nullptr, scap,
                    scratch, ctx->total.as<uint32_t>() + 1, ctx->stream, nullptr, nullptr, nullptr,

@@ -1,6 +1,6 @@
 // m3d_tile_count.hpp -- the exact fp64 count of one (tile, hypothesis) pair, shared by the scoring kernels
-// (m3d_cull_kernels.hip: score_mask_k and the recount path of score_screen_k; m3d_score_mfma.hip: the recount path of
-// score_mfma_k).  The per-point arithmetic is m3d_fp.hpp's -- the reference's own expressions and association.
+// (m3d_cull_kernels.hip: score_mask_k and the recount path of score_screen_k).  The per-point arithmetic is m3d_fp.hpp's --
+// the reference's own expressions and association.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -27,26 +27,14 @@ PATHS = {"culled": {}, "dense": {"dense_scoring": 1}, "no_early_pick": {"specula
          "plane_bound_off": {"plane_bound": 0},
          "plane_bound_fp64_paths": {"plane_bound": 2, "score_fp32_screen": 0, "cull_fp32": 0}}   # (no fp32 box-test records: plane_bound_k reads the mask words)
 
-# round 4's refuted variants: compiled with `make DEFS=-DM3D_EXPERIMENTAL` only (m3d_kernels.hpp) -- their rows join the matrix
-# when the library under test is such a build
-EXPERIMENTAL_PATHS = {"mfma": {"score_mfma": 1},   # planes: score_mfma_k, the screen on the matrix pipe
-                      "four_wave_wgs": {"score_waves4": 1},
-                      "one_pass_compaction": {"compact_one_pass": 1}}   # compact_write_k, ONE: counts published and awaited inside the launch
-try:
-    from misc3d_amd import capi as _capi_probe
-    if _capi_probe.experimental():
-        PATHS.update(EXPERIMENTAL_PATHS)
-except Exception:      # noqa: BLE001  (no library: the GPU tests cannot run anyway)
-    pass
-
 
 @pytest.fixture(params=sorted(PATHS))
 def scoring_path(request, capi):
     """Runs the test once per scoring path: the production culled path (cull_tiles_k + score_screen_k / score_mask_k
     with the device's early pick), the dense kernel (score_k: every tile x every hypothesis; the bench's reference
     point), the culled path without the speculative RefineModel, the culled path with one hypothesis group per
-    workgroup, the culled path without any fp32 (fp64 box tests cull_tiles_k, score_mask_k for every model), and the
-    culled path with the planes' screen on the matrix pipe (score_mfma_k)."""
+    workgroup, the culled path without any fp32 (fp64 box tests cull_tiles_k, score_mask_k for every model), one, two
+    and three scoring phases, and the histogram bound forced on, off, and on without the fp32 paths."""
     old = capi.set_config(**PATHS[request.param])
     yield request.param
     capi.restore_config(old)

@@ -1,6 +1,7 @@
 // mfma_f16_error.hip -- how far is v_mfma_f32_32x32x16_f16's fp32 result from the exact value of sum a_k b_k + c?
 //
-// The MFMA screen of the scoring kernels (score_mfma_k) decides a point only when the matrix pipe's value is farther
+// A screen on the matrix pipe (the matcher's, m3d_match_mfma.hip; round 4's plane screen, since removed:
+// profiles/r04_score_mfma.txt) decides a point only when the matrix pipe's value is farther
 // from the cut-off than a bound; that bound has to cover the pipe's internal accumulation, which no document specifies.
 // This measures it: fp16 operands with random exponents (heavy cancellation, one-huge-term and exactly-cancelling
 // cases included), a random fp32 addend, one MFMA and a chain of two (K = 32); the error is reported in units of
