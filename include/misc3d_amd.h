@@ -1007,6 +1007,11 @@ typedef struct m3d_config {
                                        its mask rows and the launch behind it announces them ("mask ready") before it folds the moments:
                                        the host writes the list under that launch and waits for its completion word afterwards; 0: the
                                        host waits for the completion word first (same list, same parameters) */
+    int32_t ref_bound;              /* [M3D_REF_BOUND]      default 1: a one-GPU plane fit whose first chunk has a lead pass also bins every tile's
+                                       points by their signed distance to the lead's best plane (ref_hist_tile, in the lead_fold_keep_k
+                                       launch), and plane_bound_k takes the smaller of its two bounds per (tile, hypothesis) pair -- where
+                                       plane_bound engages (bound_pays); 2: whatever the size (forces plane_bound's launch too: the tests);
+                                       0: off.  Same results, fewer hypotheses counted point by point */
 } m3d_config;
 void m3d_get_config(m3d_config *out);
 int m3d_set_config(const m3d_config *in);

@@ -40,6 +40,11 @@ int m3d_bench_cloud_setup_ms(const m3d_cloud *cloud, double out[5]);
  * Builds the cloud's tile frames if it has none yet. */
 int m3d_bench_plane_upper_bounds(m3d_cloud *cloud, double threshold, const uint32_t *samples, size_t n_hypotheses,
                                  uint32_t *ub_out);
+/* ... from the reference-plane histograms alone (ref_hist_tile / ref_pair_ub): the reference is hypothesis ref_index of the table;
+ * a pair the reference bound does not cover (a hypothesis more than acos 0.9 off the reference) counts 512.  What
+ * tests/test_gpu_ref_bound.py holds against the exact counts. */
+int m3d_bench_plane_ref_upper_bounds(m3d_cloud *cloud, double threshold, const uint32_t *samples, size_t n_hypotheses,
+                                     size_t ref_index, uint32_t *ub_out);
 /* ... for any kind (M3D_PLANE / M3D_SPHERE / M3D_CYLINDER; samples: n_hypotheses x 3 / 4 / 2 indices): spheres and cylinders are
  * bounded through the slab their shell is over one tile (m3d_bound_fp.hpp cyl_pair_ub). */
 int m3d_bench_upper_bounds(m3d_cloud *cloud, int kind, double threshold, const uint32_t *samples, size_t n_hypotheses,

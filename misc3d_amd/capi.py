@@ -270,7 +270,7 @@ class Config(C.Structure):
                                          "reg_neighbour_lists", "reg_prune", "match_brute", "match_fp32_screen",
                                          "pool_limit_mb", "kernel_timing", "reg_sorted_lists", "score_fp32_screen",
                                          "cull_fp32", "reg_fp32_screen", "sorted_tombstones", "score_mfma", "score_mfma_groups", "score_waves4", "score_waves4_groups", "score_phases", "compact_one_pass", "plane_bound",
-                                         "lanes", "wait_spin_us", "prestream", "chunk_cap", "first_chunk", "reg_cells_per_radius", "match_pipeline", "reg_cache", "device_aliases", "lanes_eager", "list_mask", "mask_early")]
+                                         "lanes", "wait_spin_us", "prestream", "chunk_cap", "first_chunk", "reg_cells_per_radius", "match_pipeline", "reg_cache", "device_aliases", "lanes_eager", "list_mask", "mask_early", "ref_bound")]
 
 
 def fp64_issue_rate(device=0, ms_target=2.0):
@@ -703,6 +703,15 @@ class Cloud:
         samples = np.ascontiguousarray(samples, dtype=np.uint32).reshape(-1, 3)
         ub = np.zeros(len(samples), dtype=np.uint32)
         _check(lib().m3d_bench_plane_upper_bounds(self._h, threshold, _p(samples), len(samples), _p(ub)))
+        return ub
+
+    def plane_ref_upper_bounds(self, threshold, samples, ref_index):
+        """m3d_bench_plane_ref_upper_bounds -> uint32 upper bounds from the histograms along hypothesis ref_index's plane alone"""
+        samples = np.ascontiguousarray(samples, dtype=np.uint32).reshape(-1, 3)
+        ub = np.zeros(len(samples), dtype=np.uint32)
+        f = lib().m3d_bench_plane_ref_upper_bounds
+        f.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+        _check(f(self._h, threshold, _p(samples), len(samples), int(ref_index), _p(ub)))
         return ub
 
     def upper_bounds(self, kind, threshold, samples):

@@ -22,6 +22,10 @@
 //                   keep bit off where ubsum[h] < best count of EARLIER hypotheses -- keep_mask_k's rule with a bound that is
 //                   within ~10 % of the true count for hypotheses near a surface instead of 512 per tile.
 //
+//                   Round 9: a one-GPU fit's first chunk also has a histogram per tile along the lead pass' best plane
+//                   (m3d_ref_hist.hpp, written in the lead_fold_keep_k launch); plane_bound_k<0, ., true> takes the smaller of
+//                   the two bounds per pair (ref_pair_ub, m3d_bound_fp.hpp): tight on clutter tiles too.
+//
 // A hypothesis dropped here has count <= ubsum < best count of hypotheses before it: it can neither beat nor tie the incumbent
 // in the sequential replay (ransac.h:595-596); its record is reported as 0 like any pruned hypothesis'.  Nothing else
 // changes: the survivors are counted by the same kernels.  Dead points (tombstones) only lower counts: the bound stays valid.
@@ -246,8 +250,9 @@ void launch_tile_frames(const SortedView& s, double* frames, uint16_t* cum, hipS
 // Arithmetic and its margins: m3d_bound_fp.hpp (plane_pair_ub: the value at the tile's centre in fp64, the rest in fp32 with every
 // number pushed outwards; tests/cpp/test_plane_bound.cpp runs the same code on the host against exact counts).
 constexpr int kBoundWaves = 8;   // (4 waves x 16 tiles each: step 0.2594-0.2621 ms; 8 x 8: 0.2570-0.2572)
-template <int KIND /* 0 plane, 1 sphere, 2 cylinder (cyl_pair_ub: the shell as a slab per tile) */, int kBoundTpw /* tiles per wave */>
-__global__ __launch_bounds__(64 * kBoundWaves) void plane_bound_k(const double* __restrict__ frames, const uint16_t* __restrict__ cum,
+template <int KIND /* 0 plane, 1 sphere, 2 cylinder (cyl_pair_ub: the shell as a slab per tile) */, int kBoundTpw /* tiles per wave */,
+          bool REF /* planes: the reference histograms as well (their LDS and registers cost the launch 8 us when it only carries them) */>
+__global__ __launch_bounds__(64 * kBoundWaves, REF ? 6 : 1 /* waves per SIMD: three workgroups to a CU, see launch_plane_bound */) void plane_bound_k(const double* __restrict__ frames, const uint16_t* __restrict__ cum,
                                                                    uint32_t n_tiles, double max_abs,
                                                                    const double* __restrict__ score,
                                                                    const unsigned long long* __restrict__ masks, uint32_t n_groups,
@@ -257,8 +262,12 @@ __global__ __launch_bounds__(64 * kBoundWaves) void plane_bound_k(const double* 
                                                                    uint32_t* __restrict__ ubsum, const uint32_t* __restrict__ best_count,
                                                                    unsigned long long* __restrict__ keep,
                                                                    uint32_t* __restrict__ tickets /* [0]: finished blocks; [1 + block] */,
-                                                                   uint32_t max_list) {
+                                                                   uint32_t max_list, RefHistArgs ref, bool ref_alone) {
     constexpr int kBoundTpb = kBoundWaves * kBoundTpw;     // tiles per workgroup
+    constexpr int kRefTpb = REF ? kBoundTpb : 1;           // (the reference histograms, m3d_ref_hist.hpp)
+    static_assert(!REF || KIND == 0, "reference histograms bound planes");
+    __shared__ double rt_s[kRefTpb][kRefTileStride];
+    __shared__ __attribute__((aligned(8))) uint16_t rcm_s[kRefTpb][kRefCumStride];
     __shared__ float bx_s[kBoundTpb][6];                   // the tile's fp32 box (cull_tiles32_k's)
     __shared__ double c_s[kBoundTpb][3];
     __shared__ float f_s[kBoundTpb][kFrameStride];         // slots 3 .. 19 of the frame in fp32 (U, V, R, W rounded up)
@@ -279,6 +288,22 @@ __global__ __launch_bounds__(64 * kBoundWaves) void plane_bound_k(const double* 
     }
     if (blockIdx.x * 64u >= total) return;   // (workgroup-uniform)
     const uint32_t t0 = blockIdx.y * (uint32_t)kBoundTpb, nt = min((uint32_t)kBoundTpb, n_tiles - t0);
+    // the fit's reference plane, if its lead pass found one (ref_hist_tile's header: uniform)
+    // (header and tile records are fetched together, not one behind the other: the block is there whatever the header says)
+    double hv[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (REF)
+        for (int k = 0; k < 6; ++k) hv[k] = ref.hdr[k];
+    const bool use_ref = REF && hv[0] != 0.0;
+    RefPlane gp;
+    gp.ok = false;
+    if (REF) {
+        gp = ref_plane_record(hv + 1, max_abs);
+        const double* __restrict__ rsrc = ref.tiles + (size_t)t0 * kRefTileStride;
+        for (uint32_t i = threadIdx.x; i < nt * (uint32_t)kRefTileStride; i += 64u * kBoundWaves) (&rt_s[0][0])[i] = rsrc[i];
+        const uint32_t* __restrict__ csrc = reinterpret_cast<const uint32_t*>(ref.cum + (size_t)t0 * kRefCumStride);
+        uint32_t* cdst = reinterpret_cast<uint32_t*>(&rcm_s[0][0]);
+        for (uint32_t i = threadIdx.x; i < nt * (uint32_t)(kRefCumStride / 2); i += 64u * kBoundWaves) cdst[i] = csrc[i];
+    }
     {
         const double* __restrict__ src = frames + (size_t)t0 * kFrameStride;
         for (uint32_t i = threadIdx.x; i < nt * (uint32_t)kFrameStride; i += 64u * kBoundWaves) {
@@ -321,9 +346,11 @@ __global__ __launch_bounds__(64 * kBoundWaves) void plane_bound_k(const double* 
         __syncthreads();   // (records -- and, the first time round, the frames -- are in LDS)
         PlaneBoundRec pr;
         CylBoundRec cr;
+        RefHypRec rr;
         if (KIND == 0) {
             pr = plane_bound_record(rec_s[lane], max_abs);
             pr.ok = pr.ok && has;
+            if (REF && use_ref) rr = ref_hyp_record(gp, rec_s[lane], max_abs);   // (uniform)
         } else {
             cr = KIND == 1 ? sphere_bound_record(rec_s[lane], max_abs) : cyl_bound_record(rec_s[lane], max_abs);
             cr.ok = cr.ok && has;
@@ -374,8 +401,12 @@ __global__ __launch_bounds__(64 * kBoundWaves) void plane_bound_k(const double* 
                 tch[i] = has && (uint32_t)tl < nt && live && !(t < 0.0f);
             }
             if (__ballot(tch[i]) == 0ull) continue;   // (wave-uniform)
-            const uint32_t u_t = KIND == 0 ? plane_pair_ub(pr, c_s[tl], f_s[tl], cm_s[tl])   // (wave-uniform addresses: broadcast reads)
-                                           : cyl_pair_ub(cr, c_s[tl], f_s[tl], f_s[tl][0], cm_s[tl]);
+            uint32_t u_t = KIND == 0 ? plane_pair_ub(pr, c_s[tl], f_s[tl], cm_s[tl])   // (wave-uniform addresses: broadcast reads)
+                                     : cyl_pair_ub(cr, c_s[tl], f_s[tl], f_s[tl][0], cm_s[tl]);
+            if (REF && use_ref) {   // (uniform) the smaller of the two bounds: both hold
+                const uint32_t u_r = ref_pair_ub(rr, pr.a, pr.b, pr.c, pr.d, rt_s[tl], rcm_s[tl]);
+                u_t = ref_alone ? u_r : min(u_t, u_r);
+            }
             ub += tch[i] ? u_t : 0u;
         }
         wsum[wave][lane] = ub;
@@ -510,7 +541,8 @@ __global__ __launch_bounds__(64 * kBoundWaves) void cyl_bound_words_k(const doub
 void launch_plane_bound(int kind, const SortedView& s, const double* score, const unsigned long long* masks, unsigned long long* keep,
                         uint32_t n_groups, uint32_t group_begin, uint32_t group_end, uint32_t* ubsum,
                         const uint32_t* best_count, uint32_t* surv_count, const uint32_t* surv, uint32_t* tickets,
-                        const float* cull32, hipStream_t st, bool always, const unsigned long long* touched, uint32_t touched_stride) {
+                        const float* cull32, hipStream_t st, bool always, const unsigned long long* touched, uint32_t touched_stride,
+                        const RefHistArgs* ref, bool ref_alone) {
     group_end = std::min(group_end, n_groups);
     if (!s.frames || !s.frame_cum || !s.n_tiles || !surv || !surv_count || !tickets || group_begin >= group_end) return;
     const uint32_t window = group_end - group_begin;
@@ -534,11 +566,12 @@ void launch_plane_bound(int kind, const SortedView& s, const double* score, cons
     if (s.radius >= 1e18 || kind == 1) cull32 = nullptr;   // (no fp32 boxes: launch_cull_mask's condition; spheres: the box tests' mask words are read)
     auto go = [&](auto kernel) {
         kernel<<<g, b, 0, st>>>(s.frames, s.frame_cum, s.n_tiles, s.max_abs, score, masks, n_groups, s.boxes, cull32, surv_count, surv,
-                                ubsum, best_count, keep, tickets, max_list);
+                                ubsum, best_count, keep, tickets, max_list, (ref && kind == 0) ? *ref : RefHistArgs{}, ref_alone);
     };
-    if (kind == 0) go(plane_bound_k<0, tpw>);
-    else if (kind == 1) go(plane_bound_k<1, tpw_cyl>);
-    else go(plane_bound_k<2, tpw_cyl>);
+    if (kind == 0 && ref) go(plane_bound_k<0, tpw, true>);
+    else if (kind == 0) go(plane_bound_k<0, tpw, false>);
+    else if (kind == 1) go(plane_bound_k<1, tpw_cyl, false>);
+    else go(plane_bound_k<2, tpw_cyl, false>);
 }
 
 }  // namespace m3d

@@ -259,4 +259,108 @@ M3D_HD uint32_t cyl_pair_ub(const CylBoundRec& r, const double* c3, const float*
     return framed ? u_t : (uint32_t)kBoundTilePoints;
 }
 
+// ---- planes: histograms along the fit's REFERENCE plane (round 9) -----------------------------------------------------------
+// The frames' histograms run along each tile's own thin direction; a clutter tile has none.  A second histogram per tile, of the
+// signed distances s_g(p) = ((a_g x + b_g y) + c_g z) + d_g (fp64, as the scoring kernels evaluate a plane) to ONE plane g -- the
+// lead pass' best hypothesis, m3d_ref_hist.hpp -- bounds every hypothesis h that is nearly parallel to g on every tile.  With any
+// number alpha, n_perp = n_h - alpha n_g and any point c,
+//   S_h(p) = alpha S_g(p) + n_perp . (p - c) + K,   K = S_h(c) - alpha S_g(c)                                  (an identity),
+// so for rho >= |p - c| over the tile,  |S_h(p)| < T_h  =>  |alpha S_g(p) + K| < T_h + |n_perp| rho:  S_g(p) lies between
+// lo = (-K - w) / alpha and hi = (-K + w) / alpha, w = T_h + |n_perp| rho (alpha > 0: h is flipped to g's side first, which changes
+// no |S_h|).  alpha = (n_h . n_g) / (n_g . n_g) makes |n_perp| smallest; ITS rounding does not matter, n_perp is formed from
+// the alpha in hand.  ref_bin is monotone in s, so the points in question number at most cum[bin(hi) + 1] - cum[bin(lo)],
+// cum[k] = points of the tile with ref_bin(s_g(p)) < k -- evaluated by ref_hist_tile and here by the same expression.
+// Roundings, all fp64 (2^-53 = 1.1e-16 per operation), each pushed outwards by far more than it can be:
+//   * the exact test and the histogram evaluate S_h(p), S_g(p) within 1e-15 M_h, 1e-15 M_g (M = |n|_1 max|coordinate| + |d|: four
+//     operations on numbers <= M), K's two centre values likewise (|c| <= max|coordinate|: a box centre) and its product and
+//     difference within 3e-16 (M_h + alpha M_g):  w carries E = 1e-13 (M_h + alpha M_g), twenty times their sum;
+//   * n_perp's components are off by <= 2.3e-16 (alpha |n_g,i| + |n_h,i|), its length by 4 more roundings: np = length (1 + 1e-12)
+//     + 1e-15 (alpha |n_g|_1 + |n_h|_1); rho comes rounded up by 1e-12 of itself (ref_hist_tile), T_h likewise;
+//   * w0 and np carry another 1e-11 of themselves for w's own two roundings; lo and hi are formed in BINS at once, (-K -+ w) sa with
+//     sa = (1 / alpha) invw: a difference, a reciprocal, two products against the single product s invw of ref_bin(s): 6e-16 of
+//     their sizes together, and they are pushed outwards by 1e-11 of their sizes before the floor both sides share.
+// Used where cos(n_h, n_g) >= kRefMinCos (beyond it |n_perp| rho is many cut-offs wide on any tile: nothing to gain) and every
+// number lies in [1e-12, 1e12] like plane_pair_ub's; else the pair counts kBoundTilePoints and the frames' bound stands alone.
+// M3D_BOUND_NO_SLACK (tests only): E = 0, nothing pushed outwards, and only the bins that lie wholly inside (lo, hi).
+#ifndef M3D_REF_BINS
+#define M3D_REF_BINS 64
+#endif
+constexpr int kRefBins = M3D_REF_BINS;        // bins of T_g 8 / kRefBins over +-4 T_g (bin 0 / kRefBins + 1: the tails)
+constexpr int kRefCumStride = kRefBins + 4;   // uint16 per tile: cum[0 .. kRefBins + 2] (+ 1: even)
+constexpr int kRefTileStride = 5;             // doubles per tile: c (3), s_g(c), rho
+constexpr int kRefHdrDoubles = 8;             // [0] 1 = a reference exists, [1 .. 5] its record (a, b, c, d, T), [6] its index
+constexpr double kRefMinCos = 0.9;
+static_assert(kRefBins >= 8 && kRefBins <= 128 && kRefBins % 8 == 0, "8 .. 128 bins");
+
+struct RefPlane {
+    double a, b, c, d, invw, n2, n1, Mg;
+    bool ok;
+};
+M3D_HD RefPlane ref_plane_record(const double* rec /* a, b, c, d, T */, double max_abs) {
+    RefPlane g;
+    g.a = rec[0]; g.b = rec[1]; g.c = rec[2]; g.d = rec[3];
+    const double T = rec[4];
+    g.n1 = (fabs(g.a) + fabs(g.b)) + fabs(g.c);
+    g.n2 = (g.a * g.a + g.b * g.b) + g.c * g.c;
+    g.Mg = g.n1 * max_abs + fabs(g.d);
+    g.invw = (double)(kRefBins / 8) / T;
+    g.ok = (T > 1e-12) && (T < 1e12) && (g.n1 > 1e-12) && (g.n1 < 1e12) && (g.Mg < 1e12);
+    return g;
+}
+// bin of a signed distance: 0 below -4 T_g, 1 .. kRefBins inside, kRefBins + 1 above (NaN: never asked).  MONOTONE in s.
+M3D_HD int ref_bin_of(double t /* a distance in bins */) {
+    return (int)fmin(fmax(floor(t), (double)(-kRefBins / 2 - 1)), (double)(kRefBins / 2)) + (kRefBins / 2 + 1);
+}
+M3D_HD int ref_bin(double s, double invw) { return ref_bin_of(s * invw); }
+// what ref_pair_ub needs of a hypothesis beside its record (four numbers: the kernel keeps them in registers beside plane_pair_ub's)
+struct RefHypRec {
+    double alpha, sa /* bins per unit of alpha S_g */, w0, np;
+    bool flip, ok;
+};
+M3D_HD RefHypRec ref_hyp_record(const RefPlane& g, const double* rec /* a, b, c, d, T */, double max_abs) {
+    RefHypRec r;
+    const double dot = (rec[0] * g.a + rec[1] * g.b) + rec[2] * g.c;
+    r.flip = dot < 0.0;
+    const double sg = r.flip ? -1.0 : 1.0;
+    const double a = sg * rec[0], b = sg * rec[1], c = sg * rec[2], d = sg * rec[3], T = rec[4];
+    r.alpha = fabs(dot) / g.n2;
+    r.sa = (1.0 / r.alpha) * g.invw;
+    const double n1 = (fabs(a) + fabs(b)) + fabs(c), n2 = (a * a + b * b) + c * c;
+    const double Mh = n1 * max_abs + fabs(d);
+    const double qa = a - r.alpha * g.a, qb = b - r.alpha * g.b, qc = c - r.alpha * g.c;
+#ifdef M3D_BOUND_NO_SLACK
+    r.np = sqrt((qa * qa + qb * qb) + qc * qc);
+    r.w0 = T;
+#else
+    r.np = (sqrt((qa * qa + qb * qb) + qc * qc) * (1.0 + 1e-12) + 1e-15 * (r.alpha * g.n1 + n1)) * (1.0 + 1e-11);
+    r.w0 = (T * (1.0 + 1e-12) + 1e-13 * (Mh + r.alpha * g.Mg)) * (1.0 + 1e-11);
+#endif
+    r.ok = g.ok && (T > 1e-12) && (T < 1e12) && (n1 > 1e-12) && (n1 < 1e12) && (Mh < 1e12) &&
+           (dot * dot >= (kRefMinCos * kRefMinCos) * (n2 * g.n2)) && (r.alpha > 1e-12) && (r.alpha < 1e12);
+    return r;
+}
+// upper bound of the inliers of hypothesis `r` -- record (a, b, c, d, .) as stored, not flipped -- among the points of one tile:
+// t = the tile's record (c, s_g(c), rho), cm = its cumulative reference histogram
+template <class CumPtr>
+M3D_HD uint32_t ref_pair_ub(const RefHypRec& r, double a, double b, double c, double d, const double* t, CumPtr cm) {
+    const double sc = ((a * t[0] + b * t[1]) + c * t[2]) + d;   // (the flipped record's value is exactly -sc)
+    const double K = (r.flip ? -sc : sc) - r.alpha * t[3];
+    const double w = r.w0 + r.np * t[4];
+    double tl = (-K - w) * r.sa, th = (-K + w) * r.sa;   // lo, hi in bins
+#ifndef M3D_BOUND_NO_SLACK
+    tl -= 1e-11 * fabs(tl);
+    th += 1e-11 * fabs(th);
+#endif
+    const bool whole = !(tl == tl) || !(th == th);   // (an infinite rho or centre: every finite point of the tile)
+    const int bl = ref_bin_of(whole ? 0.0 : tl), bh = ref_bin_of(whole ? 0.0 : th);
+#ifdef M3D_BOUND_NO_SLACK
+    const int lo_c = (int)cm[bl + 1], hi_c = (int)cm[bh];
+#else
+    const int lo_c = (int)cm[bl], hi_c = (int)cm[bh + 1];
+#endif
+    uint32_t u_t = (uint32_t)(hi_c > lo_c ? hi_c - lo_c : 0);
+    u_t = whole ? (uint32_t)cm[kRefBins + 2] : u_t;
+    return r.ok ? u_t : (uint32_t)kBoundTilePoints;
+}
+
 }  // namespace m3d

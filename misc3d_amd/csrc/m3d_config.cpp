@@ -51,6 +51,7 @@ void sanitize(m3d_config& c) {
     if (c.list_mask < 0) c.list_mask = 1;
     if (c.list_mask > 16) c.list_mask = 16;
     c.mask_early = c.mask_early != 0;
+    if (c.ref_bound < 0 || c.ref_bound > 2) c.ref_bound = 1;
 }
 void load_env() {
     std::memset(&g_cfg, 0, sizeof(g_cfg));
@@ -85,6 +86,7 @@ void load_env() {
     g_cfg.lanes_eager = (int32_t)env_long("M3D_LANES_EAGER", 2);
     g_cfg.list_mask = (int32_t)env_long("M3D_LIST_MASK", 1);
     g_cfg.mask_early = !env_is("M3D_MASK_EARLY", '0');
+    g_cfg.ref_bound = (int32_t)env_long("M3D_REF_BOUND", 1);
     sanitize(g_cfg);
 }
 }  // namespace

@@ -35,6 +35,7 @@
 
 #include "m3d_config.hpp"
 #include "m3d_fp.hpp"
+#include "m3d_ref_hist.hpp"
 #include "m3d_tile_count.hpp"
 #include "m3d_wave.hpp"
 
@@ -631,7 +632,14 @@ __global__ __launch_bounds__(64) void lead_fold_keep_k(const uint32_t* __restric
                                                         uint32_t* __restrict__ records_dev,
                                                         unsigned long long* __restrict__ pick_key,
                                                         unsigned long long* __restrict__ pick_key2,
-                                                        SurvOut surv) {
+                                                        SurvOut surv, uint32_t n_keep_groups, RefHistArgs ref) {
+    // workgroups behind the keep groups (a plane fit with reference histograms): one tile's histogram each -- a second body in
+    // the same launch, nothing added to the chain of dependent launches (they fold the lead's counters themselves)
+    __shared__ uint32_t hist[kRefHistWords];
+    if (blockIdx.x >= n_keep_groups) {   // (workgroup-uniform)
+        ref_hist_tile(ref, blockIdx.x - n_keep_groups, hist);
+        return;
+    }
     const uint32_t g = group_offset + blockIdx.x;
     const uint32_t prev = best_count[0];   // may or may not include this chunk's lead already: max() below either way
     uint32_t v = 0;
@@ -680,12 +688,21 @@ __global__ __launch_bounds__(64) void lead_fold_keep_k(const uint32_t* __restric
 void launch_lead_fold_keep(const uint32_t* counts_rep, uint32_t rep_stride, uint32_t lead, const uint8_t* valid,
                            uint32_t h_count, uint32_t* records, uint32_t* best_count, const uint32_t* ub,
                            unsigned long long* keep, uint32_t n_groups_rest, hipStream_t st, uint32_t* records_dev,
-                           uint32_t group_begin, unsigned long long* pick_key, unsigned long long* pick_key2, uint32_t* surv_count, uint32_t* surv) {
+                           uint32_t group_begin, unsigned long long* pick_key, unsigned long long* pick_key2, uint32_t* surv_count, uint32_t* surv,
+                           const RefHistArgs* ref) {
     if (group_begin == 0xFFFFFFFFu) group_begin = lead / 64u;
     // (n_groups_rest == 0 still needs the fold of the lead's counters: one workgroup whose keep word is scratch)
     if (!n_groups_rest) return;
-    lead_fold_keep_k<<<n_groups_rest, 64, 0, st>>>(counts_rep, rep_stride, lead, valid, h_count, records, best_count, ub,
-                                                   keep, const_cast<uint32_t*>(counts_rep), group_begin, records_dev, pick_key, pick_key2, SurvOut{surv_count, surv});
+    lead_fold_keep_k<<<n_groups_rest + (ref ? ref->n_tiles : 0u), 64, 0, st>>>(counts_rep, rep_stride, lead, valid, h_count, records, best_count, ub,
+                                                   keep, const_cast<uint32_t*>(counts_rep), group_begin, records_dev, pick_key, pick_key2, SurvOut{surv_count, surv},
+                                                   n_groups_rest, ref ? *ref : RefHistArgs{});
+}
+__global__ __launch_bounds__(64) void ref_hist_k(RefHistArgs ref) {
+    __shared__ uint32_t hist[kRefHistWords];
+    ref_hist_tile(ref, blockIdx.x, hist);
+}
+void launch_ref_hist(const RefHistArgs& a, hipStream_t st) {
+    if (a.n_tiles) ref_hist_k<<<a.n_tiles, 64, 0, st>>>(a);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -39,6 +39,33 @@ struct SortedView {
 
 constexpr int kTileF32Floats = 3 * kTilePoints;
 void launch_tile_frames(const SortedView& s, double* frames, uint16_t* cum, hipStream_t st);
+// The reference-plane histograms of a plane fit (m3d_ref_hist.hpp; arithmetic: m3d_bound_fp.hpp ref_*): call-scoped scratch that
+// ref_hist_tile writes -- one wave per tile, as extra workgroups of the lead_fold_keep_k launch -- and plane_bound_k<0> reads.
+struct RefHistArgs {
+    const double* sx = nullptr;
+    const double* sy = nullptr;
+    const double* sz = nullptr;
+    uint32_t n_tiles = 0;
+    const double* score = nullptr;           // the chunk's scoring records
+    const uint32_t* counts_rep = nullptr;    // the lead's counter replicas (null: the reference is hypothesis fixed_index)
+    uint32_t rep_stride = 0, lead = 0;
+    const uint8_t* valid = nullptr;
+    uint32_t h_count = 0, fixed_index = 0;
+    uint32_t min_count = 1;                  // the lead's best count below which no histograms are built
+    double max_abs = 0.0;
+    double* hdr = nullptr;                   // kRefHdrDoubles
+    double* tiles = nullptr;                 // n_tiles x kRefTileStride
+    uint16_t* cum = nullptr;                 // n_tiles x kRefCumStride
+};
+inline size_t ref_hist_bytes(uint32_t n_tiles) {
+    return sizeof(double) * (kRefHdrDoubles + (size_t)kRefTileStride * n_tiles) + sizeof(uint16_t) * (size_t)kRefCumStride * n_tiles;
+}
+inline void ref_hist_place(RefHistArgs& a, void* block) {   // (a.n_tiles set)
+    a.hdr = static_cast<double*>(block);
+    a.tiles = a.hdr + kRefHdrDoubles;
+    a.cum = reinterpret_cast<uint16_t*>(a.tiles + (size_t)kRefTileStride * a.n_tiles);
+}
+void launch_ref_hist(const RefHistArgs& a, hipStream_t st);   // a launch of its own (the bench hook; measured against the fused form)
 // ubsum[h] += upper bound of hypothesis h's inliers over the tiles it can touch, for the hypotheses of the list `surv` (written by
 // the keep kernels of groups [group_begin, group_end): *surv_count ids; ubsum zero on entry); the keep bit of a hypothesis whose
 // bound stays below best_count[0] is cleared, *surv_count ends at 0.  tickets: 1 + (hypotheses of the window / 64) words, zero
@@ -51,7 +78,9 @@ void launch_plane_bound(int kind, const SortedView& s, const double* score, cons
                         bool always = false /* false: a list longer than half of the window is discarded unbounded (nothing worth pruning against) */,
                         const unsigned long long* touched = nullptr /* launch_cull_mask's per-hypothesis words for these groups (cylinders: read
                                                                        instead of repeating the box tests) */,
-                        uint32_t touched_stride = 0);
+                        uint32_t touched_stride = 0,
+                        const RefHistArgs* ref = nullptr /* planes: the smaller of the frames' bound and the reference histograms' per pair */,
+                        bool ref_alone = false /* ... the reference histograms' bound alone (the bench hook) */);
 void launch_tile_boxes(const SortedView& s, double* boxes, hipStream_t st);
 // Tombstones (m3d_poison.hpp): the job that kills the inliers of the plane `model` (device) in place in the sorted copy
 // `s`; *total (device, cleared by the owner) accumulates the number of points killed over all launches.
@@ -159,7 +188,8 @@ void launch_lead_fold_keep(const uint32_t* counts_rep, uint32_t rep_stride, uint
                            uint32_t group_begin = 0xFFFFFFFFu /* first group of the keep window; default lead / 64 */,
                            unsigned long long* pick_key = nullptr /* PickFinal::key: the lead's best goes in */,
                            unsigned long long* pick_key2 = nullptr /* PickFinal::key2 */,
-                           uint32_t* surv_count = nullptr, uint32_t* surv = nullptr /* the kept hypotheses as a list as well */);
+                           uint32_t* surv_count = nullptr, uint32_t* surv = nullptr /* the kept hypotheses as a list as well */,
+                           const RefHistArgs* ref = nullptr /* n_tiles more workgroups: the reference-plane histograms (ref_hist_tile) */);
 void launch_count_bits(const unsigned long long* masks, const unsigned long long* keep, uint32_t n_tiles,
                        uint32_t n_groups, unsigned long long* total, hipStream_t st);
 

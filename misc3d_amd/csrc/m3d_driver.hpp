@@ -191,6 +191,7 @@ struct DeviceCtx {
     PinBuf h_reg;              // registration: a chunk's pass flags / counts and sums on their way to the host (polled, not waited for)
     uint32_t sync_seq = 0;
     DevBuf surv_list;          // plane_bound_k's input: the hypotheses the keep kernels kept (its length: best_count word 6)
+    DevBuf ref_hist;           // a plane fit's reference-plane histograms (RefHistArgs: header, tile records, cumulative counts)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     PinBuf h_match;            // the matcher's cross-checked pairs (launch_mutual_pairs): count at byte 0, (src, dst) u32 pairs from byte 64
     std::vector<hipEvent_t> aux_events;   // aux_event_of: the matcher's upload / part / scan events

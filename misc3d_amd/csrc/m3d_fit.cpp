@@ -216,6 +216,12 @@ static size_t chunk_cap_for(const CloudView& v, const SortedView& sv, size_t tim
 static bool bound_pays(uint32_t n_tiles, size_t window_hypotheses) {
     return window_hypotheses >= 8192 && (double)n_tiles * (double)window_hypotheses >= 1.5e7;
 }
+// m3d_config.plane_bound as a fit of `kind` sees it: forcing the reference histograms (ref_bound = 2, the tests' switch) forces the
+// launch they live in
+static int bound_mode(int kind) {
+    const int mode = config().plane_bound;
+    return (mode != 0 && kind == M3D_PLANE && config().ref_bound == 2) ? 2 : mode;
+}
 
 // pre_stream runs the head of a fit's later chunks (issue_chunk, `pre`) beside the main stream: whatever the main stream holds
 // when the fit starts -- a removal's compaction of this very cloud, another fit's tail -- must be behind those kernels too.
@@ -266,7 +272,9 @@ static int issue_chunk(DeviceCtx* ctx, ChunkSlot& s, const CloudView& v, const S
                                            s.pre_done in front of the keep masks) */,
                        const double* move_best_from = nullptr /* the fit's best minimal model lives in THIS slot's params, which
                                                                  the chunk is about to overwrite: moved to ctx->best_params
-                                                                 first, on the stream MinimalFit will run on */) {
+                                                                 first, on the stream MinimalFit will run on */,
+                       bool first_of_stream = false /* m3d_cloud_score_shard, one rank, from hypothesis 0: a fit's first chunk in all
+                                                       but the incumbent's clearing (the caller's): reference histograms as for new_fit */) {
     const int m = minimal_sample(kind);
     const uint32_t count = (uint32_t)(end - begin);
     const bool dense = use_dense_scoring();
@@ -412,9 +420,31 @@ static int issue_chunk(DeviceCtx* ctx, ChunkSlot& s, const CloudView& v, const S
             // the phased scoring -- whose phase counters sit where the bound sums go otherwise, so theirs get the block behind them.
             // (Spheres: C3's fit loses a third of its (tile, hypothesis) pairs and gains nothing -- 0.77 ms with and without, the bound's
             // launch costs what it saves; theirs runs when the bound is forced, m3d_config.plane_bound = 2, i.e. in the tests.)
-            const bool bound_on = (kind == M3D_CYLINDER || !ubp) && prune && bc && sv.frames && config().plane_bound != 0 &&
-                                  (config().plane_bound == 2 || (kind != M3D_SPHERE && bound_pays(sv.n_tiles, comm ? sl_pad : count))) &&
+            const bool bound_on = (kind == M3D_CYLINDER || !ubp) && prune && bc && sv.frames && bound_mode(kind) != 0 &&
+                                  (bound_mode(kind) == 2 || (kind != M3D_SPHERE && bound_pays(sv.n_tiles, comm ? sl_pad : count))) &&
                                   (use_lead || !new_fit) && std::max(g0, ga) < g1;
+            // planes, the first chunk of a one-GPU fit with a lead pass, no tombstones: a second histogram per tile, along the lead's
+            // best plane (m3d_ref_hist.hpp) -- written by extra workgroups of the lead_fold_keep_k launch, read by plane_bound_k
+            const bool ref_on = bound_on && kind == M3D_PLANE && !ubp && !comm && (new_fit || first_of_stream) && use_lead && ga && g0 == 0 && !sv.has_dead &&
+                                config().ref_bound != 0 && (config().ref_bound == 2 || bound_pays(sv.n_tiles, count));
+            RefHistArgs ref;
+            if (ref_on) {
+                RESERVE(ctx->ref_hist, ref_hist_bytes(sv.n_tiles));
+                ref.sx = sv.x; ref.sy = sv.y; ref.sz = sv.z;
+                ref.n_tiles = sv.n_tiles;
+                ref.score = s.score.as<double>();
+                ref.counts_rep = ctx->counts_rep.as<uint32_t>();
+                ref.rep_stride = h_pad;
+                ref.lead = lead;
+                ref.valid = s.valid.as<uint8_t>();
+                ref.h_count = count;
+                ref.max_abs = sv.max_abs;
+                // uniform clutter gains nothing and must not pay for the pass: no histograms unless the lead's best plane holds 8
+                // points per tile, 1 / 64 of the cloud (1 M x 10 000 clutter: the best plane holds 1 / 141; measured in
+                // profiles/r09_ref_bound.txt); forced: any count
+                ref.min_count = config().ref_bound == 2 ? 1u : 8u * sv.n_tiles;
+                ref_hist_place(ref, ctx->ref_hist.p);
+            }
             uint32_t* const ubsum = ubp ? ub + 2 * (size_t)h_pad : ub + h_pad;
             if (bound_on) {
                 const int src = reserve_survivor_scratch(ctx, h_pad);
@@ -456,14 +486,14 @@ static int issue_chunk(DeviceCtx* ctx, ChunkSlot& s, const CloudView& v, const S
                 launch_lead_fold_keep(ctx->counts_rep.as<uint32_t>(), h_pad, lead, s.valid.as<uint8_t>(), count,
                                       g0 == 0 ? rec_host : nullptr, bc, ub, keep, g1 - g_lo, ctx->stream,
                                       g0 == 0 ? rec_dev : nullptr, g_lo, pick_final ? pick_final->key : nullptr,
-                                      pick_final ? pick_final->key2 : nullptr, surv_count, surv);
+                                      pick_final ? pick_final->key2 : nullptr, surv_count, surv, ref_on ? &ref : nullptr);
             } else if (!all_prepared) {   // (all_prepared: minimal_fit_k has done it)
                 launch_keep_mask(ub, bc, g1 - g0, keep, ctx->stream, ctx->counts_rep.as<uint32_t>(), h_pad, g0, surv_count, surv);
             }
             if (bound_on)
                 launch_plane_bound(kind, sv, s.score.as<double>(), masks, keep, n_groups, g_lo, g1, ubsum, bc, surv_count, surv,
-                                   bound_tickets(ctx), c32.out, ctx->stream, config().plane_bound == 2,
-                                   touched_written && g_lo == g0 ? touched : nullptr, h_pad);
+                                   bound_tickets(ctx), c32.out, ctx->stream, bound_mode(kind) == 2,
+                                   touched_written && g_lo == g0 ? touched : nullptr, h_pad, ref_on ? &ref : nullptr);
             bool phased = false;
             if (ubp)
                 phased = launch_score_phased(kind, sv, s.score.as<double>(), masks, keep, n_groups, ctx->counts_rep.as<uint32_t>(), h_pad,
@@ -1023,7 +1053,7 @@ static int ensure_plane_frames(m3d_cloud* c, int kind, size_t n_hypotheses) {
     // 1: where it pays (bound_pays, below) -- and from 65 536 hypotheses on for a cloud that lives for one call (tile_frames_k
     // takes ~0.09 ms per million points, the bound saves ~0.02 ms per 10 000 hypotheses on them: m3d_fit_plane 0.95 -> 1.04 ms
     // otherwise); 2: always (tests)
-    const int mode = config().plane_bound;
+    const int mode = bound_mode(kind);
     if ((kind == M3D_SPHERE && mode != 2) || c->frames_ready || c->frames_failed || mode == 0 || c->work.active || c->n_tiles == 0 ||
         (mode == 1 && (!bound_pays(c->n_tiles, std::min<size_t>(n_hypotheses, chunk_cap_for(c->view(), c->sorted()))) ||
                        (c->one_shot && n_hypotheses < 65536u))))
@@ -1571,7 +1601,7 @@ int m3d_cloud_score_shard(m3d_cloud* c, m3d_sampler* sampler, double threshold, 
             if (rc != M3D_OK) return rc;
             tsrc.table = sampler->table.data();
             rc = issue_chunk(ctx, ctx->slot[cur], v, sv, kind, threshold, bb, ee, tsrc, nullptr, true, lead, false, false, nullptr, false,
-                             nullptr, false, pre);
+                             nullptr, false, pre, nullptr, /*first_of_stream=*/world == 1 && bb == 0);
             if (rc != M3D_OK) return rc;
             pend[cur].active = true;
             pend[cur].out_pos = out;
@@ -1660,7 +1690,20 @@ int m3d_bench_plane_upper_bounds(m3d_cloud* c, double threshold, const uint32_t*
     return m3d_bench_upper_bounds(c, M3D_PLANE, threshold, samples, n_hypotheses, ub_out);
 }
 // ... for any kind (spheres and cylinders: cyl_pair_ub)
+static int bench_upper_bounds(m3d_cloud* c, int kind, double threshold, const uint32_t* samples, size_t n_hypotheses, uint32_t* ub_out,
+                              long ref_index);
 int m3d_bench_upper_bounds(m3d_cloud* c, int kind, double threshold, const uint32_t* samples, size_t n_hypotheses, uint32_t* ub_out) {
+    return bench_upper_bounds(c, kind, threshold, samples, n_hypotheses, ub_out, -1);
+}
+// m3d_bench_plane_ref_upper_bounds: the same sums from the REFERENCE-plane histograms alone (ref_pair_ub, m3d_bound_fp.hpp), the
+// reference being hypothesis `ref_index` of the table (any plane is a valid reference: a fit takes its lead pass' best)
+int m3d_bench_plane_ref_upper_bounds(m3d_cloud* c, double threshold, const uint32_t* samples, size_t n_hypotheses, size_t ref_index,
+                                     uint32_t* ub_out) {
+    if (ref_index >= n_hypotheses) return fail(M3D_ERR_INVALID_ARG, "invalid argument");
+    return bench_upper_bounds(c, M3D_PLANE, threshold, samples, n_hypotheses, ub_out, (long)ref_index);
+}
+static int bench_upper_bounds(m3d_cloud* c, int kind, double threshold, const uint32_t* samples, size_t n_hypotheses, uint32_t* ub_out,
+                              long ref_index) {
     if (!c || !samples || !ub_out || n_hypotheses == 0 || n_hypotheses > 16384 || kind < M3D_PLANE || kind > M3D_CYLINDER)
         return fail(M3D_ERR_INVALID_ARG, "invalid argument");
     if (kind == M3D_CYLINDER && !c->has_normals) return fail(M3D_ERR_INVALID_ARG, "cylinder hypotheses need normals");
@@ -1701,8 +1744,19 @@ int m3d_bench_upper_bounds(m3d_cloud* c, int kind, double threshold, const uint3
     launch_cull_mask(kind, sv, s.score.as<double>(), s.valid.as<uint8_t>(), (uint32_t)n_hypotheses, n_groups, masks, nullptr,
                      ctx->stream, false, 0, 0xFFFFFFFFu, c32);
     launch_keep_mask(nullptr, nullptr, n_groups, keep, ctx->stream, nullptr, 0, 0, ctl + 1, surv);
+    RefHistArgs ref;
+    if (ref_index >= 0) {
+        RESERVE(ctx->ref_hist, ref_hist_bytes(sv.n_tiles));
+        ref.sx = sv.x; ref.sy = sv.y; ref.sz = sv.z;
+        ref.n_tiles = sv.n_tiles;
+        ref.score = s.score.as<double>();
+        ref.fixed_index = (uint32_t)ref_index;
+        ref.max_abs = sv.max_abs;
+        ref_hist_place(ref, ctx->ref_hist.p);
+        launch_ref_hist(ref, ctx->stream);
+    }
     launch_plane_bound(kind, sv, s.score.as<double>(), masks, keep, n_groups, 0, n_groups, ubsum, ctl, ctl + 1, surv,
-                       bound_tickets(ctx), c32, ctx->stream, /*always=*/true);
+                       bound_tickets(ctx), c32, ctx->stream, /*always=*/true, nullptr, 0, ref_index >= 0 ? &ref : nullptr, /*ref_alone=*/true);
     HIPCHK(hipMemcpyAsync(ub_out, ubsum, sizeof(uint32_t) * n_hypotheses, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
