@@ -1,8 +1,10 @@
 """misc3d.preprocessing.farthest_point_sampling on the MI355X: bit-exact against the plain-C restatement of the reference's
 loop (tests/cpp/fps_ref.c) on every device path -- one workgroup (M3D_FPS_PATH_SINGLE), the tile-pruned steps
 (M3D_FPS_PATH_PRUNED) and the same steps with no tile skipped (M3D_FPS_PATH_DENSE, forced through the measurement hook) --
-over sizes 1 .. 250 000, six cloud shapes and the quirk clouds; pruned == dense at 1 M x 10 000; repeatability, four threads
-on one device, the python API and the C++ mirror header."""
+over sizes 1 .. 250 000, six cloud shapes and the quirk clouds; every size at which a kernel changes its form, with its
+neighbours (the four one-workgroup instantiations, the crossover, full tiles, the tile loop's second trip at 3.1 M points,
+the unsorted layout); pruned == dense at 1 M x 10 000; repeatability, four threads on one device, the python API and the C++
+mirror header."""
 import os
 import subprocess
 import threading
@@ -10,7 +12,8 @@ import threading
 import numpy as np
 import pytest
 
-from fps_ref_util import build_ref, quirk_clouds, shaped_clouds
+from fps_ref_util import (FPS_CROSSOVER, FPS_SECOND_TRIP_N, FPS_SINGLE_SEAMS, FPS_TILE, build_ref, fps_seam_cloud,
+                          fps_tile_edge_cloud, fps_unsorted_clouds, quirk_clouds, shaped_clouds)
 
 pytestmark = pytest.mark.gpu
 
@@ -88,6 +91,111 @@ def test_quirks_on_the_pruned_path_at_scale(dev, ref):
         for path in (2, 3):
             got, _ = _run(dev, p, 300, path)
             assert np.array_equal(got, exp), (name, path)
+
+
+# ---- the kernels' seams: every size at which a kernel takes another form, one below and one above (the clouds and what they
+# promise: fps_ref_util.py, shown on the CPU in test_preprocessing.py).  Every result is bit-equal to the restatement.
+@pytest.fixture(scope="module")
+def expected(ref):
+    """the restatement's result for a named cloud, computed once and shared by the paths"""
+    cache = {}
+
+    def get(key, pts, S):
+        if (key, S) not in cache:
+            r = ref(pts, S)
+            r.setflags(write=False)
+            cache[(key, S)] = r
+        return cache[(key, S)]
+    return get
+
+
+def _tiles(n):
+    return max(1, -(-n // FPS_TILE))
+
+
+def _check(dev, expected, key, pts, S, path, n_tiles=None):
+    got, st = _run(dev, pts, S, path)
+    assert np.array_equal(got, expected(key, pts, S)), (key, S, path)
+    assert st["path"] == (path or (1 if len(pts) <= 8192 else 2))
+    if st["path"] != 1:
+        assert st["tile_steps"] == (n_tiles or _tiles(len(pts))) * (S - 1)
+        if path == 3:
+            assert st["tiles_updated"] == st["tile_steps"]
+    return st
+
+
+@pytest.mark.parametrize("path", [1, 2, 3])
+@pytest.mark.parametrize("n", FPS_SINGLE_SEAMS)
+def test_single_instantiation_seams(dev, expected, n, path):
+    """fps_single_k<1, 2, 4, 8> at 1024, 2048, 4096, 8192 points, one below and one above: the two far points sit at the end
+    of the input, in the highest slot in use; at 8192 no padding slot is left.  The tile paths at the same sizes"""
+    _check(dev, expected, ("seam", n), fps_seam_cloud(n, n), 64, path)
+
+
+@pytest.mark.parametrize("path", [1, 2, 3])
+@pytest.mark.parametrize("n", [1025, 8192])
+@pytest.mark.parametrize("S", [2, 3, -1])
+def test_single_sample_counts(dev, expected, S, n, path):
+    """one and two steps (each parity of the double-buffered LDS alone) and all n - 1 samples in one launch"""
+    _check(dev, expected, ("seam", n), fps_seam_cloud(n, n), S if S > 0 else n - 1, path)
+
+
+@pytest.mark.parametrize("path", [1, 2, 3])
+@pytest.mark.parametrize("n", [2049, 4097])
+def test_ties_across_slots(dev, expected, n, path):
+    """exact distance ties on a lattice: the lowest index wins across register slots, lanes, waves and tiles"""
+    _check(dev, expected, ("lattice", n), shaped_clouds(n)["lattice"], 500, path)
+
+
+@pytest.mark.parametrize("S,path", [(64, 0), (8192, 0), (64, 3), (8192, 3)])
+def test_crossover_8193(dev, expected, S, path):
+    """one point past the one-workgroup path: 17 tiles, the last one holds a single point -- one of the first three samples"""
+    n = FPS_CROSSOVER
+    st = _check(dev, expected, ("seam", n), fps_seam_cloud(n, n), S, path, n_tiles=17)
+    assert st["path"] == (path or 2)
+
+
+def test_crossover_both_sides(dev, expected):
+    """8192 points still take the one-workgroup path by default; 8193 cannot be forced onto it"""
+    st = _check(dev, expected, ("seam", 8192), fps_seam_cloud(8192, 8192), 64, 0)
+    assert st["path"] == 1
+    with pytest.raises(dev.M3DError, match="at most 8192 points"):
+        _run(dev, fps_seam_cloud(FPS_CROSSOVER, 0), 64, 1)
+
+
+@pytest.mark.parametrize("path", [2, 3])
+@pytest.mark.parametrize("nonfinite", [0, 3])
+@pytest.mark.parametrize("n_finite", [20 * FPS_TILE, 20 * FPS_TILE + 1])
+def test_tile_edges(dev, expected, n_finite, nonfinite, path):
+    """the finite points fill 20 tiles to the last slot, or leave one point for a 21st; with three non-finite rows outside
+    the tiles (the constant +inf candidate) and with none"""
+    pts = fps_tile_edge_cloud(n_finite, nonfinite, 3)
+    _check(dev, expected, ("edge", n_finite, nonfinite), pts, 64, path, n_tiles=_tiles(n_finite))
+
+
+@pytest.fixture(scope="module")
+def second_trip_cloud():
+    pts = np.random.default_rng(31).uniform(-1, 1, (FPS_SECOND_TRIP_N, 3))
+    pts.setflags(write=False)
+    return pts
+
+
+@pytest.mark.parametrize("path", [0, 3])
+def test_second_trip_of_the_tile_loop(dev, expected, second_trip_cloud, path):
+    """6145 tiles: the step kernel's 1024 workgroups of 4 waves walk them in two trips, a third of the tiles in the second.
+    Were that trip lost, all 31 selections would have to fall into the first two thirds: (2/3)^31 ~ 3e-6"""
+    S = 32
+    st = _check(dev, expected, "second_trip", second_trip_cloud, S, path)
+    assert st["path"] == (path or 2) and st["tile_steps"] // (S - 1) > 4096
+
+
+@pytest.mark.parametrize("path", [0, 3])
+@pytest.mark.parametrize("name", ["inf_extent", "inf_extent_nonfinite", "subnormal_extent"])
+def test_unsorted_layout(dev, expected, name, path):
+    """an extent that overflows or is subnormal: every point in input order in the tiles, the non-finite rows among them and
+    no constant candidate"""
+    st = _check(dev, expected, ("unsorted", name), fps_unsorted_clouds()[name], 40, path, n_tiles=18)
+    assert st["path"] == (path or 2)
 
 
 def test_65537_default_path(dev, ref):

@@ -1,7 +1,9 @@
 """m3d_voxel_down_sample / _multi on the MI355X: the output points, normals and colours equal the plain-C restatement of the
 contract (tests/cpp/voxel_ref.c) BIT FOR BIT and in the same order -- every comparison is np.array_equal on the fp64
 arrays viewed as uint64 -- over sizes 1 .. 250 000 x six cloud shapes x three voxel sizes, with normals, NaN normals,
-colours and neither; points on voxel faces; skew; wide keys and the forced general path; the golden PLY; the multi-level
+colours and neither; points on voxel faces; skew; wide keys and the forced general path; the seams of the kernels (0 .. 3 sort passes at exact voxel counts, 63 .. 129
+members around the 64-member batch of the means with NaN normals on its edges, element counts around the sort's, the scan's
+and the bounds kernel's tiles); the golden PLY; the multi-level
 call; the trace; 1 M points, repeated and from four threads; the errors; the Python API, the C++ mirror, and the chain
 into preprocess_fragment."""
 import os
@@ -12,7 +14,8 @@ import numpy as np
 import pytest
 
 from fps_ref_util import shaped_clouds
-from voxel_ref_util import bits, build_ref, extent, faces_cloud, faces_fraction_moved, same, unit_normals
+from voxel_ref_util import (SEAM_HEAD, VOXEL_ELEMENT_SEAMS, VOXEL_PASS_SEAMS, bits, build_ref, extent, faces_cloud,
+                            faces_fraction_moved, same, seam_head, seam_normals, unit_normals, voxel_seam_cloud)
 
 pytestmark = pytest.mark.gpu
 
@@ -115,6 +118,56 @@ def test_wide_keys_and_forced_general_path(dev, ref):
         dev.voxel_force_path(0)
     assert st_fast["path"] == dev.VOXEL_PATH_PACKED and st_wide["path"] == dev.VOXEL_PATH_WIDE
     assert _same_all(wide, fast) and _same_all(fast, ref(pts, v, nrm))
+
+
+# ---- the kernels' seams (the clouds and what they promise: voxel_ref_util.py, shown on the CPU in test_voxel.py): every
+# result equals the checker's bit for bit, trace included
+def _seam_run(dev, ref, pts, nrm, col, wide, passes):
+    dev.voxel_force_path(dev.VOXEL_PATH_WIDE if wide else 0)
+    try:
+        got, st = dev.voxel_down_sample(pts, 1.0, nrm, col, trace=True, stats=True)
+    finally:
+        dev.voxel_force_path(0)
+    exp = ref(pts, 1.0, nrm, col)
+    assert st["path"] == (dev.VOXEL_PATH_WIDE if wide else dev.VOXEL_PATH_PACKED)
+    assert st["sort_passes"] == passes and st["n_voxels"] == len(exp["points"])
+    assert _same_all(got, exp)
+    return exp
+
+
+@pytest.mark.parametrize("wide", [False, True])
+@pytest.mark.parametrize("m,n,head,passes", VOXEL_PASS_SEAMS)
+def test_sort_pass_seams(dev, ref, m, n, head, passes, wide):
+    """m voxels exactly, on both sides of every change of the number of 8-bit sort passes: 0, 1, 1, 2, 2, 3"""
+    pts, cell = voxel_seam_cloud(m, n, head, seed=m)
+    exp = _seam_run(dev, ref, pts, seam_normals(cell, m), None, wide, passes)
+    assert len(exp["points"]) == m
+
+
+@pytest.mark.parametrize("colours", [False, True])
+def test_member_seams(dev, ref, colours):
+    """voxels of 1, 63, 64, 65, 128 and 129 members around the 64 voxel_means_k stages at a time, NaN normals on the last
+    member of a batch and the first of the next: a skip flag that outlived its batch would drop or add a normal"""
+    pts, cell = voxel_seam_cloud(257, 4096, SEAM_HEAD, seed=257)
+    col = np.random.default_rng(257).uniform(0, 1, pts.shape) if colours else None
+    exp = _seam_run(dev, ref, pts, seam_normals(cell, 257), col, False, 2)
+    assert all(int((exp["counts"] == h).sum()) == 1 for h in SEAM_HEAD[1:])
+
+
+@pytest.mark.parametrize("nan_normals", [False, True])
+@pytest.mark.parametrize("n", VOXEL_ELEMENT_SEAMS)
+def test_element_seams(dev, ref, n, nan_normals):
+    """n around the sort's round and tile, the scan's tile, the bounds kernel's grid and the 256 tile sums of the scan's
+    middle step.  Without attributes: the highest cell's only point is the last row.  With NaN-row normals: the same
+    cloud reversed, so that the lattice corner -- which alone sets vmin -- is the last row"""
+    m = min(n, 300)
+    pts, _ = voxel_seam_cloud(m, n, seam_head(m, n), seed=n, highest_last=True)
+    nrm = None
+    if nan_normals:
+        pts = np.ascontiguousarray(pts[::-1])
+        nrm = unit_normals(n, n, max(n // 20, 1))
+    exp = _seam_run(dev, ref, pts, nrm, None, False, ((m - 1).bit_length() + 7) // 8)
+    assert len(exp["points"]) == m
 
 
 def test_golden_ply(dev, ref):

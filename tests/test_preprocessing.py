@@ -1,5 +1,5 @@
 """misc3d.preprocessing without a GPU: the C restatement of FarthestPointSampling (tests/cpp/fps_ref.c) against a numpy
-one, the early cases of m3d_farthest_point_sampling (decided before any device is touched), CropROIPointCloud's index
+one, what the seam clouds of the GPU tests promise (fps_ref_util.py), shown from the two restatements alone, the early cases of m3d_farthest_point_sampling (decided before any device is touched), CropROIPointCloud's index
 formula (m3d_crop_roi_indices, host only), the exported symbols, and the pruned path's tile bound on the host
 (tests/cpp/test_fps_bound.cpp over misc3d_amd/csrc/m3d_fps_fp.hpp)."""
 import ctypes
@@ -9,7 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from fps_ref_util import build_ref, fps_numpy, quirk_clouds, shaped_clouds
+from fps_ref_util import (FPS_CROSSOVER, FPS_SINGLE_SEAMS, FPS_TILE, build_ref, fps_numpy, fps_seam_cloud, fps_tie_steps,
+                          fps_tile_edge_cloud, fps_unsorted_clouds, quirk_clouds, shaped_clouds)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -42,6 +43,58 @@ def test_restatement_quirks(ref):
     assert nf[0] == 0 and (nf[1:] == 17).all()
     ov = ref(q["overflow"], 8)
     assert len(set(ov.tolist())) == 8
+
+
+@pytest.mark.parametrize("n", FPS_SINGLE_SEAMS + (FPS_CROSSOVER,))
+def test_seam_cloud_selects_its_last_two_points(ref, n):
+    """what the GPU seam tests rely on: the two points at the end of the input are among the first three samples, so a
+    kernel that loses its highest register slot, its last lane or its last tile cannot agree with the restatement"""
+    pts = fps_seam_cloud(n, n)
+    got = ref(pts, 64)
+    assert got[0] == 0 and {n - 1, n - 2} == set(got[1:3].tolist())
+    assert len(set(got.tolist())) == 64
+    assert np.array_equal(got, fps_numpy(pts, 64))
+    for S in (2, 3):
+        assert np.array_equal(ref(pts, S), got[:S])
+
+
+@pytest.mark.parametrize("n", [2049, 4097])
+def test_lattice_clouds_have_ties(ref, n):
+    """the lattice clouds of the GPU tie tests: at some steps several points hold the largest distance exactly"""
+    pts = shaped_clouds(n)["lattice"]
+    assert len(pts) == n
+    assert fps_tie_steps(pts, 500) >= 10
+    assert np.array_equal(ref(pts, 500), fps_numpy(pts, 500))
+
+
+def test_unsorted_layout_clouds(ref):
+    """the extents no sorting grid can take, and what the restatement gives on them"""
+    clouds = fps_unsorted_clouds()
+    with np.errstate(over="ignore", invalid="ignore"):
+        for name, pts in clouds.items():
+            assert pts.shape == (9001, 3)
+            fin = pts[np.isfinite(pts).all(axis=1)]
+            ext = (fin.max(axis=0) - fin.min(axis=0)).max()
+            assert np.isinf(ext) if name != "subnormal_extent" else 0 < ext < 1e-290, name
+            assert np.array_equal(ref(pts, 40), fps_numpy(pts, 40)), name
+    a = ref(clouds["inf_extent"], 40)
+    assert a[:3].tolist() == [0, 100, 7000] and len(set(a.tolist())) == 40
+    b = ref(clouds["inf_extent_nonfinite"], 40)
+    assert b[:2].tolist() == [0, 100] and (b[2:] == 5000).all()
+    assert not ref(clouds["subnormal_extent"], 40).any()
+
+
+@pytest.mark.parametrize("n_finite", [20 * FPS_TILE, 20 * FPS_TILE + 1])
+def test_tile_edge_clouds(ref, n_finite):
+    full = fps_tile_edge_cloud(n_finite, 0, 3)
+    assert len(full) == n_finite and np.isfinite(full).all()
+    assert np.array_equal(ref(full, 64), fps_numpy(full, 64))
+    pts = fps_tile_edge_cloud(n_finite, 3, 3)
+    rows = np.nonzero(~np.isfinite(pts).all(axis=1))[0]
+    assert len(pts) == n_finite + 3 and len(rows) == 3 and rows[0] > 0
+    got = ref(pts, 64)
+    assert got[0] == 0 and (got[1:] == rows[0]).all()       # the lowest non-finite index at step 1, then for ever
+    assert np.array_equal(got, fps_numpy(pts, 64))
 
 
 def test_restatement_orders_differ_only_in_association(tmp_path):

@@ -1,5 +1,6 @@
 """Voxel down-sampling without a GPU: the plain-C checker (tests/cpp/voxel_ref.c) against an independent numpy restatement of
-the contract, its error paths, properties it must have on the clouds the GPU tests use, and the C ABI's argument checks
+the contract, its error paths, properties it must have on the clouds the GPU tests use, what the seam clouds of the GPU tests promise (exactly m voxels,
+the member counts around the 64-member batch, NaN normals on the batch edges, the bounds set by the last row), and the C ABI's argument checks
 and exported symbols."""
 import ctypes as C
 
@@ -7,8 +8,9 @@ import numpy as np
 import pytest
 
 from fps_ref_util import shaped_clouds
-from voxel_ref_util import (RefError, bits, build_ref, extent, faces_cloud, faces_fraction_moved, same, unit_normals,
-                            voxel_indices, voxel_numpy)
+from voxel_ref_util import (SEAM_HEAD, VOXEL_ELEMENT_SEAMS, VOXEL_PASS_SEAMS, RefError, bits, build_ref, extent, faces_cloud,
+                            faces_fraction_moved, same, seam_head, seam_normals, unit_normals, voxel_indices, voxel_numpy,
+                            voxel_seam_cloud)
 
 
 @pytest.fixture(scope="module")
@@ -94,6 +96,70 @@ def test_checker_properties(ref, n):
             lo, hi = vmin + cell * v, vmin + (cell + 1) * v
             slack = 4 * np.finfo(np.float64).eps * (np.abs(pts).max() + abs(vmin).max() + v)
             assert np.all(r["points"] >= lo - slack) and np.all(r["points"] <= hi + slack), (name, div)
+
+
+def _seam_promise(r, m, head):
+    """from the checker's counts alone: exactly m voxels, and exactly one voxel with each member count of the head (of the
+    count 1 at least one: where n < 2 m the dealt voxels cannot but hold single points as well)"""
+    counts = r["counts"]
+    return len(counts) == m and all(int((counts == h).sum()) == 1 if h > 1 else (counts == 1).any() for h in head)
+
+
+@pytest.mark.parametrize("m,n,head,passes", VOXEL_PASS_SEAMS + ((300, 524_289, SEAM_HEAD, 2),))
+def test_seam_cloud_keeps_its_promise(ref, m, n, head, passes):
+    """the clouds of the GPU seam tests: m is exact (so the number of sort passes is known), the member counts around the
+    64-member batch are there, vmin is exactly 0, and the two restatements agree with the NaN normals in place"""
+    assert passes == ((m - 1).bit_length() + 7) // 8
+    pts, cell = voxel_seam_cloud(m, n, head, seed=m)
+    assert pts.shape == (n, 3) and np.array_equal(pts.min(axis=0), [0.5, 0.5, 0.5]) and np.array_equal(pts[0], [0.5, 0.5, 0.5])
+    nrm = seam_normals(cell, m)
+    r = ref(pts, 1.0, nrm)
+    assert _seam_promise(r, m, head)
+    assert np.array_equal(np.sort(r["counts"]), np.sort(np.bincount(cell)))
+    assert not np.isnan(r["normals"]).any()                       # a NaN normal is left out, never added
+    if n <= 70_001:
+        assert _same_all(r, voxel_numpy(pts, 1.0, nrm))
+
+
+def test_seam_normals_sit_on_the_batch_edges(ref):
+    """in the 65- and 129-member voxels the NaN normals are the members 0, 63, 64 (127, 128) in ascending point index, and
+    leaving exactly those out is what the checker does"""
+    pts, cell = voxel_seam_cloud(257, 4096, SEAM_HEAD, seed=257)
+    nrm = seam_normals(cell, 257)
+    bad = np.isnan(nrm).any(axis=1)
+    assert int(bad.sum()) == 8 and np.allclose(np.linalg.norm(nrm[~bad], axis=1), 1.0)
+    counts = np.bincount(cell)
+    r = ref(pts, 1.0, nrm)
+    for size, positions in ((65, [0, 63, 64]), (129, [0, 63, 64, 127, 128])):
+        (c,) = np.nonzero(counts == size)[0]
+        members = np.nonzero(cell == c)[0]
+        assert np.nonzero(bad[members])[0].tolist() == positions
+        keep = members[~bad[members]]
+        acc = np.zeros(3)
+        for i in keep:
+            acc += nrm[i]
+        row = int(r["point_to_voxel"][members[0]])
+        assert r["counts"][row] == size and np.array_equal(bits(r["normals"][row]), bits(acc / np.float64(size)))
+    others = ~np.isin(cell, np.nonzero((counts == 65) | (counts == 129))[0])
+    assert not bad[others].any()
+
+
+@pytest.mark.parametrize("n", VOXEL_ELEMENT_SEAMS)
+def test_element_seam_cloud_keeps_its_promise(ref, n):
+    """m = min(n, 300) voxels exactly; the highest cell's single point is the last row and alone sets an upper bound; the
+    reversed cloud has the lattice corner, which alone sets vmin, as its last row"""
+    m = min(n, 300)
+    head = seam_head(m, n)
+    pts, cell = voxel_seam_cloud(m, n, head, seed=n, highest_last=True)
+    assert cell[n - 1] == m - 1 and int((cell == m - 1).sum()) == 1
+    assert (pts[n - 1] >= pts.max(axis=0)).sum() >= 1 and (pts[: n - 1].max(axis=0) < pts.max(axis=0)).any()
+    r = ref(pts, 1.0)
+    assert _seam_promise(r, m, head) and (len(head) == 6) == (n >= 2047)
+    back = ref(pts[::-1], 1.0)
+    assert np.array_equal(pts[::-1][n - 1], [0.5, 0.5, 0.5]) and (pts[::-1][: n - 1] > 0.5).all()
+    assert len(back["counts"]) == m and np.array_equal(np.sort(back["counts"]), np.sort(r["counts"]))
+    if n <= 4097:
+        assert _same_all(r, voxel_numpy(pts, 1.0)) and _same_all(back, voxel_numpy(pts[::-1], 1.0))
 
 
 def test_symbols_exported(capi):

@@ -147,6 +147,72 @@ def faces_fraction_moved(xyz, v):
     return float((a != b).any(axis=1).mean())
 
 
+# Member counts around the 64 members voxel_means_k stages at a time: one short of a batch, a full one, one into the second,
+# two full ones, one into the third.
+SEAM_HEAD = (1, 63, 64, 65, 128, 129)
+# (m voxels, n points, head, sort passes): m on both sides of every change of (bit_width(m - 1) + 7) / 8.  The head is
+# SEAM_HEAD wherever m voxels can hold it.
+VOXEL_PASS_SEAMS = ((1, 65, (65,), 0), (2, 2049, (129,), 1), (256, 4097, SEAM_HEAD, 1), (257, 4096, SEAM_HEAD, 2),
+                    (65_536, 70_000, SEAM_HEAD, 2), (65_537, 70_001, SEAM_HEAD, 3))
+# element counts around the sort's round (64) and tile (2048, also the scan's tile) with m = min(n, 300) voxels, and around
+# the bounds kernel's grid (1024 x 256 threads) and the 256 tile sums scan_sums_k takes at a time (256 x 2048 elements)
+VOXEL_ELEMENT_SEAMS = (63, 64, 65, 2047, 2048, 2049, 4095, 4096, 4097, 262_144, 262_145, 524_287, 524_288, 524_289)
+
+
+def seam_head(m, n):
+    """SEAM_HEAD where m voxels of n points can hold it with one voxel left over for the highest cell, else no head"""
+    return SEAM_HEAD if m > len(SEAM_HEAD) and n >= sum(SEAM_HEAD) + m - len(SEAM_HEAD) else ()
+
+
+def voxel_seam_cloud(m, n, head=(), seed=0, highest_last=False):
+    """(points, cell of every point): n points in exactly m voxels of size 1.0.  Voxel c is cell c of a lattice of side
+    ceil(cbrt(m)) and holds exactly head[c] points for c < len(head); the other points are dealt at random over the other
+    voxels, at least one each.  Points are cell + 0.5 + U[0, 0.4); index 0 is the lattice corner (0.5, 0.5, 0.5), so vmin
+    is exactly 0; the order of the other points is shuffled.  highest_last: the highest cell holds one point, at index
+    n - 1 and in the cell's far corner region (cell + 0.9), so the upper bounds come from the last element read"""
+    rng = np.random.default_rng(seed)
+    head = [int(h) for h in head]
+    rest_cells = m - len(head)
+    rest_points = n - sum(head)
+    assert 1 <= m <= n and len(head) <= m and all(h >= 1 for h in head)
+    assert rest_points >= rest_cells and (rest_cells > 0 or rest_points == 0)
+    assert not highest_last or (m >= 2 and rest_cells >= (2 if rest_points > rest_cells else 1))
+    counts = np.ones(m, dtype=np.int64)
+    counts[:len(head)] = head
+    free = rest_cells - (1 if highest_last else 0)            # cells that take the points left after one each
+    extra = rest_points - rest_cells
+    if extra:
+        counts[len(head):len(head) + free] += np.bincount(rng.integers(0, free, extra), minlength=free)
+    cell = np.repeat(np.arange(m), counts)
+    assert len(cell) == n and cell[0] == 0
+    side = 1
+    while side ** 3 < m:
+        side += 1
+    ijk = np.stack([cell % side, (cell // side) % side, cell // (side * side)], 1).astype(np.float64)
+    pts = ijk + 0.5 + rng.uniform(0, 0.4, (n, 3))
+    pts[0] = 0.5
+    last = n - 1 if highest_last else n                       # (the highest cell's single point is the last row already)
+    if highest_last:
+        pts[n - 1] = ijk[n - 1] + 0.9
+    perm = np.concatenate([[0], 1 + rng.permutation(last - 1), np.arange(last, n)]).astype(np.int64)
+    return np.ascontiguousarray(pts[perm]), cell[perm]
+
+
+def seam_normals(cell, seed=0):
+    """unit normals; in the voxels with exactly 65 and 129 members, the members at positions 0, 63 and 64 in ascending point
+    index (the two sides of the first batch's end) get a NaN component, in the 129-member voxel 127 and 128 as well"""
+    nrm = unit_normals(len(cell), seed)
+    counts = np.bincount(cell)
+    k = 0
+    for size, positions in ((65, (0, 63, 64)), (129, (0, 63, 64, 127, 128))):
+        for c in np.nonzero(counts == size)[0]:
+            members = np.nonzero(cell == c)[0]
+            for pos in positions:
+                nrm[members[pos], k % 3] = np.nan
+                k += 1
+    return nrm
+
+
 def unit_normals(n, seed=0, nan_rows=0):
     rng = np.random.default_rng(seed + 1000)
     v = rng.standard_normal((n, 3))
