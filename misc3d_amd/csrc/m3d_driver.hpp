@@ -110,9 +110,12 @@ struct ChunkSlot {
 // One LANE of a device: a compute stream with everything a call needs beside its arguments (streams, events, scratch,
 // pinned words).  A device has up to m3d_config.lanes of them (created on demand); a call holds ONE lane from entry to
 // return (`mu`), so calls on different lanes -- other host threads -- run side by side on the device: one thread's upload
-// and host-side replay under another's kernels (SURVEY.md 8(b) "Threading"; the caller this is for:
-// /root/reference/src/pipeline.cpp:428-439, one std::thread per fragment pair).  Resident objects (m3d_cloud, m3d_reg)
-// stay on the lane they were created on.
+// and host-side replay under another's kernels (SURVEY.md 8(b) "Threading"; the caller this is for: the reference's
+// src/pipeline.cpp:428-439, one std::thread per fragment pair).  Resident objects (m3d_cloud, m3d_reg) stay on the lane they
+// were created on.  A lane holds RESOURCES only -- and the sequence counters that pair with its pinned completion words
+// (pick_seq, mask_seq, sync_seq): nothing here describes a call in progress or points into a caller's arrays or a cloud.
+// What a fit's caller asks for, what a segmentation keeps between its rounds and what is known of a queued compaction are
+// values with those lifetimes (FitCaller, SegmentRounds, Compaction: m3d_driver_internal.hpp), passed as arguments.
 struct DeviceCtx {
     int device = -1;    // PHYSICAL HIP ordinal (hipSetDevice)
     int logical = -1;   // the ordinal the caller used: the same unless m3d_config.device_aliases maps several logical devices to one
@@ -135,57 +138,22 @@ struct DeviceCtx {
     size_t seg_staging_cap = 0;    // ... in uint64 entries
     PinBuf h_inc;              // m3d_cloud_score_shard: the sampler's pruning incumbent on its way to / from the device
     uint32_t pick_seq = 0;     // last PickFinal::seq handed out (completion words of one-GPU speculative chunks)
-    const double* last_best_dev = nullptr;   // device address of the last fit's best minimal model (a slot's params or best_params)
     // m3d_cloud_create's upload / sort scratch (a one-shot call -- upload, fit, destroy -- otherwise spends more time
     // in hipMalloc / hipFree than in the fit; the cloud's own buffers come back through DevBuf's free list)
     DevBuf cc_stage, cc_bbox;
     CellSort cc_sort;
     DevBuf pick;               // BestPick: the device's prediction of the winning hypothesis (probability-1 fits)
-    PinBuf h_pick;             // BestPickHost mirror (+ at byte 64: inlier total of a compaction started on the prediction)
-    bool spec_compaction = false;   // RefineModel's compaction has already been queued on pick->params
-    // Deferred RefineModel (m3d_segment_plane_iterative on one GPU): a round whose early compaction ran on the hypothesis
-    // the replay then named does not wait for it -- the inlier count is the scoring pass's, the index list goes to the
-    // caller's pinned array by itself -- and its GeneralFit is finished from the pinned sums while the NEXT round's records
-    // are awaited (two slots of h_best / h_moments / the total word: the next round's compaction is queued before that)
-    // segment_impl, rounds on a large part of the cloud: the inlier list (megabytes) is written to device memory
-    // (idx_out_override, the cluster's slice of a per-call buffer) and shipped by the copy engine under the rounds that
-    // follow, instead of being stored over the host link by the compaction kernel itself (which then runs at the link's
-    // rate: 370 us for 2.5 M indices); the copy stream is waited for once, at the end of the call
-    uint64_t* idx_out_override = nullptr;
-    bool defer_copy_sync = false;
-    bool no_prune_hint = false;     // segment_impl: the next fit's chunk will prune nothing (no lead pass, no keep masks)
-    bool defer_refine = false;
-    int refine_slot = 0;
-    struct DeferredRefine {
-        bool pending = false;
-        int slot = 0;
-        uint32_t ni = 0;
-        double* params_out = nullptr;
-    } deferred;
-    // a tombstone pass that waits for the next fit's minimal_fit_k launch to ride in (cloud_remove_issue -> issue_chunk)
-    PoisonJob pending_poison;
-    bool poison_pending = false;
-    uint64_t* poison_expected_at = nullptr, poison_pending_count = 0;   // m3d_cloud::Work::poison_expected, credited at launch
-    DevBuf poison_total;            // launch_poison_plane_inliers' running count
-    bool ev_compact_early = false;  // ... and ev_compact was recorded right behind it (a removal has been queued after it)
-    bool spec_hit = false;          // ... and the replay named the same hypothesis (cloud_fit_locked)
+    PinBuf h_pick;             // BestPickHost mirror (+ from byte 64: inlier total of a compaction started on the prediction, two slots)
+    DevBuf poison_total;       // launch_poison_plane_inliers' running count (tombstones of a segmentation's sorted copy)
     PinBuf h_sums;             // GeneralFit: per-workgroup moment partials + coordinate sums, written by the kernels
     DevBuf moment_partial;     // fused RefineModel: per-workgroup raw moments of the compaction's counting pass
     PinBuf h_moments;          // ... folded (scan_blocks_k), device-visible: kFusedMomentDoubles doubles
     hipEvent_t ev_pre_gate = nullptr;         // recorded on `stream` where a fit starts; pre_stream waits for it (pre_stream_gate)
-    bool compaction_fused = false;            // the compaction in flight carried the moments
-    uint64_t* compaction_idx_host = nullptr;  // ... and wrote the index list to this page-locked destination as well
-    // ... or, compaction_mask (m3d_config.list_mask): shipped the inliers as a bit mask + per-tile counts instead, which
-    // refine() expands into compaction_idx_host after its wait (m3d_mask_expand.hpp); the device list (idx) is not written
-    bool compaction_mask = false;
+    // a mask compaction (m3d_config.list_mask, Compaction::mask in m3d_driver_internal.hpp): the inliers as a bit mask + per-tile
+    // counts, which refine() expands into the caller's page-locked list after its wait (m3d_mask_expand.hpp)
     PinBuf h_mask, h_tile_counts;
     uint32_t mask_seq = 0;   // ... whose last launch stores this value into h_sync word 1 (its completion: no signal_host_k)
-    // m3d_config.mask_early: ... and, before anything else, into h_sync word 2 ("mask ready": the mask and the tile counts are in
-    // host memory) -- refine() expands the list under that launch's fold of the moments and waits for word 1 afterwards
-    bool compaction_mask_early = false;
-    // segmentation: asked by refine() right before it queues RefineModel's compaction -- given the inlier count the scoring
-    // pass reported, where should the partition of the NON-inliers go (null: no partition in this pass)?
-    const std::function<const m3d::PartitionOut*(int64_t)>* partition_hook = nullptr;
+                             // and, m3d_config.mask_early, before anything else into h_sync word 2 ("mask ready")
     PinBuf h_best;             // best minimal model of a fit on its way to the host (read after RefineModel's wait)
     PinBuf h_sync;             // stream_wait_spin's completion word [0], a mask compaction's completion [1] and "mask ready" [2] words
     PinBuf h_reg;              // registration: a chunk's pass flags / counts and sums on their way to the host (polled, not waited for)

@@ -274,13 +274,16 @@ static int issue_chunk(DeviceCtx* ctx, ChunkSlot& s, const CloudView& v, const S
                                                                  the chunk is about to overwrite: moved to ctx->best_params
                                                                  first, on the stream MinimalFit will run on */,
                        bool first_of_stream = false /* m3d_cloud_score_shard, one rank, from hypothesis 0: a fit's first chunk in all
-                                                       but the incumbent's clearing (the caller's): reference histograms as for new_fit */) {
+                                                       but the incumbent's clearing (the caller's): reference histograms as for new_fit */,
+                       SegmentRounds* rounds = nullptr /* a segmentation's fit: the previous round's tombstone pass may be waiting
+                                                          to ride in this chunk's minimal_fit_k launch */) {
+    const bool kill_rides = rounds && rounds->poison_pending && kind == M3D_PLANE;
     const int m = minimal_sample(kind);
     const uint32_t count = (uint32_t)(end - begin);
     const bool dense = use_dense_scoring();
     // where the chunk's head runs -- decided ONCE, here, in front of everything that depends on it (the record
     // move used to repeat a part of this condition in the caller)
-    pre = pre && !dense && prune && !new_fit && !comm && lead == 0 && !ctx->poison_pending && ctx->pre_stream && s.pre_done;
+    pre = pre && !dense && prune && !new_fit && !comm && lead == 0 && !(rounds && rounds->poison_pending) && ctx->pre_stream && s.pre_done;
     hipStream_t st_pre = pre ? ctx->pre_stream : ctx->stream;
     if (move_best_from)   // (before the slot's buffers are touched: a RESERVE below may hand the old block back)
         HIPCHK(hipMemcpyAsync(ctx->best_params.p, move_best_from, sizeof(double) * kModelStride, hipMemcpyDeviceToDevice, st_pre));
@@ -329,7 +332,7 @@ static int issue_chunk(DeviceCtx* ctx, ChunkSlot& s, const CloudView& v, const S
     const bool own_real_ = !comm || (size_t)rank * sl_pad < count;
     LeadPrep lp;
     const bool lead_prepared = use_lead && new_fit && own_real_ && lead <= h_pad && (uint32_t)kPairReplicas <= h_pad;
-    // no lead pass and nothing to prune against (a new fit's only chunk on one GPU, DeviceCtx::no_prune_hint): the same
+    // no lead pass and nothing to prune against (a new fit's only chunk on one GPU, FitCaller::no_prune_hint): the same
     // set-up for ALL groups -- keep everything, clear every counter replica -- and no keep_mask_k launch below
     const bool all_prepared = nothing_to_prune && !use_lead && lead == 0 && !dense && prune && new_fit && !comm &&
                               (uint32_t)kPairReplicas <= h_pad;
@@ -346,11 +349,11 @@ static int issue_chunk(DeviceCtx* ctx, ChunkSlot& s, const CloudView& v, const S
                        s.params.as<double>(), s.valid.as<uint8_t>(), st_pre,
                        (!dense && prune) ? s.ub.as<uint32_t>() : nullptr,    // clears ub[0 .. h_pad) on the way
                        new_fit ? ctx->best_count.as<uint32_t>() : nullptr, (lead_prepared || all_prepared) ? &lp : nullptr, sv.max_abs,
-                       cull32 ? &c32 : nullptr, (ctx->poison_pending && kind == M3D_PLANE) ? &ctx->pending_poison : nullptr,
+                       cull32 ? &c32 : nullptr, kill_rides ? &rounds->pending_poison : nullptr,
                        (!dense && prune) ? s.ub.as<uint32_t>() + h_pad : nullptr);
-    if (fit_launched && ctx->poison_pending && kind == M3D_PLANE) {   // (the previous round's tombstone pass went with it)
-        ctx->poison_pending = false;
-        if (ctx->poison_expected_at) *ctx->poison_expected_at += ctx->poison_pending_count;
+    if (fit_launched && kill_rides) {   // (the previous round's tombstone pass went with it)
+        rounds->poison_pending = false;
+        if (rounds->poison_expected_at) *rounds->poison_expected_at += rounds->poison_pending_count;
     }
     if (dense)
         HIPCHK(hipMemsetAsync(s.counts.p, 0, sizeof(uint32_t) * (size_t)h_pad, ctx->stream));
@@ -648,10 +651,12 @@ static void unpack_slot(ChunkSlot& s) {
 
 // ------------------------------------------------------------------------------------------------
 // RANSAC::FitModelParallel on a resident view.  Leaves the best minimal model in
-// device memory at ctx->last_best_dev; RefineModel's first kernel forwards it to ctx->h_best (pinned host).
+// device memory at RansacOut::best_dev; RefineModel's first kernel forwards it to ctx->h_best (pinned host).
 // ------------------------------------------------------------------------------------------------
 struct RansacOut {
     m3d_replay_state st;
+    const double* best_dev = nullptr;   // the best minimal model on the device (a slot's params or ctx->best_params)
+    Compaction spec;                    // RefineModel's compaction, if it was queued early, on pick->params (spec.early)
     uint64_t hypotheses_scored = 0;
     uint64_t exact_rmse_evals = 0;
     int32_t ties = 0;
@@ -666,11 +671,14 @@ struct RansacOut {
 };
 
 static int run_ransac(DeviceCtx* ctx, const CloudView& v, const SortedView& sv, int kind, double thr,
-                      size_t max_iter, double prob, uint64_t seed, RansacOut* out, size_t iterations_hint = 0,
+                      size_t max_iter, double prob, uint64_t seed, RansacOut* out, const FitCaller* fc = nullptr,
                       const uint32_t* orig_dev = nullptr /* index map of a shrunk cloud (RefineModel's compaction) */,
                       m3d_comm* comm = nullptr /* hypotheses sharded over its ranks (issue_chunk) */,
                       uint64_t* idx_host = nullptr /* the caller's page-locked index list (early compaction writes it) */) {
     m3d_replay_init(&out->st);
+    size_t iterations_hint = fc ? fc->iterations_hint : 0;
+    SegmentRounds* const rounds = fc ? fc->rounds : nullptr;
+    const int slot = refine_slot(fc);   // of the pinned words RefineModel's kernels write
     RESERVE(ctx->best_params, sizeof(double) * kModelStride);
     RESERVE(ctx->h_small, 256);
     // Probability-1 fits: nothing but fitness == 1 stops the loop, so the winner is (up to rmse ties) the hypothesis
@@ -686,7 +694,6 @@ static int run_ransac(DeviceCtx* ctx, const CloudView& v, const SortedView& sv, 
     // it IS the replay's winner unless the loop stops early after all or an rmse tie goes to a later hypothesis -- the
     // compaction (and the round's partition) is queued on the pick at once, and the host's ~15 us of waking up, replaying
     // and launching disappear from the round.  A miss redoes RefineModel, exactly as on the probability-1 path.
-    ctx->spec_compaction = false;
     // one GPU, culled path: every chunk ends with the completion word of sum_replicas_k's tail (and its pick, which only
     // probability-1 fits act on) -- the host polls pinned memory instead of waiting for an event
     const bool poll_done = !comm && !use_dense_scoring() && max_iter > 0;
@@ -743,8 +750,8 @@ static int run_ransac(DeviceCtx* ctx, const CloudView& v, const SortedView& sv, 
         chunk = (iterations_hint + iterations_hint / 16 + 16 + 63) / 64 * 64;
         // (a segmentation round in the clutter: the best plane holds well under a percent of the cloud while every
         // hypothesis' bound -- the population of the tiles its slab meets -- is tens of times that: nothing is ever pruned,
-        // and the lead pass that exists to prune costs a launch and a fold.  The caller says so: DeviceCtx::no_prune_hint.)
-        lead = ctx->no_prune_hint ? 0u : lead_size();
+        // and the lead pass that exists to prune costs a launch and a fold.  The caller says so: FitCaller::no_prune_hint.)
+        lead = fc->no_prune_hint ? 0u : lead_size();
         iterations_hint = 0;   // (consumed: no second chunk queued on the first pass)
     }
     chunk = std::min(std::min(chunk, chunk_cap), std::max<size_t>((max_iter + 63) / 64 * 64, 64));
@@ -767,7 +774,7 @@ static int run_ransac(DeviceCtx* ctx, const CloudView& v, const SortedView& sv, 
     auto issue_next = [&](int slot_id, size_t in_flight, size_t forced = 0) -> int {
         // a later chunk of a probability-1 fit on one GPU: its MinimalFit and box tests run on pre_stream, under the scoring
         // launches of the chunk before (issue_chunk, `pre`)
-        const bool pre = prestream_on && prob >= 1.0 && !comm && next_begin > 0 && !use_dense_scoring() && !ctx->poison_pending;
+        const bool pre = prestream_on && prob >= 1.0 && !comm && next_begin > 0 && !use_dense_scoring();
         // the slot holding the best model is recycled: issue_chunk moves the record out first, on the stream that is about
         // to overwrite the slot (MinimalFit of the new chunk)
         const double* move_best_from = slot_id == best_slot ? best_dev : nullptr;
@@ -802,7 +809,7 @@ static int run_ransac(DeviceCtx* ctx, const CloudView& v, const SortedView& sv, 
         int r = issue_chunk(ctx, ctx->slot[slot_id], v, sv, kind, thr, b, e, src, &out->ms_sample, true,
                             b == 0 ? lead : 0, b == 0, spec, comm, /*caller_ships_records=*/spec && !fused_pick,
                             fused_pick ? &pf : nullptr, /*nothing_to_prune=*/b == 0 && e == max_iter && lead == 0 && !comm, pre,
-                            move_best_from);
+                            move_best_from, /*first_of_stream=*/false, rounds);
         if (move_best_from && r == M3D_OK) {
             best_dev = ctx->best_params.as<double>();
             best_slot = -1;
@@ -810,20 +817,19 @@ static int run_ransac(DeviceCtx* ctx, const CloudView& v, const SortedView& sv, 
         const bool spec_adaptive = spec_enabled && prob < 1.0 && hinted_chunk && b == 0 && !comm && !use_dense_scoring();
         if (r == M3D_OK && fused_pick && (spec || spec_adaptive) && e == max_iter) {   // last chunk: RefineModel's first stage on the prediction, now
             // (a segmentation round: the partition of the rest rides along, decided without the inlier count: -2)
-            const PartitionOut* part = spec_adaptive && ctx->partition_hook && orig_dev ? (*ctx->partition_hook)(-2) : nullptr;
-            r = issue_refine_compaction(ctx, v, orig_dev, kind, thr, ctx->pick.as<BestPick>()->params,
-                                        h_best_at(ctx), h_total_at(ctx), /*fused=*/true,
-                                        idx_host, part);
-            ctx->spec_compaction = r == M3D_OK;
+            const PartitionOut* part = spec_adaptive && fc->partition_hook && orig_dev ? (*fc->partition_hook)(-2) : nullptr;
+            r = issue_refine_compaction(ctx, v, orig_dev, kind, thr, ctx->pick.as<BestPick>()->params, h_best_at(ctx, slot),
+                                        h_total_at(ctx, slot), fc, &out->spec, /*fused=*/true, idx_host, part);
+            out->spec.early = r == M3D_OK;
             // ... and so does the removal of the same inliers from the sorted copy (-3): by the time the host has replayed
             // the round and learnt the inlier count, the device is already through both
             // (RefineModel waits for ev_compact: recorded here, in front of the removal, not when refine() gets to run)
-            // (a round that may finish its RefineModel later -- DeviceCtx::defer_refine -- waits for no event at all)
-            if (r == M3D_OK && part && ctx->defer_refine) {
-                (void)(*ctx->partition_hook)(-3);
+            // (a round that may finish its RefineModel later -- FitCaller::defer_refine -- waits for no event at all)
+            if (r == M3D_OK && part && fc->defer_refine) {
+                (void)(*fc->partition_hook)(-3);
             } else if (r == M3D_OK && part && hipEventRecord(ctx->ev_compact, ctx->stream) == hipSuccess) {
-                ctx->ev_compact_early = true;
-                (void)(*ctx->partition_hook)(-3);
+                out->spec.ev_recorded = true;
+                (void)(*fc->partition_hook)(-3);
             }
         }
         if (r == M3D_OK && spec && !fused_pick) {
@@ -837,10 +843,10 @@ static int run_ransac(DeviceCtx* ctx, const CloudView& v, const SortedView& sv, 
             if (ship) sl.host_has_records = true;
             if (!sl.done_on_copy_stream) HIPCHK(hipEventRecord(sl.done, ctx->stream));
             if (e == max_iter) {   // last chunk: RefineModel's first stage on the prediction, now
-                r = issue_refine_compaction(ctx, v, orig_dev, kind, thr, ctx->pick.as<BestPick>()->params,
-                                            h_best_at(ctx), h_total_at(ctx), /*fused=*/true,
-                                            idx_host, nullptr, /*allow_mask=*/false);   // (sharded: the device writes the list)
-                ctx->spec_compaction = r == M3D_OK;
+                r = issue_refine_compaction(ctx, v, orig_dev, kind, thr, ctx->pick.as<BestPick>()->params, h_best_at(ctx, slot),
+                                            h_total_at(ctx, slot), fc, &out->spec, /*fused=*/true, idx_host, nullptr,
+                                            /*allow_mask=*/false);   // (sharded: the device writes the list)
+                out->spec.early = r == M3D_OK;
             }
         }
         if (r == M3D_OK) {
@@ -995,7 +1001,7 @@ static int run_ransac(DeviceCtx* ctx, const CloudView& v, const SortedView& sv, 
         HIPCHK(hipMemsetAsync(ctx->best_params.p, 0, sizeof(double) * kModelStride, ctx->stream));
         best_dev = ctx->best_params.as<double>();
     }
-    ctx->last_best_dev = best_dev;
+    out->best_dev = best_dev;
     if (timing_events) out->ms_score = now_ms() - t_score0;
     // The best minimal model travels to the host (pinned ctx->h_best) with RefineModel: its first kernel stores the
     // record there and RefineModel's own wait delivers it (no wait and no copy command here).
@@ -1027,19 +1033,19 @@ uint64_t resolve_seed(const uint64_t* seed) {
     return rd();
 }
 
-// GeneralFit of a round whose RefineModel was left running (DeviceCtx::deferred): the stream has passed its kernels
-int finalize_deferred_refine(DeviceCtx* ctx) {
-    DeviceCtx::DeferredRefine& d = ctx->deferred;
+// GeneralFit of a round whose RefineModel was left running (SegmentRounds::deferred): the stream has passed its kernels
+int finalize_deferred_refine(DeviceCtx* ctx, SegmentRounds& rounds) {
+    SegmentRounds::Deferred& d = rounds.deferred;
     if (!d.pending) return M3D_OK;
     d.pending = false;
-    const double* rec = ctx->h_best.as<double>() + (size_t)d.slot * kModelStride;
+    const double* rec = h_best_at(ctx, d.slot);
     uint32_t ni_chk;
-    std::memcpy(&ni_chk, ctx->h_pick.as<uint8_t>() + 64 + 8 * d.slot, 4);
+    std::memcpy(&ni_chk, h_total_at(ctx, d.slot), 4);
     if (ni_chk != d.ni) return fail(M3D_ERR_INTERNAL, "refine pass and scoring kernel disagree on the inlier count");
     double model[4] = {rec[0], rec[1], rec[2], rec[3]};   // the best minimal model, refined in place when GeneralFit succeeds
     const double c0[3] = {rec[4], rec[5], rec[6]};
     double mean[3], sums[14], out[4];
-    moments_about_mean(ctx->h_moments.as<double>() + (size_t)d.slot * kFusedMomentDoubles, c0, (double)d.ni, mean, sums + 4);
+    moments_about_mean(h_moments_at(ctx, d.slot), c0, (double)d.ni, mean, sums + 4);
     if (plane_from_moments(mean, sums + 4, out)) std::memcpy(model, out, sizeof(out));
     std::memcpy(d.params_out, model, sizeof(model));
     return M3D_OK;
@@ -1078,9 +1084,7 @@ static int ensure_plane_frames(m3d_cloud* c, int kind, size_t n_hypotheses) {
 
 int cloud_fit_locked(m3d_cloud* c, int kind, double thr, size_t max_iter, double prob,
                             uint64_t seed, double* params, size_t* inliers, size_t* n_inliers,
-                            m3d_stats* stats, const std::function<int(int64_t)>* before_refine_wait,
-                            size_t* iterations_hint /* in: iterations of a similar fit, out: of this one */,
-                            m3d_comm* comm) {
+                            m3d_stats* stats, FitCaller* fc, m3d_comm* comm) {
     DeviceCtx* ctx = c->ctx;
     const double t0 = now_ms();
     HIPCHK(hipSetDevice(ctx->device));
@@ -1097,29 +1101,30 @@ int cloud_fit_locked(m3d_cloud* c, int kind, double thr, size_t max_iter, double
     const CloudView gather = c->base_view();   // index lists / GeneralFit refer to the cloud as created
     const uint32_t* orig = c->orig();
     RansacOut ro;
-    uint64_t* idx_host = inliers && !ctx->idx_out_override &&
+    uint64_t* idx_host = inliers && !(fc && fc->idx_dev) &&
                                  is_library_pinned(inliers, sizeof(uint64_t) * (size_t)std::max<uint32_t>(v.n, 1))
                              ? reinterpret_cast<uint64_t*>(inliers) : nullptr;
-    ctx->compaction_idx_host = nullptr;
-    ctx->compaction_fused = false;
-    ctx->compaction_mask = false;
-    ctx->spec_hit = false;
-    ctx->ev_compact_early = false;
-    if (ctx->defer_refine) ctx->refine_slot ^= 1;   // (the previous fit's words may still be waiting for finalize_deferred_refine)
-    int rc = run_ransac(ctx, v, c->sorted(), kind, thr, max_iter, prob, seed, &ro, iterations_hint ? *iterations_hint : 0,
-                        orig, comm, idx_host);
+    SegmentRounds* const rounds = fc ? fc->rounds : nullptr;
+    if (rounds) rounds->spec_hit = false;
+    if (fc && fc->defer_refine) rounds->slot ^= 1;   // (the previous fit's words may still be waiting for finalize_deferred_refine)
+    const int slot = refine_slot(fc);
+    int rc = run_ransac(ctx, v, c->sorted(), kind, thr, max_iter, prob, seed, &ro, fc, orig, comm, idx_host);
     if (rc != M3D_OK) return rc;
     // (this fit's records have arrived: the stream is past the previous fit's RefineModel)
-    rc = finalize_deferred_refine(ctx);
+    if (rounds) rc = finalize_deferred_refine(ctx, *rounds);
     if (rc != M3D_OK) return rc;
-    if (iterations_hint) *iterations_hint = (size_t)ro.st.iterations;
+    if (fc) {
+        fc->iterations_hint = (size_t)ro.st.iterations;
+        fc->best_dev = ro.best_dev;   // (before the hooks run: the removal they queue reads the model there)
+    }
     const double t1 = now_ms();
     double model[kModelStride] = {0, 0, 0, 0, 0, 0, 0, 0};   // filled from ctx->h_best by refine's wait
     size_t ni = 0;
     int gf_ok = 1;
     const int64_t expected = ro.st.best_index >= 0 ? (int64_t)ro.st.best_count : -1;
     bool refined = false, deferred_now = false;
-    if (ctx->spec_compaction) {
+    bool hook_due = true;   // fc->before_refine_wait has not run yet
+    if (ro.spec.early) {
         // the compaction is already running on the device's pick (its record reached pinned memory with the chunk's
         // completion word): RefineModel is finished on it if the replay named the same hypothesis -- it does unless an rmse
         // tie went the other way or, on the adaptive path, the loop stopped early after all.  Otherwise the speculative
@@ -1130,47 +1135,42 @@ int cloud_fit_locked(m3d_cloud* c, int kind, double thr, size_t max_iter, double
         const bool hit = !ph->tie && (ro.st.best_index >= 0 ? (ph->have && ph->index == (unsigned long long)ro.st.best_index) : !ph->have);
         ro.spec_hits = hit ? 1 : 0;
         ro.spec_misses = hit ? 0 : 1;
-        ctx->spec_hit = hit;
-        const bool defer = hit && ctx->defer_refine && !comm && kind == M3D_PLANE && expected >= 3 && ctx->compaction_fused &&
-                           inliers && ctx->compaction_idx_host == reinterpret_cast<uint64_t*>(inliers) && before_refine_wait &&
+        if (rounds) rounds->spec_hit = hit;
+        const bool defer = hit && fc && fc->defer_refine && !comm && kind == M3D_PLANE && expected >= 3 && ro.spec.fused &&
+                           inliers && ro.spec.idx_host == reinterpret_cast<uint64_t*>(inliers) && fc->before_refine_wait &&
                            (uint64_t)expected <= v.n;
         if (defer) {
             // nothing of RefineModel is needed to go on: the count is the scoring pass's, the list is on its way to the
             // caller's pinned array, the refined plane is only reported
-            const int hr = (*before_refine_wait)(expected);
-            before_refine_wait = nullptr;
+            const int hr = (*fc->before_refine_wait)(expected);
             if (hr != M3D_OK) return hr;
-            ctx->deferred.pending = true;
-            ctx->deferred.slot = refine_slot(ctx);
-            ctx->deferred.ni = (uint32_t)expected;
-            ctx->deferred.params_out = params;
+            rounds->deferred = {true, slot, (uint32_t)expected, params};
             ni = (size_t)expected;
             refined = deferred_now = true;
         } else if (hit) {
             rc = refine(ctx, v, gather, orig, kind, thr, ctx->pick.as<BestPick>()->params, model, inliers, &ni, &gf_ok,
-                        expected, before_refine_wait, h_best_at(ctx), h_total_at(ctx), /*fused=*/true);
+                        expected, ro.spec, fc, hook_due, h_best_at(ctx, slot), /*fused=*/true);
             if (rc != M3D_OK) return rc;
             refined = true;
         }
     }
-    if (ctx->spec_compaction && comm) {
+    if (ro.spec.early && comm) {
         // sharded fits: pick_best_k's record is only known to have landed once the stream has been waited for (its
         // chunk's event may sit on the copy stream, in front of it) -- the decision above is re-taken after that wait
         const BestPickHost* ph = ctx->h_pick.as<BestPickHost>();
         if (!refined) {   // (judged a miss on a record that may not have arrived yet)
             rc = refine(ctx, v, gather, orig, kind, thr, ctx->pick.as<BestPick>()->params, model, inliers, &ni, &gf_ok,
-                        expected, before_refine_wait, h_best_at(ctx), h_total_at(ctx), /*fused=*/true);
+                        expected, ro.spec, fc, hook_due, h_best_at(ctx, slot), /*fused=*/true);
             if (rc != M3D_OK) return rc;
         }
-        before_refine_wait = nullptr;   // (a speculative RefineModel has run its hook by now, in either branch)
+        hook_due = false;   // (a speculative RefineModel has run its hook by now, in either branch)
         refined = ro.st.best_index >= 0 ? (ph->have && ph->index == (unsigned long long)ro.st.best_index) : !ph->have;
         ro.spec_hits = refined ? 1 : 0;
         ro.spec_misses = refined ? 0 : 1;
     }
     if (!refined) {
-        rc = refine(ctx, v, gather, orig, kind, thr, ctx->last_best_dev, model, inliers, &ni,
-                    &gf_ok, expected, before_refine_wait, h_best_at(ctx), nullptr,
-                    /*fused=*/true);
+        rc = refine(ctx, v, gather, orig, kind, thr, ro.best_dev, model, inliers, &ni, &gf_ok, expected, Compaction{}, fc, hook_due,
+                    h_best_at(ctx, slot), /*fused=*/true);
         if (rc != M3D_OK) return rc;
     }
     if (ro.st.best_index >= 0 && ni != ro.st.best_count)
@@ -1342,8 +1342,7 @@ int m3d_cloud_fit_sharded(m3d_cloud* c, m3d_comm* comm, int kind, double thresho
     uint64_t sd = 0;
     const int rs = agree_seed(comm, seed, c->ctx->stream, &sd);
     if (rs != M3D_OK) return rs;
-    return cloud_fit_locked(c, kind, threshold, max_iteration, probability, sd, params, inliers, n_inliers, stats,
-                            nullptr, nullptr, comm);
+    return cloud_fit_locked(c, kind, threshold, max_iteration, probability, sd, params, inliers, n_inliers, stats, nullptr, comm);
 }
 
 static int one_shot_fit(int kind, const double* xyz, const double* normals, size_t n, double thr,

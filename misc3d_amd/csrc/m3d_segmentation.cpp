@@ -66,8 +66,9 @@ static bool poison_fits(const m3d_cloud* c, uint64_t removed) {
 }
 // expected_removed >= 0: the size of this removal is known (the scoring pass counted the inliers): planes may then be
 // removed from the sorted copy by tombstones (poison_fits)
+// fc: the fit of a segmentation round whose inliers these are (null: a removal on its own)
 static int cloud_remove_issue(m3d_cloud* c, int kind, double thr, const double* model_dev, bool partition_done = false,
-                              bool same_slot = false, int64_t expected_removed = -1) {
+                              bool same_slot = false, int64_t expected_removed = -1, const FitCaller* fc = nullptr) {
     DeviceCtx* ctx = c->ctx;
     m3d_cloud::Work& w = c->work;
     PartitionOut po;
@@ -95,17 +96,18 @@ static int cloud_remove_issue(m3d_cloud* c, int kind, double thr, const double* 
         // (the kills add up in ctx->poison_total, cleared by the owner of the cloud -- segment_impl -- which compares the sum
         // with the inlier lists at the end; a real compaction in between checks the live count it leaves)
         RESERVE(ctx->poison_total, 16);
-        // A round that does not wait for its RefineModel (DeviceCtx::deferred) goes straight on to the next fit: its kill
+        // A round that does not wait for its RefineModel (SegmentRounds::deferred) goes straight on to the next fit: its kill
         // rides in that fit's minimal_fit_k launch.  The model is then read from the device's pick record, which stays put
         // until the next fit's records are folded (the winner's slot of the parameter array is rewritten by that launch).
-        const bool ride = ctx->defer_refine && ctx->spec_hit && !ctx->poison_pending;
+        SegmentRounds* const rounds = fc ? fc->rounds : nullptr;
+        const bool ride = rounds && fc->defer_refine && rounds->spec_hit && !rounds->poison_pending;
         const PoisonJob job = make_poison_job(w.scur, ride ? ctx->pick.as<BestPick>()->params : model_dev, thr,
                                               ctx->poison_total.as<uint32_t>());
         if (ride) {
-            ctx->pending_poison = job;
-            ctx->poison_pending = true;
-            ctx->poison_expected_at = &w.poison_expected;
-            ctx->poison_pending_count = (uint64_t)expected_removed;
+            rounds->pending_poison = job;
+            rounds->poison_pending = true;
+            rounds->poison_expected_at = &w.poison_expected;
+            rounds->poison_pending_count = (uint64_t)expected_removed;
         } else {
             launch_poison_plane_inliers(job, ctx->stream);
             w.poison_expected += (uint64_t)expected_removed;
@@ -245,10 +247,6 @@ int m3d_cloud_remove_inliers(m3d_cloud* c, int kind, double threshold, const dou
 
 }  // extern "C"
 thread_local double m3d::g_seg_ms[6] = {0, 0, 0, 0, 0, 0};
-extern "C" {
-
-
-}  // extern "C"
 namespace m3d {
 // SegmentPlaneIterative, src/iterative_plane_segmentation.cpp:8-39
 int segment_impl(const double* xyz, size_t n, double threshold, int max_iteration, double min_ratio,
@@ -276,31 +274,14 @@ int segment_impl(const double* xyz, size_t n, double threshold, int max_iteratio
     double t_big = 0;
     {
         CtxLock lock(ctx);
-        // The cross-round state of a segmentation (a tombstone pass waiting to ride in the next fit, a RefineModel finished one
-        // round late, lists leaving through the copy engine) lives on the device context and points into THIS call's cloud and
-        // the caller's buffers: however the block is left, the context goes back to idle and keeps none of those pointers
-        // (the explicit resets below stay where their order matters).
-        struct StateGuard {
-            DeviceCtx* ctx;
-            ~StateGuard() {
-                ctx->defer_refine = false;
-                ctx->defer_copy_sync = false;
-                ctx->idx_out_override = nullptr;
-                ctx->poison_pending = false;
-                ctx->poison_expected_at = nullptr;
-                ctx->poison_pending_count = 0;
-                ctx->deferred.pending = false;
-                ctx->deferred.params_out = nullptr;
-                ctx->spec_hit = false;
-            }
-        } state_guard{ctx};
+        // The cross-round state of the call (a tombstone pass waiting to ride in the next fit, a RefineModel finished one round
+        // late) points into THIS call's cloud and the caller's buffers: it lives here and ends with the block, the lane keeps none
+        SegmentRounds rounds;
         uint64_t seed0 = 0;
         rc = agree_seed(comm, seed, ctx->stream, &seed0);
         poison_ready = ctx->poison_total.reserve(16) && hipMemsetAsync(ctx->poison_total.p, 0, 16, ctx->stream) == hipSuccess;
         if (!poison_ready) c0->work.tombstones = false;
-        ctx->deferred.pending = false;
-        ctx->poison_pending = false;
-        ctx->defer_refine = !comm && config().speculative_refine != 0;   // (one GPU: DeviceCtx::deferred)
+        const bool defer_refine = !comm && config().speculative_refine != 0;   // (one GPU: SegmentRounds::deferred)
         // A pageable destination is reached through staged copies, a blocking one per round, into pages that fault on first
         // touch (10 M points: 43 ms against 37): the rounds write into a page-locked staging array the device context keeps
         // -- the compaction kernels store the index lists straight into it -- and the lists are copied over at the end.
@@ -315,11 +296,10 @@ int segment_impl(const double* xyz, size_t n, double threshold, int max_iteratio
             }
             if (ctx->seg_staging) idx_out = static_cast<size_t*>(ctx->seg_staging);
         }
-        // rounds on a large part of the cloud: lists of megabytes leave through the copy engine (DeviceCtx::idx_out_override)
+        // rounds on a large part of the cloud: lists of megabytes leave through the copy engine (FitCaller::idx_dev)
         DevBuf seg_idx_dev;
         const bool lists_by_copy_engine = rc == M3D_OK && !comm && is_library_pinned(idx_out, sizeof(size_t) * n) &&
                                           n >= ((size_t)1 << 20) && seg_idx_dev.reserve(sizeof(uint64_t) * n);
-        ctx->defer_copy_sync = lists_by_copy_engine;
         size_t count = 0, k = 0;
         size_t iterations_hint = 0;   // iterations the previous round took: sizes this round's second chunk up front
         const size_t target = (size_t)((1 - min_ratio) * (double)n);  // :28
@@ -342,6 +322,13 @@ int segment_impl(const double* xyz, size_t n, double threshold, int max_iteratio
             // from the scoring pass, so the round costs one host wait less.  Not on the last round.
             bool removal_issued = false, partition_fused = false, spec_removal = false;
             PartitionOut part_out;
+            FitCaller fc;   // what this round asks of its fit (the two hooks below read fc.best_dev / rounds while it runs)
+            fc.rounds = &rounds;
+            fc.defer_refine = defer_refine;
+            fc.defer_copy_sync = lists_by_copy_engine;
+            fc.idx_dev = lists_by_copy_engine && big_round ? seg_idx_dev.as<uint64_t>() + off : nullptr;
+            fc.no_prune_hint = !comm && k > 0 && (uint64_t)c0->work.last_removed * 32 < c0->n;   // (the previous round's plane: < 3 % of the cloud)
+            fc.iterations_hint = iterations_hint;
             // RefineModel's compaction evaluates the very flags the removal needs: it writes the partition of the cloud
             // in creation order as well (one count, one scan and one write launch less per round)
             const std::function<const PartitionOut*(int64_t)> partition_hook = [&](int64_t expected_ni) -> const PartitionOut* {
@@ -367,18 +354,15 @@ int segment_impl(const double* xyz, size_t n, double threshold, int max_iteratio
             const std::function<int(int64_t)> issue_removal = [&](int64_t expected_ni) -> int {
                 if (expected_ni <= 0 || count + (size_t)expected_ni >= target || k + 1 >= max_clusters) return M3D_OK;
                 removal_issued = true;
-                if (spec_removal && ctx->spec_hit) return M3D_OK;   // (queued on the device's pick, which the replay confirmed)
-                return cloud_remove_issue(c0, M3D_PLANE, threshold, ctx->last_best_dev, partition_fused, /*same_slot=*/spec_removal,
-                                          expected_ni);
+                if (spec_removal && rounds.spec_hit) return M3D_OK;   // (queued on the device's pick, which the replay confirmed)
+                return cloud_remove_issue(c0, M3D_PLANE, threshold, fc.best_dev, partition_fused, /*same_slot=*/spec_removal,
+                                          expected_ni, &fc);
             };
-            ctx->partition_hook = &partition_hook;
-            ctx->idx_out_override = lists_by_copy_engine && big_round ? seg_idx_dev.as<uint64_t>() + off : nullptr;
-            ctx->no_prune_hint = !comm && k > 0 && (uint64_t)c0->work.last_removed * 32 < c0->n;   // (the previous round's plane: < 3 % of the cloud)
-            rc = cloud_fit_locked(c0, M3D_PLANE, threshold, (size_t)max_iteration, 0.9999, seed0 + k, plane,
-                                  idx_out + off, &ni, nullptr, &issue_removal, &iterations_hint, comm);
-            ctx->partition_hook = nullptr;
-            ctx->idx_out_override = nullptr;
-            ctx->no_prune_hint = false;
+            fc.partition_hook = &partition_hook;
+            fc.before_refine_wait = &issue_removal;
+            rc = cloud_fit_locked(c0, M3D_PLANE, threshold, (size_t)max_iteration, 0.9999, seed0 + k, plane, idx_out + off, &ni,
+                                  nullptr, &fc, comm);
+            iterations_hint = fc.iterations_hint;
             if (rc < 0) break;
             rc = cloud_remove_check_pending(c0);   // (the previous round's removal: this round's wait lay behind it)
             if (rc != M3D_OK) break;
@@ -396,7 +380,7 @@ int segment_impl(const double* xyz, size_t n, double threshold, int max_iteratio
             }
             if (count >= target || k >= max_clusters) break;
             // pcd_copy = pcd_copy->SelectByIndex(inliers, true), :33 -- inliers of the PRE-refinement model,
-            // still on the device (ctx->last_best_dev)
+            // still on the device (fc.best_dev)
             size_t removed = 0;
             if (partition_fused && !removal_issued) {   // (the two hooks take the same decision from the same count)
                 rc = fail(M3D_ERR_INTERNAL, "partition written without the removal being queued");
@@ -405,7 +389,7 @@ int segment_impl(const double* xyz, size_t n, double threshold, int max_iteratio
             // (a removal queued by the hook is NOT waited for: its size is the inlier count; its totals are checked after
             // the next round's wait, which the stream reaches behind them)
             rc = removal_issued ? cloud_remove_finish(c0, &removed, &ni)
-                                : cloud_remove_locked(c0, M3D_PLANE, threshold, ctx->last_best_dev, &removed);
+                                : cloud_remove_locked(c0, M3D_PLANE, threshold, fc.best_dev, &removed);
             if (rc != M3D_OK) break;
             if (removed != ni) {
                 rc = fail(M3D_ERR_INTERNAL, "removed points and inlier list disagree");
@@ -419,15 +403,12 @@ int segment_impl(const double* xyz, size_t n, double threshold, int max_iteratio
             (void)hipMemcpyAsync(&killed, ctx->poison_total.p, sizeof(killed), hipMemcpyDeviceToHost, ctx->stream);
         (void)hipStreamSynchronize(ctx->stream);
         if (lists_by_copy_engine) (void)hipStreamSynchronize(copy_stream_of(ctx));   // (the big rounds' lists)
-        ctx->defer_copy_sync = false;
         seg_idx_dev.release();
-        ctx->defer_refine = false;
-        ctx->poison_pending = false;   // (the last round's kill has nobody left to serve)
-        if (rc == M3D_OK || rc == 2) {   // the last round's RefineModel
-            const int fr = finalize_deferred_refine(ctx);
+        rounds.poison_pending = false;   // (the last round's kill has nobody left to serve: dropped, never credited)
+        if (rc == M3D_OK || rc == 2) {   // the last round's RefineModel (after a failed round its plane stays as the round left it)
+            const int fr = finalize_deferred_refine(ctx, rounds);
             if (fr != M3D_OK) rc = fr;
         }
-        ctx->deferred.pending = false;
         if (rc == M3D_OK) rc = cloud_remove_check_pending(c0);
         if ((rc == M3D_OK || rc == 2) && poison_ready && (uint64_t)killed != c0->work.poison_expected)
             rc = fail(M3D_ERR_INTERNAL, "the sorted copy's tombstones and the inlier lists disagree");
