@@ -91,6 +91,15 @@ int m3d_bench_fps_force_path(int path);
  * depend on it. */
 int m3d_bench_knn_force_path(int path);
 
+/* TEST hook (tests/test_gpu_knn_seams.py): launch_knn_tile + launch_knn_merge as run_tile issues them, for ONE chunk of m
+ * queries, `pages` pages of kk pairs (page p > 0 above the floor page p - 1 left), over `splits` splits of rows_per_split rows.
+ * idx_out / d2_out: m x (pages kk), raw -- a slot no row fills holds the kernels' sentinel (index 0xFFFFFFFF, key all ones).
+ * M3D_ERR_INVALID_ARG unless 1 <= kk <= 128, pages >= 1, 1 <= splits <= 256, rows_per_split >= 1, splits x rows_per_split >= n
+ * (trailing empty splits are allowed: a list of sentinels), 1 <= dim <= 1024, m >= 1, n >= 1 and the chunk's scratch
+ * (m3d_knn_search's own bound, 256 MiB) holds. */
+int m3d_bench_knn_tile_merge(const double *data, size_t n, int dim, const double *queries, size_t m, int kk, int pages,
+                             int splits, uint32_t rows_per_split, int device, uint32_t *idx_out, uint64_t *d2_bits_out);
+
 /* MEASUREMENT / TEST hook (tests/test_gpu_voxel.py): the key path of every later m3d_voxel_down_sample* in the process --
  * 0 = by the key widths (the default), M3D_VOXEL_PATH_PACKED (where the keys fit 63 bits, else wide), M3D_VOXEL_PATH_WIDE.
  * The result does not depend on it. */

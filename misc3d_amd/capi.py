@@ -209,6 +209,8 @@ def lib():
         L.m3d_knn_search.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int64, C.c_double, C.c_size_t,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.m3d_bench_knn_force_path.argtypes = [C.c_int]
+        L.m3d_bench_knn_tile_merge.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                                               C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
         L.m3d_estimate_normals.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                            C.c_void_p, C.c_void_p]
         L.m3d_compute_fpfh.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p,
@@ -1524,6 +1526,23 @@ def knn_create_status(data_ptr, n, dim, device=0):
 def knn_force_path(path: int):
     """test / measurement hook m3d_bench_knn_force_path: 0 = by shape, KNN_PATH_GRID / TILE / SELECT"""
     _check(lib().m3d_bench_knn_force_path(int(path)))
+
+
+def knn_tile_merge(data, queries, kk, pages, splits, rows_per_split, device=0):
+    """test hook m3d_bench_knn_tile_merge: one chunk of the tile path with the caller's geometry -> (indices uint32, key bits
+    uint64), each (m, pages kk), raw: a slot no row fills holds the sentinel (0xFFFFFFFF, all ones)"""
+    data = _f64(data)
+    if data.ndim != 2:
+        raise ValueError("data: expected an (N, dim) array")
+    n, dim = data.shape
+    q = _f64(queries).reshape(-1, max(dim, 1))
+    m = len(q)
+    width = max(int(pages), 0) * max(int(kk), 0)
+    idx = np.zeros((m, width), dtype=np.uint32)
+    key = np.zeros((m, width), dtype=np.uint64)
+    _check(lib().m3d_bench_knn_tile_merge(_p(data), n, dim, _p(q), m, int(kk), int(pages), int(splits), int(rows_per_split),
+                                          device, _p(idx), _p(key)))
+    return idx, key
 
 
 class FpfhStats(C.Structure):

@@ -221,6 +221,50 @@ int scatter(const KnnOut& o, const uint32_t* rows, uint32_t mc, int kk, size_t c
     return M3D_OK;
 }
 
+// One chunk of the tile / select path: the mc queries of qT (dim x mc, on the host) against `splits` splits of
+// rows_per_split rows, in pages of `page` pairs up to kout; page p > 0 takes only the pairs above the floor (the last
+// pair) page p - 1 left.  sink(col, kk, idx, d2) gets the host copies of each page's mc x kk results, raw.
+template <class Sink>
+int run_tile_chunk(hipStream_t s, KnnBufs& B, const double* data, uint32_t n, int dim, const std::vector<double>& qT,
+                   uint32_t mc, int64_t kout, int page, int splits, uint32_t rows_per_split, m3d_knn_stats& st,
+                   std::vector<uint32_t>& h_idx, std::vector<double>& h_d2, Sink&& sink) {
+    const int kk_max = (int)std::min<int64_t>(page, kout);
+    RESERVE(B.qT, sizeof(double) * qT.size());
+    RESERVE(B.part_key, sizeof(uint64_t) * (size_t)mc * splits * kk_max);
+    RESERVE(B.part_idx, sizeof(uint32_t) * (size_t)mc * splits * kk_max);
+    RESERVE(B.floor, sizeof(uint64_t) * 2 * mc);
+    RESERVE(B.out_d2, sizeof(double) * (size_t)mc * kk_max);
+    RESERVE(B.out_idx, sizeof(uint32_t) * (size_t)mc * kk_max);
+    HIPCHK(hipMemcpyAsync(B.qT.p, qT.data(), sizeof(double) * qT.size(), hipMemcpyHostToDevice, s));
+    for (int64_t col = 0; col < kout; col += page) {
+        const int kk = (int)std::min<int64_t>(page, kout - col);
+        launch_knn_tile(data, n, dim, B.qT.as<double>(), mc, kk, splits, rows_per_split,
+                        col ? B.floor.as<uint64_t>() : nullptr, B.part_key.as<uint64_t>(), B.part_idx.as<uint32_t>(), s);
+        launch_knn_merge(B.part_key.as<uint64_t>(), B.part_idx.as<uint32_t>(), mc, kk, splits,
+                         col + kk < kout ? B.floor.as<uint64_t>() : nullptr, B.out_d2.as<double>(),
+                         B.out_idx.as<uint32_t>(), s);
+        HIPCHK(hipGetLastError());
+        st.launches += 2;
+        st.pair_dims += (uint64_t)mc * n * (uint64_t)dim;
+        h_d2.resize((size_t)mc * kk);
+        h_idx.resize((size_t)mc * kk);
+        HIPCHK(hipMemcpyAsync(h_d2.data(), B.out_d2.p, sizeof(double) * h_d2.size(), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h_idx.data(), B.out_idx.p, sizeof(uint32_t) * h_idx.size(), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (const int r = sink((size_t)col, kk, h_idx.data(), h_d2.data()); r != M3D_OK) return r;
+    }
+    return M3D_OK;
+}
+
+// queries rows[0 .. mc) (row-major, dim each) -> qT (dim x mc)
+void transpose_queries(const double* queries, const uint32_t* rows, uint32_t mc, int dim, std::vector<double>& qT) {
+    qT.resize((size_t)dim * mc);
+    for (uint32_t q = 0; q < mc; ++q) {
+        const double* src = queries + (size_t)(rows ? rows[q] : q) * dim;
+        for (int k = 0; k < dim; ++k) qT[(size_t)k * mc + q] = src[k];
+    }
+}
+
 // Tile / select path for the queries rows[0 .. m): chunks of queries, each in pages of `page` pairs.
 int run_tile(DeviceCtx* ctx, KnnBufs& B, const m3d_knn* h, const double* queries, const std::vector<uint32_t>& rows,
              int64_t kout, int page, const KnnOut& o, m3d_knn_stats& st) {
@@ -247,36 +291,12 @@ int run_tile(DeviceCtx* ctx, KnnBufs& B, const m3d_knn* h, const double* queries
         const size_t S = splits_for(mc);
         const uint32_t rps = (uint32_t)((n + S - 1) / S);
         const int Sx = (int)((n + rps - 1) / rps);   // no empty split
-        qT.resize((size_t)dim * mc);
-        for (uint32_t q = 0; q < mc; ++q) {
-            const double* src = queries + (size_t)rows[c0 + q] * dim;
-            for (int k = 0; k < dim; ++k) qT[(size_t)k * mc + q] = src[k];
-        }
-        RESERVE(B.qT, sizeof(double) * qT.size());
-        RESERVE(B.part_key, sizeof(uint64_t) * (size_t)mc * Sx * kk_max);
-        RESERVE(B.part_idx, sizeof(uint32_t) * (size_t)mc * Sx * kk_max);
-        RESERVE(B.floor, sizeof(uint64_t) * 2 * mc);
-        RESERVE(B.out_d2, sizeof(double) * (size_t)mc * kk_max);
-        RESERVE(B.out_idx, sizeof(uint32_t) * (size_t)mc * kk_max);
-        HIPCHK(hipMemcpyAsync(B.qT.p, qT.data(), sizeof(double) * qT.size(), hipMemcpyHostToDevice, s));
-        for (int64_t col = 0; col < kout; col += page) {
-            const int kk = (int)std::min<int64_t>(page, kout - col);
-            launch_knn_tile(h->data.as<double>(), n, dim, B.qT.as<double>(), mc, kk, Sx, rps,
-                            col ? B.floor.as<uint64_t>() : nullptr, B.part_key.as<uint64_t>(), B.part_idx.as<uint32_t>(), s);
-            launch_knn_merge(B.part_key.as<uint64_t>(), B.part_idx.as<uint32_t>(), mc, kk, Sx,
-                             col + kk < kout ? B.floor.as<uint64_t>() : nullptr, B.out_d2.as<double>(),
-                             B.out_idx.as<uint32_t>(), s);
-            HIPCHK(hipGetLastError());
-            st.launches += 2;
-            st.pair_dims += (uint64_t)mc * n * (uint64_t)dim;
-            h_d2.resize((size_t)mc * kk);
-            h_idx.resize((size_t)mc * kk);
-            HIPCHK(hipMemcpyAsync(h_d2.data(), B.out_d2.p, sizeof(double) * h_d2.size(), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(h_idx.data(), B.out_idx.p, sizeof(uint32_t) * h_idx.size(), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            if (const int r = scatter(o, rows.data() + c0, mc, kk, (size_t)col, h_idx.data(), h_d2.data()); r != M3D_OK)
-                return r;
-        }
+        transpose_queries(queries, rows.data() + c0, mc, dim, qT);
+        const int r = run_tile_chunk(s, B, h->data.as<double>(), n, dim, qT, mc, kout, page, Sx, rps, st, h_idx, h_d2,
+                                     [&](size_t col, int kk, const uint32_t* idx, const double* dd) {
+                                         return scatter(o, rows.data() + c0, mc, kk, col, idx, dd);
+                                     });
+        if (r != M3D_OK) return r;
     }
     return M3D_OK;
 }
@@ -478,6 +498,51 @@ int m3d_bench_knn_force_path(int path) {
         return fail(M3D_ERR_INVALID_ARG, "path: 0 = by shape, 1 = grid, 2 = tile, 3 = select");
     g_knn_force.store(path);
     return M3D_OK;
+}
+
+// test hook (include/misc3d_amd_bench.h): run_tile's chunk with the caller's geometry, results raw
+int m3d_bench_knn_tile_merge(const double* data, size_t n, int dim, const double* queries, size_t m, int kk, int pages,
+                             int splits, uint32_t rows_per_split, int device, uint32_t* idx_out, uint64_t* d2_bits_out) {
+    if (!data || !queries || !idx_out || !d2_bits_out) return fail(M3D_ERR_INVALID_ARG, "knn_tile_merge: null argument");
+    if (dim < 1 || dim > kKnnMaxDim) return fail(M3D_ERR_INVALID_ARG, "knn_tile_merge: dim must be in [1, 1024]");
+    if (n == 0 || n >= ((size_t)1 << 31) || m == 0 || m >= ((size_t)1 << 31))
+        return fail(M3D_ERR_INVALID_ARG, "knn_tile_merge: n and m must be in [1, 2^31)");
+    if (kk < 1 || kk > kKnnPageMax) return fail(M3D_ERR_INVALID_ARG, "knn_tile_merge: kk must be in [1, 128]");
+    if (pages < 1 || pages > (1 << 20)) return fail(M3D_ERR_INVALID_ARG, "knn_tile_merge: pages must be in [1, 2^20]");
+    if (splits < 1 || splits > kKnnMaxSplits) return fail(M3D_ERR_INVALID_ARG, "knn_tile_merge: splits must be in [1, 256]");
+    if (rows_per_split < 1) return fail(M3D_ERR_INVALID_ARG, "knn_tile_merge: rows_per_split must be >= 1");
+    if ((uint64_t)splits * rows_per_split < n)
+        return fail(M3D_ERR_INVALID_ARG, "knn_tile_merge: splits x rows_per_split leaves rows out");
+    if (m * ((size_t)dim * 8 + ((size_t)splits + 1) * (size_t)kk * 12 + 16) > kKnnScratchCap)
+        return fail(M3D_ERR_INVALID_ARG, "knn_tile_merge: one chunk's scratch is capped at 256 MiB");
+    LaneLock lane(device);
+    DeviceCtx* ctx = lane.ctx;
+    if (!ctx) return M3D_ERR_DEVICE;
+    KnnBufs B;
+    DevBuf rows;
+    const size_t stride = (size_t)pages * kk;
+    const int rc = [&]() -> int {
+        HIPCHK(hipSetDevice(ctx->device));
+        hipStream_t s = ctx->stream;
+        RESERVE(rows, sizeof(double) * n * (size_t)dim);
+        HIPCHK(hipMemcpyAsync(rows.p, data, sizeof(double) * n * (size_t)dim, hipMemcpyHostToDevice, s));
+        std::vector<double> qT, h_d2;
+        std::vector<uint32_t> h_idx;
+        m3d_knn_stats st{};
+        transpose_queries(queries, nullptr, (uint32_t)m, dim, qT);
+        return run_tile_chunk(s, B, rows.as<double>(), (uint32_t)n, dim, qT, (uint32_t)m, (int64_t)stride, kk, splits,
+                              rows_per_split, st, h_idx, h_d2, [&](size_t col, int kc, const uint32_t* idx, const double* dd) {
+                                  for (size_t q = 0; q < m; ++q) {
+                                      std::memcpy(idx_out + q * stride + col, idx + q * kc, sizeof(uint32_t) * kc);
+                                      std::memcpy(d2_bits_out + q * stride + col, dd + q * kc, sizeof(double) * kc);
+                                  }
+                                  return (int)M3D_OK;
+                              });
+    }();
+    (void)hipStreamSynchronize(ctx->stream);
+    B.release();
+    rows.release();
+    return rc;
 }
 
 }  // extern "C"
