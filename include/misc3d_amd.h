@@ -607,6 +607,21 @@ int m3d_registration_icp_plane(const double *src, size_t n_src, const double *ds
                                double relative_fitness, double relative_rmse, int device, double T[16],
                                m3d_icp_stats *stats, int64_t *correspondences);
 
+/* ---- point-to-plane ICP with L1 weights: RefineMethod::PointToPlane of PPFEstimator, src/ppf_estimation.cpp:937-990 ------
+ * RegistrationICP(source, target, max_correspondence_distance, init, TransformationEstimationPointToPlane(L1Loss),
+ * ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration)).  The arguments, refusals, empty-cloud results,
+ * stats and correspondences of m3d_registration_icp_plane.  [RECALL] Open3D 0.15.1 robust_kernel.h: L1Loss::Weight(r) =
+ * 1 / |r|, applied by ComputeJTJandJTr as JTJ += J w J^T, JTr += J w r.  Rules 1 - 8 of the plane call hold, with:
+ *   L1. w = 1.0 / |r| per correspondence.
+ *   L2. the record's 21 products are (J[a] w) J[b], its 6 values (J[a] w) r; the last slot stays r r (it feeds nothing).
+ *   L3. r == 0: w is infinite and the record turns non-finite; rule 5 (a determinant that is not finite) then yields the
+ *       identity update, as Open3D would: the next result repeats the last, which meets any positive stop criteria.
+ * Device: icp_plane_l1_iter_k, a second instantiation of the plane iteration's frame; the small launch and the solve are shared. */
+int m3d_registration_icp_plane_l1(const double *src, size_t n_src, const double *dst, const double *dst_normals, size_t n_dst,
+                                  double max_correspondence_distance, const double *T_init, int max_iteration,
+                                  double relative_fitness, double relative_rmse, int device, double T[16],
+                                  m3d_icp_stats *stats, int64_t *correspondences);
+
 /* ---- coloured ICP: LocalRefineMethod::ColoredICP of MultiScaleICP (the reference's default), src/pipeline.cpp:956-962 ------
  * RegistrationColoredICP(source, target, max_correspondence_distance, init, TransformationEstimationForColoredICP(
  * lambda_geometric), ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration)).  Arrays are row-major n x 3

@@ -69,6 +69,8 @@ def registration_icp(source, target, max_correspondence_distance, init=None, max
     estimation="point_to_plane": TransformationEstimationPointToPlane(), MultiScaleICP's Point2PlaneICP
     (src/pipeline.cpp:949-955); the target then carries normals: a (points, normals) tuple or an object with .points /
     .normals (RuntimeError without them).
+    estimation="point_to_plane_l1": TransformationEstimationPointToPlane(L1Loss()), the PointToPlane refinement of
+    PPFEstimator (src/ppf_estimation.cpp:937-990); the target carries normals in the same way.
     Returns (4x4 pose, dict(fitness, inlier_rmse, correspondences, iterations, converged))."""
     import numpy as _np
 
@@ -77,13 +79,13 @@ def registration_icp(source, target, max_correspondence_distance, init=None, max
         pts = [_np.asarray(getattr(c, "points", c), dtype=_np.float64).reshape(-1, 3) for c in (source, target)]
         return _capi.registration_icp(pts[0], pts[1], max_correspondence_distance, init, max_iteration,
                                       relative_fitness, relative_rmse, device)
-    if estimation != "point_to_plane":
-        raise RuntimeError('[Misc3D Error] estimation: "point_to_point" or "point_to_plane"')
+    if estimation not in ("point_to_plane", "point_to_plane_l1"):
+        raise RuntimeError('[Misc3D Error] estimation: "point_to_point", "point_to_plane" or "point_to_plane_l1"')
     src, _ = _points_normals(source)
     dst, nrm = _points_normals(target)
     try:
         return _capi.registration_icp_plane(src, dst, nrm, max_correspondence_distance, init, max_iteration,
-                                            relative_fitness, relative_rmse, device)
+                                            relative_fitness, relative_rmse, device, l1=estimation == "point_to_plane_l1")
     except _capi.M3DError as e:
         raise RuntimeError(str(e)) from e
 

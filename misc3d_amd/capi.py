@@ -161,6 +161,7 @@ def lib():
         L.m3d_registration_icp_plane.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double,
                                                  C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
                                                  C.c_void_p]
+        L.m3d_registration_icp_plane_l1.argtypes = L.m3d_registration_icp_plane.argtypes
         L.m3d_multi_scale_icp.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                           C.c_void_p, C.c_size_t, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                           C.c_void_p, C.c_void_p]
@@ -1075,9 +1076,10 @@ def registration_icp(src, dst, max_correspondence_distance, init=None, max_itera
 
 
 def registration_icp_plane(src, dst, dst_normals, max_correspondence_distance, init=None, max_iteration=30,
-                           relative_fitness=1e-6, relative_rmse=1e-6, device=0, want_correspondences=False):
+                           relative_fitness=1e-6, relative_rmse=1e-6, device=0, want_correspondences=False, l1=False):
     """m3d_registration_icp_plane: registration_icp with TransformationEstimationPointToPlane() and the target's normals
-    (None: the library's error) -> (T, stats[, correspondences])."""
+    (None: the library's error) -> (T, stats[, correspondences]).  l1=True: m3d_registration_icp_plane_l1, the same call
+    with TransformationEstimationPointToPlane(L1Loss())."""
     src = _f64(src).reshape(-1, 3)
     dst = _f64(dst).reshape(-1, 3)
     nrm = _f64(dst_normals).reshape(-1, 3) if dst_normals is not None else None
@@ -1087,9 +1089,9 @@ def registration_icp_plane(src, dst, dst_normals, max_correspondence_distance, i
     T = np.zeros(16)
     st = IcpStats()
     corr = np.zeros(max(len(src), 1), dtype=np.int64) if want_correspondences else None
-    _check(lib().m3d_registration_icp_plane(_p(src), len(src), _p(dst), _p(nrm), len(dst), max_correspondence_distance,
-                                            _p(Ti), max_iteration, relative_fitness, relative_rmse, device, _p(T),
-                                            C.cast(C.byref(st), C.c_void_p), _p(corr)))
+    call = lib().m3d_registration_icp_plane_l1 if l1 else lib().m3d_registration_icp_plane
+    _check(call(_p(src), len(src), _p(dst), _p(nrm), len(dst), max_correspondence_distance, _p(Ti), max_iteration,
+                relative_fitness, relative_rmse, device, _p(T), C.cast(C.byref(st), C.c_void_p), _p(corr)))
     if want_correspondences:
         return T.reshape(4, 4), st.asdict(), corr[: len(src)]
     return T.reshape(4, 4), st.asdict()

@@ -205,6 +205,11 @@ int registration_icp_plane_on(DeviceCtx* held, const double* src, size_t n_src, 
                               size_t n_dst, double max_correspondence_distance, const double* T_init, int max_iteration,
                               double relative_fitness, double relative_rmse, int device, double* T_out, m3d_icp_stats* stats,
                               int64_t* correspondences);
+// m3d_registration_icp_plane_l1: the plane estimator with L1 weights, the fourth of the loop
+int registration_icp_plane_l1_on(DeviceCtx* held, const double* src, size_t n_src, const double* dst, const double* dst_normals,
+                                 size_t n_dst, double max_correspondence_distance, const double* T_init, int max_iteration,
+                                 double relative_fitness, double relative_rmse, int device, double* T_out, m3d_icp_stats* stats,
+                                 int64_t* correspondences);
 // m3d_registration_icp_colored, the same way (m3d_multi_scale_icp_colored holds the lane)
 int registration_icp_colored_on(DeviceCtx* held, const double* src, const double* src_colors, size_t n_src, const double* dst,
                                 const double* dst_normals, const double* dst_colors, size_t n_dst,

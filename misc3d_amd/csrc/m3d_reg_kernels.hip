@@ -1651,6 +1651,53 @@ void launch_icp_plane_iter(const double* ix, const double* iy, const double* iz,
     icp_plane_final_k<<<kIcpPlaneRecord, 64, 0, s>>>(partial, nb, out);
 }
 
+// Point-to-plane with Open3D's L1Loss (m3d_registration_icp_plane_l1; PPFEstimator's PointToPlane refinement): the rows of
+// icp_plane_iter_k weighted by w = 1 / |r|.  The products are (J[a] w) J[b] and (J[a] w) r; the last slot stays r r.  r == 0:
+// w is infinite, the record turns non-finite and the host's determinant check yields the identity update.
+__global__ __launch_bounds__(256) void icp_plane_l1_iter_k(const double* __restrict__ ix, const double* __restrict__ iy,
+                                                            const double* __restrict__ iz, uint32_t n,
+                                                            const double* __restrict__ T, double* __restrict__ px,
+                                                            double* __restrict__ py, double* __restrict__ pz, GridDesc g,
+                                                            const uint32_t* __restrict__ cell_start,
+                                                            const double* __restrict__ qx, const double* __restrict__ qy,
+                                                            const double* __restrict__ qz,
+                                                            const uint32_t* __restrict__ cell_orig, CloudView dst,
+                                                            uint32_t* __restrict__ nn, double* __restrict__ partial) {
+    double v[kIcpPlaneRecord];
+    for (int k = 0; k < kIcpPlaneRecord; ++k) v[k] = 0.0;
+    const IcpMatch m = icp_move_and_match(blockIdx.x * 256u + threadIdx.x, ix, iy, iz, n, T, px, py, pz, g, cell_start, qx, qy, qz,
+                                          cell_orig, nn);
+    if (m.ok) {
+        const double x = m.x, y = m.y, z = m.z;
+        const double ax = dst.nx[m.j], ay = dst.ny[m.j], az = dst.nz[m.j];
+        const double ex = x - dst.x[m.j], ey = y - dst.y[m.j], ez = z - dst.z[m.j];
+        const double r = (ex * ax + ey * ay) + ez * az;
+        const double w = 1.0 / fabs(r);
+        const double J[6] = {y * az - z * ay, z * ax - x * az, x * ay - y * ax, ax, ay, az};
+        v[0] = 1.0;
+        v[1] = m.d2;
+        int k = 2;
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+            const double Jw = J[a] * w;
+#pragma unroll
+            for (int b = a; b < 6; ++b) v[k++] = Jw * J[b];
+            v[23 + a] = Jw * r;
+        }
+        v[29] = r * r;
+    }
+    icp_record_reduce(v, partial);
+}
+void launch_icp_plane_l1_iter(const double* ix, const double* iy, const double* iz, uint32_t n, const double* T_dev, double* px,
+                              double* py, double* pz, const GridDesc& g, const uint32_t* cell_start, const double* qx,
+                              const double* qy, const double* qz, const uint32_t* cell_orig, const CloudView& dst, uint32_t* nn,
+                              double* partial, double* out, hipStream_t s) {
+    const uint32_t nb = icp_plane_blocks(n);
+    icp_plane_l1_iter_k<<<nb, 256, 0, s>>>(ix, iy, iz, n, T_dev, px, py, pz, g, cell_start, qx, qy, qz, cell_orig, dst, nn,
+                                           partial);
+    icp_plane_final_k<<<kIcpPlaneRecord, 64, 0, s>>>(partial, nb, out);
+}
+
 // Coloured: for a correspondence the thread gathers t_j, n_j, the colour gradient g_j (grad: n_dst x 3 rows) and the intensity
 // It_j, takes its own intensity Is_i (it does not move with the pose), and forms the two rows of rules C3 and C4 of
 // include/misc3d_amd.h:

@@ -164,6 +164,11 @@ void launch_icp_plane_iter(const double* ix, const double* iy, const double* iz,
                            double* py, double* pz, const GridDesc& g, const uint32_t* cell_start, const double* qx,
                            const double* qy, const double* qz, const uint32_t* cell_orig, const CloudView& dst, uint32_t* nn,
                            double* partial, double* out, hipStream_t s);
+// The same with L1 weights (icp_plane_l1_iter_k + icp_plane_final_k; m3d_registration_icp_plane_l1): w = 1 / |r| on the 27 sums
+void launch_icp_plane_l1_iter(const double* ix, const double* iy, const double* iz, uint32_t n, const double* T_dev, double* px,
+                              double* py, double* pz, const GridDesc& g, const uint32_t* cell_start, const double* qx,
+                              const double* qy, const double* qz, const uint32_t* cell_orig, const CloudView& dst, uint32_t* nn,
+                              double* partial, double* out, hipStream_t s);
 // Coloured ICP's iteration (icp_colored_iter_k + icp_plane_final_k): launch_icp_plane_iter's arguments plus the target's colour
 // gradients (grad: n_dst x 3 rows) and intensities (it_dst), the moving points' intensities (is_src) and sg = sqrt(lambda),
 // sp = sqrt(1 - lambda).  The record and `partial` are those of the plane iteration.

@@ -4,7 +4,7 @@
 //   m3d_registration_ransac  registration::RANSACSolver::Solve        src/transform_estimation.cpp:124-164
 //                            (= Open3D 0.15.1 RegistrationRANSACBasedOnCorrespondence)
 //   (m3d_match_mutual_nn -- registration::ANNMatcher::Match, src/correspondence_matching.cpp:52-84 -- lives in m3d_match.cpp)
-//   m3d_registration_icp[_plane|_colored]   Open3D RegistrationICP: one call frame, one loop, three estimators ("RegistrationICP" below)
+//   m3d_registration_icp[_plane|_plane_l1|_colored]   Open3D RegistrationICP: one call frame, one loop, four estimators ("RegistrationICP" below)
 //   m3d_information_matrix, m3d_detect_boundary_points   GetInformationMatrixFromPointClouds, DetectBoundaryPoints
 //
 // Sequential (one-thread) semantics of the Open3D loop with an explicit seed: iteration `itr` draws
@@ -1119,7 +1119,7 @@ int m3d_registration_ransac_sharded(const double* src, size_t n_src, const doubl
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------
-// RegistrationICP: one call (icp_call), one loop (icp_loop) and three estimators.  Both registration examples of the reference
+// RegistrationICP: one call (icp_call), one loop (icp_loop) and four estimators.  Both registration examples of the reference
 // run it on the RANSAC pose (examples/cpp/transform_estimation.cpp:82-86), the pipeline runs it per level
 // (m3d_multi_scale_icp.cpp).  [RECALL] of the Open3D 0.15.1 loop: oracle/misc3d_oracle_reg.c orc_registration_icp.
 //   icp_call   the argument checks and the result of an empty cloud (icp_prologue); what a call holds (IcpFrame): lane, clouds,
@@ -1129,7 +1129,7 @@ int m3d_registration_ransac_sharded(const double* src, size_t n_src, const doubl
 // An estimator is its own argument check, its reservations and two callables: iterate(first, update) moves the cloud by the
 // pending update, searches the correspondences and leaves their count and error in the frame; compute_update(U) is
 // ComputeTransformation on what iterate left behind.  Point-to-point: transform, search, error sum, Kabsch sums and one polled
-// wait, the K3x3 umeyama assembly.  Point-to-plane and coloured (icp_record_loop; they differ in the launch): one launch -- the
+// wait, the K3x3 umeyama assembly.  Point-to-plane, its L1 variant and coloured (icp_record_loop; they differ in the launch): one launch -- the
 // pending update, the search, the 30 sums -- one copy of the record and one polled wait; the 6 x 6 solve of m3d_icp_fp.hpp.
 // ------------------------------------------------------------------------------------------------
 namespace {
@@ -1280,7 +1280,7 @@ int icp_loop(IcpFrame& f, const IcpArgs& a, Iterate&& iterate, Update&& compute_
 }
 
 // The loop of the two estimators whose iteration is one launch that leaves the record of m3d_icp_fp.hpp:
-// launch(ix, iy, iz, T_dev) is launch_icp_plane_iter or launch_icp_colored_iter on the frame's buffers.
+// launch(ix, iy, iz, T_dev) is launch_icp_plane_iter, launch_icp_plane_l1_iter or launch_icp_colored_iter on the frame's buffers.
 static_assert(kIcpPlaneRecord == kIcpPlaneSums, "the kernels' record is the one m3d_icp_fp.hpp reads");
 template <class Launch>
 int icp_record_loop(IcpFrame& f, const IcpArgs& a, Launch&& launch) {
@@ -1432,6 +1432,24 @@ int m3d::registration_icp_plane_on(DeviceCtx* held, const double* src, size_t n_
     });
 }
 
+// TransformationEstimationPointToPlane(L1Loss): the plane call with the launch of the weighted rows (the contract:
+// include/misc3d_amd.h, m3d_registration_icp_plane_l1); what PPFEstimator's PointToPlane refinement runs
+int m3d::registration_icp_plane_l1_on(DeviceCtx* held, const double* src, size_t n_src, const double* dst,
+                                      const double* dst_normals, size_t n_dst, double max_correspondence_distance,
+                                      const double* T_init, int max_iteration, double relative_fitness, double relative_rmse,
+                                      int device, double* T_out, m3d_icp_stats* stats, int64_t* correspondences) {
+    const IcpArgs a{src, dst, T_init, n_src, n_dst, max_correspondence_distance, relative_fitness, relative_rmse, max_iteration,
+                    device, T_out, stats, correspondences};
+    return icp_call(held, a, !dst_normals ? kIcpNeedsNormals : nullptr, dst_normals, icp_nothing_before_upload, [&](IcpFrame& f) {
+        Scratch& S = f.S;
+        return icp_record_loop(f, a, [&](const double* ix, const double* iy, const double* iz, const double* T_dev) {
+            launch_icp_plane_l1_iter(ix, iy, iz, f.n, T_dev, f.px, f.py, f.pz, f.g, S.tgt.start.as<uint32_t>(), S.qx.as<double>(),
+                                     S.qy.as<double>(), S.qz.as<double>(), S.cell_orig.as<uint32_t>(), f.dv, f.nn.as<uint32_t>(),
+                                     S.partial_sum.as<double>(), S.sums.as<double>(), f.ctx->stream);
+        });
+    });
+}
+
 // TransformationEstimationForColoredICP (the contract: include/misc3d_amd.h, rules G1 - G7 and C1 - C6).  Before the loop: the
 // target's colour gradients and intensities (color_gradient_on: Hybrid(2 max_correspondence_distance, 30)) and the source's
 // intensities, all resident for the call.  The record has the plane call's layout: the same solve.
@@ -1481,6 +1499,14 @@ int m3d_registration_icp_plane(const double* src, size_t n_src, const double* ds
                                int64_t* correspondences) {
     return registration_icp_plane_on(nullptr, src, n_src, dst, dst_normals, n_dst, max_correspondence_distance, T_init,
                                      max_iteration, relative_fitness, relative_rmse, device, T_out, stats, correspondences);
+}
+
+int m3d_registration_icp_plane_l1(const double* src, size_t n_src, const double* dst, const double* dst_normals, size_t n_dst,
+                                  double max_correspondence_distance, const double* T_init, int max_iteration,
+                                  double relative_fitness, double relative_rmse, int device, double* T_out, m3d_icp_stats* stats,
+                                  int64_t* correspondences) {
+    return registration_icp_plane_l1_on(nullptr, src, n_src, dst, dst_normals, n_dst, max_correspondence_distance, T_init,
+                                        max_iteration, relative_fitness, relative_rmse, device, T_out, stats, correspondences);
 }
 
 int m3d_registration_icp_colored(const double* src, const double* src_colors, size_t n_src, const double* dst,

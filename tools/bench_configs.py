@@ -860,13 +860,16 @@ if "I1" in which or "I2" in which or ALL:
         def plane(it, rel):
             return capi.registration_icp_plane(p["src"], p["dst"], p["dst_normals"], 0.02, init, it, rel, rel)
 
+        def plane_l1(it, rel):
+            return capi.registration_icp_plane(p["src"], p["dst"], p["dst_normals"], 0.02, init, it, rel, rel, l1=True)
+
         def point(it, rel):
             return capi.registration_icp(p["src"], p["dst"], 0.02, init, it, rel, rel)
-        for fn in (plane, point):
+        for fn in (plane, plane_l1, point):
             fn(30, 1e-6)
-        rows = {"plane": {}, "point": {}}
+        rows = {"plane": {}, "plane_l1": {}, "point": {}}
         for rep in range(7):
-            for name, fn in (("plane", plane), ("point", point)):
+            for name, fn in (("plane", plane), ("plane_l1", plane_l1), ("point", point)):
                 for key, it, rel in (("call", 30, 1e-6), ("it10", 10, 0.0), ("it40", 40, 0.0)):
                     t0 = time.perf_counter()
                     T, st = fn(it, rel)
@@ -881,10 +884,11 @@ if "I1" in which or "I2" in which or ALL:
                          "ms_10_iterations": med["it10"][0], "ms_40_iterations": med["it40"][0],
                          "us_per_iteration": (med["it40"][0] - med["it10"][0]) / 30.0 * 1e3}
         emit("I1 registration_icp_plane vs registration_icp, 200k x 200k, 0.02 (alternating, medians of 7)", n=n,
-             point_to_plane=out["plane"], point_to_point=out["point"],
+             point_to_plane=out["plane"], point_to_plane_l1=out["plane_l1"], point_to_point=out["point"],
              launches_per_iteration={"point_to_plane": "2 (+ the completion word's)", "point_to_point": "5 + 3 final reductions (+ the completion word's)"},
              roofline={"bound": "latency: an iteration is a dependent chain of short launches, one 240-byte copy and one host wait",
-                       "us_per_iteration_plane": out["plane"]["us_per_iteration"], "us_per_iteration_point": out["point"]["us_per_iteration"]},
+                       "us_per_iteration_plane": out["plane"]["us_per_iteration"],
+                       "us_per_iteration_plane_l1": out["plane_l1"]["us_per_iteration"], "us_per_iteration_point": out["point"]["us_per_iteration"]},
              cpu_baseline=None)
 
     if "I2" in which or ALL:
