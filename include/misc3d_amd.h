@@ -616,7 +616,7 @@ int m3d_registration_icp_plane(const double *src, size_t n_src, const double *ds
  *   L2. the record's 21 products are (J[a] w) J[b], its 6 values (J[a] w) r; the last slot stays r r (it feeds nothing).
  *   L3. r == 0: w is infinite and the record turns non-finite; rule 5 (a determinant that is not finite) then yields the
  *       identity update, as Open3D would: the next result repeats the last, which meets any positive stop criteria.
- * Device: icp_plane_l1_iter_k, a second instantiation of the plane iteration's frame; the small launch and the solve are shared. */
+ * Device: icp_iter_k<IcpPlaneL1Rows>, the plane iteration's kernel template with the weighted rows; the small launch and the solve are shared. */
 int m3d_registration_icp_plane_l1(const double *src, size_t n_src, const double *dst, const double *dst_normals, size_t n_dst,
                                   double max_correspondence_distance, const double *T_init, int max_iteration,
                                   double relative_fitness, double relative_rmse, int device, double T[16],
@@ -662,7 +662,7 @@ int m3d_registration_icp_plane_l1(const double *src, size_t n_src, const double 
  * outside [0, 1] or NaN ("lambda_geometric must be in [0, 1].").  T receives the initial pose on every refusal.
  * Empty clouds: as in the plane call (no device needed, the first repeat converges).
  * Device ("Coloured ICP"): color_gradient_k once per call, then one fused launch per iteration
- * (icp_colored_iter_k) and the small launch that adds the workgroups' records. */
+ * (icp_iter_k<IcpColoredRows>) and the small launch that adds the workgroups' records. */
 /* G1 - G7 alone: out_gradient n x 3.  max_nn in [1, 128], radius >= 0. */
 int m3d_color_gradient(const double *dst, const double *dst_normals, const double *dst_colors, size_t n, double radius,
                        int max_nn, int device, double *out_gradient);

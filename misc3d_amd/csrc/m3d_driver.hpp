@@ -196,20 +196,16 @@ inline constexpr char kIcpNeedsNormals[] =
     "PointCloud.";
 inline constexpr char kIcpNeedsColors[] = "TransformationEstimationForColoredICP requires colors for the source and the target PointCloud.";
 inline constexpr char kIcpBadLambda[] = "lambda_geometric must be in [0, 1].";
-// m3d_registration_icp / m3d_registration_icp_plane: the three estimators of the one RegistrationICP loop (m3d_registration.cpp);
-// held != null: on that lane, which the caller holds (m3d_multi_scale_icp), else the call takes a lane of `device` itself
+// m3d_registration_icp / m3d_registration_icp_plane[_l1] / m3d_registration_icp_colored: the four estimators of the one
+// RegistrationICP loop (m3d_registration.cpp); held != null: on that lane, which the caller holds (m3d_multi_scale_icp), else the
+// call takes a lane of `device` itself
 int registration_icp_on(DeviceCtx* held, const double* src, size_t n_src, const double* dst, size_t n_dst,
                         double max_correspondence_distance, const double* T_init, int max_iteration, double relative_fitness,
                         double relative_rmse, int device, double* T_out, m3d_icp_stats* stats, int64_t* correspondences);
 int registration_icp_plane_on(DeviceCtx* held, const double* src, size_t n_src, const double* dst, const double* dst_normals,
                               size_t n_dst, double max_correspondence_distance, const double* T_init, int max_iteration,
                               double relative_fitness, double relative_rmse, int device, double* T_out, m3d_icp_stats* stats,
-                              int64_t* correspondences);
-// m3d_registration_icp_plane_l1: the plane estimator with L1 weights, the fourth of the loop
-int registration_icp_plane_l1_on(DeviceCtx* held, const double* src, size_t n_src, const double* dst, const double* dst_normals,
-                                 size_t n_dst, double max_correspondence_distance, const double* T_init, int max_iteration,
-                                 double relative_fitness, double relative_rmse, int device, double* T_out, m3d_icp_stats* stats,
-                                 int64_t* correspondences);
+                              int64_t* correspondences, bool l1 /* the plane estimator with L1 weights: m3d_registration_icp_plane_l1 */);
 // m3d_registration_icp_colored, the same way (m3d_multi_scale_icp_colored holds the lane)
 int registration_icp_colored_on(DeviceCtx* held, const double* src, const double* src_colors, size_t n_src, const double* dst,
                                 const double* dst_normals, const double* dst_colors, size_t n_dst,

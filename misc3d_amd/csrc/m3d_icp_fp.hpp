@@ -1,6 +1,6 @@
 // m3d_icp_fp.hpp -- the host arithmetic of the RegistrationICP loop (icp_loop, m3d_registration.cpp): the compose step every
-// estimator shares (icp_compose4), and ComputeTransformation of the two estimators that reduce an iteration to a record
-// (m3d_registration_icp_plane, m3d_registration_icp_colored): from the 30 sums to the 4 x 4 update; and the 3 x 3 solve of the
+// estimator shares (icp_compose4), and ComputeTransformation of the estimators that reduce an iteration to a record
+// (m3d_registration_icp_plane[_l1], m3d_registration_icp_colored: the rows of icp_iter_k): from the 30 sums to the 4 x 4 update; and the 3 x 3 solve of the
 // colour gradient.  Plain C++, no HIP: the library and the stand-alone check tests/cpp/test_icp_solve.cpp compile the same text
 // (build with -ffp-contract=off).
 //
@@ -8,7 +8,7 @@
 // SolveJacobianSystemAndObtainExtrinsicMatrix(JTJ, JTr) -> SolveLinearSystemPSD(JTJ, -JTr, check_det = true) ->
 // TransformVector6dToMatrix4d; the numbered rules are in include/misc3d_amd.h (m3d_registration_icp_plane).
 //
-// The record of an iteration (kIcpPlaneSums doubles, written by icp_plane_final_k):
+// The record of an iteration (kIcpPlaneSums doubles, summed per workgroup by icp_iter_k and written by icp_plane_final_k):
 //   [0] correspondences   [1] sum d^2   [2 .. 22] JTJ, upper triangle by rows ((0,0) (0,1) .. (0,5) (1,1) .. (5,5))
 //   [23 .. 28] JTr        [29] sum r^2
 #pragma once

@@ -96,7 +96,7 @@ int multi_scale_impl(const double* src, size_t n_src, const double* dst, const d
                                              nullptr);
         else if (plane)
             rc = registration_icp_plane_on(ctx, ps[l], ms[l], pd[l], pn[l], md[l], max_correspondence_distance, current,
-                                           max_iters[l], 1e-6, 1e-6, device, next, &st, nullptr);
+                                           max_iters[l], 1e-6, 1e-6, device, next, &st, nullptr, /*l1=*/false);
         else
             rc = registration_icp_on(ctx, ps[l], ms[l], pd[l], md[l], max_correspondence_distance, current, max_iters[l], 1e-6,
                                      1e-6, device, next, &st, nullptr);

@@ -124,10 +124,11 @@ __global__ void ring_min3_k(const uint8_t* __restrict__ in, const uint8_t* prev,
     out[c] = LAST ? (uint8_t)min((uint32_t)prev[c], min(m + 1u, 255u)) : (uint8_t)m;
 }
 // ring: the result (ncell bytes); tmp: 2 x ncell bytes of scratch
-void launch_reg_rings(const GridDesc& g, const uint32_t* cell_start, uint8_t* ring, uint8_t* tmp, int rounds, hipStream_t s) {
+void launch_reg_rings(const TargetGrid& t, uint8_t* ring, uint8_t* tmp, int rounds, hipStream_t s) {
+    const GridDesc& g = t.g;
     const uint32_t ncell = g.nx * g.ny * g.nz, nb = (ncell + 255) / 256;
     uint8_t *a = tmp, *b = tmp + ncell;
-    ring_init_k<<<nb, 256, 0, s>>>(cell_start, ncell, ring);
+    ring_init_k<<<nb, 256, 0, s>>>(t.cell_start, ncell, ring);
     for (int r = 0; r < rounds; ++r) {
         ring_min3_k<false><<<nb, 256, 0, s>>>(ring, nullptr, a, ncell, 1u, g.nx);
         ring_min3_k<false><<<nb, 256, 0, s>>>(a, nullptr, b, ncell, g.nx, g.ny);
@@ -275,12 +276,11 @@ __global__ __launch_bounds__(256) void reg_cache_build_k(const double* __restric
         }
 }
 
-void launch_reg_cache_build(const CloudView& src_sorted, const double* T_dev, const GridDesc& g, const uint32_t* cell_start,
-                            const double* qx, const double* qy, const double* qz, const RegCache& c, hipStream_t s) {
+void launch_reg_cache_build(const CloudView& src_sorted, const double* T_dev, const TargetGrid& t, const RegCache& c, hipStream_t s) {
     static_assert(kRegTile == 256, "layouts of the cache");
     if (!src_sorted.n_pad) return;
-    reg_cache_build_k<<<(src_sorted.n_pad + 3) / 4, 256, 0, s>>>(src_sorted.x, src_sorted.y, src_sorted.z, src_sorted.n_pad, T_dev, g,
-                                                                 cell_start, qx, qy, qz, c);
+    reg_cache_build_k<<<(src_sorted.n_pad + 3) / 4, 256, 0, s>>>(src_sorted.x, src_sorted.y, src_sorted.z, src_sorted.n_pad, T_dev, t.g,
+                                                                 t.cell_start, t.qx, t.qy, t.qz, c);
 }
 
 // ------------------------------------------------------------------------------------------------

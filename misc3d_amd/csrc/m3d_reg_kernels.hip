@@ -439,25 +439,23 @@ void launch_nl32_offsets(const uint32_t* nl_start, uint32_t ncell, uint32_t* nl3
 
 // step 1: counts + exclusive scan into nl_start[0..ncell]; the caller reads nl_start[ncell] (= entries),
 // allocates nl_pts and calls step 2.
-void launch_nl_count(const GridDesc& g, const uint32_t* cell_start, uint32_t* nl_start, uint32_t* tile_sums,
-                     uint32_t* total, hipStream_t s) {
-    const uint32_t ncell = g.nx * g.ny * g.nz;
-    nl_count_k<<<(ncell + 255) / 256, 256, 0, s>>>(g, cell_start, ncell, nl_start);
+void launch_nl_count(const TargetGrid& t, uint32_t* nl_start, uint32_t* tile_sums, uint32_t* total, hipStream_t s) {
+    const uint32_t ncell = t.g.nx * t.g.ny * t.g.nz;
+    nl_count_k<<<(ncell + 255) / 256, 256, 0, s>>>(t.g, t.cell_start, ncell, nl_start);
     const uint32_t nt = (ncell + 2047) / 2048;
     tile_scan_k<<<nt, 256, 0, s>>>(nl_start, ncell, tile_sums);
     launch_scan_blocks(tile_sums, nt, total, s);
     add_tile_offsets_k<<<(ncell + 1 + 255) / 256, 256, 0, s>>>(nl_start, ncell, tile_sums, total);
 }
-void launch_nl_fill(const GridDesc& g, const uint32_t* cell_start, const uint32_t* nl_start, double* qx,
-                    double* qy, double* qz, double4* nl_pts, hipStream_t s, const uint32_t* orig, bool sorted,
-                    uint32_t* nl_hdr, uint2* nl32, uint4* nl_rec, uint32_t* overflow, const uint32_t* nl32_start) {
-    const uint32_t ncell = g.nx * g.ny * g.nz;
-    if (sorted && !orig) {
-        sort_cells_by_x_k<<<(ncell + 255) / 256, 256, 0, s>>>(cell_start, ncell, qx, qy, qz);
-        nl_fill_sorted_k<<<(ncell + 255) / 256, 256, 0, s>>>(g, cell_start, ncell, nl_start, qx, qy, qz, nl_pts, nl_hdr, nl32, nl_rec, overflow, nl32_start);
+void launch_nl_fill(const TargetGrid& t, const uint32_t* nl_start, double4* nl_pts, hipStream_t s, bool sorted, uint32_t* nl_hdr,
+                    uint2* nl32, uint4* nl_rec, uint32_t* overflow, const uint32_t* nl32_start) {
+    const uint32_t ncell = t.g.nx * t.g.ny * t.g.nz;
+    if (sorted && !t.cell_orig) {
+        sort_cells_by_x_k<<<(ncell + 255) / 256, 256, 0, s>>>(t.cell_start, ncell, t.qx, t.qy, t.qz);
+        nl_fill_sorted_k<<<(ncell + 255) / 256, 256, 0, s>>>(t.g, t.cell_start, ncell, nl_start, t.qx, t.qy, t.qz, nl_pts, nl_hdr, nl32, nl_rec, overflow, nl32_start);
         return;
     }
-    nl_fill_k<<<(ncell + 255) / 256, 256, 0, s>>>(g, cell_start, ncell, nl_start, qx, qy, qz, nl_pts, orig);
+    nl_fill_k<<<(ncell + 255) / 256, 256, 0, s>>>(t.g, t.cell_start, ncell, nl_start, t.qx, t.qy, t.qz, nl_pts, t.cell_orig);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1066,12 +1064,11 @@ __global__ __launch_bounds__(64 * kFoldSlices) void reg_keep_k(const uint32_t* _
 // best_cnt / best_sum2: inlier count and order-free sum of squared distances of the best hypothesis of EARLIER chunks
 // (best_cnt 0: nothing to prune against).  n_points: real source points.  keep: s_pad bytes of scratch.
 // Returns the number of partial rows (what the reduce kernels fold).
-uint32_t launch_reg_validate(const CloudView& src, const double* Ts, uint32_t s_pad, const GridDesc& g,
-                             const uint32_t* cell_start, const double* qx, const double* qy, const double* qz,
-                             uint32_t* partial_cnt, double* partial_sum, double* sums, uint32_t best_cnt,
-                             uint32_t n_points, uint8_t* keep, hipStream_t s, double best_sum2, uint32_t n_hyp,
-                             const RegCache* cache) {
+uint32_t launch_reg_validate(const CloudView& src, const double* Ts, uint32_t s_pad, const TargetGrid& t, uint32_t* partial_cnt,
+                             double* partial_sum, double* sums, uint32_t best_cnt, uint32_t n_points, uint8_t* keep, hipStream_t s,
+                             double best_sum2, uint32_t n_hyp, const RegCache* cache) {
     if (!s_pad || !src.n_pad) return 0;
+    const GridDesc& g = t.g;
     const uint32_t groups = s_pad / 64;
     const uint32_t n_tiles = src.n_pad / kRegTile;
     const uint32_t tile_points = (uint32_t)kRegTile;
@@ -1104,19 +1101,19 @@ uint32_t launch_reg_validate(const CloudView& src, const double* Ts, uint32_t s_
             (void)hipMemsetAsync(cache->n_pairs, 0, sizeof(uint32_t), s);
             redo_pairs_k<<<dim3((s_pad + 255) / 256, tiles), 256, 0, s>>>(cache->redo, kp, s_pad, res_mask, n_tiles, tiles, cache->pairs, cache->n_pairs);
             if (g.nl32 && g.nl_rec && g.nl_sorted && g.nl_start && g.nl_hdr)
-                reg_validate_pairs_k<true><<<8192, 256, 0, s>>>(src.x, src.y, src.z, Ts, s_pad, g, cell_start, qx, qy, qz, partial_cnt, partial_sum,
+                reg_validate_pairs_k<true><<<8192, 256, 0, s>>>(src.x, src.y, src.z, Ts, s_pad, g, t.cell_start, t.qx, t.qy, t.qz, partial_cnt, partial_sum,
                                                                cache->pairs, cache->n_pairs);
             else
-                reg_validate_pairs_k<false><<<8192, 256, 0, s>>>(src.x, src.y, src.z, Ts, s_pad, g, cell_start, qx, qy, qz, partial_cnt, partial_sum,
+                reg_validate_pairs_k<false><<<8192, 256, 0, s>>>(src.x, src.y, src.z, Ts, s_pad, g, t.cell_start, t.qx, t.qy, t.qz, partial_cnt, partial_sum,
                                                                 cache->pairs, cache->n_pairs);
             return;
         }
         if (g.nl32 && g.nl_rec && g.nl_sorted && g.nl_start && g.nl_hdr)
-            reg_validate_k<true><<<slots * 8 * nsplit, 256, 0, s>>>(src.x, src.y, src.z, Ts, s_pad, per_split, g, cell_start, qx, qy,
-                                                                   qz, partial_cnt, partial_sum, res_mask, n_tiles, kp, tiles, nsplit);
+            reg_validate_k<true><<<slots * 8 * nsplit, 256, 0, s>>>(src.x, src.y, src.z, Ts, s_pad, per_split, g, t.cell_start, t.qx, t.qy,
+                                                                   t.qz, partial_cnt, partial_sum, res_mask, n_tiles, kp, tiles, nsplit);
         else
-            reg_validate_k<false><<<slots * 8 * nsplit, 256, 0, s>>>(src.x, src.y, src.z, Ts, s_pad, per_split, g, cell_start, qx, qy,
-                                                                    qz, partial_cnt, partial_sum, res_mask, n_tiles, kp, tiles, nsplit);
+            reg_validate_k<false><<<slots * 8 * nsplit, 256, 0, s>>>(src.x, src.y, src.z, Ts, s_pad, per_split, g, t.cell_start, t.qx, t.qy,
+                                                                    t.qz, partial_cnt, partial_sum, res_mask, n_tiles, kp, tiles, nsplit);
     };
     if (best_cnt == 0 || n_tiles < 16) {
         launch(0xFFFFFFFFu, nullptr, false);
@@ -1178,9 +1175,8 @@ __global__ void reg_min_d2_k(CloudView src, const double* __restrict__ T, GridDe
     const double3 p = move_point(T, src.x[i], src.y[i], src.z[i]);
     best[i] = nearest_d2(g, cell_start, qx, qy, qz, p.x, p.y, p.z);
 }
-void launch_reg_min_d2(const CloudView& src, const double* T, const GridDesc& g, const uint32_t* cell_start,
-                       const double* qx, const double* qy, const double* qz, double* best, hipStream_t s) {
-    if (src.n) reg_min_d2_k<<<(src.n + 255) / 256, 256, 0, s>>>(src, T, g, cell_start, qx, qy, qz, best);
+void launch_reg_min_d2(const CloudView& src, const double* T, const TargetGrid& t, double* best, hipStream_t s) {
+    if (src.n) reg_min_d2_k<<<(src.n + 255) / 256, 256, 0, s>>>(src, T, t.g, t.cell_start, t.qx, t.qy, t.qz, best);
 }
 
 // ordered compaction of the values < limit (3 passes, same structure as compact_*_k)
@@ -1269,30 +1265,29 @@ __device__ __forceinline__ void tree_reduce_256(double (&acc)[NV], double* sm) {
         __syncthreads();
     }
 }
-// pass 0: sums of src and dst coordinates (6 values); pass 1: with means -> 9 covariance + 3 variance
-template <int PASS>
-__global__ __launch_bounds__(256) void kabsch_sums_k(const double* __restrict__ src,
-                                                      const double* __restrict__ dst, uint32_t n,
-                                                      const double* __restrict__ sums0,
-                                                      double* __restrict__ partial) {
+// Eigen::umeyama sums over the pairs of a pair source: PASS 0 = the six coordinate sums, PASS 1 = covariance d s^T (9) and |s|^2 (3)
+// about the means sums0 / n.  Pairs: has(i) -> index i has a pair; pair(i, s, d) -> which; one_over_n().  Order-free tree sums: a term passes
+// through at most D = ceil(n / 65536) + 16 additions after its 3 roundings, so |sum - exact| <= (D + 3) 2^-53 sum |t_i| + m |dmean_d|
+// |dmean_s| to first order (DESIGN.md, "The registration sums and their bound"; held at twice that by tests/test_gpu_reg_sums.py).
+template <int PASS, class Pairs>
+__global__ __launch_bounds__(256) void umeyama_sums_k(Pairs pairs, uint32_t n, const double* __restrict__ sums0,
+                                                       double* __restrict__ partial) {
     constexpr int NV = PASS == 0 ? 6 : 12;
     __shared__ double sm[NV * 256];
     double acc[NV];
     for (int k = 0; k < NV; ++k) acc[k] = 0.0;
     double ms[3] = {0, 0, 0}, md[3] = {0, 0, 0};
     if (PASS == 1) {
-        const double one_over_n = 1.0 / (double)n;
+        const double one_over_n = pairs.one_over_n();
         for (int k = 0; k < 3; ++k) {
             ms[k] = sums0[k] * one_over_n;
             md[k] = sums0[3 + k] * one_over_n;
         }
     }
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += 256u * 256u) {
+        if (!pairs.has(i)) continue;
         double s[3], d[3];
-        for (int k = 0; k < 3; ++k) {
-            s[k] = src[3 * (size_t)i + k];
-            d[k] = dst[3 * (size_t)i + k];
-        }
+        pairs.pair(i, s, d);
         if (PASS == 0) {
             for (int k = 0; k < 3; ++k) {
                 acc[k] += s[k];
@@ -1312,6 +1307,19 @@ __global__ __launch_bounds__(256) void kabsch_sums_k(const double* __restrict__ 
     tree_reduce_256<NV>(acc, sm);
     if (threadIdx.x < NV) partial[blockIdx.x * 16 + threadIdx.x] = sm[threadIdx.x * 256];
 }
+// n correspondences as rows of two AoS arrays (LeastSquareSolver, m3d_kabsch): every index has its pair
+struct KabschPairs {
+    const double *src, *dst;
+    uint32_t n;
+    __device__ __forceinline__ bool has(uint32_t) const { return true; }
+    __device__ __forceinline__ void pair(uint32_t i, double (&s)[3], double (&d)[3]) const {
+        for (int k = 0; k < 3; ++k) {
+            s[k] = src[3 * (size_t)i + k];
+            d[k] = dst[3 * (size_t)i + k];
+        }
+    }
+    __device__ __forceinline__ double one_over_n() const { return 1.0 / (double)n; }
+};
 template <int NV>
 __global__ __launch_bounds__(256) void kabsch_final_k(const double* __restrict__ partial,
                                                        double* __restrict__ sums) {
@@ -1323,9 +1331,10 @@ __global__ __launch_bounds__(256) void kabsch_final_k(const double* __restrict__
 }
 void launch_kabsch_sums(const double* src, const double* dst, uint32_t n, double* partial,
                         double* sums /* 6 + 12 */, hipStream_t s) {
-    kabsch_sums_k<0><<<256, 256, 0, s>>>(src, dst, n, nullptr, partial);
+    const KabschPairs pairs{src, dst, n};
+    umeyama_sums_k<0><<<256, 256, 0, s>>>(pairs, n, nullptr, partial);
     kabsch_final_k<6><<<1, 256, 0, s>>>(partial, sums);
-    kabsch_sums_k<1><<<256, 256, 0, s>>>(src, dst, n, sums, partial);
+    umeyama_sums_k<1><<<256, 256, 0, s>>>(pairs, n, sums, partial);
     kabsch_final_k<12><<<1, 256, 0, s>>>(partial, sums + 6);
 }
 
@@ -1413,10 +1422,9 @@ __global__ void icp_nn_k(const double* __restrict__ px, const double* __restrict
     nn[i] = ok ? bo : 0xFFFFFFFFu;
     d2[i] = ok ? best : INFINITY;
 }
-void launch_icp_nn(const double* px, const double* py, const double* pz, uint32_t n, const GridDesc& g,
-                   const uint32_t* cell_start, const double* qx, const double* qy, const double* qz,
-                   const uint32_t* cell_orig, uint32_t* nn, double* d2, hipStream_t s) {
-    if (n) icp_nn_k<<<(n + 255) / 256, 256, 0, s>>>(px, py, pz, n, g, cell_start, qx, qy, qz, cell_orig, nn, d2);
+void launch_icp_nn(const double* px, const double* py, const double* pz, uint32_t n, const TargetGrid& t, uint32_t* nn, double* d2,
+                   hipStream_t s) {
+    if (n) icp_nn_k<<<(n + 255) / 256, 256, 0, s>>>(px, py, pz, n, t.g, t.cell_start, t.qx, t.qy, t.qz, t.cell_orig, nn, d2);
 }
 
 // GetRegistrationResultAndCorrespondences' error2 and correspondence count in one pass over the per-point
@@ -1442,56 +1450,28 @@ void launch_icp_err(const double* d2, uint32_t n, double r2, double* partial, do
     kabsch_final_k<2><<<1, 256, 0, s>>>(partial, out2);
 }
 
-// Eigen::umeyama sums over the correspondence set (moving point i, target point nn[i]): PASS 0 = the six
-// coordinate sums, PASS 1 = covariance d s^T (9) and |s|^2 (3) about the means.  Order-free tree sums: a term passes through
-// at most D = ceil(n / 65536) + 16 additions after its 3 roundings, so |sum - exact| <= (D + 3) 2^-53 sum |t_i| + m |dmean_d|
-// |dmean_s| to first order (DESIGN.md, "The registration sums and their bound"; held at twice that by tests/test_gpu_reg_sums.py).
-template <int PASS>
-__global__ __launch_bounds__(256) void icp_sums_k(const double* __restrict__ px, const double* __restrict__ py,
-                                                   const double* __restrict__ pz, uint32_t n, CloudView dst,
-                                                   const uint32_t* __restrict__ nn, const double* __restrict__ count,
-                                                   const double* __restrict__ sums0, double* __restrict__ partial) {
-    constexpr int NV = PASS == 0 ? 6 : 12;
-    __shared__ double sm[NV * 256];
-    double acc[NV];
-    for (int k = 0; k < NV; ++k) acc[k] = 0.0;
-    double ms[3] = {0, 0, 0}, md[3] = {0, 0, 0};
-    if (PASS == 1) {
-        const double one_over_n = 1.0 / count[0];
-        for (int k = 0; k < 3; ++k) {
-            ms[k] = sums0[k] * one_over_n;
-            md[k] = sums0[3 + k] * one_over_n;
-        }
-    }
-    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += 256u * 256u) {
+// The correspondence set of an ICP step as umeyama_sums_k's pair source: (moving point i, target point nn[i]) where i is matched;
+// their number comes from the device (icp_err_k's count, queued in front)
+struct IcpPairs {
+    const double *px, *py, *pz;
+    CloudView dst;
+    const uint32_t* nn;
+    const double* count;
+    __device__ __forceinline__ bool has(uint32_t i) const { return nn[i] != 0xFFFFFFFFu; }
+    __device__ __forceinline__ void pair(uint32_t i, double (&s)[3], double (&d)[3]) const {
         const uint32_t j = nn[i];
-        if (j == 0xFFFFFFFFu) continue;
-        double s[3] = {px[i], py[i], pz[i]}, d[3] = {dst.x[j], dst.y[j], dst.z[j]};
-        if (PASS == 0) {
-            for (int k = 0; k < 3; ++k) {
-                acc[k] += s[k];
-                acc[3 + k] += d[k];
-            }
-        } else {
-            for (int k = 0; k < 3; ++k) {
-                s[k] -= ms[k];
-                d[k] -= md[k];
-            }
-            for (int r = 0; r < 3; ++r) {
-                for (int c = 0; c < 3; ++c) acc[3 * r + c] += d[r] * s[c];
-                acc[9 + r] += s[r] * s[r];
-            }
-        }
+        s[0] = px[i], s[1] = py[i], s[2] = pz[i];
+        d[0] = dst.x[j], d[1] = dst.y[j], d[2] = dst.z[j];
     }
-    tree_reduce_256<NV>(acc, sm);
-    if (threadIdx.x < NV) partial[blockIdx.x * 16 + threadIdx.x] = sm[threadIdx.x * 256];
-}
+    __device__ __forceinline__ double one_over_n() const { return 1.0 / count[0]; }
+};
 // sums: 18 doubles laid out like launch_kabsch_sums (6 coordinate sums, 9 covariance sums, 3 squared sums)
 void launch_icp_sums(const double* px, const double* py, const double* pz, uint32_t n, const CloudView& dst,
                      const uint32_t* nn, const double* count, double* partial, double* sums, hipStream_t s) {
-    icp_sums_k<0><<<256, 256, 0, s>>>(px, py, pz, n, dst, nn, count, nullptr, partial);
+    const IcpPairs pairs{px, py, pz, dst, nn, count};
+    umeyama_sums_k<0><<<256, 256, 0, s>>>(pairs, n, nullptr, partial);
     kabsch_final_k<6><<<1, 256, 0, s>>>(partial, sums);
-    icp_sums_k<1><<<256, 256, 0, s>>>(px, py, pz, n, dst, nn, count, sums, partial);
+    umeyama_sums_k<1><<<256, 256, 0, s>>>(pairs, n, sums, partial);
     kabsch_final_k<12><<<1, 256, 0, s>>>(partial, sums + 6);
 }
 
@@ -1542,20 +1522,25 @@ void launch_icp_transform(const double* ix, const double* iy, const double* iz, 
     if (n) icp_transform_k<<<(n + 255) / 256, 256, 0, s>>>(ix, iy, iz, n, T_dev, ox, oy, oz);
 }
 
-// The iteration kernels of point-to-plane and coloured ICP (m3d_registration_icp_plane, m3d_registration_icp_colored): ONE
-// launch per iteration, one moving point per thread at every size (n < 2^31 -> at most 2^23 workgroups; no thread ever takes
-// a second point).  Both kernels are the same frame around their own rows:
+// The iteration kernel of point-to-plane, its L1 variant and coloured ICP (m3d_registration_icp_plane[_l1], m3d_registration_icp_colored):
+// ONE launch per iteration, one moving point per thread at every size (n < 2^31 -> at most 2^23 workgroups; no thread ever takes
+// a second point).  icp_iter_k<Rows> is one frame around the rows of its estimator (icp_rows, overloaded on the estimators of
+// m3d_reg_kernels.hpp):
 //   icp_move_and_match   1. applies the pending update T (12 doubles, null = none) and stores the point (in place from the
 //                           second iteration on; the first reads the source cloud);
 //                        2. searches its nearest target point (nearest_idx: lowest original index on exact ties), stores nn[i];
-//   the kernel's body    3. for a correspondence (d2 < r^2) forms the residual and Jacobian rows of its estimator and from them
-//                           the thread's record of m3d_icp_fp.hpp: count, d2, the 21 products of JTJ, the 6 of JTr, r^2 (zeros
-//                           otherwise);
+//   icp_rows             3. for a correspondence (d2 < r^2) forms the residual and Jacobian rows of its estimator and from them
+//                           the thread's record of m3d_icp_fp.hpp: count, d2, the 21 products of JTJ, the 6 of JTr, r^2 (it leaves
+//                           the zeros otherwise);
 //   icp_record_reduce    4. sums the 30 values over the wave by m3d::wave_sum (xor butterfly, order fixed); the four waves' sums
 //                           meet in LDS and wave 0 adds them in wave order: one record per workgroup.
 // icp_plane_final_k then sums the workgroups' records, value k in workgroup k: lane l adds the records l, l + 64, ... in
 // ascending order, wave_sum adds the lanes.  No atomics: the result is a fixed function of (points, update, grid) -- the same
 // bits from run to run, whatever else the device runs -- and the ONE order of these sums is what relates the estimators.
+// Two things in this text are there for the register allocator, found by compiling (profiles/icp_refactor_resources.txt).  The
+// kernel takes the target grid as restrict-qualified arguments like every kernel of this file, unpacked from the view at the
+// launch: with the view itself as the argument the coloured instantiation has 82 VGPRs, not 80, one wave per SIMD fewer.  And the
+// rows test m.ok themselves: with the test in the kernel, around the call, the same instantiation has 96.
 struct IcpMatch {
     double x, y, z;   // the moved point
     double d2;        // squared distance to the nearest target point
@@ -1599,39 +1584,90 @@ __device__ __forceinline__ void icp_record_reduce(const double (&v)[kIcpPlaneRec
     }
 }
 
-// Point-to-plane: r = (s - t_j) . n_j, J = [s x n_j, n_j]
-__global__ __launch_bounds__(256) void icp_plane_iter_k(const double* __restrict__ ix, const double* __restrict__ iy,
-                                                         const double* __restrict__ iz, uint32_t n,
-                                                         const double* __restrict__ T, double* __restrict__ px,
-                                                         double* __restrict__ py, double* __restrict__ pz, GridDesc g,
-                                                         const uint32_t* __restrict__ cell_start,
-                                                         const double* __restrict__ qx, const double* __restrict__ qy,
-                                                         const double* __restrict__ qz,
-                                                         const uint32_t* __restrict__ cell_orig, CloudView dst,
-                                                         uint32_t* __restrict__ nn, double* __restrict__ partial) {
+// Point-to-plane: r = (s - t_j) . n_j, J = [s x n_j, n_j].  L1 (Open3D's L1Loss; PPFEstimator's PointToPlane refinement): the same
+// rows weighted by w = 1 / |r| -- the products are (J[a] w) J[b] and (J[a] w) r; the last slot stays r r.  r == 0: w is infinite,
+// the record turns non-finite and the host's determinant check yields the identity update.
+template <bool L1>
+__device__ __forceinline__ void icp_plane_rows(const CloudView& dst, const IcpMatch& m, double (&v)[kIcpPlaneRecord]) {
+    if (!m.ok) return;
+    const double x = m.x, y = m.y, z = m.z;
+    const double ax = dst.nx[m.j], ay = dst.ny[m.j], az = dst.nz[m.j];
+    const double ex = x - dst.x[m.j], ey = y - dst.y[m.j], ez = z - dst.z[m.j];
+    const double r = (ex * ax + ey * ay) + ez * az;
+    const double w = L1 ? 1.0 / fabs(r) : 1.0;
+    // s x n, SURVEY.md 8a-note (iii)
+    const double J[6] = {y * az - z * ay, z * ax - x * az, x * ay - y * ax, ax, ay, az};
+    v[0] = 1.0;
+    v[1] = m.d2;
+    int k = 2;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        const double Jw = L1 ? J[a] * w : J[a];
+#pragma unroll
+        for (int b = a; b < 6; ++b) v[k++] = Jw * J[b];
+        v[23 + a] = Jw * r;
+    }
+    v[29] = r * r;
+}
+__device__ __forceinline__ void icp_rows(const IcpPlaneRows& e, uint32_t, const IcpMatch& m, double (&v)[kIcpPlaneRecord]) {
+    icp_plane_rows<false>(e.dst, m, v);
+}
+__device__ __forceinline__ void icp_rows(const IcpPlaneL1Rows& e, uint32_t, const IcpMatch& m, double (&v)[kIcpPlaneRecord]) {
+    icp_plane_rows<true>(e.dst, m, v);
+}
+// Coloured: for a correspondence the thread gathers t_j, n_j, the colour gradient g_j (grad: n_dst x 3 rows) and the intensity
+// It_j, takes its own intensity Is_i (it does not move with the pose), and forms the two rows of rules C3 and C4 of
+// include/misc3d_amd.h:
+//   e = (s - t) . n          r0 = sg e                 J0 = sg [s x n, n]
+//   q = (s - e n) - t        I0 = g . q + It           m = -(g^T (I - n n^T))       r1 = sp (Is - I0)      J1 = sp [s x m, m]
+// and contributes count, d2, the 21 products J0a J0b + J1a J1b, the 6 values J0a r0 + J1a r1 and r0 r0 + r1 r1.
+__device__ __forceinline__ void icp_colored_rows(const CloudView& dst, const double* __restrict__ grad,
+                                                 const double* __restrict__ it_dst, const double* __restrict__ is_src, double sg,
+                                                 double sp, uint32_t i, const IcpMatch& m, double (&v)[kIcpPlaneRecord]) {
+    if (!m.ok) return;
+    const double x = m.x, y = m.y, z = m.z;
+    const uint32_t bo = m.j;
+    const double ax = dst.nx[bo], ay = dst.ny[bo], az = dst.nz[bo];
+    const double tx = dst.x[bo], ty = dst.y[bo], tz = dst.z[bo];
+    const double g0 = grad[3 * (size_t)bo], g1 = grad[3 * (size_t)bo + 1], g2 = grad[3 * (size_t)bo + 2];
+    const double e = ((x - tx) * ax + (y - ty) * ay) + (z - tz) * az;
+    const double r0 = sg * e;
+    const double q0 = (x - e * ax) - tx, q1 = (y - e * ay) - ty, q2 = (z - e * az) - tz;
+    const double i0 = ((g0 * q0 + g1 * q1) + g2 * q2) + it_dst[bo];
+    const double r1 = sp * (is_src[i] - i0);
+    // m = -(g^T (I - n n^T)), the nine entries written out
+    const double m0 = -((g0 * (1.0 - ax * ax) + g1 * (-(ay * ax))) + g2 * (-(az * ax)));
+    const double m1 = -((g0 * (-(ax * ay)) + g1 * (1.0 - ay * ay)) + g2 * (-(az * ay)));
+    const double m2 = -((g0 * (-(ax * az)) + g1 * (-(ay * az))) + g2 * (1.0 - az * az));
+    // s x n and s x m, associated as in icp_plane_rows
+    const double J0[6] = {sg * (y * az - z * ay), sg * (z * ax - x * az), sg * (x * ay - y * ax), sg * ax, sg * ay, sg * az};
+    const double J1[6] = {sp * (y * m2 - z * m1), sp * (z * m0 - x * m2), sp * (x * m1 - y * m0), sp * m0, sp * m1, sp * m2};
+    v[0] = 1.0;
+    v[1] = m.d2;
+    int k = 2;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int b = a; b < 6; ++b) v[k++] = J0[a] * J0[b] + J1[a] * J1[b];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) v[23 + a] = J0[a] * r0 + J1[a] * r1;
+    v[29] = r0 * r0 + r1 * r1;
+}
+__device__ __forceinline__ void icp_rows(const IcpColoredRows& c, uint32_t i, const IcpMatch& m, double (&v)[kIcpPlaneRecord]) {
+    icp_colored_rows(c.dst, c.grad, c.it_dst, c.is_src, c.sg, c.sp, i, m, v);
+}
+
+template <class Rows>
+__global__ __launch_bounds__(256) void icp_iter_k(IcpIterArgs a, GridDesc g, const uint32_t* __restrict__ cell_start,
+                                                   const double* __restrict__ qx, const double* __restrict__ qy,
+                                                   const double* __restrict__ qz, const uint32_t* __restrict__ cell_orig, Rows rows) {
     double v[kIcpPlaneRecord];
     for (int k = 0; k < kIcpPlaneRecord; ++k) v[k] = 0.0;
-    const IcpMatch m = icp_move_and_match(blockIdx.x * 256u + threadIdx.x, ix, iy, iz, n, T, px, py, pz, g, cell_start, qx, qy, qz,
-                                          cell_orig, nn);
-    if (m.ok) {
-        const double x = m.x, y = m.y, z = m.z;
-        const double ax = dst.nx[m.j], ay = dst.ny[m.j], az = dst.nz[m.j];
-        const double ex = x - dst.x[m.j], ey = y - dst.y[m.j], ez = z - dst.z[m.j];
-        const double r = (ex * ax + ey * ay) + ez * az;
-        // s x n, SURVEY.md 8a-note (iii)
-        const double J[6] = {y * az - z * ay, z * ax - x * az, x * ay - y * ax, ax, ay, az};
-        v[0] = 1.0;
-        v[1] = m.d2;
-        int k = 2;
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-            for (int b = a; b < 6; ++b) v[k++] = J[a] * J[b];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) v[23 + a] = J[a] * r;
-        v[29] = r * r;
-    }
-    icp_record_reduce(v, partial);
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const IcpMatch m = icp_move_and_match(i, a.ix, a.iy, a.iz, a.n, a.T, a.px, a.py, a.pz, g, cell_start, qx, qy, qz,
+                                          cell_orig, a.nn);
+    icp_rows(rows, i, m, v);
+    icp_record_reduce(v, a.partial);
 }
 __global__ __launch_bounds__(64) void icp_plane_final_k(const double* __restrict__ partial, uint32_t n_blocks,
                                                          double* __restrict__ out) {
@@ -1641,125 +1677,15 @@ __global__ __launch_bounds__(64) void icp_plane_final_k(const double* __restrict
     a = wave_sum(a);
     if (threadIdx.x == 0) out[k] = a;
 }
-void launch_icp_plane_iter(const double* ix, const double* iy, const double* iz, uint32_t n, const double* T_dev, double* px,
-                           double* py, double* pz, const GridDesc& g, const uint32_t* cell_start, const double* qx,
-                           const double* qy, const double* qz, const uint32_t* cell_orig, const CloudView& dst, uint32_t* nn,
-                           double* partial, double* out, hipStream_t s) {
-    const uint32_t nb = icp_plane_blocks(n);
-    icp_plane_iter_k<<<nb, 256, 0, s>>>(ix, iy, iz, n, T_dev, px, py, pz, g, cell_start, qx, qy, qz, cell_orig, dst, nn,
-                                        partial);
-    icp_plane_final_k<<<kIcpPlaneRecord, 64, 0, s>>>(partial, nb, out);
+template <class Rows>
+void launch_icp_iter(const IcpIterArgs& a, const TargetGrid& t, const Rows& rows, double* out, hipStream_t s) {
+    const uint32_t nb = icp_plane_blocks(a.n);
+    icp_iter_k<<<nb, 256, 0, s>>>(a, t.g, t.cell_start, t.qx, t.qy, t.qz, t.cell_orig, rows);
+    icp_plane_final_k<<<kIcpPlaneRecord, 64, 0, s>>>(a.partial, nb, out);
 }
-
-// Point-to-plane with Open3D's L1Loss (m3d_registration_icp_plane_l1; PPFEstimator's PointToPlane refinement): the rows of
-// icp_plane_iter_k weighted by w = 1 / |r|.  The products are (J[a] w) J[b] and (J[a] w) r; the last slot stays r r.  r == 0:
-// w is infinite, the record turns non-finite and the host's determinant check yields the identity update.
-__global__ __launch_bounds__(256) void icp_plane_l1_iter_k(const double* __restrict__ ix, const double* __restrict__ iy,
-                                                            const double* __restrict__ iz, uint32_t n,
-                                                            const double* __restrict__ T, double* __restrict__ px,
-                                                            double* __restrict__ py, double* __restrict__ pz, GridDesc g,
-                                                            const uint32_t* __restrict__ cell_start,
-                                                            const double* __restrict__ qx, const double* __restrict__ qy,
-                                                            const double* __restrict__ qz,
-                                                            const uint32_t* __restrict__ cell_orig, CloudView dst,
-                                                            uint32_t* __restrict__ nn, double* __restrict__ partial) {
-    double v[kIcpPlaneRecord];
-    for (int k = 0; k < kIcpPlaneRecord; ++k) v[k] = 0.0;
-    const IcpMatch m = icp_move_and_match(blockIdx.x * 256u + threadIdx.x, ix, iy, iz, n, T, px, py, pz, g, cell_start, qx, qy, qz,
-                                          cell_orig, nn);
-    if (m.ok) {
-        const double x = m.x, y = m.y, z = m.z;
-        const double ax = dst.nx[m.j], ay = dst.ny[m.j], az = dst.nz[m.j];
-        const double ex = x - dst.x[m.j], ey = y - dst.y[m.j], ez = z - dst.z[m.j];
-        const double r = (ex * ax + ey * ay) + ez * az;
-        const double w = 1.0 / fabs(r);
-        const double J[6] = {y * az - z * ay, z * ax - x * az, x * ay - y * ax, ax, ay, az};
-        v[0] = 1.0;
-        v[1] = m.d2;
-        int k = 2;
-#pragma unroll
-        for (int a = 0; a < 6; ++a) {
-            const double Jw = J[a] * w;
-#pragma unroll
-            for (int b = a; b < 6; ++b) v[k++] = Jw * J[b];
-            v[23 + a] = Jw * r;
-        }
-        v[29] = r * r;
-    }
-    icp_record_reduce(v, partial);
-}
-void launch_icp_plane_l1_iter(const double* ix, const double* iy, const double* iz, uint32_t n, const double* T_dev, double* px,
-                              double* py, double* pz, const GridDesc& g, const uint32_t* cell_start, const double* qx,
-                              const double* qy, const double* qz, const uint32_t* cell_orig, const CloudView& dst, uint32_t* nn,
-                              double* partial, double* out, hipStream_t s) {
-    const uint32_t nb = icp_plane_blocks(n);
-    icp_plane_l1_iter_k<<<nb, 256, 0, s>>>(ix, iy, iz, n, T_dev, px, py, pz, g, cell_start, qx, qy, qz, cell_orig, dst, nn,
-                                           partial);
-    icp_plane_final_k<<<kIcpPlaneRecord, 64, 0, s>>>(partial, nb, out);
-}
-
-// Coloured: for a correspondence the thread gathers t_j, n_j, the colour gradient g_j (grad: n_dst x 3 rows) and the intensity
-// It_j, takes its own intensity Is_i (it does not move with the pose), and forms the two rows of rules C3 and C4 of
-// include/misc3d_amd.h:
-//   e = (s - t) . n          r0 = sg e                 J0 = sg [s x n, n]
-//   q = (s - e n) - t        I0 = g . q + It           m = -(g^T (I - n n^T))       r1 = sp (Is - I0)      J1 = sp [s x m, m]
-// and contributes count, d2, the 21 products J0a J0b + J1a J1b, the 6 values J0a r0 + J1a r1 and r0 r0 + r1 r1.
-__global__ __launch_bounds__(256) void icp_colored_iter_k(const double* __restrict__ ix, const double* __restrict__ iy,
-                                                           const double* __restrict__ iz, uint32_t n,
-                                                           const double* __restrict__ T, double* __restrict__ px,
-                                                           double* __restrict__ py, double* __restrict__ pz, GridDesc g,
-                                                           const uint32_t* __restrict__ cell_start,
-                                                           const double* __restrict__ qx, const double* __restrict__ qy,
-                                                           const double* __restrict__ qz,
-                                                           const uint32_t* __restrict__ cell_orig, CloudView dst,
-                                                           const double* __restrict__ grad, const double* __restrict__ it_dst,
-                                                           const double* __restrict__ is_src, double sg, double sp,
-                                                           uint32_t* __restrict__ nn, double* __restrict__ partial) {
-    double v[kIcpPlaneRecord];
-    for (int k = 0; k < kIcpPlaneRecord; ++k) v[k] = 0.0;
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    const IcpMatch m = icp_move_and_match(i, ix, iy, iz, n, T, px, py, pz, g, cell_start, qx, qy, qz, cell_orig, nn);
-    if (m.ok) {
-        const double x = m.x, y = m.y, z = m.z;
-        const uint32_t bo = m.j;
-        const double ax = dst.nx[bo], ay = dst.ny[bo], az = dst.nz[bo];
-        const double tx = dst.x[bo], ty = dst.y[bo], tz = dst.z[bo];
-        const double g0 = grad[3 * (size_t)bo], g1 = grad[3 * (size_t)bo + 1], g2 = grad[3 * (size_t)bo + 2];
-        const double e = ((x - tx) * ax + (y - ty) * ay) + (z - tz) * az;
-        const double r0 = sg * e;
-        const double q0 = (x - e * ax) - tx, q1 = (y - e * ay) - ty, q2 = (z - e * az) - tz;
-        const double i0 = ((g0 * q0 + g1 * q1) + g2 * q2) + it_dst[bo];
-        const double r1 = sp * (is_src[i] - i0);
-        // m = -(g^T (I - n n^T)), the nine entries written out
-        const double m0 = -((g0 * (1.0 - ax * ax) + g1 * (-(ay * ax))) + g2 * (-(az * ax)));
-        const double m1 = -((g0 * (-(ax * ay)) + g1 * (1.0 - ay * ay)) + g2 * (-(az * ay)));
-        const double m2 = -((g0 * (-(ax * az)) + g1 * (-(ay * az))) + g2 * (1.0 - az * az));
-        // s x n and s x m, associated as in icp_plane_iter_k
-        const double J0[6] = {sg * (y * az - z * ay), sg * (z * ax - x * az), sg * (x * ay - y * ax), sg * ax, sg * ay, sg * az};
-        const double J1[6] = {sp * (y * m2 - z * m1), sp * (z * m0 - x * m2), sp * (x * m1 - y * m0), sp * m0, sp * m1, sp * m2};
-        v[0] = 1.0;
-        v[1] = m.d2;
-        int k = 2;
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-            for (int b = a; b < 6; ++b) v[k++] = J0[a] * J0[b] + J1[a] * J1[b];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) v[23 + a] = J0[a] * r0 + J1[a] * r1;
-        v[29] = r0 * r0 + r1 * r1;
-    }
-    icp_record_reduce(v, partial);
-}
-void launch_icp_colored_iter(const double* ix, const double* iy, const double* iz, uint32_t n, const double* T_dev, double* px,
-                             double* py, double* pz, const GridDesc& g, const uint32_t* cell_start, const double* qx,
-                             const double* qy, const double* qz, const uint32_t* cell_orig, const CloudView& dst,
-                             const double* grad, const double* it_dst, const double* is_src, double sg, double sp, uint32_t* nn,
-                             double* partial, double* out, hipStream_t s) {
-    const uint32_t nb = icp_plane_blocks(n);
-    icp_colored_iter_k<<<nb, 256, 0, s>>>(ix, iy, iz, n, T_dev, px, py, pz, g, cell_start, qx, qy, qz, cell_orig, dst, grad,
-                                          it_dst, is_src, sg, sp, nn, partial);
-    icp_plane_final_k<<<kIcpPlaneRecord, 64, 0, s>>>(partial, nb, out);
-}
+template void launch_icp_iter(const IcpIterArgs&, const TargetGrid&, const IcpPlaneRows&, double*, hipStream_t);
+template void launch_icp_iter(const IcpIterArgs&, const TargetGrid&, const IcpPlaneL1Rows&, double*, hipStream_t);
+template void launch_icp_iter(const IcpIterArgs&, const TargetGrid&, const IcpColoredRows&, double*, hipStream_t);
 
 // ------------------------------------------------------------------------------------------------
 // DetectBoundaryPoints (src/boundary_detection.cpp:21-113), one thread per point
@@ -1967,16 +1893,15 @@ __global__ __launch_bounds__(64) void boundary_k(CloudView c, GridDesc g, const 
     if (max_dif < wrap) max_dif = wrap;
     if (max_dif > angle_thr_rad) flag[i] = 1;
 }
-void launch_boundary(const CloudView& c, const GridDesc& g, const uint32_t* cell_start, const double* qx,
-                     const double* qy, const double* qz, const uint32_t* cell_orig, int search, int max_nn,
-                     double angle_threshold_deg, uint8_t* flag, uint8_t* overflow, hipStream_t s, const uint32_t* n_sorted) {
+void launch_boundary(const CloudView& c, const TargetGrid& t, int search, int max_nn, double angle_threshold_deg, uint8_t* flag,
+                     uint8_t* overflow, hipStream_t s, const uint32_t* n_sorted) {
     if (!c.n) return;
     const double thr = angle_threshold_deg * 3.14159265358979323846 / 180.0;   // :62
     if (search != 1 && max_nn <= 32)
-        boundary_k<true><<<(c.n + 63) / 64, 64, 0, s>>>(c, g, cell_start, qx, qy, qz, cell_orig, search, max_nn, thr, flag,
+        boundary_k<true><<<(c.n + 63) / 64, 64, 0, s>>>(c, t.g, t.cell_start, t.qx, t.qy, t.qz, t.cell_orig, search, max_nn, thr, flag,
                                                         overflow, n_sorted);
     else
-        boundary_k<false><<<(c.n + 63) / 64, 64, 0, s>>>(c, g, cell_start, qx, qy, qz, cell_orig, search, max_nn, thr, flag,
+        boundary_k<false><<<(c.n + 63) / 64, 64, 0, s>>>(c, t.g, t.cell_start, t.qx, t.qy, t.qz, t.cell_orig, search, max_nn, thr, flag,
                                                          overflow, n_sorted);
 }
 

@@ -52,8 +52,15 @@ struct GridDesc {
     // three 8-byte ones in the list-free search (a call that validates a handful of hypotheses never builds the lists)
     const double4* q4 = nullptr;
 };
-
-
+// What a search of the target grid reads: the grid, the first sorted slot of every cell (ncell + 1), the points in cell order and
+// the original index of every sorted point (null where the grid keeps none).  A view: the arrays belong to whoever built the grid.
+// The points are writable through it for launch_nl_fill's sake, which orders them inside their cells; every search only reads.
+struct TargetGrid {
+    GridDesc g;
+    const uint32_t* cell_start = nullptr;
+    double *qx = nullptr, *qy = nullptr, *qz = nullptr;
+    const uint32_t* cell_orig = nullptr;
+};
 
 // The candidate cache of the validation (m3d_reg_cache.hip): per sorted source point, under a reference pose, its position
 // xa, its nearest target points in kRegCacheTiers tiers of kRegCacheK (fp32 offsets from xa in pairs, fp64 coordinates) and per
@@ -79,10 +86,8 @@ struct RegCache {
     uint32_t* n_pairs = nullptr;   // ... and their number
     const uint8_t* ring = nullptr;   // per cell of the target grid: Chebyshev distance in cells to the nearest occupied cell (launch_reg_rings)
 };
-void launch_reg_cache_build(const CloudView& src_sorted, const double* T_dev, const GridDesc& g, const uint32_t* cell_start,
-                            const double* qx, const double* qy, const double* qz, const RegCache& c, hipStream_t s);
-void launch_reg_rings(const GridDesc& g, const uint32_t* cell_start, uint8_t* ring /* ncell */, uint8_t* tmp /* 2 ncell */, int rounds,
-                      hipStream_t s);
+void launch_reg_cache_build(const CloudView& src_sorted, const double* T_dev, const TargetGrid& t, const RegCache& c, hipStream_t s);
+void launch_reg_rings(const TargetGrid& t, uint8_t* ring /* ncell */, uint8_t* tmp /* 2 ncell */, int rounds, hipStream_t s);
 void launch_reg_validate_cached(const CloudView& src, const double* Ts, uint32_t s_pad, uint32_t per_split, uint32_t nsplit,
                                 uint32_t slots, const GridDesc& g, const RegCache& c, uint32_t* partial_cnt, double* partial_sum,
                                 uint32_t res_mask, uint32_t n_tiles, const uint8_t* keep, uint32_t tiles, uint8_t* redo,
@@ -107,13 +112,12 @@ void launch_grid_scatter(const CloudView& dst, const uint32_t* cell_of_point, co
                          double4* q4 = nullptr);
 void launch_signal_host(uint32_t* word /* page-locked, device-visible */, uint32_t value, hipStream_t st);
 void launch_fill_nan(double* p, uint32_t n, hipStream_t s);
-void launch_nl_count(const GridDesc& g, const uint32_t* cell_start, uint32_t* nl_start, uint32_t* tile_sums,
-                     uint32_t* total, hipStream_t s);
-// sorted (orig must be null): the points of every grid cell are first ordered by x IN PLACE (qx / qy / qz), then the lists
-// are written in the three-column layout of GridDesc::nl_sorted; the caller sets g.nl_sorted = 1.
-void launch_nl_fill(const GridDesc& g, const uint32_t* cell_start, const uint32_t* nl_start, double* qx,
-                    double* qy, double* qz, double4* nl_pts, hipStream_t s,
-                    const uint32_t* orig = nullptr, bool sorted = false, uint32_t* nl_hdr = nullptr /* sorted: ncell words */,
+void launch_nl_count(const TargetGrid& t, uint32_t* nl_start, uint32_t* tile_sums, uint32_t* total, hipStream_t s);
+// The lists' entries carry t.cell_orig in w where the grid keeps it.  sorted (t.cell_orig must be null): the points of every grid
+// cell are first ordered by x IN PLACE (t.qx / qy / qz), then the lists are written in the three-column layout of
+// GridDesc::nl_sorted; the caller sets g.nl_sorted = 1.
+void launch_nl_fill(const TargetGrid& t, const uint32_t* nl_start, double4* nl_pts, hipStream_t s, bool sorted = false,
+                    uint32_t* nl_hdr = nullptr /* sorted: ncell words */,
                     uint2* nl32 = nullptr /* sorted, optional: as many entries as nl_pts */, uint4* nl_rec = nullptr /* ncell */,
                     uint32_t* overflow = nullptr /* one word, zero on entry: set when a list is too long for nl_rec */,
                     const uint32_t* nl32_start = nullptr /* launch_nl32_offsets */);
@@ -123,60 +127,58 @@ void launch_nl32_offsets(const uint32_t* nl_start, uint32_t ncell, uint32_t* nl3
 // partial_cnt / partial_sum: rows of s_pad entries, reg_validate_k writes one per 256 source points (the arrays are
 // sized for kRegValidateRows per 256).  Returns the rows actually used: what launch_reduce_partials folds.
 constexpr int kRegValidateRows = 4;   // rows per 256 source points
-uint32_t launch_reg_validate(const CloudView& src, const double* Ts, uint32_t s_pad, const GridDesc& g,
-                             const uint32_t* cell_start, const double* qx, const double* qy, const double* qz,
-                             uint32_t* partial_cnt, double* partial_sum, double* sums, uint32_t best_cnt,
-                             uint32_t n_points, uint8_t* keep, hipStream_t s,
+uint32_t launch_reg_validate(const CloudView& src, const double* Ts, uint32_t s_pad, const TargetGrid& t, uint32_t* partial_cnt,
+                             double* partial_sum, double* sums, uint32_t best_cnt, uint32_t n_points, uint8_t* keep, hipStream_t s,
                              double best_sum2 = 0.0 /* order-free sum of squared distances of the hypothesis behind best_cnt */,
                              uint32_t n_hyp = 0 /* real hypotheses among the s_pad records (0: unknown); a handful is spread over more workgroups */,
                              const RegCache* cache = nullptr /* built for a pose near the hypotheses': the pairs it certifies skip the walk (same results) */);
-void launch_reg_min_d2(const CloudView& src, const double* T, const GridDesc& g, const uint32_t* cell_start,
-                       const double* qx, const double* qy, const double* qz, double* best, hipStream_t s);
+void launch_reg_min_d2(const CloudView& src, const double* T, const TargetGrid& t, double* best, hipStream_t s);
 void launch_compact_vals(const double* v, uint32_t n, double limit, uint32_t* block_counts, uint32_t* total,
                          double* out, hipStream_t s);
 void launch_corr_ratio(const CloudView& src, const CloudView& dst, const uint32_t* corr_src,
                        const uint32_t* corr_dst, uint32_t m, const double* T, double r2, uint32_t* count,
                        hipStream_t s);
-void launch_icp_nn(const double* px, const double* py, const double* pz, uint32_t n, const GridDesc& g,
-                   const uint32_t* cell_start, const double* qx, const double* qy, const double* qz,
-                   const uint32_t* cell_orig, uint32_t* nn, double* d2, hipStream_t s);
+void launch_icp_nn(const double* px, const double* py, const double* pz, uint32_t n, const TargetGrid& t, uint32_t* nn, double* d2,
+                   hipStream_t s);
 void launch_icp_err(const double* d2, uint32_t n, double r2, double* partial, double* out2, hipStream_t s);
 void launch_icp_sums(const double* px, const double* py, const double* pz, uint32_t n, const CloudView& dst,
                      const uint32_t* nn, const double* count, double* partial, double* sums, hipStream_t s);
 constexpr int kBoundaryMaxNb = 128;   // neighbours kept per point in boundary_k
-void launch_boundary(const CloudView& c, const GridDesc& g, const uint32_t* cell_start, const double* qx,
-                     const double* qy, const double* qz, const uint32_t* cell_orig, int search, int max_nn,
-                     double angle_threshold_deg, uint8_t* flag, uint8_t* overflow, hipStream_t s,
+void launch_boundary(const CloudView& c, const TargetGrid& t, int search, int max_nn, double angle_threshold_deg, uint8_t* flag,
+                     uint8_t* overflow, hipStream_t s,
                      const uint32_t* n_sorted /* device: points the grid holds (launch_grid_build's total) */);
 void launch_info_sums(uint32_t n, const CloudView& dst, const uint32_t* nn, double* partial, double* sums,
                       hipStream_t s);
 void launch_icp_transform(const double* ix, const double* iy, const double* iz, uint32_t n, const double* T_dev,
                           double* ox, double* oy, double* oz, hipStream_t s);
-// The iteration of the two ICP estimators that reduce to a record (the host's icp_record_loop): one frame in the kernel file --
-// the pending update, the store of the moved point, the search, nn[i]; the record's reduction -- around each estimator's rows.
-// Point-to-plane ICP's (icp_plane_iter_k + icp_plane_final_k): the pending update T_dev (12 doubles, null = none) applied
-// to (ix, iy, iz) -> (px, py, pz), nn[i], and out[0 .. kIcpPlaneRecord) = the record of m3d_icp_fp.hpp.  partial: kIcpPlaneStride
-// doubles per workgroup of 256 points (icp_plane_blocks(n) of them).  dst needs its normals.
+// The iteration of the ICP estimators that reduce to a record (the host's icp_record_loop): ONE kernel template in the kernel file
+// (icp_iter_k<Rows>) -- the pending update, the store of the moved point, the search, nn[i]; the record's reduction -- around the
+// rows of its estimator, and icp_plane_final_k behind it: out[0 .. kIcpPlaneRecord) = the record of m3d_icp_fp.hpp.
 constexpr int kIcpPlaneRecord = 30;
 constexpr int kIcpPlaneStride = 32;
 inline uint32_t icp_plane_blocks(uint32_t n) { return n ? (n + 255u) / 256u : 1u; }
-void launch_icp_plane_iter(const double* ix, const double* iy, const double* iz, uint32_t n, const double* T_dev, double* px,
-                           double* py, double* pz, const GridDesc& g, const uint32_t* cell_start, const double* qx,
-                           const double* qy, const double* qz, const uint32_t* cell_orig, const CloudView& dst, uint32_t* nn,
-                           double* partial, double* out, hipStream_t s);
-// The same with L1 weights (icp_plane_l1_iter_k + icp_plane_final_k; m3d_registration_icp_plane_l1): w = 1 / |r| on the 27 sums
-void launch_icp_plane_l1_iter(const double* ix, const double* iy, const double* iz, uint32_t n, const double* T_dev, double* px,
-                              double* py, double* pz, const GridDesc& g, const uint32_t* cell_start, const double* qx,
-                              const double* qy, const double* qz, const uint32_t* cell_orig, const CloudView& dst, uint32_t* nn,
-                              double* partial, double* out, hipStream_t s);
-// Coloured ICP's iteration (icp_colored_iter_k + icp_plane_final_k): launch_icp_plane_iter's arguments plus the target's colour
-// gradients (grad: n_dst x 3 rows) and intensities (it_dst), the moving points' intensities (is_src) and sg = sqrt(lambda),
-// sp = sqrt(1 - lambda).  The record and `partial` are those of the plane iteration.
-void launch_icp_colored_iter(const double* ix, const double* iy, const double* iz, uint32_t n, const double* T_dev, double* px,
-                             double* py, double* pz, const GridDesc& g, const uint32_t* cell_start, const double* qx,
-                             const double* qy, const double* qz, const uint32_t* cell_orig, const CloudView& dst,
-                             const double* grad, const double* it_dst, const double* is_src, double sg, double sp, uint32_t* nn,
-                             double* partial, double* out, hipStream_t s);
+struct IcpIterArgs {   // what every estimator's iteration has
+    const double *ix, *iy, *iz;   // the n points to move: the source cloud, from the second iteration on the moving buffers themselves
+    uint32_t n;
+    const double* T;         // the pending update on the device (12 doubles, null = none)
+    double *px, *py, *pz;    // the moving buffers
+    uint32_t* nn;            // the correspondences: original target index or 0xFFFFFFFF
+    double* partial;         // kIcpPlaneStride doubles per workgroup of 256 points (icp_plane_blocks(n) of them)
+};
+// The estimators, each what its rows read besides the match.  dst needs its normals in all three.
+struct IcpPlaneRows {     // point-to-plane (m3d_registration_icp_plane)
+    CloudView dst;
+};
+struct IcpPlaneL1Rows {   // the same rows with L1 weights, w = 1 / |r| on the 27 sums (m3d_registration_icp_plane_l1)
+    CloudView dst;
+};
+struct IcpColoredRows {   // coloured ICP (m3d_registration_icp_colored): the target's colour gradients (grad: n_dst x 3 rows) and
+    CloudView dst;        // intensities (it_dst), the moving points' intensities (is_src), sg = sqrt(lambda), sp = sqrt(1 - lambda)
+    const double *grad, *it_dst, *is_src;
+    double sg, sp;
+};
+template <class Rows>
+void launch_icp_iter(const IcpIterArgs& a, const TargetGrid& t, const Rows& rows, double* out, hipStream_t s);
 void launch_kabsch_sums(const double* src, const double* dst, uint32_t n, double* partial, double* sums,
                         hipStream_t s);
 void launch_nn(const double* q, uint32_t nq, const double* db, uint32_t ndb, int dim, uint32_t splits,

@@ -68,7 +68,7 @@ struct Scratch {  // per-call device buffers (registration calls are rare and la
 struct RegCtx {
     DeviceCtx* ctx;
     CloudView src, dst;
-    GridDesc g;
+    const TargetGrid* tg;   // the session's
     Scratch* s;
     uint32_t m;
     double thr;
@@ -80,12 +80,13 @@ struct RegCtx {
 // does not fit the cell is doubled: a coarser grid with K = 1 still covers the radius); points counting-
 // sorted by cell (qx/qy/qz + cell_start), optional neighbour lists (3x3x3 block of every cell, contiguous;
 // bounded to 2 M target points; M3D_REG_NL=0 switches them off).  with_orig: also keep the original index of
-// every sorted point (S.cell_orig) and store it in the w component of the neighbour-list entries.
-int add_neighbour_lists(DeviceCtx* ctx, Scratch& S, GridDesc* gp, size_t n_dst, const uint32_t* orig);
+// every sorted point (S.cell_orig) and store it in the w component of the neighbour-list entries.  *t_out: the view of the grid
+// that every launch searching it takes; the arrays themselves stay in S.
+int add_neighbour_lists(DeviceCtx* ctx, Scratch& S, TargetGrid* tp, size_t n_dst);
 // bbox6 != null: the bounding box (lo, hi) of the points that have three finite coordinates -- the resident cloud knows it
 // from its creation (m3d_cloud::bb); the host pass over the caller's array it replaces took 0.1 ms per 200 000 points
 int build_target_grid(DeviceCtx* ctx, Scratch& S, const CloudView& dst_view, const double* dst, size_t n_dst,
-                      double radius, bool with_orig, GridDesc* g_out, int K0 = 4, bool with_nl = true,
+                      double radius, bool with_orig, TargetGrid* t_out, int K0 = 4, bool with_nl = true,
                       const double* bbox6 = nullptr) {
     double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     if (bbox6) {
@@ -107,7 +108,8 @@ int build_target_grid(DeviceCtx* ctx, Scratch& S, const CloudView& dst_view, con
         if (!(lo[k] <= hi[k])) lo[k] = hi[k] = 0.0;
     const RadiusGridGeom geom = radius_grid_geom(lo, hi, radius, K0);
     // r2: radius * radius, KDTreeFlann::SearchHybrid
-    GridDesc g = radius_grid_desc(geom, radius * radius, (0.999 * geom.h) * (0.999 * geom.h));
+    TargetGrid t;
+    GridDesc& g = t.g = radius_grid_desc(geom, radius * radius, (0.999 * geom.h) * (0.999 * geom.h));
     if (!S.tgt.reserve(n_dst, g.nx * g.ny * g.nz)) return M3D_ERR_DEVICE;
     RESERVE(S.qx, sizeof(double) * n_dst);
     RESERVE(S.qy, sizeof(double) * n_dst);
@@ -118,30 +120,34 @@ int build_target_grid(DeviceCtx* ctx, Scratch& S, const CloudView& dst_view, con
     g.q4 = S.q4.as<double4>();
     launch_grid_build(dst_view, g, S.tgt, S.qx.as<double>(), S.qy.as<double>(), S.qz.as<double>(), ctx->stream, orig,
                       S.q4.as<double4>());
+    t.cell_start = S.tgt.start.as<uint32_t>();
+    t.qx = S.qx.as<double>();
+    t.qy = S.qy.as<double>();
+    t.qz = S.qz.as<double>();
+    t.cell_orig = orig;
     if (with_nl) {
-        const int rn = add_neighbour_lists(ctx, S, &g, n_dst, orig);
+        const int rn = add_neighbour_lists(ctx, S, &t, n_dst);
         if (rn != M3D_OK) return rn;
     }
-    *g_out = g;
+    *t_out = t;
     return M3D_OK;
 }
 
-// Neighbour lists on top of a grid built by build_target_grid (its cell_start / q arrays in S): g gains nl_start /
-// nl_pts.  Separate because they only pay off once enough queries follow (173 MB for 200 k target points).
-int add_neighbour_lists(DeviceCtx* ctx, Scratch& S, GridDesc* gp, size_t n_dst, const uint32_t* orig) {
-    GridDesc& g = *gp;
+// Neighbour lists on top of a grid built by build_target_grid (the lists' arrays join the grid's in S): the view's g gains
+// nl_start / nl_pts.  Separate because they only pay off once enough queries follow (173 MB for 200 k target points).
+int add_neighbour_lists(DeviceCtx* ctx, Scratch& S, TargetGrid* tp, size_t n_dst) {
+    GridDesc& g = tp->g;
     const uint32_t ncell = g.nx * g.ny * g.nz;
     if (config().reg_neighbour_lists && n_dst <= ((size_t)2 << 20)) {
         RESERVE(S.nl_start, sizeof(uint32_t) * ((size_t)ncell + 1));
-        launch_nl_count(g, S.tgt.start.as<uint32_t>(), S.nl_start.as<uint32_t>(), S.tgt.sums.as<uint32_t>(),
-                        S.tgt.total.as<uint32_t>() + 1, ctx->stream);
+        launch_nl_count(*tp, S.nl_start.as<uint32_t>(), S.tgt.sums.as<uint32_t>(), S.tgt.total.as<uint32_t>() + 1, ctx->stream);
         uint32_t entries = 0;
         HIPCHK(hipMemcpyAsync(&entries, S.nl_start.as<uint32_t>() + ncell, sizeof(uint32_t), hipMemcpyDeviceToHost,
                               ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
         RESERVE(S.nl_pts, sizeof(double4) * std::max<size_t>(entries, 1));
         // without original indices riding in w (validation grid): x-sorted three-column lists with early termination
-        const bool sorted = orig == nullptr && config().reg_sorted_lists != 0;
+        const bool sorted = tp->cell_orig == nullptr && config().reg_sorted_lists != 0;
         if (sorted) RESERVE(S.nl_hdr, sizeof(uint32_t) * (size_t)ncell);
         // fp32 copies of the entries (GridDesc::nl32) when the offsets from a cell corner are good to fp32's last bit: the
         // corner g.o + i h and the subtraction are rounded in fp64, which must stay far below 2^-24 h
@@ -162,8 +168,7 @@ int add_neighbour_lists(DeviceCtx* ctx, Scratch& S, GridDesc* gp, size_t n_dst, 
             RESERVE(S.nl_rec, sizeof(uint4) * (size_t)ncell);
             HIPCHK(hipMemsetAsync(overflow, 0, sizeof(uint32_t), ctx->stream));
         }
-        launch_nl_fill(g, S.tgt.start.as<uint32_t>(), S.nl_start.as<uint32_t>(), S.qx.as<double>(),
-                       S.qy.as<double>(), S.qz.as<double>(), S.nl_pts.as<double4>(), ctx->stream, orig, sorted,
+        launch_nl_fill(*tp, S.nl_start.as<uint32_t>(), S.nl_pts.as<double4>(), ctx->stream, sorted,
                        sorted ? S.nl_hdr.as<uint32_t>() : nullptr, screen ? S.nl32.as<uint2>() : nullptr,
                        screen ? S.nl_rec.as<uint4>() : nullptr, overflow, screen ? S.nl32_start.as<uint32_t>() : nullptr);
         if (screen) {   // a list beyond the 16-bit offsets of nl_rec: no screen for this grid
@@ -199,9 +204,8 @@ int exact_err2(RegCtx& rc, const double* T_dev, uint64_t* count, double* err2) {
     RESERVE(s.tgt.total, 16);
     RESERVE(s.sums, sizeof(double) * 4);
     RESERVE(ctx->h_small, 256);
-    launch_reg_min_d2(rc.src, T_dev, rc.g, s.tgt.start.as<uint32_t>(), s.qx.as<double>(), s.qy.as<double>(),
-                      s.qz.as<double>(), s.best.as<double>(), ctx->stream);
-    launch_compact_vals(s.best.as<double>(), n, rc.g.r2, s.block_counts.as<uint32_t>(), s.tgt.total.as<uint32_t>(),
+    launch_reg_min_d2(rc.src, T_dev, *rc.tg, s.best.as<double>(), ctx->stream);
+    launch_compact_vals(s.best.as<double>(), n, rc.tg->g.r2, s.block_counts.as<uint32_t>(), s.tgt.total.as<uint32_t>(),
                         s.vals.as<double>(), ctx->stream);
     launch_serial_sum(s.vals.as<double>(), s.tgt.total.as<uint32_t>(), s.sums.as<double>(), ctx->stream);
     uint8_t* h = ctx->h_small.as<uint8_t>();
@@ -227,9 +231,8 @@ int tree_err2(RegCtx& rc, const double* T_dev, uint64_t* count, double* err2) {
     RESERVE(s.sums, sizeof(double) * 32);
     RESERVE(s.partial_sum, sizeof(double) * 256 * 16);
     RESERVE(ctx->h_small, 256);
-    launch_reg_min_d2(rc.src, T_dev, rc.g, s.tgt.start.as<uint32_t>(), s.qx.as<double>(), s.qy.as<double>(),
-                      s.qz.as<double>(), s.best.as<double>(), ctx->stream);
-    launch_icp_err(s.best.as<double>(), n, rc.g.r2, s.partial_sum.as<double>(), s.sums.as<double>() + 24, ctx->stream);
+    launch_reg_min_d2(rc.src, T_dev, *rc.tg, s.best.as<double>(), ctx->stream);
+    launch_icp_err(s.best.as<double>(), n, rc.tg->g.r2, s.partial_sum.as<double>(), s.sums.as<double>() + 24, ctx->stream);
     uint8_t* h = ctx->h_small.as<uint8_t>();
     HIPCHK(hipMemcpyAsync(h, s.sums.as<double>() + 24, 16, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipGetLastError());
@@ -247,7 +250,7 @@ int corr_inlier_ratio(RegCtx& rc, const double* T_dev, double* ratio) {
     RESERVE(s.ratio, 16);
     RESERVE(ctx->h_small, 256);
     launch_corr_ratio(rc.src, rc.dst, s.corr_src.as<uint32_t>(), s.corr_dst.as<uint32_t>(), rc.m, T_dev,
-                      rc.g.r2, s.ratio.as<uint32_t>(), ctx->stream);
+                      rc.tg->g.r2, s.ratio.as<uint32_t>(), ctx->stream);
     HIPCHK(hipMemcpyAsync(ctx->h_small.p, s.ratio.p, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipGetLastError());
     if (const int wr = stream_wait_spin(ctx); wr != M3D_OK) return wr;   // (results in page-locked memory: a polled word instead of the runtime's wait, which wakes 10-20 us late)
@@ -329,7 +332,7 @@ struct m3d_reg {
     bool keep_orig = false;   // the target grid keeps its points' original indices: information_matrix_on then searches THIS grid (global_registration_on)
     Scratch S;
     RegCtx R;
-    GridDesc g;
+    TargetGrid tg;   // the target grid (its arrays in S); R.tg points here
     CloudView src_sorted;
     size_t n_src = 0, n_dst = 0, m = 0;
     double threshold = 0, edge_length_threshold = 0, confidence = 0;
@@ -390,6 +393,7 @@ int m3d_reg::setup(const double* src, const double* dst, const size_t* corr_src,
     static_assert(kScoreTile % kRegTile == 0, "padding of resident clouds must cover the reg tiles");
     R.dst = this->cdst->view();
     R.s = &S;
+    R.tg = &tg;
     R.m = (uint32_t)m;
     R.thr = threshold;
 
@@ -400,10 +404,9 @@ int m3d_reg::setup(const double* src, const double* dst, const size_t* corr_src,
         // points: 1.33 with 4, 1.51 with 3, 2.09 with 2)
         const int k_cfg = config().reg_cells_per_radius;
         const int k0 = std::max(1, std::min(k_cfg, (int)std::lround(k_cfg * std::cbrt((double)n_dst / 200000.0))));
-        const int rc_grid = build_target_grid(ctx, S, R.dst, dst, n_dst, threshold, keep_orig, &g, k0, /*with_nl=*/false,
+        const int rc_grid = build_target_grid(ctx, S, R.dst, dst, n_dst, threshold, keep_orig, &tg, k0, /*with_nl=*/false,
                                               cdst->bb_known ? cdst->bb : nullptr);
         if (rc_grid != M3D_OK) return rc_grid;
-        R.g = g;
         n_dst_points = n_dst;
     }
 
@@ -527,9 +530,8 @@ int m3d_reg::begin_chunk(size_t* n_survivors) {
     validated_total += ns;
     if (!nl_built && validated_total > 48) {
         nl_built = true;
-        const int rn = add_neighbour_lists(ctx, S, &g, n_dst_points, keep_orig ? S.cell_orig.as<uint32_t>() : nullptr);
+        const int rn = add_neighbour_lists(ctx, S, &tg, n_dst_points);
         if (rn != M3D_OK) return rn;
-        R.g = g;
     }
 
     if (ns) {
@@ -585,17 +587,15 @@ int m3d_reg::ensure_cache(uint32_t s_pad) {
     cache.R = S.cc_R.as<float>();
     cache.stats = S.cc_stats.as<unsigned long long>();
     if (!cache.ring) {   // the target grid's cell rings, once per session (K + 1 rounds: a ring beyond K certifies "nothing in reach")
-        const size_t ncell = (size_t)g.nx * g.ny * g.nz;
+        const size_t ncell = (size_t)tg.g.nx * tg.g.ny * tg.g.nz;
         RESERVE(S.cc_ring, ncell);
         RESERVE(S.cc_ring_tmp, 2 * ncell);
-        launch_reg_rings(g, S.tgt.start.as<uint32_t>(), S.cc_ring.as<uint8_t>(), S.cc_ring_tmp.as<uint8_t>(), g.K + 1, ctx->stream);
+        launch_reg_rings(tg, S.cc_ring.as<uint8_t>(), S.cc_ring_tmp.as<uint8_t>(), tg.g.K + 1, ctx->stream);
         S.cc_ring_tmp.release();
         cache.ring = S.cc_ring.as<uint8_t>();
-        g.ring = cache.ring;     // the walk's outer search looks them up as well (nearest_d2)
-        R.g = g;
+        tg.g.ring = cache.ring;     // the walk's outer search looks them up as well (nearest_d2)
     }
-    launch_reg_cache_build(src_sorted, best_T_dev, g, S.tgt.start.as<uint32_t>(), S.qx.as<double>(), S.qy.as<double>(),
-                           S.qz.as<double>(), cache, ctx->stream);
+    launch_reg_cache_build(src_sorted, best_T_dev, tg, cache, ctx->stream);
     cache_valid = true;
     cache_ref_index = best_index;
     cache_ref_cnt = best_cnt;
@@ -628,7 +628,7 @@ int m3d_reg::validate(size_t s_begin, size_t s_end, uint32_t* counts_out, double
         const int cc = config().reg_cache;
         // (a cell edge within [1e-12, 1e12]: the cache's fp32 squares neither underflow below its rounding bound nor reach the
         //  empty slots' 1e18 -- m3d_reg_cache.hip)
-        const double h_cell = 1.0 / g.inv_h;
+        const double h_cell = 1.0 / tg.g.inv_h;
         const bool use_cache = best_index >= 0 && src_sorted.n_pad <= ((size_t)2 << 20) && h_cell > 1e-12 && h_cell < 1e12 &&
                                (cc == 2 || (cc == 1 && nl_built && ns >= 192));
         if (use_cache) {
@@ -636,11 +636,9 @@ int m3d_reg::validate(size_t s_begin, size_t s_end, uint32_t* counts_out, double
             if (rcache != M3D_OK) return rcache;
         }
         // bound-and-prune against the best of EARLIER chunks (m3d_config.reg_prune = 0 switches it off)
-        const uint32_t rows = launch_reg_validate(src_sorted, Ts, s_pad, g, S.tgt.start.as<uint32_t>(),
-                            S.qx.as<double>(), S.qy.as<double>(), S.qz.as<double>(),
-                            S.partial.as<uint32_t>(), S.partial_sum.as<double>(), S.sum2.as<double>(),
-                            reg_prune ? best_cnt : 0u, (uint32_t)n_src, S.keep.as<uint8_t>(), ctx->stream, best_sum2, ns,
-                            use_cache ? &cache : nullptr);
+        const uint32_t rows = launch_reg_validate(src_sorted, Ts, s_pad, tg, S.partial.as<uint32_t>(), S.partial_sum.as<double>(),
+                            S.sum2.as<double>(), reg_prune ? best_cnt : 0u, (uint32_t)n_src, S.keep.as<uint8_t>(), ctx->stream,
+                            best_sum2, ns, use_cache ? &cache : nullptr);
         HIPCHK(hipMemsetAsync(S.counts.p, 0, sizeof(uint32_t) * s_pad, ctx->stream));
         launch_reduce_partials(S.partial.as<uint32_t>(), rows, s_pad, S.counts.as<uint32_t>(),
                                ctx->stream);
@@ -779,16 +777,16 @@ int m3d_reg::finish(double* T_out, m3d_reg_stats* stats) {
             stats->lds_wave_hypotheses = cs2[0];
             stats->global_wave_hypotheses = cs2[1];
         }
-        stats->nn_fp32_screen = g.nl32 ? 1 : 0;
+        stats->nn_fp32_screen = tg.g.nl32 ? 1 : 0;
         stats->nn_screen_fallbacks = 0;
-        if (g.nl32_fallbacks) {
+        if (tg.g.nl32_fallbacks) {
             unsigned long long fb = 0;
-            HIPCHK(hipMemcpy(&fb, g.nl32_fallbacks, sizeof(fb), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(&fb, tg.g.nl32_fallbacks, sizeof(fb), hipMemcpyDeviceToHost));
             stats->nn_screen_fallbacks = fb;
 #ifdef M3D_REG_TRIP_STATS
             {   // the walk's trip counts (sorted_walk32): lane trips, wave maxima, histogram of the lanes' counts
                 unsigned long long t[64];
-                HIPCHK(hipMemcpy(t, g.nl32_fallbacks, sizeof(t), hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(t, tg.g.nl32_fallbacks, sizeof(t), hipMemcpyDeviceToHost));
                 fprintf(stderr, "walk trips: queries %llu lane-trips %llu (mean %.2f) wave-queries %llu sum of wave maxima %llu (mean %.2f); lanes by trips:",
                         t[8], t[9], (double)t[9] / (double)(t[8] ? t[8] : 1), t[10], t[11], (double)t[11] / (double)(t[10] ? t[10] : 1));
                 for (int k = 0; k < 24; ++k) fprintf(stderr, " %d:%.3f", k, (double)t[16 + k] / (double)(t[8] ? t[8] : 1));
@@ -1128,9 +1126,10 @@ int m3d_registration_ransac_sharded(const double* src, size_t n_src, const doubl
 //   icp_loop   result, update, compose, next result, the two-criteria convergence test, the outputs
 // An estimator is its own argument check, its reservations and two callables: iterate(first, update) moves the cloud by the
 // pending update, searches the correspondences and leaves their count and error in the frame; compute_update(U) is
-// ComputeTransformation on what iterate left behind.  Point-to-point: transform, search, error sum, Kabsch sums and one polled
-// wait, the K3x3 umeyama assembly.  Point-to-plane, its L1 variant and coloured (icp_record_loop; they differ in the launch): one launch -- the
-// pending update, the search, the 30 sums -- one copy of the record and one polled wait; the 6 x 6 solve of m3d_icp_fp.hpp.
+// ComputeTransformation on what iterate left behind.  Point-to-point: transform, search, error sum, Kabsch sums (icp_point_step)
+// and one polled wait, the K3x3 umeyama assembly.  Point-to-plane, its L1 variant and coloured (icp_record_loop; they differ in
+// the rows they hand launch_icp_iter): one launch -- the pending update, the search, the 30 sums -- one copy of the record and
+// one polled wait; the 6 x 6 solve of m3d_icp_fp.hpp.
 // ------------------------------------------------------------------------------------------------
 namespace {
 
@@ -1153,7 +1152,7 @@ struct IcpFrame {   // what a call holds
     CloudView sv, dv;
     uint32_t n = 0;   // moving points
     Scratch S;
-    GridDesc g;
+    TargetGrid tg;   // the target's grid with original indices (its arrays in S)
     DevBuf mx, my, mz, nn;                            // the moving cloud and its correspondences (original target indices)
     double *px = nullptr, *py = nullptr, *pz = nullptr;   // ... = mx, my, mz
     DevBuf extra[4];    // the estimator's own: d2 (point-to-point); grad, it_dst, is_src, col_src (coloured)
@@ -1213,7 +1212,7 @@ int icp_call(DeviceCtx* held, const IcpArgs& a, const char* estimator_error, con
         f.sv = f.csrc->view();
         f.dv = f.cdst->view();
         f.n = f.sv.n;
-        const int rg = build_target_grid(ctx, f.S, f.dv, a.dst, a.n_dst, a.max_correspondence_distance, true, &f.g);
+        const int rg = build_target_grid(ctx, f.S, f.dv, a.dst, a.n_dst, a.max_correspondence_distance, true, &f.tg);
         if (rg != M3D_OK) return rg;
         RESERVE(f.mx, sizeof(double) * f.n);
         RESERVE(f.my, sizeof(double) * f.n);
@@ -1279,11 +1278,11 @@ int icp_loop(IcpFrame& f, const IcpArgs& a, Iterate&& iterate, Update&& compute_
     return M3D_OK;
 }
 
-// The loop of the two estimators whose iteration is one launch that leaves the record of m3d_icp_fp.hpp:
-// launch(ix, iy, iz, T_dev) is launch_icp_plane_iter, launch_icp_plane_l1_iter or launch_icp_colored_iter on the frame's buffers.
+// The loop of the estimators whose iteration is one launch that leaves the record of m3d_icp_fp.hpp: launch_icp_iter with the
+// estimator's rows (IcpPlaneRows, IcpPlaneL1Rows, IcpColoredRows) on the frame's grid and buffers.
 static_assert(kIcpPlaneRecord == kIcpPlaneSums, "the kernels' record is the one m3d_icp_fp.hpp reads");
-template <class Launch>
-int icp_record_loop(IcpFrame& f, const IcpArgs& a, Launch&& launch) {
+template <class Rows>
+int icp_record_loop(IcpFrame& f, const IcpArgs& a, const Rows& rows) {
     DeviceCtx* ctx = f.ctx;
     Scratch& S = f.S;
     RESERVE(S.sums, sizeof(double) * kIcpPlaneStride);
@@ -1295,7 +1294,10 @@ int icp_record_loop(IcpFrame& f, const IcpArgs& a, Launch&& launch) {
     // ComputeTransformation.  update == null: the source cloud as it is (an identity init)
     auto iterate = [&](bool first, const double* update) -> int {
         if (update) HIPCHK(hipMemcpyAsync(S.one_T.p, update, sizeof(double) * 12, hipMemcpyHostToDevice, ctx->stream));
-        launch(first ? f.sv.x : f.px, first ? f.sv.y : f.py, first ? f.sv.z : f.pz, update ? S.one_T.as<double>() : nullptr);
+        const IcpIterArgs it{first ? f.sv.x : f.px, first ? f.sv.y : f.py, first ? f.sv.z : f.pz, f.n,
+                             update ? S.one_T.as<double>() : nullptr, f.px, f.py, f.pz, f.nn.as<uint32_t>(),
+                             S.partial_sum.as<double>()};
+        launch_icp_iter(it, f.tg, rows, S.sums.as<double>(), ctx->stream);
         uint8_t* h = ctx->h_small.as<uint8_t>();
         HIPCHK(hipMemcpyAsync(h, S.sums.p, sizeof(hs), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipGetLastError());
@@ -1306,6 +1308,31 @@ int icp_record_loop(IcpFrame& f, const IcpArgs& a, Launch&& launch) {
         return M3D_OK;
     };
     return icp_loop(f, a, iterate, [&](double* U) { icp_plane_update(hs, U); });
+}
+
+// The point-to-point step on a frame, queued without a wait: the moving cloud = Transform(update) of the source cloud (first) or of
+// itself, update == null: the source cloud as it is; GetRegistrationResultAndCorrespondences -- nearest target point within the
+// radius, error2 and count to sums[24], sums[25]; the sums of the NEXT ComputeTransformation to sums[0, 18), queued behind it at
+// once (they read the count from the device): one host wait per iteration instead of two; after the last iteration they go unused.
+// The caller reserves d2 = f.extra[0] (n doubles), S.sums (>= 32 doubles), S.partial_sum (256 x 16) and S.one_T.
+int icp_point_step(IcpFrame& f, bool first, const double* update) {
+    DeviceCtx* ctx = f.ctx;
+    Scratch& S = f.S;
+    const uint32_t n = f.n;
+    double *d2 = f.extra[0].as<double>(), *sums = S.sums.as<double>();
+    if (update) {
+        HIPCHK(hipMemcpyAsync(S.one_T.p, update, sizeof(double) * 12, hipMemcpyHostToDevice, ctx->stream));
+        launch_icp_transform(first ? f.sv.x : f.px, first ? f.sv.y : f.py, first ? f.sv.z : f.pz, n, S.one_T.as<double>(), f.px, f.py,
+                             f.pz, ctx->stream);
+    } else {
+        HIPCHK(hipMemcpyAsync(f.px, f.sv.x, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(f.py, f.sv.y, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(f.pz, f.sv.z, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    launch_icp_nn(f.px, f.py, f.pz, n, f.tg, f.nn.as<uint32_t>(), d2, ctx->stream);
+    launch_icp_err(d2, n, f.tg.g.r2, S.partial_sum.as<double>(), sums + 24, ctx->stream);
+    launch_icp_sums(f.px, f.py, f.pz, n, f.dv, f.nn.as<uint32_t>(), sums + 25, S.partial_sum.as<double>(), sums, ctx->stream);
+    return M3D_OK;
 }
 
 }  // namespace
@@ -1321,8 +1348,7 @@ int m3d::registration_icp_on(DeviceCtx* held, const double* src, size_t n_src, c
         DeviceCtx* ctx = f.ctx;
         Scratch& S = f.S;
         const uint32_t n = f.n;
-        DevBuf& d2 = f.extra[0];
-        RESERVE(d2, sizeof(double) * n);
+        RESERVE(f.extra[0], sizeof(double) * n);
         RESERVE(S.vals, sizeof(double) * n);
         RESERVE(S.block_counts, sizeof(uint32_t) * ((size_t)((n + 2047) / 2048) + 1));
         RESERVE(S.tgt.total, 16);
@@ -1332,23 +1358,7 @@ int m3d::registration_icp_on(DeviceCtx* held, const double* src, size_t n_src, c
         RESERVE(ctx->h_small, 512);
         double hs[18];   // sums of the correspondence set for umeyama
         auto iterate = [&](bool first, const double* update) -> int {
-            if (update) {
-                HIPCHK(hipMemcpyAsync(S.one_T.p, update, sizeof(double) * 12, hipMemcpyHostToDevice, ctx->stream));
-                launch_icp_transform(first ? f.sv.x : f.px, first ? f.sv.y : f.py, first ? f.sv.z : f.pz, n, S.one_T.as<double>(),
-                                     f.px, f.py, f.pz, ctx->stream);
-            } else {
-                HIPCHK(hipMemcpyAsync(f.px, f.sv.x, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream));
-                HIPCHK(hipMemcpyAsync(f.py, f.sv.y, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream));
-                HIPCHK(hipMemcpyAsync(f.pz, f.sv.z, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream));
-            }
-            // GetRegistrationResultAndCorrespondences: nearest target point within the radius, count + error2
-            launch_icp_nn(f.px, f.py, f.pz, n, f.g, S.tgt.start.as<uint32_t>(), S.qx.as<double>(), S.qy.as<double>(),
-                          S.qz.as<double>(), S.cell_orig.as<uint32_t>(), f.nn.as<uint32_t>(), d2.as<double>(), ctx->stream);
-            launch_icp_err(d2.as<double>(), n, f.g.r2, S.partial_sum.as<double>(), S.sums.as<double>() + 24, ctx->stream);
-            // the sums of the NEXT ComputeTransformation are queued behind it at once (they read the count from
-            // the device): one host wait per iteration instead of two; after the last iteration they go unused
-            launch_icp_sums(f.px, f.py, f.pz, n, f.dv, f.nn.as<uint32_t>(), S.sums.as<double>() + 25, S.partial_sum.as<double>(),
-                            S.sums.as<double>(), ctx->stream);
+            if (const int r = icp_point_step(f, first, update); r != M3D_OK) return r;
             uint8_t* h = ctx->h_small.as<uint8_t>();
             HIPCHK(hipMemcpyAsync(h, S.sums.as<double>() + 24, 16, hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(hipMemcpyAsync(h + 32, S.sums.p, sizeof(hs), hipMemcpyDeviceToHost, ctx->stream));
@@ -1372,7 +1382,7 @@ int m3d::registration_icp_on(DeviceCtx* held, const double* src, size_t n_src, c
 }
 
 // test hook (include/misc3d_amd_bench.h): one evaluation of the point-to-point step under T -- the call frame, grid and
-// launches of registration_icp_on's iterate, then information_matrix_on's moments of the same correspondence set
+// launches of registration_icp_on's iterate (icp_point_step), then information_matrix_on's moments of the same correspondence set
 extern "C" int m3d_bench_icp_sums(const double* src, size_t n_src, const double* dst, size_t n_dst,
                                   double max_correspondence_distance, const double* T, int device, double out[29],
                                   int64_t* corr) {
@@ -1384,20 +1394,13 @@ extern "C" int m3d_bench_icp_sums(const double* src, size_t n_src, const double*
         DeviceCtx* ctx = f.ctx;
         Scratch& S = f.S;
         const uint32_t n = f.n;
-        DevBuf& d2 = f.extra[0];
-        RESERVE(d2, sizeof(double) * n);
+        RESERVE(f.extra[0], sizeof(double) * n);
         RESERVE(S.sums, sizeof(double) * 48);   // [0, 18) the update's sums, [24] error, [25] count, [32, 41) the moments
         RESERVE(S.partial_sum, sizeof(double) * 256 * 16);
         RESERVE(S.one_T, sizeof(double) * kRegTStride);
         RESERVE(ctx->h_small, 512);
-        double* sums = S.sums.as<double>();
-        HIPCHK(hipMemcpyAsync(S.one_T.p, f.T, sizeof(double) * 12, hipMemcpyHostToDevice, ctx->stream));
-        launch_icp_transform(f.sv.x, f.sv.y, f.sv.z, n, S.one_T.as<double>(), f.px, f.py, f.pz, ctx->stream);
-        launch_icp_nn(f.px, f.py, f.pz, n, f.g, S.tgt.start.as<uint32_t>(), S.qx.as<double>(), S.qy.as<double>(),
-                      S.qz.as<double>(), S.cell_orig.as<uint32_t>(), f.nn.as<uint32_t>(), d2.as<double>(), ctx->stream);
-        launch_icp_err(d2.as<double>(), n, f.g.r2, S.partial_sum.as<double>(), sums + 24, ctx->stream);
-        launch_icp_sums(f.px, f.py, f.pz, n, f.dv, f.nn.as<uint32_t>(), sums + 25, S.partial_sum.as<double>(), sums, ctx->stream);
-        launch_info_sums(n, f.dv, f.nn.as<uint32_t>(), S.partial_sum.as<double>(), sums + 32, ctx->stream);
+        if (const int r = icp_point_step(f, true, f.T); r != M3D_OK) return r;
+        launch_info_sums(n, f.dv, f.nn.as<uint32_t>(), S.partial_sum.as<double>(), S.sums.as<double>() + 32, ctx->stream);
         double h[41];
         HIPCHK(hipMemcpyAsync(ctx->h_small.p, S.sums.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipGetLastError());
@@ -1415,38 +1418,16 @@ extern "C" int m3d_bench_icp_sums(const double* src, size_t n_src, const double*
     });
 }
 
-// TransformationEstimationPointToPlane (the contract: include/misc3d_amd.h)
+// TransformationEstimationPointToPlane, l1: with L1Loss -- the same call with the weighted rows, what PPFEstimator's PointToPlane
+// refinement runs (the contracts: include/misc3d_amd.h, m3d_registration_icp_plane and m3d_registration_icp_plane_l1)
 int m3d::registration_icp_plane_on(DeviceCtx* held, const double* src, size_t n_src, const double* dst, const double* dst_normals,
                                    size_t n_dst, double max_correspondence_distance, const double* T_init, int max_iteration,
                                    double relative_fitness, double relative_rmse, int device, double* T_out,
-                                   m3d_icp_stats* stats, int64_t* correspondences) {
+                                   m3d_icp_stats* stats, int64_t* correspondences, bool l1) {
     const IcpArgs a{src, dst, T_init, n_src, n_dst, max_correspondence_distance, relative_fitness, relative_rmse, max_iteration,
                     device, T_out, stats, correspondences};
     return icp_call(held, a, !dst_normals ? kIcpNeedsNormals : nullptr, dst_normals, icp_nothing_before_upload, [&](IcpFrame& f) {
-        Scratch& S = f.S;
-        return icp_record_loop(f, a, [&](const double* ix, const double* iy, const double* iz, const double* T_dev) {
-            launch_icp_plane_iter(ix, iy, iz, f.n, T_dev, f.px, f.py, f.pz, f.g, S.tgt.start.as<uint32_t>(), S.qx.as<double>(),
-                                  S.qy.as<double>(), S.qz.as<double>(), S.cell_orig.as<uint32_t>(), f.dv, f.nn.as<uint32_t>(),
-                                  S.partial_sum.as<double>(), S.sums.as<double>(), f.ctx->stream);
-        });
-    });
-}
-
-// TransformationEstimationPointToPlane(L1Loss): the plane call with the launch of the weighted rows (the contract:
-// include/misc3d_amd.h, m3d_registration_icp_plane_l1); what PPFEstimator's PointToPlane refinement runs
-int m3d::registration_icp_plane_l1_on(DeviceCtx* held, const double* src, size_t n_src, const double* dst,
-                                      const double* dst_normals, size_t n_dst, double max_correspondence_distance,
-                                      const double* T_init, int max_iteration, double relative_fitness, double relative_rmse,
-                                      int device, double* T_out, m3d_icp_stats* stats, int64_t* correspondences) {
-    const IcpArgs a{src, dst, T_init, n_src, n_dst, max_correspondence_distance, relative_fitness, relative_rmse, max_iteration,
-                    device, T_out, stats, correspondences};
-    return icp_call(held, a, !dst_normals ? kIcpNeedsNormals : nullptr, dst_normals, icp_nothing_before_upload, [&](IcpFrame& f) {
-        Scratch& S = f.S;
-        return icp_record_loop(f, a, [&](const double* ix, const double* iy, const double* iz, const double* T_dev) {
-            launch_icp_plane_l1_iter(ix, iy, iz, f.n, T_dev, f.px, f.py, f.pz, f.g, S.tgt.start.as<uint32_t>(), S.qx.as<double>(),
-                                     S.qy.as<double>(), S.qz.as<double>(), S.cell_orig.as<uint32_t>(), f.dv, f.nn.as<uint32_t>(),
-                                     S.partial_sum.as<double>(), S.sums.as<double>(), f.ctx->stream);
-        });
+        return l1 ? icp_record_loop(f, a, IcpPlaneL1Rows{f.dv}) : icp_record_loop(f, a, IcpPlaneRows{f.dv});
     });
 }
 
@@ -1467,19 +1448,13 @@ int m3d::registration_icp_colored_on(DeviceCtx* held, const double* src, const d
                                  f.extra[1], nullptr);
     };
     return icp_call(held, a, bad, dst_normals, gradients, [&](IcpFrame& f) -> int {
-        Scratch& S = f.S;
         DevBuf &grad = f.extra[0], &it_dst = f.extra[1], &is_src = f.extra[2], &col_src = f.extra[3];
         const double sg = std::sqrt(lambda_geometric), sp = std::sqrt(1.0 - lambda_geometric);
         RESERVE(col_src, sizeof(double) * 3 * n_src);
         RESERVE(is_src, sizeof(double) * n_src);
         HIPCHK(hipMemcpyAsync(col_src.p, src_colors, sizeof(double) * 3 * n_src, hipMemcpyHostToDevice, f.ctx->stream));
         launch_color_intensity(col_src.as<double>(), f.n, is_src.as<double>(), f.ctx->stream);
-        return icp_record_loop(f, a, [&](const double* ix, const double* iy, const double* iz, const double* T_dev) {
-            launch_icp_colored_iter(ix, iy, iz, f.n, T_dev, f.px, f.py, f.pz, f.g, S.tgt.start.as<uint32_t>(), S.qx.as<double>(),
-                                    S.qy.as<double>(), S.qz.as<double>(), S.cell_orig.as<uint32_t>(), f.dv, grad.as<double>(),
-                                    it_dst.as<double>(), is_src.as<double>(), sg, sp, f.nn.as<uint32_t>(),
-                                    S.partial_sum.as<double>(), S.sums.as<double>(), f.ctx->stream);
-        });
+        return icp_record_loop(f, a, IcpColoredRows{f.dv, grad.as<double>(), it_dst.as<double>(), is_src.as<double>(), sg, sp});
     });
 }
 
@@ -1498,15 +1473,15 @@ int m3d_registration_icp_plane(const double* src, size_t n_src, const double* ds
                                double relative_fitness, double relative_rmse, int device, double* T_out, m3d_icp_stats* stats,
                                int64_t* correspondences) {
     return registration_icp_plane_on(nullptr, src, n_src, dst, dst_normals, n_dst, max_correspondence_distance, T_init,
-                                     max_iteration, relative_fitness, relative_rmse, device, T_out, stats, correspondences);
+                                     max_iteration, relative_fitness, relative_rmse, device, T_out, stats, correspondences, false);
 }
 
 int m3d_registration_icp_plane_l1(const double* src, size_t n_src, const double* dst, const double* dst_normals, size_t n_dst,
                                   double max_correspondence_distance, const double* T_init, int max_iteration,
                                   double relative_fitness, double relative_rmse, int device, double* T_out, m3d_icp_stats* stats,
                                   int64_t* correspondences) {
-    return registration_icp_plane_l1_on(nullptr, src, n_src, dst, dst_normals, n_dst, max_correspondence_distance, T_init,
-                                        max_iteration, relative_fitness, relative_rmse, device, T_out, stats, correspondences);
+    return registration_icp_plane_on(nullptr, src, n_src, dst, dst_normals, n_dst, max_correspondence_distance, T_init,
+                                     max_iteration, relative_fitness, relative_rmse, device, T_out, stats, correspondences, true);
 }
 
 int m3d_registration_icp_colored(const double* src, const double* src_colors, size_t n_src, const double* dst,
@@ -1557,7 +1532,7 @@ int m3d::information_matrix_on(DeviceCtx* ctx, m3d_cloud* csrc, m3d_cloud* cdst,
     // original indices kept (registration_ransac_on, session_out): its grid is searched instead of building one (a grid + its
     // neighbour lists for ONE pass of nearest-neighbour queries took 0.3 of the 0.4 ms this call took on 50 000-point fragments)
     const bool shared = session && session->ctx == ctx && session->keep_orig && !session->trivial && session->cdst == cdst &&
-                        session->threshold == max_correspondence_distance && session->S.cell_orig.p;
+                        session->threshold == max_correspondence_distance && session->tg.cell_orig;
     Scratch S;
     DevBuf mx, my, mz, nn, d2;
     for (int k = 0; k < 36; ++k) info[k] = 0.0;   // (the entries the sums below do not touch are zeros of the matrix)
@@ -1568,15 +1543,13 @@ int m3d::information_matrix_on(DeviceCtx* ctx, m3d_cloud* csrc, m3d_cloud* cdst,
             HIPCHK(hipSetDevice(ctx->device));
             const CloudView sv = csrc->view(), dv = cdst->view();
             const uint32_t n = sv.n;
-            GridDesc g;
-            if (shared) {
-                g = session->g;
-            } else {
-                const int rg = build_target_grid(ctx, S, dv, dst, n_dst, max_correspondence_distance, true, &g, 4, true,
+            TargetGrid own;
+            if (!shared) {
+                const int rg = build_target_grid(ctx, S, dv, dst, n_dst, max_correspondence_distance, true, &own, 4, true,
                                                  cdst->bb_known ? cdst->bb : nullptr);
                 if (rg != M3D_OK) return rg;
             }
-            Scratch& G = shared ? session->S : S;   // (the grid's arrays)
+            const TargetGrid& tg = shared ? session->tg : own;
             RESERVE(mx, sizeof(double) * n);
             RESERVE(my, sizeof(double) * n);
             RESERVE(mz, sizeof(double) * n);
@@ -1593,10 +1566,8 @@ int m3d::information_matrix_on(DeviceCtx* ctx, m3d_cloud* csrc, m3d_cloud* cdst,
             HIPCHK(hipMemcpyAsync(S.one_T.p, T, sizeof(double) * 12, hipMemcpyHostToDevice, ctx->stream));
             launch_icp_transform(sv.x, sv.y, sv.z, n, S.one_T.as<double>(), mx.as<double>(), my.as<double>(),
                                  mz.as<double>(), ctx->stream);
-            launch_icp_nn(mx.as<double>(), my.as<double>(), mz.as<double>(), n, g, G.tgt.start.as<uint32_t>(),
-                          G.qx.as<double>(), G.qy.as<double>(), G.qz.as<double>(), G.cell_orig.as<uint32_t>(),
-                          nn.as<uint32_t>(), d2.as<double>(), ctx->stream);
-            launch_compact_vals(d2.as<double>(), n, g.r2, S.block_counts.as<uint32_t>(), S.tgt.total.as<uint32_t>(),
+            launch_icp_nn(mx.as<double>(), my.as<double>(), mz.as<double>(), n, tg, nn.as<uint32_t>(), d2.as<double>(), ctx->stream);
+            launch_compact_vals(d2.as<double>(), n, tg.g.r2, S.block_counts.as<uint32_t>(), S.tgt.total.as<uint32_t>(),
                                 S.vals.as<double>(), ctx->stream);   // only for the count
             launch_info_sums(n, dv, nn.as<uint32_t>(), S.partial_sum.as<double>(), S.sums.as<double>(), ctx->stream);
             uint8_t* h = ctx->h_small.as<uint8_t>();
@@ -1663,7 +1634,7 @@ int m3d_detect_boundary_points(const double* xyz, const double* normals, size_t 
         rc = [&]() -> int {
             HIPCHK(hipSetDevice(ctx->device));
             const CloudView v = c->view();
-            GridDesc g;
+            TargetGrid tg;
             double cell = radius;
             if (search == 0) {   // KNN: a cell that holds ~max_nn / 4 points on average (bounding-box density)
                 double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -1683,13 +1654,12 @@ int m3d_detect_boundary_points(const double* xyz, const double* normals, size_t 
                 cell = emax > 0.0 ? std::cbrt(vol * (double)max_nn / (4.0 * (double)n)) : 1.0;
                 if (!(cell > 0.0) || !std::isfinite(cell)) cell = 1.0;
             }
-            const int rg = build_target_grid(ctx, S, v, xyz, n, cell, true, &g, /*K0=*/1, /*with_nl=*/false);
+            const int rg = build_target_grid(ctx, S, v, xyz, n, cell, true, &tg, /*K0=*/1, /*with_nl=*/false);
             if (rg != M3D_OK) return rg;
             RESERVE(flags, (size_t)v.n + 8);
             HIPCHK(hipMemsetAsync(flags.p, 0, (size_t)v.n + 8, ctx->stream));
-            launch_boundary(v, g, S.tgt.start.as<uint32_t>(), S.qx.as<double>(), S.qy.as<double>(), S.qz.as<double>(),
-                            S.cell_orig.as<uint32_t>(), search, max_nn, angle_threshold_deg, flags.as<uint8_t>(),
-                            flags.as<uint8_t>() + v.n, ctx->stream, S.tgt.total.as<uint32_t>());
+            launch_boundary(v, tg, search, max_nn, angle_threshold_deg, flags.as<uint8_t>(), flags.as<uint8_t>() + v.n, ctx->stream,
+                            S.tgt.total.as<uint32_t>());
             std::vector<uint8_t> hf((size_t)v.n + 8);
             HIPCHK(hipMemcpyAsync(hf.data(), flags.p, hf.size(), hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(hipGetLastError());

@@ -1,4 +1,5 @@
-"""The registration sums (m3d_reg_kernels.hip: kabsch_sums_k, icp_err_k, icp_sums_k, info_sums_k + kabsch_final_k) restated:
+"""The registration sums (m3d_reg_kernels.hip: umeyama_sums_k over the pairs of m3d_kabsch and over an ICP step's correspondences
+-- recorded under the keys "kabsch_sums_k" and "icp_sums_k" --, icp_err_k, info_sums_k + kabsch_final_k) restated:
 an exact reference, the error bound their summation shape implies, a numpy emulation of that shape with the mutations the
 tests must notice, and the input families of tests/test_reg_sums.py (CPU) and tests/test_gpu_reg_sums.py.
 

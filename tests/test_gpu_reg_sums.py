@@ -1,4 +1,5 @@
-"""The registration sums on the MI355X -- kabsch_sums_k, icp_err_k, icp_sums_k, info_sums_k and kabsch_final_k, through the
+"""The registration sums on the MI355X -- umeyama_sums_k with both of its pair sources (the record keys "kabsch_sums_k" and
+"icp_sums_k"), icp_err_k, info_sums_k and kabsch_final_k, through the
 test hooks m3d_bench_kabsch_sums and m3d_bench_icp_sums -- against the exact reference of tests/reg_sums_ref_util.py at every
 seam of their reduction (the workgroup edge 255 / 256 / 257, the grid-stride edge 65535 / 65536 / 65537, three trips at
 131073): bit for bit on the exact-integer and probe inputs, within the bound derived from the summation shape (factor 2 over

@@ -240,7 +240,7 @@ if "C4" in which:
          iterations=st3["iterations"], fitness=st3["fitness"], rmse=st3["inlier_rmse"],
          pose_err=float(np.abs(T3 - d["T"]).max()),
          roofline={"bound": "hbm on the 8(d) unit (24 B per query); the call is a chain of short launches per iteration (grid search, sums, "
-                            "3x3 solve on the host)", "kernel": "m3d::icp_nn_k + icp_sums_k", "achieved": q3 * 24.0 / (sorted(ts)[1] * 1e-3) / 1e9,
+                            "3x3 solve on the host)", "kernel": "m3d::icp_nn_k + umeyama_sums_k<PASS, IcpPairs>", "achieved": q3 * 24.0 / (sorted(ts)[1] * 1e-3) / 1e9,
                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": q3 * 24.0 / (sorted(ts)[1] * 1e-3) / 1e9 / HBM_PEAK_GBS, "queries": q3},
          cpu_baseline=None if NO_CPU else icp_cpu())
 
