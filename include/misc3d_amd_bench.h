@@ -121,6 +121,12 @@ int m3d_bench_fpfh_pair_bins(const double *pairs, size_t m, int32_t *bins, doubl
  * bit 3: the fp32 screen, bit 4: fp64 brute force. */
 unsigned m3d_bench_match_last_path(void);
 
+/* MEASUREMENT / TEST hook (tools/bench_configs.py, tests/test_gpu_ppf.py): every later m3d_ppf_vote in the process keeps its
+ * accumulators in device memory when device_memory_path != 0 (0: by (n, alpha_model_num), the default), and runs at most
+ * max_groups workgroups (0: as many as the scratch allows, the default; a small value makes each workgroup take several
+ * reference positions in turn).  The result does not depend on either. */
+int m3d_bench_ppf_force(int device_memory_path, int max_groups);
+
 #ifdef __cplusplus
 }
 #endif

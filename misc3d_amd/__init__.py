@@ -25,6 +25,8 @@ Drop-in for the reference's python API on this path (module layout of python/py_
     T, info  = m3d.reconstruction.refine_fragment_pair(frag_s, frag_t, voxel_size, edge_pose)          # pipeline.cpp:686-697
     renderer = m3d.pose_estimation.RayCastRenderer(intrinsic); renderer.cast_rays([mesh, mesh], [pose, pose2])
     depth    = renderer.get_depth_map().numpy(); instance = renderer.get_instance_map().numpy()        # ray_cast_renderer.cpp
+    voting   = m3d.pose_estimation.PPFVoting(model_points, model_normals, diameter, r_min)             # ppf_estimation.cpp:603-640
+    poses, num_votes, corr_mi, reference = voting.vote(scene_points, scene_normals, reference_indices) # ppf_estimation.cpp:399-524
 
 Layout (only what the path needs):
   csrc/      HIP kernels, host driver, C ABI            -> lib/libmisc3d_amd.so
@@ -600,9 +602,56 @@ class RayCastRenderer:
         return [self._cloud(self._res["geometry_ids"] == i) for i in range(self._n)]
 
 
+class PPFVoting:
+    """The two device hot paths of misc3d.pose_estimation.PPFEstimator (src/ppf_estimation.cpp): the point-pair table of a model
+    (CalcHashTable, :603-640) and the vote of a scene against it (VotingAndGetPose, :399-524).  points / normals: the ALREADY
+    SAMPLED model points with unit normals ((N, 3) arrays, 2 <= N <= 65535); diameter, r_min: what PreprocessTrain derives
+    from the model's bounding box.  params: rel_sample_dist (0.05), angle_step (radians, 12 degrees), min_dist_thresh (1/3),
+    min_angle_thresh (radians, 30 degrees), faster_mode (True) -- the reference's config fields.  The preprocessing, the pose
+    clustering, the scoring and the PPFEstimator class itself are not part of this build."""
+
+    def __init__(self, points, normals, diameter, r_min, *, device=0, **params):
+        from . import capi as _capi
+        try:
+            self._model = _capi.PpfModel(points, normals, diameter, r_min, device, **params)
+        except _capi.M3DError as e:
+            raise RuntimeError(str(e)) from e
+
+    @property
+    def centroid(self):
+        """the centroid the model was centred by (Train, :551-560): the raw poses are those of the centred model"""
+        return self._model.centroid.copy()
+
+    def __len__(self):
+        return self._model.n
+
+    def table(self):
+        """the flat table: dict(cell_offsets, entry_i, entry_alpha, nbr_offsets, nbr_indices, tmg, centroid, table_size, ...)"""
+        from . import capi as _capi
+        try:
+            return self._model.table()
+        except _capi.M3DError as e:
+            raise RuntimeError(str(e)) from e
+
+    def vote(self, scene_points, scene_normals, reference_indices):
+        """The reference's pose_list before clustering, in ascending (reference position, model index): poses (K, 4, 4) of the
+        centred model, num_votes (K,), corr_mi (K,) -- Pose6D's fields -- and reference (K,), the position in reference_indices
+        of the scene point each pose was voted at."""
+        import numpy as _np
+
+        from . import capi as _capi
+        try:
+            r = self._model.vote(scene_points, scene_normals, reference_indices)
+        except _capi.M3DError as e:
+            raise RuntimeError(str(e)) from e
+        return r["poses"], r["votes"].astype(_np.int64), r["model_index"].astype(_np.int64), r["ref_pos"].astype(_np.int64)
+
+
 class _PoseEstimation:
-    """misc3d.pose_estimation (python/py_pose_estimation.cpp): RayCastRenderer.  PPFEstimator is not part of this build."""
+    """misc3d.pose_estimation (python/py_pose_estimation.cpp): RayCastRenderer.  PPFEstimator is not part of this build; its
+    table and its voting are here, as PPFVoting."""
     RayCastRenderer = RayCastRenderer
+    PPFVoting = PPFVoting
 
 
 pose_estimation = _PoseEstimation()

@@ -34,6 +34,7 @@ OK, FALSE = 1, 0
 ERR_PROBABILITY, ERR_TOO_FEW_POINTS, ERR_NO_NORMALS, ERR_SIZE_MISMATCH = -1, -2, -3, -4
 ERR_INVALID_ARG, ERR_DEVICE, ERR_INTERNAL = -5, -6, -7
 ERR_NON_FINITE = -8
+ERR_CAPACITY = -9
 
 
 class M3DError(RuntimeError):
@@ -212,6 +213,18 @@ def lib():
         L.m3d_bench_knn_force_path.argtypes = [C.c_int]
         L.m3d_bench_knn_tile_merge.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
                                                C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
+        L.m3d_ppf_default_params.restype = None
+        L.m3d_ppf_default_params.argtypes = [C.c_void_p]
+        L.m3d_ppf_model_create.restype = C.c_void_p
+        L.m3d_ppf_model_create.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_void_p]
+        L.m3d_ppf_model_destroy.restype = None
+        L.m3d_ppf_model_destroy.argtypes = [C.c_void_p]
+        L.m3d_ppf_model_size.restype = C.c_size_t
+        L.m3d_ppf_model_size.argtypes = [C.c_void_p]
+        L.m3d_ppf_model_centroid.argtypes = [C.c_void_p, C.c_void_p]
+        L.m3d_ppf_model_table.argtypes = [C.c_void_p] * 8
+        L.m3d_ppf_vote.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t] + [C.c_void_p] * 7
+        L.m3d_bench_ppf_force.argtypes = [C.c_int, C.c_int]
         L.m3d_estimate_normals.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                            C.c_void_p, C.c_void_p]
         L.m3d_compute_fpfh.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p,
@@ -1545,6 +1558,119 @@ def knn_tile_merge(data, queries, kk, pages, splits, rows_per_split, device=0):
     _check(lib().m3d_bench_knn_tile_merge(_p(data), n, dim, _p(q), m, int(kk), int(pages), int(splits), int(rows_per_split),
                                           device, _p(idx), _p(key)))
     return idx, key
+
+
+PPF_PATH_LDS, PPF_PATH_DEVICE = 1, 2
+
+
+class PpfParams(C.Structure):
+    """m3d_ppf_params (angles in radians)"""
+    _fields_ = [("rel_sample_dist", C.c_double), ("angle_step", C.c_double), ("min_dist_thresh", C.c_double),
+                ("min_angle_thresh", C.c_double), ("faster_mode", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PpfTableInfo(C.Structure):
+    """m3d_ppf_table_info"""
+    _fields_ = [("table_size", C.c_uint64), ("n_entries", C.c_uint64), ("n_neighbors", C.c_uint64), ("angle_num", C.c_int32),
+                ("alpha_model_num", C.c_int32), ("dist_num", C.c_int32), ("path", C.c_int32)]
+
+
+class PpfVoteStats(C.Structure):
+    """m3d_ppf_vote_stats"""
+    _fields_ = [("path", C.c_int32), ("launches", C.c_uint32), ("groups", C.c_uint32), ("reserved", C.c_uint32),
+                ("neighbours_visited", C.c_uint64), ("increments", C.c_uint64), ("ms_device", C.c_double), ("ms_total", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+def ppf_params(**kw):
+    """the defaults of m3d_ppf_default_params with the given fields replaced"""
+    P = PpfParams()
+    lib().m3d_ppf_default_params(C.cast(C.byref(P), C.c_void_p))
+    for k, v in kw.items():
+        if k not in dict(PpfParams._fields_) or k == "reserved":
+            raise TypeError(f"ppf_params: no parameter {k!r}")
+        setattr(P, k, int(bool(v)) if k == "faster_mode" else float(v))
+    return P
+
+
+class PpfModel:
+    """m3d_ppf_model_create / _table / m3d_ppf_vote / _destroy: the PPF table of already sampled model points with unit
+    normals, and the vote of a scene against it (include/misc3d_amd.h, "PPF voting")."""
+
+    def __init__(self, points, normals, diameter, r_min, device=0, **params):
+        pts, nrm = _f64(points).reshape(-1, 3), _f64(normals).reshape(-1, 3)
+        if len(pts) != len(nrm):
+            raise ValueError("ppf: one normal per point")
+        P = ppf_params(**params)
+        status = C.c_int(0)
+        self.h = lib().m3d_ppf_model_create(_p(pts), _p(nrm), len(pts), float(diameter), float(r_min), C.cast(C.byref(P), C.c_void_p),
+                                            int(device), C.cast(C.byref(status), C.c_void_p))
+        if not self.h:
+            raise M3DError(status.value, last_error())
+        self.n = len(pts)
+        c = np.zeros(3)
+        _check(lib().m3d_ppf_model_centroid(self.h, _p(c)))
+        self.centroid = c
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().m3d_ppf_model_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def info(self):
+        I = PpfTableInfo()
+        _check(lib().m3d_ppf_model_table(self.h, C.cast(C.byref(I), C.c_void_p), None, None, None, None, None, None))
+        return {k: int(getattr(I, k)) for k, _ in PpfTableInfo._fields_}
+
+    def table(self):
+        """-> dict(cell_offsets, entry_i, entry_alpha, nbr_offsets, nbr_indices, tmg (n, 4, 4), centroid) + the info fields"""
+        I = self.info()
+        t = dict(cell_offsets=np.zeros(I["table_size"] + 1, np.uint32), entry_i=np.zeros(I["n_entries"], np.uint16),
+                 entry_alpha=np.zeros(I["n_entries"], np.uint8), nbr_offsets=np.zeros(self.n + 1, np.uint32),
+                 nbr_indices=np.zeros(I["n_neighbors"], np.uint32), tmg=np.zeros((self.n, 4, 4)))
+        _check(lib().m3d_ppf_model_table(self.h, None, *(_p(t[k]) for k in ("cell_offsets", "entry_i", "entry_alpha", "nbr_offsets",
+                                                                             "nbr_indices", "tmg"))))
+        t["centroid"] = self.centroid.copy()
+        t.update(I)
+        return t
+
+    def vote(self, scene_points, scene_normals, reference, capacity=None, stats=False):
+        """-> dict(ref_pos, model_index, alpha_index, votes (uint32 each), poses (K, 4, 4)) (+ the stats dict).  capacity=None:
+        the call is repeated once with the needed capacity when the first guess was too small; a given capacity is final
+        (M3DError with code ERR_CAPACITY and .needed set)."""
+        sp, sn = _f64(scene_points).reshape(-1, 3), _f64(scene_normals).reshape(-1, 3)
+        if len(sp) != len(sn):
+            raise ValueError("ppf: one normal per scene point")
+        ref = np.ascontiguousarray(reference, dtype=np.uint64).reshape(-1)
+        cap = max(256, 4 * len(ref)) if capacity is None else int(capacity)
+        while True:
+            out = [np.zeros(max(cap, 1), np.uint32) for _ in range(4)]
+            poses = np.zeros((max(cap, 1), 4, 4))
+            k = C.c_size_t(0)
+            st = PpfVoteStats()
+            rc = lib().m3d_ppf_vote(self.h, _p(sp), _p(sn), len(sp), _p(ref), len(ref), cap, C.cast(C.byref(k), C.c_void_p),
+                                    *(_p(o) for o in out), _p(poses), C.cast(C.byref(st), C.c_void_p))
+            if rc == ERR_CAPACITY and capacity is None:
+                cap = k.value
+                continue
+            if rc < 0:
+                e = M3DError(rc, last_error())
+                e.needed = k.value
+                raise e
+            break
+        res = dict(ref_pos=out[0][:k.value], model_index=out[1][:k.value], alpha_index=out[2][:k.value], votes=out[3][:k.value],
+                   poses=poses[:k.value])
+        return (res, st.asdict()) if stats else res
+
+
+def ppf_force(device_memory_path=False, max_groups=0):
+    """test / measurement hook m3d_bench_ppf_force: accumulators in device memory, at most max_groups workgroups (0: default)"""
+    _check(lib().m3d_bench_ppf_force(int(bool(device_memory_path)), int(max_groups)))
 
 
 class FpfhStats(C.Structure):

@@ -1,0 +1,503 @@
+// m3d_ppf.cpp -- the table and the vote of misc3d::pose_estimation::PPFEstimator (src/ppf_estimation.cpp) behind the C ABI:
+// m3d_ppf_model_create (CalcHashTable, GenerateModelPCNeighbor), m3d_ppf_vote (VotingAndGetPose, CalcLocalMaximum).  The
+// contract is in include/misc3d_amd.h "PPF voting"; the frames (CalcTNormal2RegionX) and the pose products are the host's.
+// Nothing here depends on M3D_FP_ORDER (every sum is written out).
+#include "m3d_driver_internal.hpp"
+#include "m3d_ppf.hpp"
+#include "m3d_radix_sort.hpp"
+
+#include "../../include/misc3d_amd_bench.h"
+
+#include <atomic>
+
+#pragma clang fp contract(off)
+
+using namespace m3d;
+
+namespace {
+
+// m3d_bench_ppf_force
+std::atomic<int> g_ppf_force_device{0};
+std::atomic<int> g_ppf_max_groups{0};
+
+constexpr size_t kPpfScratchCap = (size_t)256 << 20;        // device scratch of one vote (bytes)
+constexpr size_t kPpfFlagBudget = (size_t)160 << 20;        // ... of which the flag arrays
+constexpr size_t kPpfAccBudget = (size_t)64 << 20;          // ... and the device-memory accumulators with the row records
+constexpr uint64_t kPpfMaxSortPairs = (uint64_t)1 << 28;    // 16 bytes of sort scratch a pair: 4 GiB
+constexpr uint32_t kPpfMaxGroups = 256;                     // one workgroup per CU
+
+bool finite3(const double* a, size_t n) {
+    for (size_t i = 0; i < 3 * n; ++i)
+        if (!std::isfinite(a[i])) return false;
+    return true;
+}
+
+// CalcTNormal2RegionX (ppf_estimation.cpp:674-697), rule M3; T row-major 4 x 4
+void ppf_frame(const double* p, const double* n, double* T) {
+    double u1 = n[2], u2 = -n[1];
+    const double norm = std::sqrt(u1 * u1 + u2 * u2);
+    if (norm > 1.0e-6) {
+        const double inv = 1 / norm;
+        u1 *= inv;
+        u2 *= inv;
+    } else {
+        u1 = 1.0;
+        u2 = 0.0;
+    }
+    const double nx = n[0] > 1.0 ? 1.0 : (n[0] < -1.0 ? -1.0 : n[0]);
+    const double half = std::acos(nx) / 2;
+    const double q0 = std::cos(half), q1 = 0.0, q2 = std::sin(half) * u1, q3 = std::sin(half) * u2;
+    double R[9];
+    R[0] = 1 - 2 * (q2 * q2 + q3 * q3);
+    R[1] = 2 * (q1 * q2 - q0 * q3);
+    R[2] = 2 * (q0 * q2 + q1 * q3);
+    R[3] = 2 * (q1 * q2 + q0 * q3);
+    R[4] = 1 - 2 * (q1 * q1 + q3 * q3);
+    R[5] = 2 * (q2 * q3 - q0 * q1);
+    R[6] = 2 * (q1 * q3 - q0 * q2);
+    R[7] = 2 * (q0 * q1 + q2 * q3);
+    R[8] = 1 - 2 * (q1 * q1 + q2 * q2);
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) T[4 * r + c] = R[3 * r + c];
+        T[4 * r + 3] = -((R[3 * r] * p[0] + R[3 * r + 1] * p[1]) + R[3 * r + 2] * p[2]);
+    }
+    T[12] = T[13] = T[14] = 0.0;
+    T[15] = 1.0;
+}
+
+// C = A B, row-major 4 x 4, every sum ((a0 b0 + a1 b1) + a2 b2) + a3 b3
+void mul4(const double* A, const double* B, double* C) {
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c)
+            C[4 * r + c] = ((A[4 * r] * B[c] + A[4 * r + 1] * B[4 + c]) + A[4 * r + 2] * B[8 + c]) + A[4 * r + 3] * B[12 + c];
+}
+
+// rule V8: tsg^-1 Rx(alpha) tmg, the inverse being [R^T | -R^T t]
+void ppf_pose(const double* tsg, double alpha, const double* tmg, double* out) {
+    double inv[16], rx[16], tmp[16];
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) inv[4 * r + c] = tsg[4 * c + r];
+        inv[4 * r + 3] = -((tsg[r] * tsg[3] + tsg[4 + r] * tsg[7]) + tsg[8 + r] * tsg[11]);
+    }
+    inv[12] = inv[13] = inv[14] = 0.0;
+    inv[15] = 1.0;
+    const double ca = std::cos(alpha), sa = std::sin(alpha);
+    const double rxv[16] = {1, 0, 0, 0, 0, ca, -sa, 0, 0, sa, ca, 0, 0, 0, 0, 1};
+    std::memcpy(rx, rxv, sizeof(rx));
+    mul4(inv, rx, tmp);   // (tsg_inv * tr) * tmg, as Eigen evaluates the product
+    mul4(tmp, tmg, out);
+}
+
+void frame_rows(const double* T, double* rows8) { std::memcpy(rows8, T + 4, sizeof(double) * 8); }
+
+struct VoteBufs {
+    DevBuf spts, snrm, ref, sframes, flags, acc, rowinfo, out, small;
+    void release() {
+        for (DevBuf* b : {&spts, &snrm, &ref, &sframes, &flags, &acc, &rowinfo, &out, &small}) b->release();
+    }
+};
+
+}  // namespace
+
+struct m3d_ppf_model {
+    int device = 0;
+    uint32_t n = 0;
+    double r_min = 0.0, angle_step = 0.0, min_dist_thresh = 0.0, min_angle_thresh = 0.0;
+    PpfSizes sizes{};
+    PpfTables T{};                // (dist_edge2 points at edge2 below: the host's copy)
+    std::vector<double> edge2;
+    double centroid[3] = {0, 0, 0};
+    std::vector<double> tmg;      // n x 16
+    uint32_t n_entries = 0, n_neighbors = 0;
+    m3d::DevBuf pts, nrm, frames, d_edge2, cell_off, entries, nbr_off, nbr_idx;
+    void release() {
+        for (m3d::DevBuf* b : {&pts, &nrm, &frames, &d_edge2, &cell_off, &entries, &nbr_off, &nbr_idx}) b->release();
+    }
+    PpfModelView view() const {
+        PpfModelView v;
+        v.T = T;
+        v.T.dist_edge2 = d_edge2.as<double>();
+        v.n = n;
+        v.table_size = (uint32_t)sizes.table_size;
+        v.pts = pts.as<double>();
+        v.nrm = nrm.as<double>();
+        v.frames = frames.as<double>();
+        v.cell_off = cell_off.as<uint32_t>();
+        v.entries = entries.as<uint32_t>();
+        v.nbr_off = nbr_off.as<uint32_t>();
+        v.nbr_idx = nbr_idx.as<uint32_t>();
+        return v;
+    }
+};
+
+namespace {
+
+int ppf_check_params(const m3d_ppf_params& P, double diameter, double r_min, PpfSizes* sizes) {
+    auto pos = [](double v) { return v > 0.0 && std::isfinite(v); };
+    if (!pos(diameter) || !pos(r_min)) return fail(M3D_ERR_INVALID_ARG, "ppf: diameter and r_min must be positive and finite");
+    if (!pos(P.rel_sample_dist) || !pos(P.angle_step) || !pos(P.min_dist_thresh) || !pos(P.min_angle_thresh))
+        return fail(M3D_ERR_INVALID_ARG, "ppf: rel_sample_dist, angle_step, min_dist_thresh and min_angle_thresh must be positive and finite");
+    const PpfSizes s = ppf_sizes(diameter, P.rel_sample_dist, P.angle_step);
+    if (s.angle_num == 0 || s.alpha_num < 3)
+        return fail(M3D_ERR_INVALID_ARG, "ppf: angle_step / rel_sample_dist give fewer than 3 alpha bins or sizes out of range");
+    if (s.alpha_num > kPpfMaxAlphaBins)
+        return fail(M3D_ERR_INVALID_ARG, "ppf: alpha_model_num = " + std::to_string(s.alpha_num) + " > 64 (angle_step too small)");
+    if (s.table_size >= (int64_t)kPpfMaxTableSize) return fail(M3D_ERR_INVALID_ARG, "ppf: hash_table_size must be < 2^24");
+    if (!pos(s.dist_step)) return fail(M3D_ERR_INVALID_ARG, "ppf: dist_step is not positive and finite");
+    *sizes = s;
+    return M3D_OK;
+}
+
+// the table and the neighbour lists of a model whose points, normals, frames and edges are on the device
+int ppf_build_table(DeviceCtx* ctx, m3d_ppf_model* h) {
+    hipStream_t st = ctx->stream;
+    const uint32_t n = h->n, table_size = (uint32_t)h->sizes.table_size;
+    const uint32_t pairs = n * n;
+    DevBuf keys, k0, v0, k1, v1, counts, scan, total, ncount;
+    auto release = [&]() {
+        for (DevBuf* b : {&keys, &k0, &v0, &k1, &v1, &counts, &scan, &total, &ncount}) b->release();
+    };
+    const int rc = [&]() -> int {
+        uint32_t tile = 0, blocks = 0;
+        voxel_sort_shape(pairs, &tile, &blocks);
+        const size_t n_counts = (size_t)kVoxelSortRadix * blocks;
+        const uint32_t passes = table_size < (1u << 8) ? 1 : (table_size < (1u << 16) ? 2 : 3);   // (the skipped pairs' key is table_size)
+        RESERVE(keys, sizeof(uint32_t) * pairs);
+        for (DevBuf* b : {&k0, &v0, &k1, &v1}) RESERVE(*b, sizeof(uint32_t) * pairs);
+        RESERVE(counts, sizeof(uint32_t) * n_counts);
+        RESERVE(scan, sizeof(uint32_t) * voxel_scan_scratch(std::max<size_t>(n_counts, n + 1)));
+        RESERVE(total, 16);
+        RESERVE(ncount, sizeof(uint32_t) * (n + 1));
+        RESERVE(h->cell_off, sizeof(uint32_t) * ((size_t)table_size + 1));
+        RESERVE(h->nbr_off, sizeof(uint32_t) * (n + 1));
+        PpfModelView v = h->view();
+        launch_ppf_pair_keys(v, keys.as<uint32_t>(), st);
+        const uint32_t *sk = nullptr, *sv = nullptr;
+        launch_radix_sort_pairs(keys.as<uint32_t>(), nullptr, pairs, passes, k0.as<uint32_t>(), v0.as<uint32_t>(), k1.as<uint32_t>(),
+                                v1.as<uint32_t>(), counts.as<uint32_t>(), scan.as<uint32_t>(), total.as<uint32_t>(), &sk, &sv, st);
+        launch_ppf_cell_offsets(sk, pairs, table_size, h->cell_off.as<uint32_t>(), st);
+        HIPCHK(hipGetLastError());
+        // the neighbour lists: counts, their scan, the fill
+        const double r = 0.5 * h->r_min, r2 = r * r;
+        HIPCHK(hipMemsetAsync(ncount.p, 0, sizeof(uint32_t) * (n + 1), st));
+        launch_ppf_nbr_count(v.pts, n, r2, ncount.as<uint32_t>(), st);
+        launch_scan_exclusive(ncount.as<uint32_t>(), h->nbr_off.as<uint32_t>(), n + 1, scan.as<uint32_t>(), total.as<uint32_t>(), st);
+        HIPCHK(hipGetLastError());
+        uint32_t n_entries = 0, n_nbr = 0;
+        HIPCHK(hipMemcpyAsync(&n_entries, h->cell_off.as<uint32_t>() + table_size, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(&n_nbr, h->nbr_off.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (n_entries > pairs - n || n_nbr < n || (uint64_t)n_nbr > (uint64_t)pairs)
+            return fail(M3D_ERR_INTERNAL, "ppf: the table's totals are out of range (self-check)");
+        h->n_entries = n_entries;
+        h->n_neighbors = n_nbr;
+        RESERVE(h->entries, sizeof(uint32_t) * std::max<size_t>(n_entries, 1));
+        RESERVE(h->nbr_idx, sizeof(uint32_t) * n_nbr);
+        launch_ppf_entries(sk, sv, n_entries, n, table_size, h->entries.as<uint32_t>(), st);
+        launch_ppf_nbr_fill(v.pts, n, r2, h->nbr_off.as<uint32_t>(), h->nbr_idx.as<uint32_t>(), st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));   // published to every lane once built
+        return M3D_OK;
+    }();
+    (void)hipStreamSynchronize(st);
+    release();
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+void m3d_ppf_default_params(m3d_ppf_params* out) {
+    if (!out) return;
+    out->rel_sample_dist = 0.05;
+    out->angle_step = 12.0 / 180.0 * M_PI;
+    out->min_dist_thresh = 1.0 / 3.0;
+    out->min_angle_thresh = 30.0 / 180.0 * M_PI;
+    out->faster_mode = 1;
+    out->reserved = 0;
+}
+
+m3d_ppf_model* m3d_ppf_model_create(const double* points, const double* normals, size_t n, double diameter, double r_min,
+                                    const m3d_ppf_params* params, int device, int* status) {
+    if (status) *status = M3D_ERR_INVALID_ARG;
+    m3d_ppf_params P;
+    m3d_ppf_default_params(&P);
+    if (params) P = *params;
+    if (!points || !normals) {
+        fail(M3D_ERR_INVALID_ARG, "ppf: null points or normals");
+        return nullptr;
+    }
+    if (n < 2 || n > kPpfMaxPoints) {
+        fail(M3D_ERR_INVALID_ARG, "ppf: the model must have 2 .. 65535 points, got " + std::to_string(n));
+        return nullptr;
+    }
+    PpfSizes sizes;
+    if (ppf_check_params(P, diameter, r_min, &sizes) != M3D_OK) return nullptr;
+    if (!finite3(points, n) || !finite3(normals, n)) {
+        fail(M3D_ERR_INVALID_ARG, "ppf: a model point or normal is not finite");
+        return nullptr;
+    }
+    if (status) *status = M3D_ERR_DEVICE;
+    if ((uint64_t)n * n > kPpfMaxSortPairs) {
+        fail(M3D_ERR_DEVICE, "ppf: the table's sort scratch (16 bytes a pair) is capped at 4 GiB: n <= 16383");
+        return nullptr;
+    }
+    m3d_ppf_model* h = new m3d_ppf_model;
+    h->device = device;
+    h->n = (uint32_t)n;
+    h->r_min = r_min;
+    h->angle_step = P.angle_step;
+    h->min_dist_thresh = P.min_dist_thresh;
+    h->min_angle_thresh = P.min_angle_thresh;
+    h->sizes = sizes;
+    ppf_make_tables(sizes, P.angle_step, P.faster_mode != 0, &h->T, &h->edge2);
+    // rule M2: the centroid, serially; the centred points; rule M3: the frames
+    double c[3] = {0, 0, 0};
+    for (size_t i = 0; i < n; ++i)
+        for (int k = 0; k < 3; ++k) c[k] += points[3 * i + k];
+    for (int k = 0; k < 3; ++k) h->centroid[k] = c[k] / static_cast<double>(n);
+    std::vector<double> centred(3 * n), rows(8 * n);
+    h->tmg.resize(16 * n);
+    for (size_t i = 0; i < n; ++i) {
+        for (int k = 0; k < 3; ++k) centred[3 * i + k] = points[3 * i + k] - h->centroid[k];
+        ppf_frame(&centred[3 * i], normals + 3 * i, &h->tmg[16 * i]);
+        frame_rows(&h->tmg[16 * i], &rows[8 * i]);
+    }
+    if (!finite3(centred.data(), n)) {
+        fail(M3D_ERR_INVALID_ARG, "ppf: a centred model point is not finite");
+        if (status) *status = M3D_ERR_INVALID_ARG;
+        delete h;
+        return nullptr;
+    }
+    int rc = M3D_ERR_DEVICE;
+    {
+        LaneLock lane(device);
+        DeviceCtx* ctx = lane.ctx;
+        if (ctx) {
+            rc = [&]() -> int {
+                HIPCHK(hipSetDevice(ctx->device));
+                hipStream_t st = ctx->stream;
+                RESERVE(h->pts, sizeof(double) * 3 * n);
+                RESERVE(h->nrm, sizeof(double) * 3 * n);
+                RESERVE(h->frames, sizeof(double) * 8 * n);
+                RESERVE(h->d_edge2, sizeof(double) * h->edge2.size());
+                HIPCHK(hipMemcpyAsync(h->pts.p, centred.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
+                HIPCHK(hipMemcpyAsync(h->nrm.p, normals, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
+                HIPCHK(hipMemcpyAsync(h->frames.p, rows.data(), sizeof(double) * 8 * n, hipMemcpyHostToDevice, st));
+                HIPCHK(hipMemcpyAsync(h->d_edge2.p, h->edge2.data(), sizeof(double) * h->edge2.size(), hipMemcpyHostToDevice, st));
+                HIPCHK(hipStreamSynchronize(st));
+                return ppf_build_table(ctx, h);
+            }();
+            if (rc != M3D_OK) {
+                (void)hipStreamSynchronize(ctx->stream);
+                h->release();
+            }
+        }
+    }
+    if (rc != M3D_OK) {
+        if (status) *status = rc;
+        delete h;
+        return nullptr;
+    }
+    if (status) *status = M3D_OK;
+    return h;
+}
+
+void m3d_ppf_model_destroy(m3d_ppf_model* h) {
+    if (!h) return;
+    h->release();
+    delete h;
+}
+
+size_t m3d_ppf_model_size(const m3d_ppf_model* h) { return h ? h->n : 0; }
+
+int m3d_ppf_model_centroid(const m3d_ppf_model* h, double centroid[3]) {
+    if (!h || !centroid) return fail(M3D_ERR_INVALID_ARG, "ppf: null argument");
+    std::memcpy(centroid, h->centroid, sizeof(double) * 3);
+    return M3D_OK;
+}
+
+int m3d_ppf_model_table(const m3d_ppf_model* h, m3d_ppf_table_info* info, uint32_t* cell_offsets, uint16_t* entry_i,
+                        uint8_t* entry_alpha, uint32_t* nbr_offsets, uint32_t* nbr_indices, double* tmg) {
+    if (!h) return fail(M3D_ERR_INVALID_ARG, "ppf: null model");
+    if (info) {
+        info->table_size = (uint64_t)h->sizes.table_size;
+        info->n_entries = h->n_entries;
+        info->n_neighbors = h->n_neighbors;
+        info->angle_num = (int32_t)h->sizes.angle_num;
+        info->alpha_model_num = (int32_t)h->sizes.alpha_num;
+        info->dist_num = (int32_t)h->sizes.dist_num;
+        info->path = ppf_acc_in_lds(h->n, (int)h->sizes.alpha_num) ? M3D_PPF_PATH_LDS : M3D_PPF_PATH_DEVICE;
+    }
+    if (tmg) std::memcpy(tmg, h->tmg.data(), sizeof(double) * h->tmg.size());
+    if (!cell_offsets && !entry_i && !entry_alpha && !nbr_offsets && !nbr_indices) return M3D_OK;
+    LaneLock lane(h->device);
+    DeviceCtx* ctx = lane.ctx;
+    if (!ctx) return M3D_ERR_DEVICE;
+    return [&]() -> int {
+        HIPCHK(hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        std::vector<uint32_t> ent;
+        if (cell_offsets)
+            HIPCHK(hipMemcpyAsync(cell_offsets, h->cell_off.p, sizeof(uint32_t) * ((size_t)h->sizes.table_size + 1), hipMemcpyDeviceToHost, st));
+        if (nbr_offsets) HIPCHK(hipMemcpyAsync(nbr_offsets, h->nbr_off.p, sizeof(uint32_t) * (h->n + 1), hipMemcpyDeviceToHost, st));
+        if (nbr_indices) HIPCHK(hipMemcpyAsync(nbr_indices, h->nbr_idx.p, sizeof(uint32_t) * h->n_neighbors, hipMemcpyDeviceToHost, st));
+        if ((entry_i || entry_alpha) && h->n_entries) {
+            ent.resize(h->n_entries);
+            HIPCHK(hipMemcpyAsync(ent.data(), h->entries.p, sizeof(uint32_t) * h->n_entries, hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t t = 0; t < ent.size(); ++t) {
+            if (entry_i) entry_i[t] = (uint16_t)(ent[t] & 0xFFFFu);
+            if (entry_alpha) entry_alpha[t] = (uint8_t)(ent[t] >> 16);
+        }
+        return M3D_OK;
+    }();
+}
+
+int m3d_ppf_vote(const m3d_ppf_model* h, const double* scene_points, const double* scene_normals, size_t m,
+                 const size_t* reference, size_t n_ref, size_t capacity, size_t* n_maxima, uint32_t* ref_pos,
+                 uint32_t* model_index, uint32_t* alpha_index, uint32_t* votes, double* poses, m3d_ppf_vote_stats* stats) {
+    const double t0 = now_ms();
+    m3d_ppf_vote_stats S{};
+    if (stats) *stats = S;
+    if (n_maxima) *n_maxima = 0;
+    if (!h) return fail(M3D_ERR_INVALID_ARG, "ppf: null model");
+    if (!scene_points || !scene_normals || !reference || !n_maxima) return fail(M3D_ERR_INVALID_ARG, "ppf: null argument");
+    if (capacity && (!ref_pos || !model_index || !alpha_index || !votes)) return fail(M3D_ERR_INVALID_ARG, "ppf: null result array");
+    if (n_ref == 0) return fail(M3D_ERR_INVALID_ARG, "ppf: no reference points");
+    if (m == 0 || m >= ((size_t)1 << 31) || n_ref >= ((size_t)1 << 31)) return fail(M3D_ERR_INVALID_ARG, "ppf: the scene must have 1 .. 2^31 - 1 points");
+    if (!finite3(scene_points, m) || !finite3(scene_normals, m)) return fail(M3D_ERR_INVALID_ARG, "ppf: a scene point or normal is not finite");
+    std::vector<uint32_t> ref32(n_ref);
+    for (size_t s = 0; s < n_ref; ++s) {
+        if (reference[s] >= m) return fail(M3D_ERR_INVALID_ARG, "ppf: a reference index is out of range");
+        ref32[s] = (uint32_t)reference[s];
+    }
+    const uint32_t n = h->n;
+    const int A = (int)h->sizes.alpha_num;
+    const uint32_t table_size = (uint32_t)h->sizes.table_size;
+    std::vector<double> tsg(16 * n_ref), rows(8 * n_ref);
+    for (size_t s = 0; s < n_ref; ++s) {
+        ppf_frame(scene_points + 3 * (size_t)ref32[s], scene_normals + 3 * (size_t)ref32[s], &tsg[16 * s]);
+        frame_rows(&tsg[16 * s], &rows[8 * s]);
+    }
+    const bool lds = ppf_acc_in_lds(n, A) && g_ppf_force_device.load() == 0;
+    const size_t acc_words = ppf_acc_words(n, A);
+    // the workgroups: what the flag arrays (and, in device memory, the accumulators) leave of the call's scratch
+    size_t groups = std::min<size_t>(n_ref, kPpfMaxGroups);
+    groups = std::min(groups, std::max<size_t>(1, kPpfFlagBudget / (sizeof(unsigned long long) * table_size)));
+    const size_t per_group = sizeof(uint32_t) * ((lds ? 0 : acc_words) + n);
+    groups = std::min(groups, std::max<size_t>(1, kPpfAccBudget / per_group));
+    if (const int cap = g_ppf_max_groups.load(); cap > 0) groups = std::min<size_t>(groups, (size_t)cap);
+    S.path = lds ? M3D_PPF_PATH_LDS : M3D_PPF_PATH_DEVICE;
+    S.groups = (uint32_t)groups;
+
+    LaneLock lane(h->device);
+    DeviceCtx* ctx = lane.ctx;
+    if (!ctx) return M3D_ERR_DEVICE;
+    VoteBufs B;
+    std::vector<PpfMaximum> found;
+    const int rc = [&]() -> int {
+        HIPCHK(hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        HIPCHK(hipEventRecord(ctx->ev0, st));
+        const size_t fixed = sizeof(double) * (6 * m + 8 * n_ref) + sizeof(uint32_t) * n_ref;
+        size_t out_cap = std::max<size_t>(1024, 4 * n_ref);
+        if (fixed + groups * (sizeof(unsigned long long) * table_size + per_group) + sizeof(PpfMaximum) * out_cap > kPpfScratchCap)
+            return fail(M3D_ERR_INVALID_ARG, "ppf: the scene and its reference points do not fit the call's 256 MiB of scratch");
+        RESERVE(B.spts, sizeof(double) * 3 * m);
+        RESERVE(B.snrm, sizeof(double) * 3 * m);
+        RESERVE(B.ref, sizeof(uint32_t) * n_ref);
+        RESERVE(B.sframes, sizeof(double) * 8 * n_ref);
+        RESERVE(B.flags, sizeof(unsigned long long) * table_size * groups);
+        if (!lds) RESERVE(B.acc, sizeof(uint32_t) * acc_words * groups);
+        RESERVE(B.rowinfo, sizeof(uint32_t) * (size_t)n * groups);
+        RESERVE(B.small, 64);
+        HIPCHK(hipMemcpyAsync(B.spts.p, scene_points, sizeof(double) * 3 * m, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(B.snrm.p, scene_normals, sizeof(double) * 3 * m, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(B.ref.p, ref32.data(), sizeof(uint32_t) * n_ref, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(B.sframes.p, rows.data(), sizeof(double) * 8 * n_ref, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(B.flags.p, 0, sizeof(unsigned long long) * table_size * groups, st));
+        PpfVoteArgs a;
+        a.M = h->view();
+        a.spts = B.spts.as<double>();
+        a.snrm = B.snrm.as<double>();
+        a.m = (uint32_t)m;
+        a.n_ref = (uint32_t)n_ref;
+        a.ref = B.ref.as<uint32_t>();
+        a.sframes = B.sframes.as<double>();
+        a.r2 = h->r_min * h->r_min;
+        a.dist_thresh = h->min_dist_thresh * h->r_min;
+        a.cos_thresh = std::cos(h->min_angle_thresh);
+        a.gate = (uint32_t)(size_t)((double)n * 0.2);
+        a.acc_words = (uint32_t)acc_words;
+        a.flags = B.flags.as<unsigned long long>();
+        a.acc = lds ? nullptr : B.acc.as<uint32_t>();
+        a.rowinfo = B.rowinfo.as<uint32_t>();
+        a.out_count = B.small.as<uint32_t>();
+        a.counters = reinterpret_cast<unsigned long long*>(B.small.as<char>() + 8);
+        uint64_t head[3] = {0, 0, 0};   // out_count (+ padding), neighbours visited, increments
+        for (int attempt = 0; attempt < 2; ++attempt) {
+            RESERVE(B.out, sizeof(PpfMaximum) * out_cap);
+            a.out = B.out.as<PpfMaximum>();
+            a.out_cap = (uint32_t)out_cap;
+            HIPCHK(hipMemsetAsync(B.small.p, 0, 24, st));
+            HIPCHK(launch_ppf_vote(a, (uint32_t)groups, lds, st));
+            S.launches += 1;
+            HIPCHK(hipMemcpyAsync(head, B.small.p, 24, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            const size_t count = (uint32_t)head[0];
+            if (count <= out_cap) {
+                found.resize(count);
+                if (count) HIPCHK(hipMemcpy(found.data(), B.out.p, sizeof(PpfMaximum) * count, hipMemcpyDeviceToHost));
+                break;
+            }
+            if (attempt == 1) return fail(M3D_ERR_INTERNAL, "ppf: the second vote found more maxima than the first (self-check)");
+            out_cap = count;   // (a maximum is a model row of a reference position: the second run finds the same ones)
+        }
+        S.neighbours_visited = head[1];
+        S.increments = head[2];
+        HIPCHK(hipEventRecord(ctx->ev1, st));
+        HIPCHK(hipEventSynchronize(ctx->ev1));
+        float ms = 0.0f;
+        HIPCHK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        S.ms_device = ms;
+        return M3D_OK;
+    }();
+    (void)hipStreamSynchronize(ctx->stream);
+    B.release();
+    if (rc != M3D_OK) return rc;
+    // rule V8: ascending (reference position, model index) -- every pair occurs once
+    std::sort(found.begin(), found.end(), [](const PpfMaximum& x, const PpfMaximum& y) {
+        return x.ref_pos != y.ref_pos ? x.ref_pos < y.ref_pos : x.model_index < y.model_index;
+    });
+    for (const PpfMaximum& x : found)
+        if (x.ref_pos >= n_ref || x.model_index >= n || x.alpha_index >= (uint32_t)A)
+            return fail(M3D_ERR_INTERNAL, "ppf: a maximum is out of range (self-check)");
+    *n_maxima = found.size();
+    S.ms_total = now_ms() - t0;
+    if (stats) *stats = S;
+    if (found.size() > capacity)
+        return fail(M3D_ERR_CAPACITY, "ppf: " + std::to_string(found.size()) + " maxima, the result arrays hold " + std::to_string(capacity));
+    for (size_t k = 0; k < found.size(); ++k) {
+        ref_pos[k] = found[k].ref_pos;
+        model_index[k] = found[k].model_index;
+        alpha_index[k] = found[k].alpha_index;
+        votes[k] = found[k].votes;
+        if (poses)
+            ppf_pose(&tsg[16 * (size_t)found[k].ref_pos], (double)found[k].alpha_index * h->angle_step,
+                     &h->tmg[16 * (size_t)found[k].model_index], poses + 16 * k);
+    }
+    return M3D_OK;
+}
+
+// measurement / test hook (include/misc3d_amd_bench.h)
+int m3d_bench_ppf_force(int device_memory_path, int max_groups) {
+    if (max_groups < 0) return fail(M3D_ERR_INVALID_ARG, "ppf: max_groups must be >= 0");
+    g_ppf_force_device.store(device_memory_path != 0);
+    g_ppf_max_groups.store(max_groups);
+    return M3D_OK;
+}
+
+}  // extern "C"

@@ -15,6 +15,7 @@ bench.py); these lines feed DESIGN.md section 6 and check that the full sizes ru
      point-to-point and coloured)
   R1 - R3 RayCastRenderer: the reference example (640 x 480, obj.ply at its two poses), 1920 x 1080 with 64 instances, and a
           100-frame batch of the example
+  PV1 PPFVoting: the table of a 2 000-point model and the vote of a 20 000-point scene at ratio 0.6, LDS / device memory A/B
 """
 import json
 import os
@@ -987,3 +988,56 @@ if any(t in which for t in ("R1", "R2", "R3")) or ALL:
             b[1, 3] -= 0.001 * f
             frames.append([a, b])
         ray_line("R3", "ray cast, a 100-frame batch of the reference example (one call)", [mesh, mesh], frames, ex_cam, reps=7)
+
+if "PV1" in which or ALL:
+    # pose_estimation.PPFVoting ("PPF voting") through the C ABI: the table of a 2 000-point model (box
+    # family of the PPF tests) and the vote of a 20 000-point scene -- the posed model in 18 000 points of clutter -- at ratio 0.6:
+    # 12 000 reference points.  Median of 5 calls after 1 warm-up; the vote once more with its accumulators forced into device
+    # memory (the A/B of the LDS path).  cpu_baseline = the contract's C restatement (tests/cpp/ppf_ref.c) under OpenMP on 16
+    # threads: the table whole, the vote on every tenth reference point, scaled.
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ppf_ref_util as ppf_util
+
+    pts, nrm, diameter, r_min = ppf_util.model_case("box", 2000)
+    sp, sn, _ = ppf_util.scene_of(pts, nrm, ppf_util.pose(1), 18_000, 1)
+    refs = np.sort(np.random.default_rng(1).permutation(len(sp))[: int(0.6 * len(sp))])
+
+    def ppf_median(fn, reps=5):
+        fn()
+        runs = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            r = fn()
+            runs.append(((time.perf_counter() - t0) * 1e3, r))
+        runs.sort(key=lambda t: t[0])
+        return runs[len(runs) // 2]
+
+    ms_table, model = ppf_median(lambda: capi.PpfModel(pts, nrm, diameter, r_min))
+    ms_vote, (res, st) = ppf_median(lambda: model.vote(sp, sn, refs, stats=True))
+    capi.ppf_force(True, 0)
+    try:
+        ms_vote_dev, (res_dev, st_dev) = ppf_median(lambda: model.vote(sp, sn, refs, stats=True))
+    finally:
+        capi.ppf_force(False, 0)
+    cpu_b = None
+    if not NO_CPU:
+        os.environ.setdefault("OMP_NUM_THREADS", "16")
+        ref = ppf_util.PpfRef(tempfile.mkdtemp(), openmp=True)
+        t0 = time.perf_counter()
+        rm = ref.model(pts, nrm, diameter, r_min)
+        t1 = time.perf_counter()
+        rv = rm.vote(sp, sn, refs[::10])
+        t2 = time.perf_counter()
+        cpu_b = {"ms_table": (t1 - t0) * 1e3, "ms_vote": (t2 - t1) * 1e3 * len(refs) / len(refs[::10]), "unit": "ms",
+                 "vote_sampled": "every 10th reference point, scaled by the count", "increments_sampled": rv["increments"],
+                 "what": "tests/cpp/ppf_ref.c: the contract's restatement, gcc -O2 -ffp-contract=off -fopenmp, 16 threads"}
+    emit("PV1 ppf table 2 000 points + vote 20 000-point scene, 12 000 reference points", n=len(pts), m=len(sp), n_ref=len(refs),
+         ms_table=ms_table, ms_vote=ms_vote, ms_vote_device=st["ms_device"], path=st["path"], groups=st["groups"],
+         launches=st["launches"], neighbours_visited=st["neighbours_visited"], increments=st["increments"], maxima=len(res["votes"]),
+         increments_per_second=st["increments"] / (st["ms_device"] * 1e-3),
+         device_memory_path={"ms_vote": ms_vote_dev, "ms_vote_device": st_dev["ms_device"], "path": st_dev["path"],
+                             "same_result": bool(all(np.array_equal(res[k], res_dev[k]) for k in res))},
+         roofline={"bound": "atomic increments (LDS or L2) and the divergent walk over table cells; no HBM or VALU ceiling is meaningful",
+                   "share_of_peak": "not measured"},
+         cpu_baseline=cpu_b)
