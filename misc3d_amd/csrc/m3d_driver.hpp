@@ -94,17 +94,21 @@ struct ChunkSlot {
                         // tests can run (DeviceCtx::pre_stream) while this chunk is being scored
     hipEvent_t pre_done = nullptr;   // MinimalFit + box tests of the chunk finished on pre_stream
     PinBuf h_samples, h_counts, h_valid;
-    bool lead_fused = false;   // the chunk's lead pass ran inside cull_lead_k (no launch, no timing events of its own)
     hipEvent_t done = nullptr;
     hipEvent_t k0 = nullptr, k1 = nullptr;  // around the scoring kernel of the chunk (m3d_stats.ms_score_kernel)
-    hipEvent_t k2 = nullptr, k3 = nullptr;  // around the scoring launch of the chunk's leading hypotheses (lead_groups > 0)
-    uint32_t lead_groups = 0;
-    bool host_has_records = true;   // sharded: the gathered records are (being) written to h_counts
-    bool done_on_copy_stream = false;   // sharded RCCL windows: `done` follows the record copy on the copy stream
-    bool scored = false;   // a scoring launch was issued for the chunk (k0 / k1 recorded)
-    uint32_t poll_seq = 0;   // != 0: no `done` event; completion = BestPickHost::seq reaching this value (PickFinal)
-    size_t begin = 0, end = 0;
-    uint32_t h_pad = 0;
+    hipEvent_t k2 = nullptr, k3 = nullptr;  // around the scoring launch of the chunk's leading hypotheses (Issued::lead_groups > 0)
+    // What became of the chunk last issued on the slot: reset as a whole by issue_chunk, filled in by its stages
+    struct Issued {
+        size_t begin = 0, end = 0;
+        uint32_t h_pad = 0;
+        bool cull32 = false;   // the chunk's box tests ran in fp32: their records are in the slot's cull32
+        uint32_t lead_groups = 0;
+        bool lead_fused = false;   // the chunk's lead pass ran inside cull_lead_k (no launch, no timing events of its own)
+        bool scored = false;   // a scoring launch was issued for the chunk (k0 / k1 recorded)
+        uint32_t poll_seq = 0;   // != 0: no `done` event; completion = BestPickHost::seq reaching this value (PickFinal)
+        bool host_has_records = true;   // sharded: the gathered records are (being) written to h_counts
+        bool done_on_copy_stream = false;   // sharded RCCL windows: `done` follows the record copy on the copy stream
+    } issued;
 };
 
 // One LANE of a device: a compute stream with everything a call needs beside its arguments (streams, events, scratch,

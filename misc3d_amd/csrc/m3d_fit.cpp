@@ -18,6 +18,7 @@
 // in point order, only when such a tie occurs (exact_error()).
 //
 // There is no CPU fallback: every entry point needs a HIP device.
+#include "m3d_chunk_plan.hpp"
 #include "m3d_driver_internal.hpp"
 #include "m3d_generalfit_fp.hpp"
 
@@ -207,23 +208,7 @@ static size_t chunk_cap_for(const CloudView& v, const SortedView& sv, size_t tim
     return std::max<size_t>(cap, 64);
 }
 
-// Where the planes' histogram bound is worth its launch: plane_bound_k costs 12-25 us per window whatever it prunes, and it halves
-// a scoring launch -- worth it when that launch is long.  Measured on C2-shaped clouds, resident, ms per fit without / with:
-//   points x hypotheses   50 k x 3000 0.103 / 0.135   150 k x 10 000 0.166 / 0.178   150 k x 40 000 0.325 / 0.377   400 k x 10 000 0.176 / 0.175
-//   400 k x 40 000 0.413 / 0.386   1 M x 3000 0.207 / 0.213   1 M x 10 000 0.300 / 0.274   1 M x 40 000 0.654 / 0.606
-//   4 M x 3000 0.530 / 0.569   4 M x 10 000 0.864 / 0.809   4 M x 40 000 1.876 / 1.671
-// i.e. windows of 8192 hypotheses and more on tiles x hypotheses >= 1.5e7.
-static bool bound_pays(uint32_t n_tiles, size_t window_hypotheses) {
-    return window_hypotheses >= 8192 && (double)n_tiles * (double)window_hypotheses >= 1.5e7;
-}
-// m3d_config.plane_bound as a fit of `kind` sees it: forcing the reference histograms (ref_bound = 2, the tests' switch) forces the
-// launch they live in
-static int bound_mode(int kind) {
-    const int mode = config().plane_bound;
-    return (mode != 0 && kind == M3D_PLANE && config().ref_bound == 2) ? 2 : mode;
-}
-
-// pre_stream runs the head of a fit's later chunks (issue_chunk, `pre`) beside the main stream: whatever the main stream holds
+// pre_stream runs the head of a fit's later chunks (ChunkPlan::head) beside the main stream: whatever the main stream holds
 // when the fit starts -- a removal's compaction of this very cloud, another fit's tail -- must be behind those kernels too.
 static bool prestream_enabled() { return config().prestream != 0; }   // (0: everything on the main stream)
 static int pre_stream_gate(DeviceCtx* ctx) {
@@ -255,306 +240,337 @@ static uint32_t* bound_list(DeviceCtx* ctx) { return ctx->surv_list.as<uint32_t>
 // hypotheses, for the pruning incumbent; their owner is rank 0).  The slices' records are then all-gathered in place
 // in s.counts, so that everything after it (pick_best_k, the replay, the tie rule reading s.params) sees the whole
 // chunk exactly as the one-GPU path does.
-static int issue_chunk(DeviceCtx* ctx, ChunkSlot& s, const CloudView& v, const SortedView& sv, int kind,
-                       double thr, size_t begin, size_t end, SampleSource& src, double* ms_sample,
-                       bool prune = false, uint32_t lead = 0, bool new_fit = false /* clears the running best count */,
-                       bool device_records = false /* culled path: keep a device copy of the records in s.counts */,
-                       m3d_comm* comm = nullptr,
-                       bool caller_ships_records = false /* the caller queues pick_best_k behind the chunk and records s.done
-                                                            behind THAT (an event between two kernels costs a ~5 us
-                                                            gap on this stream; behind pick_best_k nothing follows at once) */,
-                       const PickFinal* pick_final = nullptr /* one GPU: the chunk's last kernel takes pick_best_k's decision
-                                                                and stores the completion word the host polls (no event) */,
-                       bool nothing_to_prune = false /* the fit's ONLY chunk, issued without a lead pass: no incumbent will
-                                                        ever exist while it runs */,
-                       bool pre = false /* a later chunk of a one-GPU fit: MinimalFit and the box tests go to ctx->pre_stream and
-                                           run under the scoring launches of the chunk before (the main stream waits for
-                                           s.pre_done in front of the keep masks) */,
-                       const double* move_best_from = nullptr /* the fit's best minimal model lives in THIS slot's params, which
-                                                                 the chunk is about to overwrite: moved to ctx->best_params
-                                                                 first, on the stream MinimalFit will run on */,
-                       bool first_of_stream = false /* m3d_cloud_score_shard, one rank, from hypothesis 0: a fit's first chunk in all
-                                                       but the incumbent's clearing (the caller's): reference histograms as for new_fit */,
-                       SegmentRounds* rounds = nullptr /* a segmentation's fit: the previous round's tombstone pass may be waiting
-                                                          to ride in this chunk's minimal_fit_k launch */) {
-    const bool kill_rides = rounds && rounds->poison_pending && kind == M3D_PLANE;
-    const int m = minimal_sample(kind);
-    const uint32_t count = (uint32_t)(end - begin);
-    const bool dense = use_dense_scoring();
-    // where the chunk's head runs -- decided ONCE, here, in front of everything that depends on it (the record
-    // move used to repeat a part of this condition in the caller)
-    pre = pre && !dense && prune && !new_fit && !comm && lead == 0 && !(rounds && rounds->poison_pending) && ctx->pre_stream && s.pre_done;
-    hipStream_t st_pre = pre ? ctx->pre_stream : ctx->stream;
-    if (move_best_from)   // (before the slot's buffers are touched: a RESERVE below may hand the old block back)
-        HIPCHK(hipMemcpyAsync(ctx->best_params.p, move_best_from, sizeof(double) * kModelStride, hipMemcpyDeviceToDevice, st_pre));
-    const bool timing = config().kernel_timing != 0;
-    if (comm && dense) return fail(M3D_ERR_INVALID_ARG, "sharded fits use the culled scoring path (m3d_config.dense_scoring = 0)");
-    const uint32_t world = comm ? (uint32_t)comm->world : 1u, rank = comm ? (uint32_t)comm->rank : 0u;
-    const uint32_t sl_pad = round_up((count + world - 1) / world, 64);   // hypotheses per rank
-    const uint32_t h_pad = comm ? sl_pad * world : round_up(count, 64);
-    const uint32_t n_tiles = v.n_pad / kScoreTile;
-    if (comm) device_records = true;
-    s.begin = begin;
-    s.end = end;
-    s.h_pad = h_pad;
-    RESERVE(s.samples, sizeof(uint32_t) * (size_t)count * m);
-    RESERVE(s.score, sizeof(double) * kModelStride * ((size_t)h_pad + 1));
-    RESERVE(s.params, sizeof(double) * kModelStride * ((size_t)h_pad + 1));
-    RESERVE(s.valid, (size_t)h_pad + 1);
-    Cull32Out c32;
-    const bool cull32 = !dense && config().cull_fp32 != 0 && sv.radius < 1e18;
-    if (cull32) {
-        RESERVE(s.cull32, sizeof(float) * 24 * ((size_t)h_pad / 2 + 1));
-        c32.out = s.cull32.as<float>();
-        for (int k = 0; k < 3; ++k) c32.origin[k] = sv.origin[k];
-        c32.radius = sv.radius;
+//
+// issue_chunk in three pieces: the caller's ChunkRequest, the ChunkPlan that plan_chunk (m3d_chunk_plan.hpp) makes of it and of the
+// ChunkFacts read here, and the stages below, which reserve and launch what the plan says, in this order, and decide nothing
+// but what a launch helper tells them at run time.
+static_assert(kPlanScoreTile == (uint32_t)kScoreTile && kPlanPairReplicas == (uint32_t)kPairReplicas,
+              "m3d_chunk_plan.hpp restates these constants");
+
+static ChunkFacts chunk_facts(const DeviceCtx* ctx, const ChunkSlot& s, const CloudView& v, const SortedView& sv, int kind,
+                              const ChunkRequest& rq) {
+    const m3d_config& cfg = config();
+    ChunkFacts f;
+    f.kind = kind;
+    f.n_pad = v.n_pad;
+    f.n_tiles = sv.n_tiles;
+    f.radius = sv.radius;
+    f.has_dead = sv.has_dead;
+    f.has_frames = sv.frames != nullptr;
+    f.has_pre_stream = ctx->pre_stream != nullptr;
+    f.has_pre_done = s.pre_done != nullptr;
+    f.tombstones_pending = rq.rounds && rq.rounds->poison_pending;
+    if (rq.comm) {
+        f.has_comm = true;
+        f.world = (uint32_t)rq.comm->world;
+        f.rank = (uint32_t)rq.comm->rank;
+        f.rccl = rq.comm->transport == m3d_comm::kRccl;
     }
-    if (dense || device_records) RESERVE(s.counts, sizeof(uint32_t) * ((size_t)h_pad + 1));   // (culled path: records go straight to h_counts)
-    uint32_t* rec_dev = (!dense && device_records) ? s.counts.as<uint32_t>() : nullptr;
-    RESERVE(s.h_samples, sizeof(uint32_t) * (size_t)count * m);
-    RESERVE(s.h_counts, sizeof(uint32_t) * ((size_t)h_pad + 4));   // + the launch's pair counters behind the records
-    RESERVE(s.h_valid, (size_t)h_pad + 1);
-    if (dense) {
-        RESERVE(ctx->partial, sizeof(uint32_t) * (size_t)n_tiles * h_pad);
+    f.dense = use_dense_scoring();
+    f.cull_fp32 = cfg.cull_fp32;
+    f.plane_bound = cfg.plane_bound;
+    f.ref_bound = cfg.ref_bound;
+    f.kernel_timing = cfg.kernel_timing;
+    f.score_phases = score_phases_for(kind);
+    return f;
+}
+
+// The plan's buffers as addresses once the scratch is reserved (null: the plan does not use it), and what one stage of the
+// culled path hands a later one
+struct ChunkBuffers {
+    uint32_t* ub = nullptr;       // touched tiles per hypothesis: ub[h_pad], then the phase counters ubp[h_pad], then the cylinders' bound sums
+    uint32_t* ubp = nullptr;      // phased scoring: the touched tiles per phase
+    uint32_t* ubsum = nullptr;    // the histogram bound's sums
+    uint32_t* bc = nullptr;       // the device-side running maximum of the fit (prune)
+    uint32_t* counts_rep = nullptr;
+    uint32_t* pair_rep = nullptr;
+    uint32_t* h_pairs = nullptr;  // pinned, device-visible: the launch's pair counters behind the records
+    uint32_t* rec_host = nullptr;
+    uint32_t* rec_dev = nullptr;
+    unsigned long long* masks = nullptr;
+    unsigned long long* keep = nullptr;
+    Cull32Out c32;
+    uint32_t* surv_count = nullptr;   // bound_on: the kept hypotheses as a list (prepare_bound)
+    uint32_t* surv = nullptr;
+    RefHistArgs ref;                  // ref_on
+    unsigned long long* touched = nullptr;   // the box tests' per-hypothesis words, if launch_cull_mask wrote them
+    bool touched_written = false;
+};
+
+static hipStream_t head_stream(const DeviceCtx* ctx, const ChunkPlan& p) {
+    return p.head == HeadStream::kPre ? ctx->pre_stream : ctx->stream;
+}
+
+// 1. the slot's and the lane's scratch
+static int reserve_chunk_scratch(DeviceCtx* ctx, ChunkSlot& s, const ChunkPlan& p, const SortedView& sv, ChunkBuffers& b) {
+    const size_t h_pad = p.h_pad;
+    RESERVE(s.samples, sizeof(uint32_t) * (size_t)p.count * p.m);
+    RESERVE(s.score, sizeof(double) * kModelStride * (h_pad + 1));
+    RESERVE(s.params, sizeof(double) * kModelStride * (h_pad + 1));
+    RESERVE(s.valid, h_pad + 1);
+    if (p.cull32) {
+        RESERVE(s.cull32, sizeof(float) * 24 * (h_pad / 2 + 1));
+        b.c32.out = s.cull32.as<float>();
+        for (int k = 0; k < 3; ++k) b.c32.origin[k] = sv.origin[k];
+        b.c32.radius = sv.radius;
+    }
+    if (p.counts_reserved) RESERVE(s.counts, sizeof(uint32_t) * (h_pad + 1));
+    RESERVE(s.h_samples, sizeof(uint32_t) * (size_t)p.count * p.m);
+    RESERVE(s.h_counts, sizeof(uint32_t) * (h_pad + 4));   // + the launch's pair counters behind the records
+    RESERVE(s.h_valid, h_pad + 1);
+    if (p.dense) {
+        RESERVE(ctx->partial, sizeof(uint32_t) * (size_t)p.dense_tiles * h_pad);
     } else {
-        RESERVE(s.masks, sizeof(uint64_t) * (size_t)std::max<uint32_t>(sv.n_tiles, 1) * (h_pad / 64));
-        RESERVE(ctx->keep, sizeof(uint64_t) * (size_t)(h_pad / 64));
+        RESERVE(s.masks, sizeof(uint64_t) * (size_t)std::max<uint32_t>(sv.n_tiles, 1) * p.n_groups);
+        RESERVE(ctx->keep, sizeof(uint64_t) * (size_t)p.n_groups);
         RESERVE(ctx->counts_rep, sizeof(uint32_t) * ((size_t)kCountReplicas * h_pad + kPairReplicas));
     }
+    if (p.prune_scratch) {
+        RESERVE(s.ub, sizeof(uint32_t) * 3 * h_pad);
+        b.ub = s.ub.as<uint32_t>();
+    }
+    b.h_pairs = s.h_counts.as<uint32_t>() + h_pad;
+    if (p.dense) return M3D_OK;
+    if (p.phased) b.ubp = b.ub + h_pad;
+    if (p.bound_on) b.ubsum = b.ub + p.ubsum_at;
+    if (p.prune) b.bc = ctx->best_count.as<uint32_t>();
+    if (p.records_on_device) b.rec_dev = s.counts.as<uint32_t>();
+    b.counts_rep = ctx->counts_rep.as<uint32_t>();
+    b.pair_rep = b.counts_rep + (size_t)kCountReplicas * h_pad;
+    b.masks = s.masks.as<unsigned long long>();
+    b.keep = ctx->keep.as<unsigned long long>();
+    if (p.records_to_host) b.rec_host = s.h_counts.as<uint32_t>();
+    return M3D_OK;
+}
+
+// 2. the sample table and minimal_fit_k, with what rides in its launch: the clearing of the slot's counters and of a new fit's
+// incumbent, the lead pass' set-up (LeadPrep), the fp32 box-test records, a segmentation's pending tombstone pass
+static int issue_head(DeviceCtx* ctx, ChunkSlot& s, const ChunkPlan& p, const ChunkBuffers& b, const CloudView& v, const SortedView& sv,
+                      int kind, double thr, SampleSource& src, const ChunkRequest& rq) {
     const double t0 = now_ms();
-    src.fill(begin, end, s.h_samples.as<uint32_t>());
-    if (ms_sample) *ms_sample += now_ms() - t0;
-    // the sample table is read by minimal_fit_k straight from the slot's page-locked host array (device-visible): 12 bytes
-    // per hypothesis over the host link inside the kernel instead of a copy command in front of it
-    if (!dense && prune) RESERVE(s.ub, sizeof(uint32_t) * 3 * (size_t)h_pad);   // ub[h_pad], then the phase counters ubp[h_pad], then the cylinders' histogram bound sums
-    // (decided here because minimal_fit_k prepares the lead pass of a NEW fit itself: see LeadPrep)
-    const bool use_lead = !dense && prune && lead >= 64 && lead % 64 == 0 && lead + 64 <= count && (!comm || sl_pad >= lead + 64);
-    const bool own_real_ = !comm || (size_t)rank * sl_pad < count;
+    src.fill(rq.begin, rq.end, s.h_samples.as<uint32_t>());
+    if (rq.ms_sample) *rq.ms_sample += now_ms() - t0;
     LeadPrep lp;
-    const bool lead_prepared = use_lead && new_fit && own_real_ && lead <= h_pad && (uint32_t)kPairReplicas <= h_pad;
-    // no lead pass and nothing to prune against (a new fit's only chunk on one GPU, FitCaller::no_prune_hint): the same
-    // set-up for ALL groups -- keep everything, clear every counter replica -- and no keep_mask_k launch below
-    const bool all_prepared = nothing_to_prune && !use_lead && lead == 0 && !dense && prune && new_fit && !comm &&
-                              (uint32_t)kPairReplicas <= h_pad;
-    if (lead_prepared || all_prepared) {
+    if (p.lead_prepared || p.all_prepared) {
         lp.counts_rep = ctx->counts_rep.as<uint32_t>();
         lp.keep = ctx->keep.as<unsigned long long>();
-        lp.rep_stride = h_pad;
+        lp.rep_stride = p.h_pad;
         lp.n_rep = kCountReplicas;
-        lp.n_lead = all_prepared ? h_pad : lead;
+        lp.n_lead = p.all_prepared ? p.h_pad : rq.lead;
         lp.n_pair = kPairReplicas;
     }
+    // the sample table is read by minimal_fit_k straight from the slot's page-locked host array (device-visible): 12 bytes
+    // per hypothesis over the host link inside the kernel instead of a copy command in front of it
     const bool fit_launched =
-        launch_minimal_fit(kind, v, s.h_samples.as<uint32_t>(), count, h_pad + 1, thr, s.score.as<double>(),
-                       s.params.as<double>(), s.valid.as<uint8_t>(), st_pre,
-                       (!dense && prune) ? s.ub.as<uint32_t>() : nullptr,    // clears ub[0 .. h_pad) on the way
-                       new_fit ? ctx->best_count.as<uint32_t>() : nullptr, (lead_prepared || all_prepared) ? &lp : nullptr, sv.max_abs,
-                       cull32 ? &c32 : nullptr, kill_rides ? &rounds->pending_poison : nullptr,
-                       (!dense && prune) ? s.ub.as<uint32_t>() + h_pad : nullptr);
-    if (fit_launched && kill_rides) {   // (the previous round's tombstone pass went with it)
-        rounds->poison_pending = false;
-        if (rounds->poison_expected_at) *rounds->poison_expected_at += rounds->poison_pending_count;
+        launch_minimal_fit(kind, v, s.h_samples.as<uint32_t>(), p.count, p.h_pad + 1, thr, s.score.as<double>(),
+                           s.params.as<double>(), s.valid.as<uint8_t>(), head_stream(ctx, p),
+                           b.ub,    // clears ub[0 .. h_pad) on the way
+                           rq.new_fit ? ctx->best_count.as<uint32_t>() : nullptr, (p.lead_prepared || p.all_prepared) ? &lp : nullptr,
+                           sv.max_abs, p.cull32 ? &b.c32 : nullptr, p.tombstones_ride ? &rq.rounds->pending_poison : nullptr,
+                           b.ub ? b.ub + p.h_pad : nullptr);
+    if (fit_launched && p.tombstones_ride) {   // (the previous round's tombstone pass went with it)
+        rq.rounds->poison_pending = false;
+        if (rq.rounds->poison_expected_at) *rq.rounds->poison_expected_at += rq.rounds->poison_pending_count;
     }
-    if (dense)
-        HIPCHK(hipMemsetAsync(s.counts.p, 0, sizeof(uint32_t) * (size_t)h_pad, ctx->stream));
-    // (culled path: keep_mask_k clears the counter replicas on its way)
-    s.lead_groups = 0;
-    s.lead_fused = false;
-    s.scored = false;
-    s.poll_seq = 0;
-    s.host_has_records = true;
-    s.done_on_copy_stream = false;
-    uint32_t* h_pairs = s.h_counts.as<uint32_t>() + h_pad;   // pinned, device-visible
-    if (dense) {
-        HIPCHK(hipEventRecord(s.k0, ctx->stream));
-        launch_score(kind, v, s.score.as<double>(), h_pad, pick_splits(n_tiles, h_pad),
-                     ctx->partial.as<uint32_t>(), ctx->stream);
-        HIPCHK(hipEventRecord(s.k1, ctx->stream));
-        launch_reduce_partials(ctx->partial.as<uint32_t>(), n_tiles, h_pad, s.counts.as<uint32_t>(),
-                               ctx->stream);
-        s.scored = true;
-    } else {
-        // prune (fits only): hypotheses that cannot reach the best count of EARLIER hypotheses are masked
-        // out (keep_mask_k); ctx->best_count is the device-side running maximum of the fit
-        const uint32_t n_groups = h_pad / 64;
-        // this rank's groups [g0, g1) of the chunk
-        const uint32_t g0 = comm ? rank * (sl_pad / 64) : 0u, g1 = comm ? g0 + sl_pad / 64 : n_groups;
-        const bool own_real = (size_t)g0 * 64 < count;   // (a short last window can leave the highest ranks without work)
-        uint32_t* ub = prune ? s.ub.as<uint32_t>() : nullptr;
-        // phased scoring (launch_score_phased): an incumbent exists, the fp32 box tests run (they count the touched tiles per
-        // phase), no tombstones
-        uint32_t* ubp = (prune && (use_lead || !new_fit) && c32.out && !sv.has_dead && score_phases_for(kind) != 0) ? ub + h_pad : nullptr;   // (an incumbent exists: this chunk's lead pass, or earlier chunks / windows -- sharded fits included: every rank prunes its slice against the same incumbent)
-        auto* masks = s.masks.as<unsigned long long>();
-        auto* keep = ctx->keep.as<unsigned long long>();
-        uint32_t* pair_rep = ctx->counts_rep.as<uint32_t>() + (size_t)kCountReplicas * h_pad;
-        uint32_t* bc = prune ? ctx->best_count.as<uint32_t>() : nullptr;
-        // sharded: the host gets the GATHERED records -- unless the communicator has ONE rank: its slice is the window, the
-        // gather the identity, and the records go to the host the way the one-GPU path sends them (written by the folding
-        // kernels themselves: no copy command, no detour over the copy stream)
-        const bool solo = comm && comm->world == 1 && comm->transport == m3d_comm::kRccl;   // (a caller-supplied all-gather is always called)
-        uint32_t* rec_host = (comm && !solo) ? nullptr : s.h_counts.as<uint32_t>();
-        PickFinal pfin;
-        if (pick_final) {
-            pfin = *pick_final;
-            pfin.params = s.params.as<double>();
-        }
-        // lead > 0 (a fit's first chunk): the first `lead` hypotheses are counted on their own, and their best
-        // count then prunes the rest of the SAME chunk -- what a separate small first chunk did, without its
-        // own sample copy, MinimalFit and box-test launches.  The records are complete after the second pass.
-        const uint32_t ga = use_lead ? lead / 64 : 0u;
-        if (own_real) {
-            // fp32 box tests and fp32 screen on: the box tests of the chunk (this rank's slice) and the counting of its leading groups
-            // share ONE launch (cull_lead_k; the lead pass runs its own box tests) -- two latency-bound launches less the
-            // time of one.  It is not among the timed scoring launches (s.lead_fused: m3d_stats.pairs_timed).
-            s.lead_fused = false;
-            if (ga && g0 == 0 && c32.out) {   // (sharded fits: the rank that owns the leading groups)
-                if (!lead_prepared)   // (a new fit: minimal_fit_k has done it)
-                    launch_keep_mask(ub, bc, ga, keep, ctx->stream, ctx->counts_rep.as<uint32_t>(), h_pad, 0);
-                s.lead_fused = launch_cull_lead(kind, sv, s.score.as<double>(), c32.out, masks, keep, n_groups, ga,
-                                                ctx->counts_rep.as<uint32_t>(), h_pad, pair_rep, ub, g1, ctx->stream, ubp);
-            }
-            // (Tried and removed: the chunk's box tests inside the scoring launch, and all of a tile's groups in one scoring
-            //  workgroup -- both slower on C5's clutter rounds, profiles/r06_c5_tail_rounds.txt.)
-            // planes with an incumbent and tile frames: a histogram upper bound per touched (tile, hypothesis) pair replaces
-            // "512 per touched tile" in the keep rule (m3d_bound.hip).  The keep kernels below hand plane_bound_k the kept
-            // hypotheses as a list (its length: word 6 of best_count); ubsum is the slot's phase-counter array, zeroed by
-            // minimal_fit_k and unused when the scoring is not phased.
-            // Spheres and cylinders (round 5): the same bound with the shell taken as a slab per tile (cyl_pair_ub); cylinders in front of
-            // the phased scoring -- whose phase counters sit where the bound sums go otherwise, so theirs get the block behind them.
-            // (Spheres: C3's fit loses a third of its (tile, hypothesis) pairs and gains nothing -- 0.77 ms with and without, the bound's
-            // launch costs what it saves; theirs runs when the bound is forced, m3d_config.plane_bound = 2, i.e. in the tests.)
-            const bool bound_on = (kind == M3D_CYLINDER || !ubp) && prune && bc && sv.frames && bound_mode(kind) != 0 &&
-                                  (bound_mode(kind) == 2 || (kind != M3D_SPHERE && bound_pays(sv.n_tiles, comm ? sl_pad : count))) &&
-                                  (use_lead || !new_fit) && std::max(g0, ga) < g1;
-            // planes, the first chunk of a one-GPU fit with a lead pass, no tombstones: a second histogram per tile, along the lead's
-            // best plane (m3d_ref_hist.hpp) -- written by extra workgroups of the lead_fold_keep_k launch, read by plane_bound_k
-            const bool ref_on = bound_on && kind == M3D_PLANE && !ubp && !comm && (new_fit || first_of_stream) && use_lead && ga && g0 == 0 && !sv.has_dead &&
-                                config().ref_bound != 0 && (config().ref_bound == 2 || bound_pays(sv.n_tiles, count));
-            RefHistArgs ref;
-            if (ref_on) {
-                RESERVE(ctx->ref_hist, ref_hist_bytes(sv.n_tiles));
-                ref.sx = sv.x; ref.sy = sv.y; ref.sz = sv.z;
-                ref.n_tiles = sv.n_tiles;
-                ref.score = s.score.as<double>();
-                ref.counts_rep = ctx->counts_rep.as<uint32_t>();
-                ref.rep_stride = h_pad;
-                ref.lead = lead;
-                ref.valid = s.valid.as<uint8_t>();
-                ref.h_count = count;
-                ref.max_abs = sv.max_abs;
-                // uniform clutter gains nothing and must not pay for the pass: no histograms unless the lead's best plane holds 8
-                // points per tile, 1 / 64 of the cloud (1 M x 10 000 clutter: the best plane holds 1 / 141; measured in
-                // profiles/r09_ref_bound.txt); forced: any count
-                ref.min_count = config().ref_bound == 2 ? 1u : 8u * sv.n_tiles;
-                ref_hist_place(ref, ctx->ref_hist.p);
-            }
-            uint32_t* const ubsum = ubp ? ub + 2 * (size_t)h_pad : ub + h_pad;
-            if (bound_on) {
-                const int src = reserve_survivor_scratch(ctx, h_pad);
-                if (src != M3D_OK) return src;
-                if (ubp) HIPCHK(hipMemsetAsync(ubsum, 0, sizeof(uint32_t) * h_pad, ctx->stream));   // (the block behind ub is cleared by minimal_fit_k)
-            }
-            uint32_t* const surv_count = bound_on ? bc + 6 : nullptr;
-            uint32_t* const surv = bound_on ? bound_list(ctx) : nullptr;
-            // cylinders in front of the bound: the box tests also leave a word per hypothesis and 64 tiles (cull_hyp32_k), which
-            // plane_bound_k reads instead of repeating the tests
-            unsigned long long* touched = nullptr;
-            bool touched_written = false;
-            if (bound_on && kind == M3D_CYLINDER && c32.out && !s.lead_fused && !(ga && g0 >= ga) && g1 - g0 >= 128u) {
-                RESERVE(s.touched, sizeof(uint64_t) * (size_t)((sv.n_tiles + 63u) / 64u) * h_pad);
-                touched = s.touched.as<unsigned long long>();
-            }
-            if (!s.lead_fused) {
-                if (ga && g0 >= ga)   // (rank > 0: the lead is somebody else's slice)
-                    launch_cull_mask(kind, sv, s.score.as<double>(), s.valid.as<uint8_t>(), count, n_groups, masks, ub,
-                                     ctx->stream, /*ub_is_zero=*/true, 0, ga, c32.out);
-                launch_cull_mask(kind, sv, s.score.as<double>(), s.valid.as<uint8_t>(), count, n_groups, masks, ub, st_pre,
-                                 /*ub_is_zero=*/true, g0, g1, c32.out, ubp, touched, h_pad, &touched_written);
-            }
-            if (pre) {   // everything below needs the records, the masks and ub: the main stream picks up here
-                HIPCHK(hipEventRecord(s.pre_done, ctx->pre_stream));
-                HIPCHK(hipStreamWaitEvent(ctx->stream, s.pre_done, 0));
-            }
-            uint32_t g_lo = g0;
-            if (ga) {
-                s.lead_groups = ga;
-                g_lo = std::max(g0, ga);
-                if (!s.lead_fused) {
-                    if (!lead_prepared)   // (a new fit: minimal_fit_k has done it)
-                        launch_keep_mask(ub, bc, ga, keep, ctx->stream, ctx->counts_rep.as<uint32_t>(), h_pad, 0);
-                    launch_score_mask(kind, sv, s.score.as<double>(), masks, keep, n_groups, ctx->counts_rep.as<uint32_t>(),
-                                      h_pad, pair_rep, ctx->stream, 0, ga, timing ? s.k2 : nullptr, timing ? s.k3 : nullptr);
-                }
-                // fold of the lead's counters + keep masks of the rest of this rank's groups: one launch
-                launch_lead_fold_keep(ctx->counts_rep.as<uint32_t>(), h_pad, lead, s.valid.as<uint8_t>(), count,
-                                      g0 == 0 ? rec_host : nullptr, bc, ub, keep, g1 - g_lo, ctx->stream,
-                                      g0 == 0 ? rec_dev : nullptr, g_lo, pick_final ? pick_final->key : nullptr,
-                                      pick_final ? pick_final->key2 : nullptr, surv_count, surv, ref_on ? &ref : nullptr);
-            } else if (!all_prepared) {   // (all_prepared: minimal_fit_k has done it)
-                launch_keep_mask(ub, bc, g1 - g0, keep, ctx->stream, ctx->counts_rep.as<uint32_t>(), h_pad, g0, surv_count, surv);
-            }
-            if (bound_on)
-                launch_plane_bound(kind, sv, s.score.as<double>(), masks, keep, n_groups, g_lo, g1, ubsum, bc, surv_count, surv,
-                                   bound_tickets(ctx), c32.out, ctx->stream, bound_mode(kind) == 2,
-                                   touched_written && g_lo == g0 ? touched : nullptr, h_pad, ref_on ? &ref : nullptr);
-            bool phased = false;
-            if (ubp)
-                phased = launch_score_phased(kind, sv, s.score.as<double>(), masks, keep, n_groups, ctx->counts_rep.as<uint32_t>(), h_pad,
-                                             pair_rep, ub, ubp, bc, ctx->stream, g_lo, g1, timing ? s.k0 : nullptr, timing ? s.k1 : nullptr);
-            if (!phased)
-                launch_score_mask(kind, sv, s.score.as<double>(), masks, keep, n_groups, ctx->counts_rep.as<uint32_t>(), h_pad,
-                                  pair_rep, ctx->stream, g_lo, g1, timing ? s.k0 : nullptr, timing ? s.k1 : nullptr, bound_on);
-            // one launch: fold the counter replicas, tag MinimalFit's return into bit 31, update the incumbent
-            // ... and (one GPU) write the records straight into the slot's pinned host array (device-visible): no copy
-            // command behind the kernel (a 39 KB D2H copy started ~20 us after the kernel that fed it)
-            launch_sum_replicas(ctx->counts_rep.as<uint32_t>(), h_pad, g1 * 64u, rec_host, pair_rep, h_pairs,
-                                s.valid.as<uint8_t>(), count, bc, ctx->stream, g_lo * 64u, rec_dev, pick_final ? &pfin : nullptr,
-                                phased ? keep : nullptr);
-            if (pick_final) s.poll_seq = pick_final->seq;
-            s.scored = timing;
-        } else {
-            HIPCHK(hipMemsetAsync(rec_dev + (size_t)g0 * 64, 0, sizeof(uint32_t) * sl_pad, ctx->stream));
-            h_pairs[0] = h_pairs[1] = h_pairs[2] = 0;
-        }
-        if (solo) {
-            comm->collectives++;   // (the window's exchange, degenerate)
-            s.host_has_records = true;
-        } else if (comm) {
-            // the one exchange of the window: every rank's slice of records, in place (RCCL: ncclAllGather on this
-            // stream, nothing on the host; host transports wait for the stream and leave the records in h_counts)
-            int host_has_all = 0;
-            const int rc = comm->allgather_u32_device(rec_dev, sl_pad, ctx->stream, s.h_counts.as<uint32_t>(), &host_has_all);
-            if (rc != M3D_OK) return rc;
-            s.host_has_records = host_has_all != 0;
-            if (!host_has_all && caller_ships_records) {
-                // the gathered window (world x slice records: hundreds of KB at 8 ranks) goes to the host through the copy
-                // engine, on the copy stream, while pick_best_k and the early compaction run on the main stream; s.done
-                // then sits on the copy stream.  (pick_best_k's one workgroup would need 40 us for 80 000 records.)
-                HIPCHK(hipEventRecord(ctx->ev_compact, ctx->stream));
-                HIPCHK(hipStreamWaitEvent(copy_stream_of(ctx), ctx->ev_compact, 0));
-                HIPCHK(hipMemcpyAsync(s.h_counts.p, rec_dev, sizeof(uint32_t) * (size_t)count, hipMemcpyDeviceToHost,
-                                      copy_stream_of(ctx)));
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipEventRecord(s.done, copy_stream_of(ctx)));
-                s.host_has_records = true;
-                s.done_on_copy_stream = true;
-                return M3D_OK;
-            }
-            if (!host_has_all && !caller_ships_records) {
-                HIPCHK(hipMemcpyAsync(s.h_counts.p, rec_dev, sizeof(uint32_t) * (size_t)count, hipMemcpyDeviceToHost,
-                                      ctx->stream));
-                s.host_has_records = true;
-            }
-        }
-    }
-    // counts of the chunk + (culled path) the number of (tile, hypothesis) pairs the launch evaluated
-    if (dense)
-        HIPCHK(hipMemcpyAsync(s.h_counts.p, s.counts.p, sizeof(uint32_t) * (size_t)count, hipMemcpyDeviceToHost,
-                              ctx->stream));
-    if (dense) HIPCHK(hipMemcpyAsync(s.h_valid.p, s.valid.p, (size_t)count, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipGetLastError());
-    if (!caller_ships_records && !s.poll_seq) HIPCHK(hipEventRecord(s.done, ctx->stream));
     return M3D_OK;
+}
+
+// 3. the dense path: every tile x every hypothesis
+static int issue_dense(DeviceCtx* ctx, ChunkSlot& s, const ChunkPlan& p, const CloudView& v, int kind) {
+    HIPCHK(hipMemsetAsync(s.counts.p, 0, sizeof(uint32_t) * (size_t)p.h_pad, ctx->stream));
+    HIPCHK(hipEventRecord(s.k0, ctx->stream));
+    launch_score(kind, v, s.score.as<double>(), p.h_pad, pick_splits(p.dense_tiles, p.h_pad), ctx->partial.as<uint32_t>(), ctx->stream);
+    HIPCHK(hipEventRecord(s.k1, ctx->stream));
+    launch_reduce_partials(ctx->partial.as<uint32_t>(), p.dense_tiles, p.h_pad, s.counts.as<uint32_t>(), ctx->stream);
+    s.issued.scored = true;
+    return M3D_OK;
+}
+
+// 4. the culled path (keep_mask_k clears the counter replicas on its way)
+// 4a. cull_lead_k: not among the timed scoring launches (Issued::lead_fused: m3d_stats.pairs_timed)
+static void issue_fused_lead(DeviceCtx* ctx, ChunkSlot& s, const ChunkPlan& p, const ChunkBuffers& b, const SortedView& sv, int kind) {
+    if (!p.fuse_lead) return;
+    if (!p.lead_prepared)   // (a new fit: minimal_fit_k has done it)
+        launch_keep_mask(b.ub, b.bc, p.ga, b.keep, ctx->stream, b.counts_rep, p.h_pad, 0);
+    s.issued.lead_fused = launch_cull_lead(kind, sv, s.score.as<double>(), b.c32.out, b.masks, b.keep, p.n_groups, p.ga, b.counts_rep,
+                                           p.h_pad, b.pair_rep, b.ub, p.g1, ctx->stream, b.ubp);
+}
+
+// The bound's scratch, at its place in the stream: behind the fused lead, in front of the box tests
+static int prepare_bound(DeviceCtx* ctx, ChunkSlot& s, const ChunkPlan& p, ChunkBuffers& b, const SortedView& sv, uint32_t lead) {
+    if (p.ref_on) {
+        RefHistArgs& ref = b.ref;
+        RESERVE(ctx->ref_hist, ref_hist_bytes(sv.n_tiles));
+        ref.sx = sv.x; ref.sy = sv.y; ref.sz = sv.z;
+        ref.n_tiles = sv.n_tiles;
+        ref.score = s.score.as<double>();
+        ref.counts_rep = b.counts_rep;
+        ref.rep_stride = p.h_pad;
+        ref.lead = lead;
+        ref.valid = s.valid.as<uint8_t>();
+        ref.h_count = p.count;
+        ref.max_abs = sv.max_abs;
+        ref.min_count = p.ref_min_count;
+        ref_hist_place(ref, ctx->ref_hist.p);
+    }
+    if (!p.bound_on) return M3D_OK;
+    const int rc = reserve_survivor_scratch(ctx, p.h_pad);
+    if (rc != M3D_OK) return rc;
+    if (p.phased) HIPCHK(hipMemsetAsync(b.ubsum, 0, sizeof(uint32_t) * p.h_pad, ctx->stream));   // (the block behind ub is cleared by minimal_fit_k)
+    b.surv_count = b.bc + 6;
+    b.surv = bound_list(ctx);
+    return M3D_OK;
+}
+
+// 4a. the box tests of this rank's groups, on the head's stream; the main stream picks up behind them
+// (Tried and removed: the chunk's box tests inside the scoring launch, and all of a tile's groups in one scoring
+//  workgroup -- both slower on C5's clutter rounds, profiles/r06_c5_tail_rounds.txt.)
+static int issue_box_tests(DeviceCtx* ctx, ChunkSlot& s, const ChunkPlan& p, ChunkBuffers& b, const SortedView& sv, int kind) {
+    if (!s.issued.lead_fused) {
+        if (p.touched_wanted) {
+            RESERVE(s.touched, sizeof(uint64_t) * (size_t)((sv.n_tiles + 63u) / 64u) * p.h_pad);
+            b.touched = s.touched.as<unsigned long long>();
+        }
+        if (p.lead_elsewhere)
+            launch_cull_mask(kind, sv, s.score.as<double>(), s.valid.as<uint8_t>(), p.count, p.n_groups, b.masks, b.ub, ctx->stream,
+                             /*ub_is_zero=*/true, 0, p.ga, b.c32.out);
+        launch_cull_mask(kind, sv, s.score.as<double>(), s.valid.as<uint8_t>(), p.count, p.n_groups, b.masks, b.ub, head_stream(ctx, p),
+                         /*ub_is_zero=*/true, p.g0, p.g1, b.c32.out, b.ubp, b.touched, p.h_pad, &b.touched_written);
+    }
+    if (p.head == HeadStream::kPre) {   // everything behind needs the records, the masks and ub
+        HIPCHK(hipEventRecord(s.pre_done, ctx->pre_stream));
+        HIPCHK(hipStreamWaitEvent(ctx->stream, s.pre_done, 0));
+    }
+    return M3D_OK;
+}
+
+// 4b. the lead pass (unless cull_lead_k ran it), its fold and the keep masks of the rest of this rank's groups
+static void issue_keep_masks(DeviceCtx* ctx, ChunkSlot& s, const ChunkPlan& p, const ChunkBuffers& b, const SortedView& sv, int kind,
+                             const ChunkRequest& rq) {
+    if (p.ga) {
+        s.issued.lead_groups = p.ga;
+        if (!s.issued.lead_fused) {
+            if (!p.lead_prepared)   // (a new fit: minimal_fit_k has done it)
+                launch_keep_mask(b.ub, b.bc, p.ga, b.keep, ctx->stream, b.counts_rep, p.h_pad, 0);
+            launch_score_mask(kind, sv, s.score.as<double>(), b.masks, b.keep, p.n_groups, b.counts_rep, p.h_pad, b.pair_rep,
+                              ctx->stream, 0, p.ga, p.timing ? s.k2 : nullptr, p.timing ? s.k3 : nullptr);
+        }
+        // fold of the lead's counters + keep masks of the rest of this rank's groups: one launch
+        launch_lead_fold_keep(b.counts_rep, p.h_pad, rq.lead, s.valid.as<uint8_t>(), p.count, p.g0 == 0 ? b.rec_host : nullptr, b.bc,
+                              b.ub, b.keep, p.g1 - p.g_lo, ctx->stream, p.g0 == 0 ? b.rec_dev : nullptr, p.g_lo,
+                              rq.pick_final ? rq.pick_final->key : nullptr, rq.pick_final ? rq.pick_final->key2 : nullptr,
+                              b.surv_count, b.surv, p.ref_on ? &b.ref : nullptr);
+    } else if (!p.all_prepared) {   // (all_prepared: minimal_fit_k has done it)
+        launch_keep_mask(b.ub, b.bc, p.g1 - p.g0, b.keep, ctx->stream, b.counts_rep, p.h_pad, p.g0, b.surv_count, b.surv);
+    }
+}
+
+// 4c. the histogram bound on the hypotheses the keep kernels listed
+static void issue_bound(DeviceCtx* ctx, ChunkSlot& s, const ChunkPlan& p, const ChunkBuffers& b, const SortedView& sv, int kind) {
+    if (!p.bound_on) return;
+    launch_plane_bound(kind, sv, s.score.as<double>(), b.masks, b.keep, p.n_groups, p.g_lo, p.g1, b.ubsum, b.bc, b.surv_count, b.surv,
+                       bound_tickets(ctx), b.c32.out, ctx->stream, p.bound_forced,
+                       b.touched_written && p.g_lo == p.g0 ? b.touched : nullptr, p.h_pad, p.ref_on ? &b.ref : nullptr);
+}
+
+// 4d. scoring, and one launch behind it: fold the counter replicas, tag MinimalFit's return into bit 31, update the incumbent
+// ... and (one GPU) write the records straight into the slot's pinned host array (device-visible): no copy
+// command behind the kernel (a 39 KB D2H copy started ~20 us after the kernel that fed it)
+static void issue_scoring(DeviceCtx* ctx, ChunkSlot& s, const ChunkPlan& p, const ChunkBuffers& b, const SortedView& sv, int kind,
+                          const ChunkRequest& rq) {
+    hipEvent_t const k0 = p.timing ? s.k0 : nullptr, k1 = p.timing ? s.k1 : nullptr;
+    bool phased = false;
+    if (p.phased)
+        phased = launch_score_phased(kind, sv, s.score.as<double>(), b.masks, b.keep, p.n_groups, b.counts_rep, p.h_pad, b.pair_rep, b.ub,
+                                     b.ubp, b.bc, ctx->stream, p.g_lo, p.g1, k0, k1);
+    if (!phased)
+        launch_score_mask(kind, sv, s.score.as<double>(), b.masks, b.keep, p.n_groups, b.counts_rep, p.h_pad, b.pair_rep, ctx->stream,
+                          p.g_lo, p.g1, k0, k1, p.bound_on);
+    PickFinal pfin;
+    if (rq.pick_final) {
+        pfin = *rq.pick_final;
+        pfin.params = s.params.as<double>();
+    }
+    launch_sum_replicas(b.counts_rep, p.h_pad, p.g1 * 64u, b.rec_host, b.pair_rep, b.h_pairs, s.valid.as<uint8_t>(), p.count, b.bc,
+                        ctx->stream, p.g_lo * 64u, b.rec_dev, rq.pick_final ? &pfin : nullptr, phased ? b.keep : nullptr);
+    if (p.polls) s.issued.poll_seq = rq.pick_final->seq;
+    s.issued.scored = p.timing;
+}
+
+static int issue_culled(DeviceCtx* ctx, ChunkSlot& s, const ChunkPlan& p, ChunkBuffers& b, const SortedView& sv, int kind,
+                        const ChunkRequest& rq) {
+    if (!p.own_real) {   // a slice without real hypotheses reports zeros
+        HIPCHK(hipMemsetAsync(b.rec_dev + (size_t)p.g0 * 64, 0, sizeof(uint32_t) * p.sl_pad, ctx->stream));
+        b.h_pairs[0] = b.h_pairs[1] = b.h_pairs[2] = 0;
+        return M3D_OK;
+    }
+    issue_fused_lead(ctx, s, p, b, sv, kind);
+    int rc = prepare_bound(ctx, s, p, b, sv, rq.lead);
+    if (rc != M3D_OK) return rc;
+    rc = issue_box_tests(ctx, s, p, b, sv, kind);
+    if (rc != M3D_OK) return rc;
+    issue_keep_masks(ctx, s, p, b, sv, kind, rq);
+    issue_bound(ctx, s, p, b, sv, kind);
+    issue_scoring(ctx, s, p, b, sv, kind, rq);
+    return M3D_OK;
+}
+
+// 5. the records on their way to the host, and the `done` event behind them
+static int ship_records(DeviceCtx* ctx, ChunkSlot& s, const ChunkPlan& p, const ChunkBuffers& b, const ChunkRequest& rq) {
+    if (p.solo) {
+        rq.comm->collectives++;   // (the window's exchange, degenerate)
+    } else if (rq.comm) {
+        // the one exchange of the window: every rank's slice of records, in place (RCCL: ncclAllGather on this
+        // stream, nothing on the host; host transports wait for the stream and leave the records in h_counts)
+        int host_has_all = 0;
+        const int rc = rq.comm->allgather_u32_device(b.rec_dev, p.sl_pad, ctx->stream, s.h_counts.as<uint32_t>(), &host_has_all);
+        if (rc != M3D_OK) return rc;
+        if (!host_has_all && rq.caller_ships_records) {
+            // the gathered window (world x slice records: hundreds of KB at 8 ranks) goes to the host through the copy
+            // engine, on the copy stream, while pick_best_k and the early compaction run on the main stream; s.done
+            // then sits on the copy stream.  (pick_best_k's one workgroup would need 40 us for 80 000 records.)
+            HIPCHK(hipEventRecord(ctx->ev_compact, ctx->stream));
+            HIPCHK(hipStreamWaitEvent(copy_stream_of(ctx), ctx->ev_compact, 0));
+            HIPCHK(hipMemcpyAsync(s.h_counts.p, b.rec_dev, sizeof(uint32_t) * (size_t)p.count, hipMemcpyDeviceToHost,
+                                  copy_stream_of(ctx)));
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(s.done, copy_stream_of(ctx)));
+            s.issued.done_on_copy_stream = true;
+            return M3D_OK;
+        }
+        if (!host_has_all)
+            HIPCHK(hipMemcpyAsync(s.h_counts.p, b.rec_dev, sizeof(uint32_t) * (size_t)p.count, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    // dense: counts and MinimalFit's returns of the chunk
+    if (p.dense) {
+        HIPCHK(hipMemcpyAsync(s.h_counts.p, s.counts.p, sizeof(uint32_t) * (size_t)p.count, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(s.h_valid.p, s.valid.p, (size_t)p.count, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(hipGetLastError());
+    if (!rq.caller_ships_records && !s.issued.poll_seq) HIPCHK(hipEventRecord(s.done, ctx->stream));
+    return M3D_OK;
+}
+
+static int issue_chunk(DeviceCtx* ctx, ChunkSlot& s, const CloudView& v, const SortedView& sv, int kind, double thr, SampleSource& src,
+                       const ChunkRequest& rq) {
+    const ChunkPlan p = plan_chunk(chunk_facts(ctx, s, v, sv, kind, rq), rq);
+    if (rq.move_best_from)   // (before the slot's buffers are touched: a RESERVE below may hand the old block back)
+        HIPCHK(hipMemcpyAsync(ctx->best_params.p, rq.move_best_from, sizeof(double) * kModelStride, hipMemcpyDeviceToDevice,
+                              head_stream(ctx, p)));
+    if (rq.comm && p.dense) return fail(M3D_ERR_INVALID_ARG, "sharded fits use the culled scoring path (m3d_config.dense_scoring = 0)");
+    s.issued = ChunkSlot::Issued{};
+    s.issued.begin = rq.begin;
+    s.issued.end = rq.end;
+    s.issued.h_pad = p.h_pad;
+    s.issued.cull32 = p.cull32;
+    ChunkBuffers b;
+    int rc = reserve_chunk_scratch(ctx, s, p, sv, b);
+    if (rc != M3D_OK) return rc;
+    rc = issue_head(ctx, s, p, b, v, sv, kind, thr, src, rq);
+    if (rc != M3D_OK) return rc;
+    rc = p.dense ? issue_dense(ctx, s, p, v, kind) : issue_culled(ctx, s, p, b, sv, kind, rq);
+    if (rc != M3D_OK) return rc;
+    return ship_records(ctx, s, p, b, rq);
 }
 
 // Completion of a chunk issued with a PickFinal: the last kernel of the chunk stores `seq` into the pinned
@@ -642,7 +658,7 @@ static void unpack_slot(ChunkSlot& s) {
     if (use_dense_scoring()) return;
     uint32_t* c = s.h_counts.as<uint32_t>();
     uint8_t* v = s.h_valid.as<uint8_t>();
-    const size_t n = s.end - s.begin;
+    const size_t n = s.issued.end - s.issued.begin;
     for (size_t i = 0; i < n; ++i) {
         v[i] = (uint8_t)(c[i] >> 31);
         c[i] &= 0x7FFFFFFFu;
@@ -772,12 +788,6 @@ static int run_ransac(DeviceCtx* ctx, const CloudView& v, const SortedView& sv, 
     // in_flight: hypotheses already issued whose records have not been replayed yet
     const bool prestream_on = prestream_enabled();
     auto issue_next = [&](int slot_id, size_t in_flight, size_t forced = 0) -> int {
-        // a later chunk of a probability-1 fit on one GPU: its MinimalFit and box tests run on pre_stream, under the scoring
-        // launches of the chunk before (issue_chunk, `pre`)
-        const bool pre = prestream_on && prob >= 1.0 && !comm && next_begin > 0 && !use_dense_scoring();
-        // the slot holding the best model is recycled: issue_chunk moves the record out first, on the stream that is about
-        // to overwrite the slot (MinimalFit of the new chunk)
-        const double* move_best_from = slot_id == best_slot ? best_dev : nullptr;
         size_t want = chunk;
         if (forced) {
             want = forced;
@@ -806,11 +816,27 @@ static int run_ransac(DeviceCtx* ctx, const CloudView& v, const SortedView& sv, 
             pf.seq = ctx->pick_seq;
             // (pf.params: issue_chunk fills in the slot's parameter array once it has reserved it)
         }
-        int r = issue_chunk(ctx, ctx->slot[slot_id], v, sv, kind, thr, b, e, src, &out->ms_sample, true,
-                            b == 0 ? lead : 0, b == 0, spec, comm, /*caller_ships_records=*/spec && !fused_pick,
-                            fused_pick ? &pf : nullptr, /*nothing_to_prune=*/b == 0 && e == max_iter && lead == 0 && !comm, pre,
-                            move_best_from, /*first_of_stream=*/false, rounds);
-        if (move_best_from && r == M3D_OK) {
+        ChunkRequest rq;
+        rq.begin = b;
+        rq.end = e;
+        rq.prune = true;
+        rq.lead = b == 0 ? lead : 0;
+        rq.new_fit = b == 0;
+        rq.device_records = spec;
+        rq.comm = comm;
+        rq.caller_ships_records = spec && !fused_pick;
+        rq.pick_final = fused_pick ? &pf : nullptr;
+        rq.nothing_to_prune = b == 0 && e == max_iter;
+        // a later chunk of a probability-1 fit: its MinimalFit and box tests may run on pre_stream, under the scoring
+        // launches of the chunk before
+        rq.pre_wanted = prestream_on && prob >= 1.0 && b > 0;
+        // the slot holding the best model is recycled: issue_chunk moves the record out first, on the stream that is about
+        // to overwrite the slot (MinimalFit of the new chunk)
+        rq.move_best_from = slot_id == best_slot ? best_dev : nullptr;
+        rq.rounds = rounds;
+        rq.ms_sample = &out->ms_sample;
+        int r = issue_chunk(ctx, ctx->slot[slot_id], v, sv, kind, thr, src, rq);
+        if (rq.move_best_from && r == M3D_OK) {
             best_dev = ctx->best_params.as<double>();
             best_slot = -1;
         }
@@ -836,12 +862,12 @@ static int run_ransac(DeviceCtx* ctx, const CloudView& v, const SortedView& sv, 
             ChunkSlot& sl = ctx->slot[slot_id];
             // (sharded: the records are the gathered ones; the other ranks' counts raise this rank's incumbent too.  Should the
             // records not be on their way to the host yet, the kernel passes them on to the pinned array the replay reads.)
-            const bool ship = comm && !sl.host_has_records;
+            const bool ship = comm && !sl.issued.host_has_records;
             launch_pick_best(sl.counts.as<uint32_t>(), (uint32_t)(e - b), (unsigned long long)b, sl.params.as<double>(),
                              b == 0, ctx->pick.as<BestPick>(), ctx->h_pick.as<BestPickHost>(), ctx->stream,
                              ship ? sl.h_counts.as<uint32_t>() : nullptr, comm ? ctx->best_count.as<uint32_t>() : nullptr);
-            if (ship) sl.host_has_records = true;
-            if (!sl.done_on_copy_stream) HIPCHK(hipEventRecord(sl.done, ctx->stream));
+            if (ship) sl.issued.host_has_records = true;
+            if (!sl.issued.done_on_copy_stream) HIPCHK(hipEventRecord(sl.done, ctx->stream));
             if (e == max_iter) {   // last chunk: RefineModel's first stage on the prediction, now
                 r = issue_refine_compaction(ctx, v, orig_dev, kind, thr, ctx->pick.as<BestPick>()->params, h_best_at(ctx, slot),
                                             h_total_at(ctx, slot), fc, &out->spec, /*fused=*/true, idx_host, nullptr,
@@ -857,7 +883,7 @@ static int run_ransac(DeviceCtx* ctx, const CloudView& v, const SortedView& sv, 
         return r;
     };
     if (max_iter > 0) {
-        if (prestream_on && prob >= 1.0 && !comm && max_iter > chunk && !use_dense_scoring()) {   // (a fit of several chunks)
+        if (prestream_on && prob >= 1.0 && max_iter > chunk && pre_stream_possible(use_dense_scoring(), comm != nullptr)) {   // (a fit of several chunks)
             rc = pre_stream_gate(ctx);
             if (rc != M3D_OK) return rc;
         }
@@ -870,23 +896,23 @@ static int run_ransac(DeviceCtx* ctx, const CloudView& v, const SortedView& sv, 
             if (next_begin < max_iter) {
                 // speculate only when the adaptive bound cannot be reached inside the current chunk
                 const bool safe = prob >= 1.0 || (out->st.best_index >= 0 &&
-                                                  out->st.current_iteration > out->st.count + (s.end - s.begin));
+                                                  out->st.current_iteration > out->st.count + (s.issued.end - s.issued.begin));
                 if (safe) {
-                    rc = issue_next(cur ^ 1, s.end - s.begin);
+                    rc = issue_next(cur ^ 1, s.issued.end - s.issued.begin);
                     if (rc != M3D_OK) break;
                     issued = true;
-                } else if (first_pass && prob < 1.0 && iterations_hint > s.end) {
+                } else if (first_pass && prob < 1.0 && iterations_hint > s.issued.end) {
                     // the caller knows how many iterations a similar fit just took (segmentation rounds): queue
                     // that many behind the first chunk without waiting for its counts (they prune on the device)
-                    const size_t left = iterations_hint - s.end;
-                    rc = issue_next(cur ^ 1, s.end - s.begin, (left + left / 16 + 16 + 63) / 64 * 64);
+                    const size_t left = iterations_hint - s.issued.end;
+                    rc = issue_next(cur ^ 1, s.issued.end - s.issued.begin, (left + left / 16 + 16 + 63) / 64 * 64);
                     if (rc != M3D_OK) break;
                     issued = true;
                 }
             }
             first_pass = false;
-            if (s.poll_seq) {
-                const int wrc = wait_pick_seq(ctx, s.poll_seq);
+            if (s.issued.poll_seq) {
+                const int wrc = wait_pick_seq(ctx, s.issued.poll_seq);
                 if (wrc != M3D_OK) return wrc;
             } else {
                 HIPCHK(hipEventSynchronize(s.done));
@@ -894,18 +920,18 @@ static int run_ransac(DeviceCtx* ctx, const CloudView& v, const SortedView& sv, 
             if (use_dense_scoring()) unpack_slot(s);   // (culled path: the replay reads the packed records as shipped)
             {
                 float kms = 0;
-                if (s.scored && hipEventElapsedTime(&kms, s.k0, s.k1) == hipSuccess) {
+                if (s.issued.scored && hipEventElapsedTime(&kms, s.k0, s.k1) == hipSuccess) {
                     out->ms_score_kernel += kms;
                     out->score_launches++;
                 }
-                if (s.scored && s.lead_groups && !s.lead_fused && hipEventElapsedTime(&kms, s.k2, s.k3) == hipSuccess) {
+                if (s.issued.scored && s.issued.lead_groups && !s.issued.lead_fused && hipEventElapsedTime(&kms, s.k2, s.k3) == hipSuccess) {
                     out->ms_score_kernel += kms;
                     out->score_launches++;
                 }
                 if (!use_dense_scoring()) {
-                    out->pairs_scored += s.h_counts.as<uint32_t>()[s.h_pad];
-                    out->pairs_exact += s.h_counts.as<uint32_t>()[s.h_pad + 1];
-                    out->pairs_timed += s.h_counts.as<uint32_t>()[s.h_pad] - (s.lead_fused ? s.h_counts.as<uint32_t>()[s.h_pad + 2] : 0u);
+                    out->pairs_scored += s.h_counts.as<uint32_t>()[s.issued.h_pad];
+                    out->pairs_exact += s.h_counts.as<uint32_t>()[s.issued.h_pad + 1];
+                    out->pairs_timed += s.h_counts.as<uint32_t>()[s.issued.h_pad] - (s.issued.lead_fused ? s.h_counts.as<uint32_t>()[s.issued.h_pad + 2] : 0u);
                 }
             }
             int cb_rc = M3D_OK;
@@ -926,7 +952,7 @@ static int run_ransac(DeviceCtx* ctx, const CloudView& v, const SortedView& sv, 
             // apart than the two margins (x2 safety) the comparison of the serial sums is decided.
             // Stage 2 (rare: equal or near-equal hypotheses): the serial sums themselves.
             auto tie = [&](size_t i, uint32_t cnt, double* trial_rmse, bool* trial_known) -> bool {
-                const double* model_t = s.params.as<double>() + (i - s.begin) * kModelStride;
+                const double* model_t = s.params.as<double>() + (i - s.issued.begin) * kModelStride;
                 *trial_known = false;
                 pending_valid = false;
                 out->ties++;
@@ -970,19 +996,19 @@ static int run_ransac(DeviceCtx* ctx, const CloudView& v, const SortedView& sv, 
             };
             auto on_best = [&](size_t i) {
                 // the model stays in the chunk's slot (issue_next moves it out before the slot is recycled)
-                best_dev = s.params.as<double>() + (i - s.begin) * kModelStride;
+                best_dev = s.params.as<double>() + (i - s.issued.begin) * kModelStride;
                 best_slot = cur;
                 best_approx_known = pending_valid;
                 best_approx = pending_approx;
                 pending_valid = false;
             };
             if (use_dense_scoring())
-                replay_range(&out->st, v.n, kind, max_iter, prob, s.begin, s.end, s.h_valid.as<uint8_t>(),
+                replay_range(&out->st, v.n, kind, max_iter, prob, s.issued.begin, s.issued.end, s.h_valid.as<uint8_t>(),
                              s.h_counts.as<uint32_t>(), tie, on_best);
             else if (prob >= 1.0)
-                replay_range_exhaustive(&out->st, v.n, kind, max_iter, s.begin, s.end, s.h_counts.as<uint32_t>(), tie, on_best);
+                replay_range_exhaustive(&out->st, v.n, kind, max_iter, s.issued.begin, s.issued.end, s.h_counts.as<uint32_t>(), tie, on_best);
             else
-                replay_range(&out->st, v.n, kind, max_iter, prob, s.begin, s.end, nullptr, s.h_counts.as<uint32_t>(), tie,
+                replay_range(&out->st, v.n, kind, max_iter, prob, s.issued.begin, s.issued.end, nullptr, s.h_counts.as<uint32_t>(), tie,
                              on_best);
             if (cb_rc != M3D_OK) {
                 rc = cb_rc;
@@ -1059,7 +1085,7 @@ static int ensure_plane_frames(m3d_cloud* c, int kind, size_t n_hypotheses) {
     // 1: where it pays (bound_pays, below) -- and from 65 536 hypotheses on for a cloud that lives for one call (tile_frames_k
     // takes ~0.09 ms per million points, the bound saves ~0.02 ms per 10 000 hypotheses on them: m3d_fit_plane 0.95 -> 1.04 ms
     // otherwise); 2: always (tests)
-    const int mode = bound_mode(kind);
+    const int mode = bound_mode(kind, config().plane_bound, config().ref_bound);
     if ((kind == M3D_SPHERE && mode != 2) || c->frames_ready || c->frames_failed || mode == 0 || c->work.active || c->n_tiles == 0 ||
         (mode == 1 && (!bound_pays(c->n_tiles, std::min<size_t>(n_hypotheses, chunk_cap_for(c->view(), c->sorted()))) ||
                        (c->one_shot && n_hypotheses < 65536u))))
@@ -1441,7 +1467,10 @@ int m3d_cloud_score_range(m3d_cloud* c, int kind, double threshold, const uint32
     ChunkSlot& s = ctx->slot[0];
     for (size_t b = begin; b < end; b += chunk_cap) {
         const size_t e = std::min(end, b + chunk_cap);
-        const int rc = issue_chunk(ctx, s, v, sv, kind, threshold, b, e, src, nullptr);
+        ChunkRequest rq;
+        rq.begin = b;
+        rq.end = e;
+        const int rc = issue_chunk(ctx, s, v, sv, kind, threshold, src, rq);
         if (rc != M3D_OK) return rc;
         HIPCHK(hipEventSynchronize(s.done));
         unpack_slot(s);
@@ -1542,11 +1571,11 @@ int m3d_cloud_score_shard(m3d_cloud* c, m3d_sampler* sampler, double threshold, 
     bool first_piece = true;
     // Slices of several pieces (what a low world size leaves a rank): a SHORT first own piece -- its best count is what prunes
     // the pieces behind it (run_ransac's short first chunk) -- and MinimalFit + box tests of every later piece on pre_stream,
-    // under the scoring launches of the piece before (issue_chunk, `pre`).
+    // under the scoring launches of the piece before (ChunkRequest::pre_wanted).
     const bool prestream_on = prestream_enabled();
     constexpr size_t kFirstPiece = 2048;
     bool first_own = true;
-    if (prestream_on && !use_dense_scoring()) {
+    if (prestream_on && pre_stream_possible(use_dense_scoring(), /*has_comm=*/false)) {
         const int grc = pre_stream_gate(ctx);
         if (grc != M3D_OK) return grc;
     }
@@ -1569,7 +1598,11 @@ int m3d_cloud_score_shard(m3d_cloud* c, m3d_sampler* sampler, double threshold, 
             const size_t w = std::min<size_t>(std::min<size_t>(lead_size(), chunk_cap), first_own - begin);
             sampler->draw_until(begin + w);
             tsrc.table = sampler->table.data();
-            const int rc = issue_chunk(ctx, ctx->slot[cur], v, sv, kind, threshold, begin, begin + w, tsrc, nullptr, true);
+            ChunkRequest rq;
+            rq.begin = begin;
+            rq.end = begin + w;
+            rq.prune = true;
+            const int rc = issue_chunk(ctx, ctx->slot[cur], v, sv, kind, threshold, tsrc, rq);
             if (rc != M3D_OK) return rc;
             pend[cur].active = pend[cur].discard = true;
             pend[cur].n = w;
@@ -1588,19 +1621,24 @@ int m3d_cloud_score_shard(m3d_cloud* c, m3d_sampler* sampler, double threshold, 
         }
         // bound-and-prune against LOWER-index hypotheses only, which is what the sequential replay allows
         for (size_t bb = b; bb < e;) {
-            // the first launch of the call counts its first lead_size() hypotheses on their own (issue_chunk's `lead`)
+            // the first launch of the call counts its first lead_size() hypotheses on their own (ChunkRequest::lead)
             const uint32_t lead = first_piece ? lead_size() : 0u;
             first_piece = false;
             const bool short_first = first_own && e - bb > chunk_cap && kFirstPiece >= 2 * (size_t)lead_size();
             const size_t ee = std::min(e, bb + (short_first ? kFirstPiece : chunk_cap));
-            const bool pre = prestream_on && !first_own && lead == 0;
+            ChunkRequest rq;
+            rq.begin = bb;
+            rq.end = ee;
+            rq.prune = true;
+            rq.lead = lead;
+            rq.pre_wanted = prestream_on && !first_own;
+            rq.first_of_stream = world == 1 && bb == 0;
             first_own = false;
             sampler->draw_until(ee);
             int rc = collect(cur);
             if (rc != M3D_OK) return rc;
             tsrc.table = sampler->table.data();
-            rc = issue_chunk(ctx, ctx->slot[cur], v, sv, kind, threshold, bb, ee, tsrc, nullptr, true, lead, false, false, nullptr, false,
-                             nullptr, false, pre, nullptr, /*first_of_stream=*/world == 1 && bb == 0);
+            rc = issue_chunk(ctx, ctx->slot[cur], v, sv, kind, threshold, tsrc, rq);
             if (rc != M3D_OK) return rc;
             pend[cur].active = true;
             pend[cur].out_pos = out;
@@ -1637,20 +1675,22 @@ int m3d_bench_time_score(m3d_cloud* c, int kind, double threshold, const uint32_
     src.table = samples;
     src.m = minimal_sample(kind);
     ChunkSlot& s = ctx->slot[0];
-    int rc = issue_chunk(ctx, s, v, sv, kind, threshold, 0, n_hypotheses, src, nullptr);  // warm-up + records
+    ChunkRequest rq;
+    rq.end = n_hypotheses;
+    int rc = issue_chunk(ctx, s, v, sv, kind, threshold, src, rq);  // warm-up + records
     if (rc != M3D_OK) return rc;
     const uint32_t count = (uint32_t)n_hypotheses;
     const uint32_t n_tiles = v.n_pad / kScoreTile;
-    // make sure the buffers of the timed mode exist whatever path issue_chunk took
-    RESERVE(ctx->partial, sizeof(uint32_t) * (size_t)n_tiles * s.h_pad);
-    const uint32_t n_groups = s.h_pad / 64;
+    // the buffers of the timed modes: the lane's own masks, and the dense path's partial counts whichever path the chunk took
+    RESERVE(ctx->partial, sizeof(uint32_t) * (size_t)n_tiles * s.issued.h_pad);
+    const uint32_t n_groups = s.issued.h_pad / 64;
     RESERVE(ctx->masks, sizeof(uint64_t) * (size_t)std::max<uint32_t>(sv.n_tiles, 1) * n_groups);
     RESERVE(ctx->keep, sizeof(uint64_t) * (size_t)n_groups);
-    RESERVE(ctx->counts_rep, sizeof(uint32_t) * ((size_t)kCountReplicas * s.h_pad + kPairReplicas));
+    RESERVE(ctx->counts_rep, sizeof(uint32_t) * ((size_t)kCountReplicas * s.issued.h_pad + kPairReplicas));
     RESERVE(ctx->small, 256);
     auto* masks = ctx->masks.as<unsigned long long>();
     auto* keep = ctx->keep.as<unsigned long long>();
-    const float* c32 = (!use_dense_scoring() && config().cull_fp32 != 0 && sv.radius < 1e18) ? s.cull32.as<float>() : nullptr;
+    const float* c32 = s.issued.cull32 ? s.cull32.as<float>() : nullptr;
     launch_cull_mask(kind, sv, s.score.as<double>(), s.valid.as<uint8_t>(), count, n_groups, masks, nullptr, ctx->stream, false, 0,
                      0xFFFFFFFFu, c32);
     launch_keep_mask(nullptr, nullptr, n_groups, keep, ctx->stream);
@@ -1661,17 +1701,17 @@ int m3d_bench_time_score(m3d_cloud* c, int kind, double threshold, const uint32_
         HIPCHK(hipStreamSynchronize(ctx->stream));
         *listed_pairs = tot;  // (tile, hypothesis) pairs that survive the box test
     }
-    const uint32_t splits = pick_splits(n_tiles, s.h_pad);
+    const uint32_t splits = pick_splits(n_tiles, s.issued.h_pad);
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
     for (int r = 0; r < reps; ++r) {
         if (mode == 0)
             launch_score_mask(kind, sv, s.score.as<double>(), masks, keep, n_groups, ctx->counts_rep.as<uint32_t>(),
-                              s.h_pad, ctx->counts_rep.as<uint32_t>() + (size_t)kCountReplicas * s.h_pad, ctx->stream);
+                              s.issued.h_pad, ctx->counts_rep.as<uint32_t>() + (size_t)kCountReplicas * s.issued.h_pad, ctx->stream);
         else if (mode == 1)
             launch_cull_mask(kind, sv, s.score.as<double>(), s.valid.as<uint8_t>(), count, n_groups, masks, nullptr,
                              ctx->stream, false, 0, 0xFFFFFFFFu, c32);
         else
-            launch_score(kind, v, s.score.as<double>(), s.h_pad, splits, ctx->partial.as<uint32_t>(), ctx->stream);
+            launch_score(kind, v, s.score.as<double>(), s.issued.h_pad, splits, ctx->partial.as<uint32_t>(), ctx->stream);
     }
     HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
     HIPCHK(hipGetLastError());
@@ -1723,22 +1763,24 @@ static int bench_upper_bounds(m3d_cloud* c, int kind, double threshold, const ui
     src.table = samples;
     src.m = (uint32_t)minimal_sample(kind);
     ChunkSlot& s = ctx->slot[0];
-    int rc = issue_chunk(ctx, s, v, sv, kind, threshold, 0, n_hypotheses, src, nullptr);   // records (+ fp32 box-test records)
+    ChunkRequest rq;
+    rq.end = n_hypotheses;
+    int rc = issue_chunk(ctx, s, v, sv, kind, threshold, src, rq);   // records (+ fp32 box-test records)
     if (rc != M3D_OK) return rc;
-    const uint32_t n_groups = s.h_pad / 64;
+    const uint32_t n_groups = s.issued.h_pad / 64;
     RESERVE(ctx->masks, sizeof(uint64_t) * (size_t)std::max<uint32_t>(sv.n_tiles, 1) * n_groups);
     RESERVE(ctx->keep, sizeof(uint64_t) * (size_t)n_groups);
     RESERVE(ctx->small, 256);
-    RESERVE(s.ub, sizeof(uint32_t) * 3 * (size_t)s.h_pad);
-    rc = reserve_survivor_scratch(ctx, s.h_pad);
+    RESERVE(s.ub, sizeof(uint32_t) * 3 * (size_t)s.issued.h_pad);
+    rc = reserve_survivor_scratch(ctx, s.issued.h_pad);
     if (rc != M3D_OK) return rc;
     auto* masks = ctx->masks.as<unsigned long long>();
     auto* keep = ctx->keep.as<unsigned long long>();
-    uint32_t* ubsum = s.ub.as<uint32_t>() + s.h_pad;
+    uint32_t* ubsum = s.ub.as<uint32_t>() + s.issued.h_pad;
     uint32_t* ctl = ctx->small.as<uint32_t>();   // [0]: an incumbent of 0 (the keep rule stays inert); [1]: the list's length
     uint32_t* surv = bound_list(ctx);
-    const float* c32 = (!use_dense_scoring() && config().cull_fp32 != 0 && sv.radius < 1e18) ? s.cull32.as<float>() : nullptr;
-    HIPCHK(hipMemsetAsync(ubsum, 0, sizeof(uint32_t) * (size_t)s.h_pad, ctx->stream));
+    const float* c32 = s.issued.cull32 ? s.cull32.as<float>() : nullptr;
+    HIPCHK(hipMemsetAsync(ubsum, 0, sizeof(uint32_t) * (size_t)s.issued.h_pad, ctx->stream));
     HIPCHK(hipMemsetAsync(ctl, 0, 8, ctx->stream));
     launch_cull_mask(kind, sv, s.score.as<double>(), s.valid.as<uint8_t>(), (uint32_t)n_hypotheses, n_groups, masks, nullptr,
                      ctx->stream, false, 0, 0xFFFFFFFFu, c32);

@@ -112,3 +112,16 @@ def test_grid_cell_lookup_is_pinned_on_the_host():
     subprocess.run(["make", "-C", cpp, "_build/test_grid_cell"], check=True, capture_output=True)
     r = subprocess.run([os.path.join(cpp, "_build", "test_grid_cell")], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and r.stdout.rstrip().endswith("OK") and "FAILED" not in r.stdout, r.stdout + r.stderr
+
+
+def test_chunk_plan_is_pinned_on_the_host():
+    """tests/cpp/test_chunk_plan.cpp compiles misc3d_amd/csrc/m3d_chunk_plan.hpp -- plan_chunk, where issue_chunk decides what a
+    chunk of hypotheses will do -- with g++, compares the whole plan of named scenarios (plain records, C2's fit with ref_bound
+    0 / 1 / 2, without frames, with an unknown radius, with tombstones, later chunks with and without a pre-stream, cylinder and
+    sphere windows, a chunk with nothing to prune, dense scoring, two ranks, a rank without hypotheses, one rank over RCCL and
+    over a host transport, a pending tombstone pass) with literals, and holds every combination of the boolean inputs at three
+    window lengths and two tile counts to the implications the stages rely on."""
+    cpp = os.path.join(ROOT, "tests", "cpp")
+    subprocess.run(["make", "-C", cpp, "_build/test_chunk_plan"], check=True, capture_output=True)
+    r = subprocess.run([os.path.join(cpp, "_build", "test_chunk_plan")], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.rstrip().endswith("all ok") and "FAILED" not in r.stdout, r.stdout + r.stderr
