@@ -1,10 +1,11 @@
-// misc3d/pose_estimation/ppf_voting.h -- host mirror over the C ABI (m3d_ppf_*) of the two device hot paths of the
-// reference's PPFEstimator (src/ppf_estimation.cpp): the point-pair table of a model (CalcHashTable, :603-640) and the vote of
-// a scene against it (VotingAndGetPose, :399-524).  Header-only; no Eigen / Open3D needed.
+// misc3d/pose_estimation/ppf_voting.h -- host mirror over the C ABI (m3d_ppf_*) of the device hot paths of the reference's
+// PPFEstimator (src/ppf_estimation.cpp): the point-pair table of a model (CalcHashTable, :603-640), the vote of a scene
+// against it (VotingAndGetPose, :399-524), and the way from the raw poses to ranked, refined results (ClusterPoses,
+// PoseAverage, RefineSparsePose, the centre shift and the scoring).  Header-only; no Eigen / Open3D needed.
 //
-// Both take ALREADY SAMPLED points with unit normals.  PreprocessTrain / PreprocessEstimate, ClusterPoses / PoseAverage, the
-// EdgePoints mode, the scoring and the PPFEstimator class itself are not part of this build; the contract of what is here is
-// written down next to m3d_ppf_vote in include/misc3d_amd.h.
+// All take ALREADY SAMPLED points with unit normals.  PreprocessTrain / PreprocessEstimate, the EdgePoints mode and the
+// PPFEstimator / PPFEstimatorConfig classes themselves are not part of this build; the contract of what is here is written down
+// next to m3d_ppf_vote and m3d_ppf_estimate in include/misc3d_amd.h.
 #pragma once
 #include <array>
 #include <cstdint>
@@ -24,6 +25,44 @@ struct VotedPose {
     size_t corr_mi;                // model index
     size_t reference;              // position in the reference index list the pose was voted at
     size_t alpha_index;
+};
+
+/** The reference's Pose6D (data_structure.h): a result of Estimate, for the UNCENTRED model. */
+struct Pose6D {
+    std::array<double, 16> pose;   // row-major 4 x 4
+    std::array<double, 4> q;       // w, x, y, z
+    std::array<double, 3> t;
+    size_t num_votes;
+    double score;
+    int object_id;
+};
+
+/** PPFEstimatorConfig::RefineMethod */
+enum class RefineMethod { NoRefine = M3D_PPF_REFINE_NONE, PointToPoint = M3D_PPF_REFINE_POINT_TO_POINT, PointToPlane = M3D_PPF_REFINE_POINT_TO_PLANE };
+
+/** m3d_ppf_cluster_params with the method as the reference's enum. */
+struct PPFClusterParams {
+    double dist_threshold, angle_threshold, ratio, score_thresh, rel_dist_sparse_thresh;
+    int num_result;
+    RefineMethod refine_method;
+    int object_id;
+    m3d_ppf_cluster_params c() const {
+        return m3d_ppf_cluster_params{dist_threshold, angle_threshold, ratio, score_thresh, rel_dist_sparse_thresh, num_result,
+                                      static_cast<int32_t>(refine_method), object_id, 0};
+    }
+};
+
+/** What ClusterPoses returns: per valid pose (votes descending, ties by input index), per translation cluster, per sub-cluster. */
+struct PoseClusters {
+    std::vector<uint32_t> order, count_t, count_r;
+    std::vector<int32_t> label_t, label_r;
+    int32_t min_num_pt_t = 0;
+    std::vector<int32_t> min_num_pt_r;
+    std::vector<uint64_t> cluster_votes;
+    std::vector<std::array<double, 16>> avg_poses;
+    std::vector<uint64_t> avg_votes;
+    std::vector<uint32_t> avg_cluster;
+    m3d_ppf_cluster_stats stats{};
 };
 
 class PPFVoting {
@@ -86,6 +125,79 @@ public:
             out[k].corr_mi = mi[k];
             out[k].reference = rp[k];
             out[k].alpha_index = ai[k];
+        }
+        return out;
+    }
+
+    /** The reference's defaults; dist_threshold = 0.05 x the trained model's diameter. */
+    PPFClusterParams DefaultClusterParams() const {
+        m3d_ppf_cluster_params p;
+        m3d_ppf_default_cluster_params(model_, &p);
+        return PPFClusterParams{p.dist_threshold, p.angle_threshold, p.ratio, p.score_thresh, p.rel_dist_sparse_thresh, p.num_result,
+                                static_cast<RefineMethod>(p.refine_method), p.object_id};
+    }
+
+    /** ClusterPoses with PoseAverage (K1 - K6 of "PPF pose clustering"): poses row-major 4 x 4 each, as Vote returns them. */
+    PoseClusters ClusterPoses(const double* poses, const uint32_t* num_votes, size_t n_poses, const PPFClusterParams& params,
+                              int device = 0) const {
+        const m3d_ppf_cluster_params p = params.c();
+        PoseClusters out;
+        size_t pcap = n_poses, ccap = 64, nv = 0, nt = 0, nr = 0;
+        std::vector<double> avg;
+        for (int attempt = 0; attempt < 2; ++attempt) {
+            out.order.assign(pcap, 0);
+            out.count_t.assign(pcap, 0);
+            out.count_r.assign(pcap, 0);
+            out.label_t.assign(pcap, -1);
+            out.label_r.assign(pcap, -1);
+            out.min_num_pt_r.assign(ccap, 0);
+            out.cluster_votes.assign(ccap, 0);
+            out.avg_votes.assign(ccap, 0);
+            out.avg_cluster.assign(ccap, 0);
+            avg.assign(16 * ccap, 0.0);
+            const int rc = m3d_ppf_cluster_poses(poses, num_votes, n_poses, &p, device, pcap, &nv, out.order.data(), out.count_t.data(),
+                                                 out.label_t.data(), out.count_r.data(), out.label_r.data(), ccap, &nt, &nr,
+                                                 &out.min_num_pt_t, out.min_num_pt_r.data(), out.cluster_votes.data(), avg.data(),
+                                                 out.avg_votes.data(), out.avg_cluster.data(), &out.stats);
+            if (rc == M3D_ERR_CAPACITY && attempt == 0 && nv <= pcap) {
+                ccap = nt > nr ? nt : nr;
+                continue;
+            }
+            CheckStatus(rc);
+            break;
+        }
+        for (auto* v : {&out.order, &out.count_t, &out.count_r}) v->resize(nv);
+        out.label_t.resize(nv);
+        out.label_r.resize(nv);
+        out.min_num_pt_r.resize(nt);
+        out.cluster_votes.resize(nt);
+        out.avg_votes.resize(nr);
+        out.avg_cluster.resize(nr);
+        out.avg_poses.resize(nr);
+        for (size_t k = 0; k < nr; ++k)
+            for (int e = 0; e < 16; ++e) out.avg_poses[k][e] = avg[16 * k + e];
+        return out;
+    }
+
+    /** Estimate from the vote on (:304-395): vote, cluster, average, refine, shift by the centroid, score; best first. */
+    std::vector<Pose6D> Estimate(const double* scene_points, const double* scene_normals, size_t m, const std::vector<size_t>& reference,
+                                 const PPFClusterParams& params, m3d_ppf_estimate_stats* stats = nullptr) const {
+        if (!model_) LogError("PPFVoting: not trained");
+        const m3d_ppf_cluster_params p = params.c();
+        const size_t cap = params.num_result > 0 ? static_cast<size_t>(params.num_result) : 1;
+        std::vector<double> poses(16 * cap), q(4 * cap), t(3 * cap), scores(cap);
+        std::vector<uint64_t> votes(cap);
+        size_t count = 0;
+        CheckStatus(m3d_ppf_estimate(model_, scene_points, scene_normals, m, reference.data(), reference.size(), &p, cap, &count,
+                                     poses.data(), q.data(), t.data(), votes.data(), scores.data(), stats));
+        std::vector<Pose6D> out(count);
+        for (size_t k = 0; k < count; ++k) {
+            for (int e = 0; e < 16; ++e) out[k].pose[e] = poses[16 * k + e];
+            for (int e = 0; e < 4; ++e) out[k].q[e] = q[4 * k + e];
+            for (int e = 0; e < 3; ++e) out[k].t[e] = t[3 * k + e];
+            out[k].num_votes = static_cast<size_t>(votes[k]);
+            out[k].score = scores[k];
+            out[k].object_id = params.object_id;
         }
         return out;
     }

@@ -1034,8 +1034,9 @@ int m3d_set_config(const m3d_config *in);
 /* ---- PPF voting: the table and the vote of misc3d::pose_estimation::PPFEstimator, src/ppf_estimation.cpp -----------------
  * The two device hot paths of the class: CalcHashTable (:603-640) with GenerateModelPCNeighbor (:1236-1253) behind
  * m3d_ppf_model_create, VotingAndGetPose (:399-524) with CalcLocalMaximum (:1170-1234) behind m3d_ppf_vote.  Both take
- * ALREADY SAMPLED points with unit normals (row-major n x 3 doubles): PreprocessTrain / PreprocessEstimate, ClusterPoses /
- * PoseAverage, the EdgePoints mode, the scoring and the PPFEstimator class itself are not part of this build.
+ * ALREADY SAMPLED points with unit normals (row-major n x 3 doubles).  ClusterPoses / PoseAverage, the refinement and the
+ * scoring are below ("PPF pose clustering"); PreprocessTrain / PreprocessEstimate, the EdgePoints mode and the PPFEstimator
+ * class itself are not part of this build.
  * The text below is the contract; tests/cpp/ppf_ref.c restates it in serial C.
  *
  * MODEL (Train, :537-570, VotingMode::SampledPoints).  points[n], normals[n], diameter, r_min and m3d_ppf_params.
@@ -1146,6 +1147,120 @@ int m3d_ppf_model_table(const m3d_ppf_model *model, m3d_ppf_table_info *info, ui
 int m3d_ppf_vote(const m3d_ppf_model *model, const double *scene_points, const double *scene_normals, size_t m,
                  const size_t *reference, size_t n_ref, size_t capacity, size_t *n_maxima, uint32_t *ref_pos,
                  uint32_t *model_index, uint32_t *alpha_index, uint32_t *votes, double *poses, m3d_ppf_vote_stats *stats);
+
+/* ---- PPF pose clustering: ClusterPoses, PoseAverage, RefineSparsePose, the centre shift and the scoring of
+ * misc3d::pose_estimation::PPFEstimator, src/ppf_estimation.cpp -------------------------------------------------------------
+ * Raw poses in, ranked and refined Pose6D results out: ClusterPoses (:871-935) with GatherPose (:778-836), CalcPoseNeighbor
+ * (:838-869) and MatchPose (:745-776), PoseAverage (:992-1016), RefineSparsePose (:937-990), the centre shift (:342-351) and the
+ * scoring (:353-392).  m3d_ppf_cluster_poses is K1 - K6, m3d_ppf_estimate is the vote and K1 - K8 (Estimate from :304 on).
+ * PreprocessTrain / PreprocessEstimate, the EdgePoints voting mode and the PPFEstimator / PPFEstimatorConfig classes are not
+ * part of this build.  The text below is the contract; tests/cpp/ppf_cluster_ref.c restates it in serial C.
+ *
+ * INPUT.  poses[P] (row-major 4 x 4 doubles, poses of the CENTRED model as m3d_ppf_vote returns them) and votes[P].
+ *   K1. Order: by votes descending, ties by ascending input index (the reference's std::sort leaves ties open; m3d_ppf_vote's
+ *       output order is (reference position, model index), so this order is a fixed one).  Every index below is a position
+ *       in this sorted list.
+ *   K2. Cut: threshold = size_t(votes[0] 0.5); the valid poses are the prefix with votes >= threshold (:880-886).
+ *   K3. Translation neighbours (:888-907): j is a neighbour of i (and i of itself) when d2 < r r, d2 = (dx dx + dy dy) + dz dz
+ *       without contraction, r = dist_threshold (the reference's rel_dist_thresh_ x diameter), r r computed once on the host.
+ *       d2 < r^2 is the library's neighbourhood rule and nanoflann's.
+ *   K4. GatherPose, restated without its stack.  min_num_pt = int(max(6, the largest neighbour count) / 2.0).  A pose is a
+ *       core when its count, itself included, is >= min_num_pt.  A cluster is a connected component of cores under the
+ *       neighbour relation.  A non-core pose joins the cluster that starts first among the clusters of its core neighbours --
+ *       a cluster starts at its lowest core index, so that is the cluster with the lowest minimum core index -- and is dropped
+ *       when it has no core neighbour.  Cluster votes are the integer sum of member votes.  Clusters are sorted by votes
+ *       descending, ties by lowest member.  Members are kept in ascending index.
+ *   K5. Level 2, inside each translation cluster with its members ascending.  The match relation is MatchPose(.., 3)'s:
+ *       d2 < r r and ca > cos_edge, ca = (trace - 1) / 2, trace the serial sum of the nine products src(r, c) dst(r, c) in
+ *       row-major order, cos_edge = cos(angle_threshold) computed once on the host.  No acos runs on the device: acos(ca) <
+ *       thr is ca > cos(thr), and the reference's clamps at ca > 1 and ca < -1 fall out of the compare.  Level 2 uses d2 < r r
+ *       where the reference compares norm() < r; they differ only within an ulp of the threshold.  Then K4 again inside the
+ *       cluster, with the cluster's own min_num_pt and the level-2 counts.
+ *   K6. PoseAverage per sub-cluster, members ascending, on the host: the 10 distinct sums of q q^T with q = MatToQuat(R)
+ *       (data_structure.h:58-87), the three t sums, the integer vote sum; the eigenvector of the largest eigenvalue by a
+ *       cyclic Jacobi solver for the symmetric 4 x 4, signed so that its component of largest magnitude (lowest index on ties)
+ *       is positive; t_avg = sum x (1.0 / count); the pose by QuatToMat.
+ *   K7. Refinement per translation cluster that has at least one sub-cluster, in translation-cluster order: the averaged pose
+ *       with the most votes (the first wins ties: std::max_element); ICP of the model's centred points against the scene from
+ *       that pose, max_correspondence_distance = rel_dist_sparse_thresh x dist_step, criteria (1e-6, 1e-6, 30).
+ *       refine_method: M3D_PPF_REFINE_NONE, M3D_PPF_REFINE_POINT_TO_POINT (the body of m3d_registration_icp) or
+ *       M3D_PPF_REFINE_POINT_TO_PLANE (the body of m3d_registration_icp_plane_l1), unchanged, on the call's own lane.  The result
+ *       keeps the picked sub-cluster's votes.
+ *   K8. Centre shift T(i, 3) -= (c0 T(i, 0) + c1 T(i, 1)) + c2 T(i, 2); a STABLE sort by votes descending; expected =
+ *       ((ratio n) n) 0.25 with n the model size (0.25 is VOTES_NUM_REDUCTION_FACTOR: this build votes in SampledPoints mode
+ *       only), score = min(1.0, votes / expected); results are cut at the first score below score_thresh and capped at
+ *       num_result; q and t of each result by MatToQuat, as UpdateByPose does.
+ * WHERE THE REFERENCE'S ORDER IS ARRIVAL ORDER.  The reference keeps a cluster's members in the depth-first order in which its
+ * stack met them, and walks level 2 in that order; here members are ascending.  At level 1 the member sets are the reference's
+ * exactly.  At level 2 the order decides only two things: which sub-cluster a border pose with core neighbours in two
+ * sub-clusters joins, and the order of sub-clusters whose votes tie.  PoseAverage adds the members in depth-first order there,
+ * so its floating-point sums can differ in the last bits.  RefineSparsePose appends its results inside a `critical` section:
+ * here they come in translation-cluster order.
+ * REFUSALS AND EMPTY CASES.  M3D_ERR_INVALID_ARG: a non-finite pose entry; dist_threshold not positive and finite;
+ * angle_threshold outside (0, pi]; ratio, score_thresh or rel_dist_sparse_thresh not finite, or ratio <= 0; an unknown
+ * refine_method.  M3D_OK with zero results: P == 0, or no clusters (the reference's `return false`).  More than 262 144 valid
+ * poses (K2's prefix): M3D_ERR_CAPACITY.  The call's device scratch is 124 bytes a valid pose, 31 MiB at that cap.
+ * DEVICE ("PPF pose clustering").  Per level six launches on one lane and one stream: a tiled all-pairs count
+ * (256 poses a workgroup, the j side through LDS in tiles of 256), an atomic max (one word at level 1, one per translation
+ * cluster at level 2 -- the host makes no round trip between the launches or the levels), the core flags, a lock-free union of
+ * matching cores that hooks the larger root under the smaller, a flatten pass, and the border poses' minimum root.  Every
+ * output of the device is an integer (counts, flags, labels) and none depends on scheduling or on how the j range is split
+ * over workgroups.  One read-back carries counts, labels and largest counts of both levels; K1, K2 and K6 - K8 are the host's. */
+#define M3D_PPF_REFINE_NONE 0
+#define M3D_PPF_REFINE_POINT_TO_POINT 1
+#define M3D_PPF_REFINE_POINT_TO_PLANE 2
+typedef struct m3d_ppf_cluster_params {
+    double dist_threshold;          /* rel_dist_thresh_ x diameter: 0.05 x diameter */
+    double angle_threshold;         /* rel_angle_thresh_ in RADIANS (12 degrees = pi / 15) */
+    double ratio;                   /* ref_param_.ratio, 0.6 */
+    double score_thresh;            /* score_thresh_, 0.6 */
+    double rel_dist_sparse_thresh;  /* refine_param_.rel_dist_sparse_thresh, 5 */
+    int32_t num_result;             /* num_result_, 10 */
+    int32_t refine_method;          /* M3D_PPF_REFINE_*, PointToPlane */
+    int32_t object_id;              /* object_id_, 0: copied to the results by the callers' wrappers */
+    int32_t reserved;
+} m3d_ppf_cluster_params;
+typedef struct m3d_ppf_cluster_stats {
+    uint64_t n_valid;      /* poses that survive K2 */
+    uint64_t clusters_t;   /* translation clusters (level 1) */
+    uint64_t clusters_r;   /* sub-clusters of all translation clusters (level 2) = averaged poses */
+    uint64_t pair_tests;   /* 6 n_valid^2: three all-pairs launches a level */
+    uint32_t launches;     /* kernel launches of the clustering */
+    uint32_t splits;       /* workgroups that share the j tiles of a row block */
+    double ms_device;      /* HIP events around the clustering's device work */
+    double ms_total;       /* wall clock of the call */
+} m3d_ppf_cluster_stats;
+typedef struct m3d_ppf_estimate_stats {
+    m3d_ppf_vote_stats vote;
+    m3d_ppf_cluster_stats cluster;
+    uint64_t n_raw;        /* raw poses of the vote */
+    uint32_t icp_calls;    /* K7's ICP calls */
+    uint32_t icp_iterations;
+    double ms_vote, ms_cluster, ms_refine, ms_host;   /* wall clock: the vote, K1 - K6, K7, and the rest (K8, copies) */
+    double ms_total;
+} m3d_ppf_estimate_stats;
+/* the reference's defaults; dist_threshold = 0.05 x the model's diameter (model == NULL: 0.05) */
+void m3d_ppf_default_cluster_params(const m3d_ppf_model *model, m3d_ppf_cluster_params *out);
+/* K1 - K6.  Per valid pose (pose_capacity entries each): order (its input index), count_t / count_r (neighbour counts of the
+ * two levels, count_r 0 outside every translation cluster), label_t (the rank of its translation cluster, -1: dropped),
+ * label_r (the rank of its sub-cluster inside that cluster, -1: dropped).  min_num_pt_t: one value.  Per translation
+ * cluster (cluster_capacity entries each): min_num_pt_r, cluster_votes.  Per averaged pose, in (translation cluster,
+ * sub-cluster) order (cluster_capacity entries each): avg_poses (x 16 doubles), avg_votes, avg_cluster (its translation
+ * cluster).  *n_valid, *n_clusters_t and *n_clusters_r are always set.  n_valid > pose_capacity, or a cluster count >
+ * cluster_capacity: M3D_ERR_CAPACITY, nothing is written to the arrays, and the three counts say what the call needs.  Every
+ * array may be NULL when its capacity is 0. */
+int m3d_ppf_cluster_poses(const double *poses, const uint32_t *votes, size_t P, const m3d_ppf_cluster_params *params, int device,
+                          size_t pose_capacity, size_t *n_valid, uint32_t *order, uint32_t *count_t, int32_t *label_t,
+                          uint32_t *count_r, int32_t *label_r, size_t cluster_capacity, size_t *n_clusters_t, size_t *n_clusters_r,
+                          int32_t *min_num_pt_t, int32_t *min_num_pt_r, uint64_t *cluster_votes, double *avg_poses,
+                          uint64_t *avg_votes, uint32_t *avg_cluster, m3d_ppf_cluster_stats *stats);
+/* The vote and K1 - K8.  scene_points / scene_normals / reference as m3d_ppf_vote takes them; params == NULL: the defaults.
+ * Results (capacity entries each; capacity >= num_result always suffices): poses (x 16 doubles, of the UNCENTRED model), q (x 4:
+ * w, x, y, z), t (x 3), votes, scores.  More results than capacity: M3D_ERR_CAPACITY with *n_results the needed count. */
+int m3d_ppf_estimate(const m3d_ppf_model *model, const double *scene_points, const double *scene_normals, size_t m,
+                     const size_t *reference, size_t n_ref, const m3d_ppf_cluster_params *params, size_t capacity,
+                     size_t *n_results, double *poses, double *q, double *t, uint64_t *votes, double *scores,
+                     m3d_ppf_estimate_stats *stats);
 
 /* ---- misc -------------------------------------------------------------------------------------- */
 const char *m3d_last_error(void); /* thread-local; reference message text for M3D_ERR_* */

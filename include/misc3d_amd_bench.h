@@ -127,6 +127,11 @@ unsigned m3d_bench_match_last_path(void);
  * reference positions in turn).  The result does not depend on either. */
 int m3d_bench_ppf_force(int device_memory_path, int max_groups);
 
+/* MEASUREMENT / TEST hook (tests/test_gpu_ppf_cluster.py): every later m3d_ppf_cluster_poses / m3d_ppf_estimate in the
+ * process lets `splits` workgroups share the j tiles of a row block of the pair kernels (0: by the number of row blocks, the
+ * default).  The result does not depend on it. */
+int m3d_bench_ppf_cluster_force(int splits);
+
 #ifdef __cplusplus
 }
 #endif

@@ -607,8 +607,10 @@ class PPFVoting:
     (CalcHashTable, :603-640) and the vote of a scene against it (VotingAndGetPose, :399-524).  points / normals: the ALREADY
     SAMPLED model points with unit normals ((N, 3) arrays, 2 <= N <= 65535); diameter, r_min: what PreprocessTrain derives
     from the model's bounding box.  params: rel_sample_dist (0.05), angle_step (radians, 12 degrees), min_dist_thresh (1/3),
-    min_angle_thresh (radians, 30 degrees), faster_mode (True) -- the reference's config fields.  The preprocessing, the pose
-    clustering, the scoring and the PPFEstimator class itself are not part of this build."""
+    min_angle_thresh (radians, 30 degrees), faster_mode (True) -- the reference's config fields.  cluster_poses and estimate
+    turn the raw poses into ranked, refined results (ClusterPoses, PoseAverage, RefineSparsePose, the centre shift and the
+    scoring).  The preprocessing (PreprocessTrain / PreprocessEstimate), the EdgePoints voting mode and the PPFEstimator /
+    PPFEstimatorConfig classes themselves are not part of this build: the caller samples the points."""
 
     def __init__(self, points, normals, diameter, r_min, *, device=0, **params):
         from . import capi as _capi
@@ -646,12 +648,50 @@ class PPFVoting:
             raise RuntimeError(str(e)) from e
         return r["poses"], r["votes"].astype(_np.int64), r["model_index"].astype(_np.int64), r["ref_pos"].astype(_np.int64)
 
+    def cluster_poses(self, poses, num_votes, **params):
+        """ClusterPoses with PoseAverage (:871-935, :992-1016) of raw poses as vote() returns them.  params: dist_threshold
+        (0.05 x diameter), angle_threshold (radians, 12 degrees) and the other fields of m3d_ppf_cluster_params.  -> dict: per valid
+        pose (votes descending, ties by input index) order, count_t, label_t, count_r, label_r; min_num_pt_t; per translation
+        cluster min_num_pt_r, cluster_votes; per sub-cluster, in (translation cluster, sub-cluster) order, avg_poses (K, 4, 4),
+        avg_votes, avg_cluster; stats."""
+        from . import capi as _capi
+        try:
+            return _capi.ppf_cluster_poses(poses, num_votes, device=self._model.device, model=self._model, **params)
+        except _capi.M3DError as e:
+            raise RuntimeError(str(e)) from e
+
+    def estimate(self, scene_points, scene_normals, reference_indices, **params):
+        """Estimate from the vote on (:304-395): vote, cluster, average, refine, shift by the centroid, score.  params: the fields
+        of m3d_ppf_cluster_params -- dist_threshold, angle_threshold (radians), ratio (0.6), score_thresh (0.6),
+        rel_dist_sparse_thresh (5), num_result (10), refine_method ("NoRefine", "PointToPoint" or "PointToPlane", the default),
+        object_id.  -> a list of Pose6D (pose of the UNCENTRED model, q, t, num_votes, score, object_id), best first."""
+        from . import capi as _capi
+        try:
+            r = _capi.ppf_estimate(self._model, scene_points, scene_normals, reference_indices, **params)
+        except _capi.M3DError as e:
+            raise RuntimeError(str(e)) from e
+        return [Pose6D(r["poses"][k].copy(), r["q"][k].copy(), r["t"][k].copy(), int(r["votes"][k]), float(r["scores"][k]), r["object_id"])
+                for k in range(len(r["votes"]))]
+
+
+class Pose6D:
+    """misc3d.pose_estimation.Pose6D's fields (data_structure.h): pose (4, 4), q (w, x, y, z), t, num_votes, score, object_id"""
+    __slots__ = ("pose", "q", "t", "num_votes", "score", "object_id")
+
+    def __init__(self, pose, q, t, num_votes, score, object_id):
+        self.pose, self.q, self.t, self.num_votes, self.score, self.object_id = pose, q, t, num_votes, score, object_id
+
+    def __repr__(self):
+        return f"Pose6D(num_votes={self.num_votes}, score={self.score:.4f}, object_id={self.object_id})"
+
 
 class _PoseEstimation:
-    """misc3d.pose_estimation (python/py_pose_estimation.cpp): RayCastRenderer.  PPFEstimator is not part of this build; its
-    table and its voting are here, as PPFVoting."""
+    """misc3d.pose_estimation (python/py_pose_estimation.cpp): RayCastRenderer.  PPFEstimator is not part of this build as a
+    class; its table, its voting, its pose clustering, refinement and scoring are here, as PPFVoting (the preprocessing is the
+    caller's)."""
     RayCastRenderer = RayCastRenderer
     PPFVoting = PPFVoting
+    Pose6D = Pose6D
 
 
 pose_estimation = _PoseEstimation()

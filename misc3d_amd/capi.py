@@ -225,6 +225,12 @@ def lib():
         L.m3d_ppf_model_table.argtypes = [C.c_void_p] * 8
         L.m3d_ppf_vote.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t] + [C.c_void_p] * 7
         L.m3d_bench_ppf_force.argtypes = [C.c_int, C.c_int]
+        L.m3d_ppf_default_cluster_params.restype = None
+        L.m3d_ppf_default_cluster_params.argtypes = [C.c_void_p, C.c_void_p]
+        L.m3d_ppf_cluster_poses.argtypes = ([C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 6 +
+                                            [C.c_size_t] + [C.c_void_p] * 9)
+        L.m3d_ppf_estimate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_void_p] * 7
+        L.m3d_bench_ppf_cluster_force.argtypes = [C.c_int]
         L.m3d_estimate_normals.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                            C.c_void_p, C.c_void_p]
         L.m3d_compute_fpfh.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p,
@@ -1610,6 +1616,7 @@ class PpfModel:
         if not self.h:
             raise M3DError(status.value, last_error())
         self.n = len(pts)
+        self.device = int(device)
         c = np.zeros(3)
         _check(lib().m3d_ppf_model_centroid(self.h, _p(c)))
         self.centroid = c
@@ -1666,6 +1673,116 @@ class PpfModel:
         res = dict(ref_pos=out[0][:k.value], model_index=out[1][:k.value], alpha_index=out[2][:k.value], votes=out[3][:k.value],
                    poses=poses[:k.value])
         return (res, st.asdict()) if stats else res
+
+
+PPF_REFINE_NONE, PPF_REFINE_POINT_TO_POINT, PPF_REFINE_POINT_TO_PLANE = 0, 1, 2
+PPF_REFINE_METHODS = {"NoRefine": PPF_REFINE_NONE, "PointToPoint": PPF_REFINE_POINT_TO_POINT, "PointToPlane": PPF_REFINE_POINT_TO_PLANE}
+
+
+class PpfClusterParams(C.Structure):
+    """m3d_ppf_cluster_params (angle in radians)"""
+    _fields_ = [("dist_threshold", C.c_double), ("angle_threshold", C.c_double), ("ratio", C.c_double), ("score_thresh", C.c_double),
+                ("rel_dist_sparse_thresh", C.c_double), ("num_result", C.c_int32), ("refine_method", C.c_int32),
+                ("object_id", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PpfClusterStats(C.Structure):
+    """m3d_ppf_cluster_stats"""
+    _fields_ = [("n_valid", C.c_uint64), ("clusters_t", C.c_uint64), ("clusters_r", C.c_uint64), ("pair_tests", C.c_uint64),
+                ("launches", C.c_uint32), ("splits", C.c_uint32), ("ms_device", C.c_double), ("ms_total", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PpfEstimateStats(C.Structure):
+    """m3d_ppf_estimate_stats"""
+    _fields_ = [("vote", PpfVoteStats), ("cluster", PpfClusterStats), ("n_raw", C.c_uint64), ("icp_calls", C.c_uint32),
+                ("icp_iterations", C.c_uint32), ("ms_vote", C.c_double), ("ms_cluster", C.c_double), ("ms_refine", C.c_double),
+                ("ms_host", C.c_double), ("ms_total", C.c_double)]
+
+    def asdict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("vote", "cluster")}
+        d["vote"], d["cluster"] = self.vote.asdict(), self.cluster.asdict()
+        return d
+
+
+def ppf_cluster_params(model=None, **kw):
+    """the defaults of m3d_ppf_default_cluster_params (dist_threshold = 0.05 x the model's diameter; 0.05 without a model) with
+    the given fields replaced; refine_method may be one of the reference's names (NoRefine, PointToPoint, PointToPlane)"""
+    P = PpfClusterParams()
+    lib().m3d_ppf_default_cluster_params(model.h if model is not None else None, C.cast(C.byref(P), C.c_void_p))
+    for k, v in kw.items():
+        if k not in dict(PpfClusterParams._fields_) or k == "reserved":
+            raise TypeError(f"ppf_cluster_params: no parameter {k!r}")
+        if k == "refine_method" and isinstance(v, str):
+            v = PPF_REFINE_METHODS[v]
+        setattr(P, k, int(v) if k in ("num_result", "refine_method", "object_id") else float(v))
+    return P
+
+
+def ppf_cluster_poses(poses, votes, device=0, model=None, pose_capacity=None, cluster_capacity=None, **params):
+    """m3d_ppf_cluster_poses (K1 - K6 of "PPF pose clustering") -> dict(order, count_t, label_t, count_r, label_r (per valid pose),
+    min_num_pt_t, min_num_pt_r, cluster_votes (per translation cluster), avg_poses (K, 4, 4), avg_votes, avg_cluster, stats).
+    Capacities None: the call is repeated once with the needed ones; given capacities are final (M3DError with code
+    ERR_CAPACITY and .needed = (n_valid, clusters_t, clusters_r))."""
+    T = _f64(poses).reshape(-1, 4, 4)
+    v = np.ascontiguousarray(votes, dtype=np.uint32).reshape(-1)
+    if len(T) != len(v):
+        raise ValueError("ppf: one vote count per pose")
+    P = ppf_cluster_params(model, **params)
+    fixed = pose_capacity is not None or cluster_capacity is not None
+    pcap = len(T) if pose_capacity is None else int(pose_capacity)
+    ccap = 64 if cluster_capacity is None else int(cluster_capacity)
+    while True:
+        per_pose = [np.zeros(max(pcap, 1), dt) for dt in (np.uint32, np.uint32, np.int32, np.uint32, np.int32)]
+        min_r, cvotes = np.zeros(max(ccap, 1), np.int32), np.zeros(max(ccap, 1), np.uint64)
+        avg, avotes, acl = np.zeros((max(ccap, 1), 4, 4)), np.zeros(max(ccap, 1), np.uint64), np.zeros(max(ccap, 1), np.uint32)
+        nv, nt, nr, min_t = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_int32(0)
+        st = PpfClusterStats()
+        ref = lambda x: C.cast(C.byref(x), C.c_void_p)
+        rc = lib().m3d_ppf_cluster_poses(_p(T), _p(v), len(T), ref(P), int(device), pcap, ref(nv), *(_p(a) for a in per_pose), ccap,
+                                         ref(nt), ref(nr), ref(min_t), _p(min_r), _p(cvotes), _p(avg), _p(avotes), _p(acl), ref(st))
+        if rc == ERR_CAPACITY and not fixed and (nv.value > pcap or max(nt.value, nr.value) > ccap):
+            pcap, ccap, fixed = max(pcap, nv.value), max(ccap, nt.value, nr.value), True
+            continue
+        if rc < 0:
+            e = M3DError(rc, last_error())
+            e.needed = (nv.value, nt.value, nr.value)
+            raise e
+        break
+    n, ct, cr = nv.value, nt.value, nr.value
+    return dict(order=per_pose[0][:n], count_t=per_pose[1][:n], label_t=per_pose[2][:n], count_r=per_pose[3][:n], label_r=per_pose[4][:n],
+                min_num_pt_t=int(min_t.value), min_num_pt_r=min_r[:ct], cluster_votes=cvotes[:ct], avg_poses=avg[:cr],
+                avg_votes=avotes[:cr], avg_cluster=acl[:cr], stats=st.asdict())
+
+
+def ppf_estimate(model, scene_points, scene_normals, reference, capacity=None, **params):
+    """m3d_ppf_estimate (the vote and K1 - K8) on a PpfModel -> dict(poses (K, 4, 4), q (K, 4), t (K, 3), votes, scores, object_id,
+    stats)"""
+    sp, sn = _f64(scene_points).reshape(-1, 3), _f64(scene_normals).reshape(-1, 3)
+    if len(sp) != len(sn):
+        raise ValueError("ppf: one normal per scene point")
+    ref = np.ascontiguousarray(reference, dtype=np.uint64).reshape(-1)
+    P = ppf_cluster_params(model, **params)
+    cap = max(int(P.num_result), 1) if capacity is None else int(capacity)
+    poses, q, t = np.zeros((max(cap, 1), 4, 4)), np.zeros((max(cap, 1), 4)), np.zeros((max(cap, 1), 3))
+    votes, scores = np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1))
+    k = C.c_size_t(0)
+    st = PpfEstimateStats()
+    rc = lib().m3d_ppf_estimate(model.h, _p(sp), _p(sn), len(sp), _p(ref), len(ref), C.cast(C.byref(P), C.c_void_p), cap,
+                                C.cast(C.byref(k), C.c_void_p), _p(poses), _p(q), _p(t), _p(votes), _p(scores), C.cast(C.byref(st), C.c_void_p))
+    if rc < 0:
+        e = M3DError(rc, last_error())
+        e.needed = k.value
+        raise e
+    n = k.value
+    return dict(poses=poses[:n], q=q[:n], t=t[:n], votes=votes[:n], scores=scores[:n], object_id=int(P.object_id), stats=st.asdict())
+
+
+def ppf_cluster_force(splits=0):
+    """test / measurement hook m3d_bench_ppf_cluster_force: `splits` workgroups share the j tiles of a row block (0: default)"""
+    _check(lib().m3d_bench_ppf_cluster_force(int(splits)))
 
 
 def ppf_force(device_memory_path=False, max_groups=0):

@@ -4,6 +4,7 @@
 // Nothing here depends on M3D_FP_ORDER (every sum is written out).
 #include "m3d_driver_internal.hpp"
 #include "m3d_ppf.hpp"
+#include "m3d_ppf_cluster.hpp"
 #include "m3d_radix_sort.hpp"
 
 #include "../../include/misc3d_amd_bench.h"
@@ -102,12 +103,13 @@ struct VoteBufs {
 struct m3d_ppf_model {
     int device = 0;
     uint32_t n = 0;
-    double r_min = 0.0, angle_step = 0.0, min_dist_thresh = 0.0, min_angle_thresh = 0.0;
+    double diameter = 0.0, r_min = 0.0, angle_step = 0.0, min_dist_thresh = 0.0, min_angle_thresh = 0.0;
     PpfSizes sizes{};
     PpfTables T{};                // (dist_edge2 points at edge2 below: the host's copy)
     std::vector<double> edge2;
     double centroid[3] = {0, 0, 0};
     std::vector<double> tmg;      // n x 16
+    std::vector<double> centred;  // n x 3: the host's copy of pts (the source cloud of m3d_ppf_estimate's refinement)
     uint32_t n_entries = 0, n_neighbors = 0;
     m3d::DevBuf pts, nrm, frames, d_edge2, cell_off, entries, nbr_off, nbr_idx;
     void release() {
@@ -206,6 +208,18 @@ int ppf_build_table(DeviceCtx* ctx, m3d_ppf_model* h) {
 
 }  // namespace
 
+// what m3d_ppf_cluster.cpp reads of a model (m3d_ppf_cluster.hpp)
+m3d::PpfModelHost m3d::ppf_model_host(const m3d_ppf_model* h) {
+    PpfModelHost v;
+    v.n = h->n;
+    v.device = h->device;
+    v.diameter = h->diameter;
+    v.dist_step = h->sizes.dist_step;
+    v.centroid = h->centroid;
+    v.centred = h->centred.data();
+    return v;
+}
+
 extern "C" {
 
 void m3d_ppf_default_params(m3d_ppf_params* out) {
@@ -246,6 +260,7 @@ m3d_ppf_model* m3d_ppf_model_create(const double* points, const double* normals,
     m3d_ppf_model* h = new m3d_ppf_model;
     h->device = device;
     h->n = (uint32_t)n;
+    h->diameter = diameter;
     h->r_min = r_min;
     h->angle_step = P.angle_step;
     h->min_dist_thresh = P.min_dist_thresh;
@@ -257,7 +272,9 @@ m3d_ppf_model* m3d_ppf_model_create(const double* points, const double* normals,
     for (size_t i = 0; i < n; ++i)
         for (int k = 0; k < 3; ++k) c[k] += points[3 * i + k];
     for (int k = 0; k < 3; ++k) h->centroid[k] = c[k] / static_cast<double>(n);
-    std::vector<double> centred(3 * n), rows(8 * n);
+    std::vector<double>& centred = h->centred;
+    centred.resize(3 * n);
+    std::vector<double> rows(8 * n);
     h->tmg.resize(16 * n);
     for (size_t i = 0; i < n; ++i) {
         for (int k = 0; k < 3; ++k) centred[3 * i + k] = points[3 * i + k] - h->centroid[k];

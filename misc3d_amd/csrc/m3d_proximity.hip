@@ -2,55 +2,19 @@
 // components of the graph "j in the radius neighbourhood of i and evaluator(i, j, dist)" ("Proximity
 // extraction"), found with a lock-free union-find over original point indices.
 //
-// parent[] invariant: parent[x] <= x, and only a root (parent[x] == x) is ever written -- by a compare-and-swap that hooks
-// the LARGER of two roots under the smaller.  Pointers only decrease, so every walk ends, no cycle can form, and the root
-// of a finished tree is the smallest index of its component.
-//
-// Coherence (MI355X: one L2 per XCD, a plain load may hit a line another XCD has since changed): the walks read parent[]
-// with agent-scope atomic loads, and every write is an agent-scope compare-and-swap.  Correctness rests on the CAS return
-// values alone: a stale read can only show an older -- larger or equal -- ancestor, which is still in the same tree, and a
-// CAS on a "root" that has been hooked meanwhile fails and returns the new parent to continue from.  Hooking b under a
-// non-root a < b is harmless for the same reason.  The flatten kernel runs after the union launch has ended and reads
-// with plain loads.
+// The union-find (uf_find, uf_unite), its parent[] invariant and its coherence argument are in m3d_union_find.hpp; the
+// flatten kernel runs after the union launch has ended and reads with plain loads.
 #include <hip/hip_runtime.h>
 
 #include "m3d_grid_cell.hpp"
 #include "m3d_proximity.hpp"
+#include "m3d_union_find.hpp"
 
 #pragma clang fp contract(off)
 
 namespace m3d {
 
 namespace {
-
-__device__ __forceinline__ uint32_t prox_load(const uint32_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint32_t prox_find(const uint32_t* parent, uint32_t x) {
-    for (;;) {
-        const uint32_t p = prox_load(parent + x);
-        if (p == x) return x;
-        x = p;
-    }
-}
-__device__ __forceinline__ void prox_unite(uint32_t* parent, uint32_t a, uint32_t b) {
-    a = prox_find(parent, a);
-    b = prox_find(parent, b);
-    for (;;) {
-        if (a == b) return;
-        if (a > b) {
-            const uint32_t t = a;
-            a = b;
-            b = t;
-        }
-        uint32_t expected = b;   // hook root b under a < b
-        if (__hip_atomic_compare_exchange_strong(parent + b, &expected, a, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT))
-            return;
-        b = prox_find(parent, expected);   // b was hooked meanwhile: continue from its tree's root
-        a = prox_find(parent, a);
-    }
-}
 
 // visit(u, d2) for every grid slot u of the 3x3x3 block around sorted point t whose d2 is within the radius (t included)
 template <class F>
@@ -106,7 +70,7 @@ __global__ __launch_bounds__(256) void prox_union_grid_k(GridDesc g, const uint3
         const uint32_t j = cell_orig[u];
         if (j <= i) return;   // every unordered pair once (both built-in evaluators are symmetric)
         const double dot = normals ? dot3(ax, ay, az, snx[u], sny[u], snz[u]) : 0.0;
-        if (prox_accept(cut, d2, dot)) prox_unite(parent, i, j);
+        if (prox_accept(cut, d2, dot)) uf_unite(parent, i, j);
     });
 }
 
@@ -125,7 +89,7 @@ __global__ __launch_bounds__(256) void prox_union_lists_k(CloudView c, const uin
         const double dx = px - c.x[j], dy = py - c.y[j], dz = pz - c.z[j];
         const double d2 = dot3(dx, dy, dz, dx, dy, dz);   // (p_i - p_j).norm() before its sqrt
         const double dot = normals ? dot3(ax, ay, az, c.nx[j], c.ny[j], c.nz[j]) : 0.0;
-        if (prox_accept(cut, d2, dot)) prox_unite(parent, i, j);
+        if (prox_accept(cut, d2, dot)) uf_unite(parent, i, j);
     }
 }
 

@@ -16,6 +16,7 @@ bench.py); these lines feed DESIGN.md section 6 and check that the full sizes ru
   R1 - R3 RayCastRenderer: the reference example (640 x 480, obj.ply at its two poses), 1920 x 1080 with 64 instances, and a
           100-frame batch of the example
   PV1 PPFVoting: the table of a 2 000-point model and the vote of a 20 000-point scene at ratio 0.6, LDS / device memory A/B
+  PC1 PPF pose clustering on PV1's scene: the vote's raw poses through m3d_ppf_cluster_poses, and the whole m3d_ppf_estimate
 """
 import json
 import os
@@ -1039,5 +1040,60 @@ if "PV1" in which or ALL:
          device_memory_path={"ms_vote": ms_vote_dev, "ms_vote_device": st_dev["ms_device"], "path": st_dev["path"],
                              "same_result": bool(all(np.array_equal(res[k], res_dev[k]) for k in res))},
          roofline={"bound": "atomic increments (LDS or L2) and the divergent walk over table cells; no HBM or VALU ceiling is meaningful",
+                   "share_of_peak": "not measured"},
+         cpu_baseline=cpu_b)
+
+if "PC1" in which or ALL:
+    # PPF pose clustering ("PPF pose clustering") on PV1's model and scene: the vote's raw poses through
+    # m3d_ppf_cluster_poses (median of 5 calls after 1 warm-up), then the whole m3d_ppf_estimate with its own split into vote,
+    # cluster, refine and host (median of 3 by total; score_thresh 0 so that the list is not empty: the reference's expected
+    # votes assume its own sampling).  cpu_baseline = the contract's C restatement of K1 - K6 (tests/cpp/ppf_cluster_ref.c)
+    # under OpenMP on 16 threads, on the same raw poses.
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ppf_cluster_ref_util as pc_util
+    import ppf_ref_util as ppf_util
+
+    pts, nrm, diameter, r_min = ppf_util.model_case("box", 2000)
+    sp, sn, _ = ppf_util.scene_of(pts, nrm, ppf_util.pose(1), 18_000, 1)
+    refs = np.sort(np.random.default_rng(1).permutation(len(sp))[: int(0.6 * len(sp))])
+
+    def pc_median(fn, reps):
+        fn()
+        runs = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            r = fn()
+            runs.append(((time.perf_counter() - t0) * 1e3, r))
+        runs.sort(key=lambda t: t[0])
+        return runs[len(runs) // 2]
+
+    model = capi.PpfModel(pts, nrm, diameter, r_min)
+    raw = model.vote(sp, sn, refs)
+    ms_cluster, cl = pc_median(lambda: capi.ppf_cluster_poses(raw["poses"], raw["votes"], model=model), 5)
+    ms_estimate, est = pc_median(lambda: capi.ppf_estimate(model, sp, sn, refs, score_thresh=0.0), 3)
+    ms_norefine, est0 = pc_median(lambda: capi.ppf_estimate(model, sp, sn, refs, score_thresh=0.0, refine_method="NoRefine"), 3)
+    es = est["stats"]
+    cpu_b = None
+    if not NO_CPU:
+        os.environ.setdefault("OMP_NUM_THREADS", "16")
+        ref = pc_util.PcRef(tempfile.mkdtemp(), openmp=True)
+        t0 = time.perf_counter()
+        rc = ref.cluster(raw["poses"], raw["votes"], 0.05 * diameter, 12.0 / 180.0 * np.pi)
+        cpu_b = {"ms_cluster": (time.perf_counter() - t0) * 1e3, "unit": "ms",
+                 "same_integers": bool(all(np.array_equal(np.asarray(rc[k]).astype(np.int64), np.asarray(cl[k]).astype(np.int64)) for k in pc_util.INT_KEYS)),
+                 "what": "tests/cpp/ppf_cluster_ref.c: the contract's restatement of K1 - K6, gcc -O2 -ffp-contract=off -fopenmp, 16 threads"}
+    st = cl["stats"]
+    emit("PC1 ppf pose clustering of PV1's raw poses + the whole m3d_ppf_estimate", n=len(pts), m=len(sp), n_ref=len(refs),
+         raw_poses=len(raw["votes"]), n_valid=st["n_valid"], clusters_t=st["clusters_t"], clusters_r=st["clusters_r"],
+         min_num_pt_t=cl["min_num_pt_t"], pair_tests=st["pair_tests"], launches=st["launches"], splits=st["splits"],
+         ms_cluster=ms_cluster, ms_cluster_device=st["ms_device"], pair_tests_per_second=st["pair_tests"] / (st["ms_device"] * 1e-3),
+         estimate={"ms_total": ms_estimate, "ms_vote": es["ms_vote"], "ms_cluster": es["ms_cluster"], "ms_refine": es["ms_refine"],
+                   "ms_host": es["ms_host"], "icp_calls": es["icp_calls"], "icp_iterations": es["icp_iterations"],
+                   "results": len(est["votes"]), "top_votes": int(est["votes"][0]) if len(est["votes"]) else 0,
+                   "top_score": float(est["scores"][0]) if len(est["votes"]) else 0.0,
+                   "top_pose_error": float(np.abs(est["poses"][0] - ppf_util.pose(1)).max()) if len(est["votes"]) else None,
+                   "ms_total_no_refine": ms_norefine},
+         roofline={"bound": "fp64 VALU of the all-pairs loops (three launches a level) and the LDS broadcast feeding them",
                    "share_of_peak": "not measured"},
          cpu_baseline=cpu_b)
