@@ -1035,8 +1035,8 @@ int m3d_set_config(const m3d_config *in);
  * The two device hot paths of the class: CalcHashTable (:603-640) with GenerateModelPCNeighbor (:1236-1253) behind
  * m3d_ppf_model_create, VotingAndGetPose (:399-524) with CalcLocalMaximum (:1170-1234) behind m3d_ppf_vote.  Both take
  * ALREADY SAMPLED points with unit normals (row-major n x 3 doubles).  ClusterPoses / PoseAverage, the refinement and the
- * scoring are below ("PPF pose clustering"); PreprocessTrain / PreprocessEstimate, the EdgePoints mode and the PPFEstimator
- * class itself are not part of this build.
+ * scoring are below ("PPF pose clustering"), the EdgePoints mode and PreprocessEstimate below this block ("PPF voting,
+ * EdgePoints mode", m3d_ppf_prepare_scene); PreprocessTrain and the PPFEstimator class itself are not part of this build.
  * The text below is the contract; tests/cpp/ppf_ref.c restates it in serial C.
  *
  * MODEL (Train, :537-570, VotingMode::SampledPoints).  points[n], normals[n], diameter, r_min and m3d_ppf_params.
@@ -1148,13 +1148,78 @@ int m3d_ppf_vote(const m3d_ppf_model *model, const double *scene_points, const d
                  const size_t *reference, size_t n_ref, size_t capacity, size_t *n_maxima, uint32_t *ref_pos,
                  uint32_t *model_index, uint32_t *alpha_index, uint32_t *votes, double *poses, m3d_ppf_vote_stats *stats);
 
+/* ---- PPF voting, EdgePoints mode: VotingMode::EdgePoints of PPFEstimator, src/ppf_estimation.cpp -------------------------
+ * The reference's second voting mode, for flat parts whose shape is in their boundary: the table pairs the model sample with
+ * the model's EDGE points (Train, :572-593, CalcHashTable with b_same_pointset == false), the vote pairs a scene sample point
+ * with the scene's edge points (Estimate, :319-328).  Only what differs from M1 - M6, V1 - V8, U1 - U6 and K1 - K8 is said
+ * here; tests/cpp/ppf_edge_ref.c restates it in serial C.
+ *   E1. Inputs: points[n], normals[n] (the model sample), edge_points[n_e], edge_normals[n_e], diameter, r_min, params.  Sizes
+ *       as M1.  The centroid is M2's, from the n sample points alone; BOTH sets are centred by it.
+ *   E2. tmg[i] as M3, for the sample points.
+ *   E3. One candidate per ordered pair (i in the sample, j in the edges), all n n_e of them, EQUAL INDICES INCLUDED (the two
+ *       sets are different sets).  Features and bins as M4 with p_j, n_j from the edge set and alpha from tmg[i] applied to
+ *       the edge point.  U2 applies and matters: a pair with d2 == 0 is skipped -- both samplers of the reference pick
+ *       original points, so an edge point that coincides with a sample point is normal.  U3 applies.
+ *   E4. The layout is M5's: within a cell the entries (i, quant_alpha) are in ascending (i, j).
+ *   E5. The neighbour lists are M6's over the sample points.
+ *   E6. The vote takes the scene sample points[m], normals[m], reference[n_ref] (indices into the sample) and the scene's edge
+ *       points[m_e], normals[m_e].  tsg as V1 from the reference point.  The neighbours are the scene EDGE points with d2 <
+ *       r_min^2 of the reference point; n_searched is their number (the reference point is in general not one of them).
+ *   E7. The gate: vote only when n_searched > size_t(n_e 0.2) (refered_model_num = n_e, :450); maxima need max_votes >=
+ *       size_t(n_e 0.2) (:1204).
+ *   E8. V4 - V8 otherwise unchanged: n accumulator rows, the sample's neighbour lists, the output order.
+ *   E9. m3d_ppf_estimate_edges runs K1 - K7 unchanged: the ICP is the centred model sample against the scene SAMPLE (:339),
+ *       not against the edges.  K8 uses expected = (ratio n) n, without the 0.25 (:358-364: both counts are the sample's size
+ *       in either mode, the reduction factor applies to SampledPoints only).
+ * WHERE THE REFERENCE IS WRONG.  It builds a centred copy of the dense model sample (:573-584) and never uses it: :588-589
+ * select the edge points from the UNCENTRED dense_model_sample_.  Its table so pairs centred sample points with uncentred
+ * edge points and is right only for a model whose centroid is the origin.  E1 centres both sets (tests/test_ppf_edge.py shows
+ * a known pose recovered with E1 and lost with the edge set left uncentred).
+ * LIMITS.  1 <= n_e <= 65535: U6's argument gives every count <= n_e, so the 16-bit counters hold, and a row's three-window
+ * sum is <= 3 x 65535 and fits rowinfo.  n n_e <= 2^28 pairs (the 4 GiB sort scratch), beyond it M3D_ERR_DEVICE.  1 <= m_e <
+ * 2^31.  A non-finite edge point or normal is M3D_ERR_INVALID_ARG.  The 256 MiB scratch rule counts m_e scanned points and
+ * the n_ref reference points: only those are uploaded.  The accumulator path is still a function of (n, alpha_model_num).
+ * MODE MISMATCHES.  m3d_ppf_vote / m3d_ppf_estimate on an edge model, and the _edges calls on a sampled model, are
+ * M3D_ERR_INVALID_ARG with a message that names the model's mode, decided before any device is touched. */
+/* E1 - E5.  The model holds the sample with its frames, neighbour lists, centroid and ICP source, and the edge table; the
+ * same-set table is not built.  Otherwise as m3d_ppf_model_create. */
+m3d_ppf_model *m3d_ppf_model_create_edges(const double *points, const double *normals, size_t n, const double *edge_points,
+                                          const double *edge_normals, size_t n_edge, double diameter, double r_min,
+                                          const m3d_ppf_params *params, int device, int *status);
+/* n_e; 0 for a SampledPoints model (m3d_ppf_model_table reports the edge table of an edge model) */
+size_t m3d_ppf_model_edge_size(const m3d_ppf_model *model);
+/* E6 - E8; results, M3D_ERR_CAPACITY and stats exactly as m3d_ppf_vote */
+int m3d_ppf_vote_edges(const m3d_ppf_model *model, const double *scene_points, const double *scene_normals, size_t m,
+                       const size_t *reference, size_t n_ref, const double *scene_edge_points,
+                       const double *scene_edge_normals, size_t m_edge, size_t capacity, size_t *n_maxima, uint32_t *ref_pos,
+                       uint32_t *model_index, uint32_t *alpha_index, uint32_t *votes, double *poses, m3d_ppf_vote_stats *stats);
+
+/* ---- PPFEstimator::PreprocessEstimate, src/ppf_estimation.cpp:243-278: a host composition of calls of this library ---------
+ * on one device, in the reference's order:
+ *   1. points with a non-finite coordinate are dropped, order kept, their normals' rows with them (RemoveNonFinitePoints);
+ *      none left: M3D_ERR_INVALID_ARG "There is no scene point clouds." (so is n == 0).
+ *   2. normals == NULL: m3d_estimate_normals(Hybrid, radius = calc_normal_relative diameter, max_nn 30, no orientation).
+ *   3. NormalConsistent (include/misc3d/utils.h:130-144) on the host without contraction: a normal is negated when
+ *      (p.x n.x + p.y n.y) + p.z n.z > 0; then s = (n.x n.x + n.y n.y) + n.z n.z and each component is divided by sqrt(s) when
+ *      s > 0.
+ *   4. m3d_voxel_down_sample(points, normals, dist_step) -> sample_xyz / sample_normals, *n_sample rows.
+ *   5. dist_step_dense > 0: m3d_voxel_down_sample(points, normals, dist_step_dense) -> dense_xyz / dense_normals, *n_dense
+ *      rows, and m3d_detect_boundary_points(dense, dense normals, Hybrid, the radius of step 2, max_nn = pts_num, 90 degrees) ->
+ *      edge_indices (ascending, into the dense sample), *n_edges.  dist_step_dense <= 0 or NaN: no edge part, *n_dense =
+ *      *n_edges = 0 and the three dense arrays may be NULL.
+ * The voxel means' normals are NOT re-normalised (rule 5 of the voxel contract, as in the reference): they go to the vote as
+ * they are.  Every output array has capacity n rows.  Errors are those of the composed calls. */
+int m3d_ppf_prepare_scene(const double *xyz, const double *normals, size_t n, double diameter, double calc_normal_relative,
+                          double dist_step, double dist_step_dense, int pts_num, int device, double *sample_xyz,
+                          double *sample_normals, size_t *n_sample, double *dense_xyz, double *dense_normals, size_t *n_dense,
+                          size_t *edge_indices, size_t *n_edges);
+
 /* ---- PPF pose clustering: ClusterPoses, PoseAverage, RefineSparsePose, the centre shift and the scoring of
  * misc3d::pose_estimation::PPFEstimator, src/ppf_estimation.cpp -------------------------------------------------------------
  * Raw poses in, ranked and refined Pose6D results out: ClusterPoses (:871-935) with GatherPose (:778-836), CalcPoseNeighbor
  * (:838-869) and MatchPose (:745-776), PoseAverage (:992-1016), RefineSparsePose (:937-990), the centre shift (:342-351) and the
  * scoring (:353-392).  m3d_ppf_cluster_poses is K1 - K6, m3d_ppf_estimate is the vote and K1 - K8 (Estimate from :304 on).
- * PreprocessTrain / PreprocessEstimate, the EdgePoints voting mode and the PPFEstimator / PPFEstimatorConfig classes are not
- * part of this build.  The text below is the contract; tests/cpp/ppf_cluster_ref.c restates it in serial C.
+ * PreprocessTrain and the PPFEstimator / PPFEstimatorConfig classes are not part of this build.  The text below is the contract; tests/cpp/ppf_cluster_ref.c restates it in serial C.
  *
  * INPUT.  poses[P] (row-major 4 x 4 doubles, poses of the CENTRED model as m3d_ppf_vote returns them) and votes[P].
  *   K1. Order: by votes descending, ties by ascending input index (the reference's std::sort leaves ties open; m3d_ppf_vote's
@@ -1187,8 +1252,8 @@ int m3d_ppf_vote(const m3d_ppf_model *model, const double *scene_points, const d
  *       M3D_PPF_REFINE_POINT_TO_PLANE (the body of m3d_registration_icp_plane_l1), unchanged, on the call's own lane.  The result
  *       keeps the picked sub-cluster's votes.
  *   K8. Centre shift T(i, 3) -= (c0 T(i, 0) + c1 T(i, 1)) + c2 T(i, 2); a STABLE sort by votes descending; expected =
- *       ((ratio n) n) 0.25 with n the model size (0.25 is VOTES_NUM_REDUCTION_FACTOR: this build votes in SampledPoints mode
- *       only), score = min(1.0, votes / expected); results are cut at the first score below score_thresh and capped at
+ *       ((ratio n) n) 0.25 with n the model size (0.25 is VOTES_NUM_REDUCTION_FACTOR of the SampledPoints mode; an EdgePoints
+ *       model: rule E9), score = min(1.0, votes / expected); results are cut at the first score below score_thresh and capped at
  *       num_result; q and t of each result by MatToQuat, as UpdateByPose does.
  * WHERE THE REFERENCE'S ORDER IS ARRIVAL ORDER.  The reference keeps a cluster's members in the depth-first order in which its
  * stack met them, and walks level 2 in that order; here members are ascending.  At level 1 the member sets are the reference's
@@ -1261,6 +1326,13 @@ int m3d_ppf_estimate(const m3d_ppf_model *model, const double *scene_points, con
                      const size_t *reference, size_t n_ref, const m3d_ppf_cluster_params *params, size_t capacity,
                      size_t *n_results, double *poses, double *q, double *t, uint64_t *votes, double *scores,
                      m3d_ppf_estimate_stats *stats);
+/* The same for an EdgePoints model (rule E9 of "PPF voting, EdgePoints mode"): the vote of m3d_ppf_vote_edges, K1 - K7 with the
+ * ICP against the scene SAMPLE, K8 with expected = (ratio n) n.  Results and stats as m3d_ppf_estimate. */
+int m3d_ppf_estimate_edges(const m3d_ppf_model *model, const double *scene_points, const double *scene_normals, size_t m,
+                           const size_t *reference, size_t n_ref, const double *scene_edge_points,
+                           const double *scene_edge_normals, size_t m_edge, const m3d_ppf_cluster_params *params,
+                           size_t capacity, size_t *n_results, double *poses, double *q, double *t, uint64_t *votes,
+                           double *scores, m3d_ppf_estimate_stats *stats);
 
 /* ---- misc -------------------------------------------------------------------------------------- */
 const char *m3d_last_error(void); /* thread-local; reference message text for M3D_ERR_* */

@@ -609,15 +609,23 @@ class PPFVoting:
     from the model's bounding box.  params: rel_sample_dist (0.05), angle_step (radians, 12 degrees), min_dist_thresh (1/3),
     min_angle_thresh (radians, 30 degrees), faster_mode (True) -- the reference's config fields.  cluster_poses and estimate
     turn the raw poses into ranked, refined results (ClusterPoses, PoseAverage, RefineSparsePose, the centre shift and the
-    scoring).  The preprocessing (PreprocessTrain / PreprocessEstimate), the EdgePoints voting mode and the PPFEstimator /
-    PPFEstimatorConfig classes themselves are not part of this build: the caller samples the points."""
+    scoring).  With edge_points / edge_normals (the model's edge points, 1 <= N_e <= 65535, N N_e <= 2^28) the model is
+    trained in VotingMode::EdgePoints (Train, :572-593): the table pairs the sample with the edge points, and vote / estimate
+    take the scene's edge points as well; pose_estimation.ppf_prepare_scene is PreprocessEstimate.  PreprocessTrain and the
+    PPFEstimator / PPFEstimatorConfig classes themselves are not part of this build: the caller samples the model."""
 
-    def __init__(self, points, normals, diameter, r_min, *, device=0, **params):
+    def __init__(self, points, normals, diameter, r_min, *, edge_points=None, edge_normals=None, device=0, **params):
         from . import capi as _capi
         try:
-            self._model = _capi.PpfModel(points, normals, diameter, r_min, device, **params)
+            self._model = _capi.PpfModel(points, normals, diameter, r_min, device, edge_points=edge_points, edge_normals=edge_normals,
+                                         **params)
         except _capi.M3DError as e:
             raise RuntimeError(str(e)) from e
+
+    @property
+    def voting_mode(self):
+        """"SampledPoints" or "EdgePoints" (PPFEstimatorConfig::VotingMode)"""
+        return "EdgePoints" if self._model.n_edge else "SampledPoints"
 
     @property
     def centroid(self):
@@ -635,15 +643,16 @@ class PPFVoting:
         except _capi.M3DError as e:
             raise RuntimeError(str(e)) from e
 
-    def vote(self, scene_points, scene_normals, reference_indices):
+    def vote(self, scene_points, scene_normals, reference_indices, edge_points=None, edge_normals=None):
         """The reference's pose_list before clustering, in ascending (reference position, model index): poses (K, 4, 4) of the
         centred model, num_votes (K,), corr_mi (K,) -- Pose6D's fields -- and reference (K,), the position in reference_indices
-        of the scene point each pose was voted at."""
+        of the scene point each pose was voted at.  edge_points / edge_normals: the scene's edge points, required on an
+        EdgePoints model (the neighbours of a reference point are taken from them) and refused on a SampledPoints one."""
         import numpy as _np
 
         from . import capi as _capi
         try:
-            r = self._model.vote(scene_points, scene_normals, reference_indices)
+            r = self._model.vote(scene_points, scene_normals, reference_indices, edge_points=edge_points, edge_normals=edge_normals)
         except _capi.M3DError as e:
             raise RuntimeError(str(e)) from e
         return r["poses"], r["votes"].astype(_np.int64), r["model_index"].astype(_np.int64), r["ref_pos"].astype(_np.int64)
@@ -660,14 +669,17 @@ class PPFVoting:
         except _capi.M3DError as e:
             raise RuntimeError(str(e)) from e
 
-    def estimate(self, scene_points, scene_normals, reference_indices, **params):
+    def estimate(self, scene_points, scene_normals, reference_indices, edge_points=None, edge_normals=None, **params):
         """Estimate from the vote on (:304-395): vote, cluster, average, refine, shift by the centroid, score.  params: the fields
         of m3d_ppf_cluster_params -- dist_threshold, angle_threshold (radians), ratio (0.6), score_thresh (0.6),
         rel_dist_sparse_thresh (5), num_result (10), refine_method ("NoRefine", "PointToPoint" or "PointToPlane", the default),
-        object_id.  -> a list of Pose6D (pose of the UNCENTRED model, q, t, num_votes, score, object_id), best first."""
+        object_id.  edge_points / edge_normals as vote takes them; on an EdgePoints model the refinement still runs against the
+        scene sample and the score's expected votes are ratio n n.  -> a list of Pose6D (pose of the UNCENTRED model, q, t,
+        num_votes, score, object_id), best first."""
         from . import capi as _capi
         try:
-            r = _capi.ppf_estimate(self._model, scene_points, scene_normals, reference_indices, **params)
+            r = _capi.ppf_estimate(self._model, scene_points, scene_normals, reference_indices, edge_points=edge_points,
+                                   edge_normals=edge_normals, **params)
         except _capi.M3DError as e:
             raise RuntimeError(str(e)) from e
         return [Pose6D(r["poses"][k].copy(), r["q"][k].copy(), r["t"][k].copy(), int(r["votes"][k]), float(r["scores"][k]), r["object_id"])
@@ -687,11 +699,23 @@ class Pose6D:
 
 class _PoseEstimation:
     """misc3d.pose_estimation (python/py_pose_estimation.cpp): RayCastRenderer.  PPFEstimator is not part of this build as a
-    class; its table, its voting, its pose clustering, refinement and scoring are here, as PPFVoting (the preprocessing is the
-    caller's)."""
+    class; its table and its voting in both modes (SampledPoints, EdgePoints), its pose clustering, refinement and scoring are
+    here, as PPFVoting, and its PreprocessEstimate as ppf_prepare_scene (PreprocessTrain is the caller's)."""
     RayCastRenderer = RayCastRenderer
     PPFVoting = PPFVoting
     Pose6D = Pose6D
+
+    @staticmethod
+    def ppf_prepare_scene(points, normals, diameter, calc_normal_relative, dist_step, dist_step_dense=0.0, pts_num=30, device=0):
+        """PPFEstimator::PreprocessEstimate (ppf_estimation.cpp:243-278): non-finite points dropped, normals estimated when None
+        (Hybrid(calc_normal_relative x diameter, 30)), NormalConsistent, VoxelDownSample(dist_step) and, with dist_step_dense > 0,
+        VoxelDownSample(dist_step_dense) with DetectBoundaryPoints(Hybrid(the same radius, pts_num)).  -> dict(sample_points,
+        sample_normals, dense_points, dense_normals, edge_indices): the voxel means' normals are not re-normalised."""
+        from . import capi as _capi
+        try:
+            return _capi.ppf_prepare_scene(points, normals, diameter, calc_normal_relative, dist_step, dist_step_dense, pts_num, device)
+        except _capi.M3DError as e:
+            raise RuntimeError(str(e)) from e
 
 
 pose_estimation = _PoseEstimation()

@@ -224,12 +224,22 @@ def lib():
         L.m3d_ppf_model_centroid.argtypes = [C.c_void_p, C.c_void_p]
         L.m3d_ppf_model_table.argtypes = [C.c_void_p] * 8
         L.m3d_ppf_vote.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t] + [C.c_void_p] * 7
+        L.m3d_ppf_model_create_edges.restype = C.c_void_p
+        L.m3d_ppf_model_create_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double,
+                                                 C.c_void_p, C.c_int, C.c_void_p]
+        L.m3d_ppf_model_edge_size.restype = C.c_size_t
+        L.m3d_ppf_model_edge_size.argtypes = [C.c_void_p]
+        L.m3d_ppf_vote_edges.argtypes = ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                          C.c_size_t, C.c_size_t] + [C.c_void_p] * 7)
+        L.m3d_ppf_prepare_scene.argtypes = ([C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_double] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 8)
         L.m3d_bench_ppf_force.argtypes = [C.c_int, C.c_int]
         L.m3d_ppf_default_cluster_params.restype = None
         L.m3d_ppf_default_cluster_params.argtypes = [C.c_void_p, C.c_void_p]
         L.m3d_ppf_cluster_poses.argtypes = ([C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 6 +
                                             [C.c_size_t] + [C.c_void_p] * 9)
         L.m3d_ppf_estimate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_void_p] * 7
+        L.m3d_ppf_estimate_edges.argtypes = ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                              C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_void_p] * 7)
         L.m3d_bench_ppf_cluster_force.argtypes = [C.c_int]
         L.m3d_estimate_normals.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                            C.c_void_p, C.c_void_p]
@@ -1601,21 +1611,44 @@ def ppf_params(**kw):
     return P
 
 
-class PpfModel:
-    """m3d_ppf_model_create / _table / m3d_ppf_vote / _destroy: the PPF table of already sampled model points with unit
-    normals, and the vote of a scene against it (include/misc3d_amd.h, "PPF voting")."""
+def _edge_arrays(edge_points, edge_normals):
+    """the scene's (or model's) edge points as two (k, 3) float64 arrays, or (None, None)"""
+    if (edge_points is None) != (edge_normals is None):
+        raise ValueError("ppf: edge_points and edge_normals come together")
+    if edge_points is None:
+        return None, None
+    ep, en = _f64(edge_points).reshape(-1, 3), _f64(edge_normals).reshape(-1, 3)
+    if len(ep) != len(en):
+        raise ValueError("ppf: one normal per edge point")
+    return ep, en
 
-    def __init__(self, points, normals, diameter, r_min, device=0, **params):
+
+class PpfModel:
+    """m3d_ppf_model_create / _create_edges / _table / m3d_ppf_vote / _vote_edges / _destroy: the PPF table of already sampled model
+    points with unit normals, and the vote of a scene against it (include/misc3d_amd.h, "PPF voting").  With edge_points /
+    edge_normals the model is trained in EdgePoints mode ("PPF voting, EdgePoints mode") and vote() needs the scene's edge points."""
+
+    def __init__(self, points, normals, diameter, r_min, device=0, edge_points=None, edge_normals=None, **params):
         pts, nrm = _f64(points).reshape(-1, 3), _f64(normals).reshape(-1, 3)
         if len(pts) != len(nrm):
             raise ValueError("ppf: one normal per point")
+        if (edge_points is None) != (edge_normals is None):
+            raise ValueError("ppf: edge_points and edge_normals come together")
         P = ppf_params(**params)
         status = C.c_int(0)
-        self.h = lib().m3d_ppf_model_create(_p(pts), _p(nrm), len(pts), float(diameter), float(r_min), C.cast(C.byref(P), C.c_void_p),
-                                            int(device), C.cast(C.byref(status), C.c_void_p))
+        if edge_points is None:
+            self.h = lib().m3d_ppf_model_create(_p(pts), _p(nrm), len(pts), float(diameter), float(r_min), C.cast(C.byref(P), C.c_void_p),
+                                                int(device), C.cast(C.byref(status), C.c_void_p))
+        else:
+            ep, en = _f64(edge_points).reshape(-1, 3), _f64(edge_normals).reshape(-1, 3)
+            if len(ep) != len(en):
+                raise ValueError("ppf: one normal per edge point")
+            self.h = lib().m3d_ppf_model_create_edges(_p(pts), _p(nrm), len(pts), _p(ep), _p(en), len(ep), float(diameter), float(r_min),
+                                                      C.cast(C.byref(P), C.c_void_p), int(device), C.cast(C.byref(status), C.c_void_p))
         if not self.h:
             raise M3DError(status.value, last_error())
         self.n = len(pts)
+        self.n_edge = int(lib().m3d_ppf_model_edge_size(self.h))
         self.device = int(device)
         c = np.zeros(3)
         _check(lib().m3d_ppf_model_centroid(self.h, _p(c)))
@@ -1646,13 +1679,15 @@ class PpfModel:
         t.update(I)
         return t
 
-    def vote(self, scene_points, scene_normals, reference, capacity=None, stats=False):
+    def vote(self, scene_points, scene_normals, reference, capacity=None, stats=False, edge_points=None, edge_normals=None):
         """-> dict(ref_pos, model_index, alpha_index, votes (uint32 each), poses (K, 4, 4)) (+ the stats dict).  capacity=None:
         the call is repeated once with the needed capacity when the first guess was too small; a given capacity is final
-        (M3DError with code ERR_CAPACITY and .needed set)."""
+        (M3DError with code ERR_CAPACITY and .needed set).  edge_points / edge_normals: the scene's edge points, which send the
+        call through m3d_ppf_vote_edges (the library refuses the call that does not match the model's mode)."""
         sp, sn = _f64(scene_points).reshape(-1, 3), _f64(scene_normals).reshape(-1, 3)
         if len(sp) != len(sn):
             raise ValueError("ppf: one normal per scene point")
+        ep, en = _edge_arrays(edge_points, edge_normals)
         ref = np.ascontiguousarray(reference, dtype=np.uint64).reshape(-1)
         cap = max(256, 4 * len(ref)) if capacity is None else int(capacity)
         while True:
@@ -1660,8 +1695,13 @@ class PpfModel:
             poses = np.zeros((max(cap, 1), 4, 4))
             k = C.c_size_t(0)
             st = PpfVoteStats()
-            rc = lib().m3d_ppf_vote(self.h, _p(sp), _p(sn), len(sp), _p(ref), len(ref), cap, C.cast(C.byref(k), C.c_void_p),
-                                    *(_p(o) for o in out), _p(poses), C.cast(C.byref(st), C.c_void_p))
+            if ep is None:
+                rc = lib().m3d_ppf_vote(self.h, _p(sp), _p(sn), len(sp), _p(ref), len(ref), cap, C.cast(C.byref(k), C.c_void_p),
+                                        *(_p(o) for o in out), _p(poses), C.cast(C.byref(st), C.c_void_p))
+            else:
+                rc = lib().m3d_ppf_vote_edges(self.h, _p(sp), _p(sn), len(sp), _p(ref), len(ref), _p(ep), _p(en), len(ep), cap,
+                                              C.cast(C.byref(k), C.c_void_p), *(_p(o) for o in out), _p(poses),
+                                              C.cast(C.byref(st), C.c_void_p))
             if rc == ERR_CAPACITY and capacity is None:
                 cap = k.value
                 continue
@@ -1757,12 +1797,13 @@ def ppf_cluster_poses(poses, votes, device=0, model=None, pose_capacity=None, cl
                 avg_votes=avotes[:cr], avg_cluster=acl[:cr], stats=st.asdict())
 
 
-def ppf_estimate(model, scene_points, scene_normals, reference, capacity=None, **params):
+def ppf_estimate(model, scene_points, scene_normals, reference, capacity=None, edge_points=None, edge_normals=None, **params):
     """m3d_ppf_estimate (the vote and K1 - K8) on a PpfModel -> dict(poses (K, 4, 4), q (K, 4), t (K, 3), votes, scores, object_id,
-    stats)"""
+    stats).  edge_points / edge_normals: the scene's edge points, which send the call through m3d_ppf_estimate_edges."""
     sp, sn = _f64(scene_points).reshape(-1, 3), _f64(scene_normals).reshape(-1, 3)
     if len(sp) != len(sn):
         raise ValueError("ppf: one normal per scene point")
+    ep, en = _edge_arrays(edge_points, edge_normals)
     ref = np.ascontiguousarray(reference, dtype=np.uint64).reshape(-1)
     P = ppf_cluster_params(model, **params)
     cap = max(int(P.num_result), 1) if capacity is None else int(capacity)
@@ -1770,14 +1811,43 @@ def ppf_estimate(model, scene_points, scene_normals, reference, capacity=None, *
     votes, scores = np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1))
     k = C.c_size_t(0)
     st = PpfEstimateStats()
-    rc = lib().m3d_ppf_estimate(model.h, _p(sp), _p(sn), len(sp), _p(ref), len(ref), C.cast(C.byref(P), C.c_void_p), cap,
-                                C.cast(C.byref(k), C.c_void_p), _p(poses), _p(q), _p(t), _p(votes), _p(scores), C.cast(C.byref(st), C.c_void_p))
+    if ep is None:
+        rc = lib().m3d_ppf_estimate(model.h, _p(sp), _p(sn), len(sp), _p(ref), len(ref), C.cast(C.byref(P), C.c_void_p), cap,
+                                    C.cast(C.byref(k), C.c_void_p), _p(poses), _p(q), _p(t), _p(votes), _p(scores), C.cast(C.byref(st), C.c_void_p))
+    else:
+        rc = lib().m3d_ppf_estimate_edges(model.h, _p(sp), _p(sn), len(sp), _p(ref), len(ref), _p(ep), _p(en), len(ep),
+                                          C.cast(C.byref(P), C.c_void_p), cap, C.cast(C.byref(k), C.c_void_p), _p(poses), _p(q), _p(t),
+                                          _p(votes), _p(scores), C.cast(C.byref(st), C.c_void_p))
     if rc < 0:
         e = M3DError(rc, last_error())
         e.needed = k.value
         raise e
     n = k.value
     return dict(poses=poses[:n], q=q[:n], t=t[:n], votes=votes[:n], scores=scores[:n], object_id=int(P.object_id), stats=st.asdict())
+
+
+def ppf_prepare_scene(points, normals, diameter, calc_normal_relative, dist_step, dist_step_dense=0.0, pts_num=30, device=0):
+    """m3d_ppf_prepare_scene (PreprocessEstimate): normals may be None (then estimated); dist_step_dense <= 0: no edge part.
+    -> dict(sample_points, sample_normals, dense_points, dense_normals ((k, 3) each), edge_indices (into the dense sample,
+    ascending))"""
+    xyz = _f64(points).reshape(-1, 3)
+    nrm = None if normals is None else _f64(normals).reshape(-1, 3)
+    if nrm is not None and len(nrm) != len(xyz):
+        raise ValueError("ppf: one normal per point")
+    n = len(xyz)
+    dense = bool(dist_step_dense > 0.0)
+    sp, sn = np.zeros((max(n, 1), 3)), np.zeros((max(n, 1), 3))
+    dp, dn = (np.zeros((max(n, 1), 3)), np.zeros((max(n, 1), 3))) if dense else (None, None)
+    ei = np.zeros(max(n, 1), np.uint64) if dense else None
+    ns, nd, ne = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    ref = lambda x: C.cast(C.byref(x), C.c_void_p)
+    _check(lib().m3d_ppf_prepare_scene(_p(xyz), _p(nrm), n, float(diameter), float(calc_normal_relative), float(dist_step),
+                                       float(dist_step_dense), int(pts_num), int(device), _p(sp), _p(sn), ref(ns), _p(dp), _p(dn),
+                                       ref(nd), _p(ei), ref(ne)))
+    return dict(sample_points=sp[:ns.value].copy(), sample_normals=sn[:ns.value].copy(),
+                dense_points=dp[:nd.value].copy() if dense else np.zeros((0, 3)),
+                dense_normals=dn[:nd.value].copy() if dense else np.zeros((0, 3)),
+                edge_indices=ei[:ne.value].astype(np.int64) if dense else np.zeros(0, np.int64))
 
 
 def ppf_cluster_force(splits=0):

@@ -1,6 +1,7 @@
 // m3d_ppf.cpp -- the table and the vote of misc3d::pose_estimation::PPFEstimator (src/ppf_estimation.cpp) behind the C ABI:
-// m3d_ppf_model_create (CalcHashTable, GenerateModelPCNeighbor), m3d_ppf_vote (VotingAndGetPose, CalcLocalMaximum).  The
-// contract is in include/misc3d_amd.h "PPF voting"; the frames (CalcTNormal2RegionX) and the pose products are the host's.
+// m3d_ppf_model_create / _create_edges (CalcHashTable, GenerateModelPCNeighbor), m3d_ppf_vote / _vote_edges (VotingAndGetPose,
+// CalcLocalMaximum).  The contract is in include/misc3d_amd.h "PPF voting" and "PPF voting, EdgePoints mode"; the frames
+// (CalcTNormal2RegionX) and the pose products are the host's.
 // Nothing here depends on M3D_FP_ORDER (every sum is written out).
 #include "m3d_driver_internal.hpp"
 #include "m3d_ppf.hpp"
@@ -92,9 +93,9 @@ void ppf_pose(const double* tsg, double alpha, const double* tmg, double* out) {
 void frame_rows(const double* T, double* rows8) { std::memcpy(rows8, T + 4, sizeof(double) * 8); }
 
 struct VoteBufs {
-    DevBuf spts, snrm, ref, sframes, flags, acc, rowinfo, out, small;
+    DevBuf rpts, rnrm, spts, snrm, ref, sframes, flags, acc, rowinfo, out, small;   // (rpts, rnrm: EdgePoints mode only)
     void release() {
-        for (DevBuf* b : {&spts, &snrm, &ref, &sframes, &flags, &acc, &rowinfo, &out, &small}) b->release();
+        for (DevBuf* b : {&rpts, &rnrm, &spts, &snrm, &ref, &sframes, &flags, &acc, &rowinfo, &out, &small}) b->release();
     }
 };
 
@@ -103,6 +104,7 @@ struct VoteBufs {
 struct m3d_ppf_model {
     int device = 0;
     uint32_t n = 0;
+    uint32_t n_e = 0;             // the model's edge points (EdgePoints mode), 0 for a SampledPoints model
     double diameter = 0.0, r_min = 0.0, angle_step = 0.0, min_dist_thresh = 0.0, min_angle_thresh = 0.0;
     PpfSizes sizes{};
     PpfTables T{};                // (dist_edge2 points at edge2 below: the host's copy)
@@ -111,10 +113,11 @@ struct m3d_ppf_model {
     std::vector<double> tmg;      // n x 16
     std::vector<double> centred;  // n x 3: the host's copy of pts (the source cloud of m3d_ppf_estimate's refinement)
     uint32_t n_entries = 0, n_neighbors = 0;
-    m3d::DevBuf pts, nrm, frames, d_edge2, cell_off, entries, nbr_off, nbr_idx;
+    m3d::DevBuf pts, nrm, frames, epts, enrm, d_edge2, cell_off, entries, nbr_off, nbr_idx;   // (epts, enrm: edge models only)
     void release() {
-        for (m3d::DevBuf* b : {&pts, &nrm, &frames, &d_edge2, &cell_off, &entries, &nbr_off, &nbr_idx}) b->release();
+        for (m3d::DevBuf* b : {&pts, &nrm, &frames, &epts, &enrm, &d_edge2, &cell_off, &entries, &nbr_off, &nbr_idx}) b->release();
     }
+    bool edges() const { return n_e != 0; }
     PpfModelView view() const {
         PpfModelView v;
         v.T = T;
@@ -124,6 +127,10 @@ struct m3d_ppf_model {
         v.pts = pts.as<double>();
         v.nrm = nrm.as<double>();
         v.frames = frames.as<double>();
+        v.same_set = !edges();
+        v.epts = edges() ? epts.as<double>() : v.pts;
+        v.enrm = edges() ? enrm.as<double>() : v.nrm;
+        v.n_e = edges() ? n_e : n;
         v.cell_off = cell_off.as<uint32_t>();
         v.entries = entries.as<uint32_t>();
         v.nbr_off = nbr_off.as<uint32_t>();
@@ -154,7 +161,8 @@ int ppf_check_params(const m3d_ppf_params& P, double diameter, double r_min, Ppf
 int ppf_build_table(DeviceCtx* ctx, m3d_ppf_model* h) {
     hipStream_t st = ctx->stream;
     const uint32_t n = h->n, table_size = (uint32_t)h->sizes.table_size;
-    const uint32_t pairs = n * n;
+    const uint32_t n_e = h->edges() ? h->n_e : n;
+    const uint32_t pairs = n * n_e;   // (<= 2^28: checked by the caller)
     DevBuf keys, k0, v0, k1, v1, counts, scan, total, ncount;
     auto release = [&]() {
         for (DevBuf* b : {&keys, &k0, &v0, &k1, &v1, &counts, &scan, &total, &ncount}) b->release();
@@ -189,13 +197,13 @@ int ppf_build_table(DeviceCtx* ctx, m3d_ppf_model* h) {
         HIPCHK(hipMemcpyAsync(&n_entries, h->cell_off.as<uint32_t>() + table_size, 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(&n_nbr, h->nbr_off.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        if (n_entries > pairs - n || n_nbr < n || (uint64_t)n_nbr > (uint64_t)pairs)
+        if (n_entries > (h->edges() ? pairs : pairs - n) || n_nbr < n || (uint64_t)n_nbr > (uint64_t)n * n)
             return fail(M3D_ERR_INTERNAL, "ppf: the table's totals are out of range (self-check)");
         h->n_entries = n_entries;
         h->n_neighbors = n_nbr;
         RESERVE(h->entries, sizeof(uint32_t) * std::max<size_t>(n_entries, 1));
         RESERVE(h->nbr_idx, sizeof(uint32_t) * n_nbr);
-        launch_ppf_entries(sk, sv, n_entries, n, table_size, h->entries.as<uint32_t>(), st);
+        launch_ppf_entries(sk, sv, n_entries, n_e, table_size, h->entries.as<uint32_t>(), st);
         launch_ppf_nbr_fill(v.pts, n, r2, h->nbr_off.as<uint32_t>(), h->nbr_idx.as<uint32_t>(), st);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));   // published to every lane once built
@@ -206,34 +214,10 @@ int ppf_build_table(DeviceCtx* ctx, m3d_ppf_model* h) {
     return rc;
 }
 
-}  // namespace
-
-// what m3d_ppf_cluster.cpp reads of a model (m3d_ppf_cluster.hpp)
-m3d::PpfModelHost m3d::ppf_model_host(const m3d_ppf_model* h) {
-    PpfModelHost v;
-    v.n = h->n;
-    v.device = h->device;
-    v.diameter = h->diameter;
-    v.dist_step = h->sizes.dist_step;
-    v.centroid = h->centroid;
-    v.centred = h->centred.data();
-    return v;
-}
-
-extern "C" {
-
-void m3d_ppf_default_params(m3d_ppf_params* out) {
-    if (!out) return;
-    out->rel_sample_dist = 0.05;
-    out->angle_step = 12.0 / 180.0 * M_PI;
-    out->min_dist_thresh = 1.0 / 3.0;
-    out->min_angle_thresh = 30.0 / 180.0 * M_PI;
-    out->faster_mode = 1;
-    out->reserved = 0;
-}
-
-m3d_ppf_model* m3d_ppf_model_create(const double* points, const double* normals, size_t n, double diameter, double r_min,
-                                    const m3d_ppf_params* params, int device, int* status) {
+// Train (:537-593) in either mode.  edge == false: rules M1 - M6; edge == true: E1 - E5, the referred set being the n_e edge points.
+m3d_ppf_model* ppf_model_create(const double* points, const double* normals, size_t n, const double* edge_points,
+                                const double* edge_normals, size_t n_e, bool edge, double diameter, double r_min,
+                                const m3d_ppf_params* params, int device, int* status) {
     if (status) *status = M3D_ERR_INVALID_ARG;
     m3d_ppf_params P;
     m3d_ppf_default_params(&P);
@@ -246,20 +230,34 @@ m3d_ppf_model* m3d_ppf_model_create(const double* points, const double* normals,
         fail(M3D_ERR_INVALID_ARG, "ppf: the model must have 2 .. 65535 points, got " + std::to_string(n));
         return nullptr;
     }
+    if (edge && (!edge_points || !edge_normals)) {
+        fail(M3D_ERR_INVALID_ARG, "ppf: null edge points or normals");
+        return nullptr;
+    }
+    if (edge && (n_e < 1 || n_e > kPpfMaxPoints)) {
+        fail(M3D_ERR_INVALID_ARG, "ppf: the model must have 1 .. 65535 edge points, got " + std::to_string(n_e));
+        return nullptr;
+    }
     PpfSizes sizes;
     if (ppf_check_params(P, diameter, r_min, &sizes) != M3D_OK) return nullptr;
     if (!finite3(points, n) || !finite3(normals, n)) {
         fail(M3D_ERR_INVALID_ARG, "ppf: a model point or normal is not finite");
         return nullptr;
     }
+    if (edge && (!finite3(edge_points, n_e) || !finite3(edge_normals, n_e))) {
+        fail(M3D_ERR_INVALID_ARG, "ppf: a model edge point or normal is not finite");
+        return nullptr;
+    }
     if (status) *status = M3D_ERR_DEVICE;
-    if ((uint64_t)n * n > kPpfMaxSortPairs) {
-        fail(M3D_ERR_DEVICE, "ppf: the table's sort scratch (16 bytes a pair) is capped at 4 GiB: n <= 16383");
+    if ((uint64_t)n * (edge ? n_e : n) > kPpfMaxSortPairs) {
+        fail(M3D_ERR_DEVICE, edge ? "ppf: the table's sort scratch (16 bytes a pair) is capped at 4 GiB: n x n_edge <= 2^28"
+                                  : "ppf: the table's sort scratch (16 bytes a pair) is capped at 4 GiB: n <= 16383");
         return nullptr;
     }
     m3d_ppf_model* h = new m3d_ppf_model;
     h->device = device;
     h->n = (uint32_t)n;
+    h->n_e = edge ? (uint32_t)n_e : 0;
     h->diameter = diameter;
     h->r_min = r_min;
     h->angle_step = P.angle_step;
@@ -281,7 +279,11 @@ m3d_ppf_model* m3d_ppf_model_create(const double* points, const double* normals,
         ppf_frame(&centred[3 * i], normals + 3 * i, &h->tmg[16 * i]);
         frame_rows(&h->tmg[16 * i], &rows[8 * i]);
     }
-    if (!finite3(centred.data(), n)) {
+    // rule E1: the edge points are centred by the SAMPLE's centroid
+    std::vector<double> ecentred(edge ? 3 * n_e : 0);
+    for (size_t j = 0; j < ecentred.size() / 3; ++j)
+        for (int k = 0; k < 3; ++k) ecentred[3 * j + k] = edge_points[3 * j + k] - h->centroid[k];
+    if (!finite3(centred.data(), n) || !finite3(ecentred.data(), ecentred.size() / 3)) {
         fail(M3D_ERR_INVALID_ARG, "ppf: a centred model point is not finite");
         if (status) *status = M3D_ERR_INVALID_ARG;
         delete h;
@@ -303,6 +305,12 @@ m3d_ppf_model* m3d_ppf_model_create(const double* points, const double* normals,
                 HIPCHK(hipMemcpyAsync(h->nrm.p, normals, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
                 HIPCHK(hipMemcpyAsync(h->frames.p, rows.data(), sizeof(double) * 8 * n, hipMemcpyHostToDevice, st));
                 HIPCHK(hipMemcpyAsync(h->d_edge2.p, h->edge2.data(), sizeof(double) * h->edge2.size(), hipMemcpyHostToDevice, st));
+                if (edge) {
+                    RESERVE(h->epts, sizeof(double) * 3 * n_e);
+                    RESERVE(h->enrm, sizeof(double) * 3 * n_e);
+                    HIPCHK(hipMemcpyAsync(h->epts.p, ecentred.data(), sizeof(double) * 3 * n_e, hipMemcpyHostToDevice, st));
+                    HIPCHK(hipMemcpyAsync(h->enrm.p, edge_normals, sizeof(double) * 3 * n_e, hipMemcpyHostToDevice, st));
+                }
                 HIPCHK(hipStreamSynchronize(st));
                 return ppf_build_table(ctx, h);
             }();
@@ -321,71 +329,49 @@ m3d_ppf_model* m3d_ppf_model_create(const double* points, const double* normals,
     return h;
 }
 
-void m3d_ppf_model_destroy(m3d_ppf_model* h) {
-    if (!h) return;
-    h->release();
-    delete h;
+}  // namespace
+
+// what m3d_ppf_cluster.cpp reads of a model (m3d_ppf_cluster.hpp)
+m3d::PpfModelHost m3d::ppf_model_host(const m3d_ppf_model* h) {
+    PpfModelHost v;
+    v.n = h->n;
+    v.device = h->device;
+    v.diameter = h->diameter;
+    v.dist_step = h->sizes.dist_step;
+    v.centroid = h->centroid;
+    v.centred = h->centred.data();
+    v.edges = h->edges();
+    return v;
 }
 
-size_t m3d_ppf_model_size(const m3d_ppf_model* h) { return h ? h->n : 0; }
+namespace {
 
-int m3d_ppf_model_centroid(const m3d_ppf_model* h, double centroid[3]) {
-    if (!h || !centroid) return fail(M3D_ERR_INVALID_ARG, "ppf: null argument");
-    std::memcpy(centroid, h->centroid, sizeof(double) * 3);
-    return M3D_OK;
-}
-
-int m3d_ppf_model_table(const m3d_ppf_model* h, m3d_ppf_table_info* info, uint32_t* cell_offsets, uint16_t* entry_i,
-                        uint8_t* entry_alpha, uint32_t* nbr_offsets, uint32_t* nbr_indices, double* tmg) {
-    if (!h) return fail(M3D_ERR_INVALID_ARG, "ppf: null model");
-    if (info) {
-        info->table_size = (uint64_t)h->sizes.table_size;
-        info->n_entries = h->n_entries;
-        info->n_neighbors = h->n_neighbors;
-        info->angle_num = (int32_t)h->sizes.angle_num;
-        info->alpha_model_num = (int32_t)h->sizes.alpha_num;
-        info->dist_num = (int32_t)h->sizes.dist_num;
-        info->path = ppf_acc_in_lds(h->n, (int)h->sizes.alpha_num) ? M3D_PPF_PATH_LDS : M3D_PPF_PATH_DEVICE;
-    }
-    if (tmg) std::memcpy(tmg, h->tmg.data(), sizeof(double) * h->tmg.size());
-    if (!cell_offsets && !entry_i && !entry_alpha && !nbr_offsets && !nbr_indices) return M3D_OK;
-    LaneLock lane(h->device);
-    DeviceCtx* ctx = lane.ctx;
-    if (!ctx) return M3D_ERR_DEVICE;
-    return [&]() -> int {
-        HIPCHK(hipSetDevice(ctx->device));
-        hipStream_t st = ctx->stream;
-        std::vector<uint32_t> ent;
-        if (cell_offsets)
-            HIPCHK(hipMemcpyAsync(cell_offsets, h->cell_off.p, sizeof(uint32_t) * ((size_t)h->sizes.table_size + 1), hipMemcpyDeviceToHost, st));
-        if (nbr_offsets) HIPCHK(hipMemcpyAsync(nbr_offsets, h->nbr_off.p, sizeof(uint32_t) * (h->n + 1), hipMemcpyDeviceToHost, st));
-        if (nbr_indices) HIPCHK(hipMemcpyAsync(nbr_indices, h->nbr_idx.p, sizeof(uint32_t) * h->n_neighbors, hipMemcpyDeviceToHost, st));
-        if ((entry_i || entry_alpha) && h->n_entries) {
-            ent.resize(h->n_entries);
-            HIPCHK(hipMemcpyAsync(ent.data(), h->entries.p, sizeof(uint32_t) * h->n_entries, hipMemcpyDeviceToHost, st));
-        }
-        HIPCHK(hipStreamSynchronize(st));
-        for (size_t t = 0; t < ent.size(); ++t) {
-            if (entry_i) entry_i[t] = (uint16_t)(ent[t] & 0xFFFFu);
-            if (entry_alpha) entry_alpha[t] = (uint8_t)(ent[t] >> 16);
-        }
-        return M3D_OK;
-    }();
-}
-
-int m3d_ppf_vote(const m3d_ppf_model* h, const double* scene_points, const double* scene_normals, size_t m,
-                 const size_t* reference, size_t n_ref, size_t capacity, size_t* n_maxima, uint32_t* ref_pos,
-                 uint32_t* model_index, uint32_t* alpha_index, uint32_t* votes, double* poses, m3d_ppf_vote_stats* stats) {
+// VotingAndGetPose (:399-524) in either mode.  edge == false (m3d_ppf_vote): the scene is scanned and holds the reference points.
+// edge == true (m3d_ppf_vote_edges, rules E6 - E8): the reference points are read from the scene sample, the scene's m_e edge
+// points are scanned; only the n_ref reference points (gathered) and the edge points go to the device.
+int ppf_vote(const m3d_ppf_model* h, bool edge, const double* scene_points, const double* scene_normals, size_t m,
+             const size_t* reference, size_t n_ref, const double* edge_points, const double* edge_normals, size_t m_e, size_t capacity,
+             size_t* n_maxima, uint32_t* ref_pos, uint32_t* model_index, uint32_t* alpha_index, uint32_t* votes, double* poses,
+             m3d_ppf_vote_stats* stats) {
     const double t0 = now_ms();
     m3d_ppf_vote_stats S{};
     if (stats) *stats = S;
     if (n_maxima) *n_maxima = 0;
     if (!h) return fail(M3D_ERR_INVALID_ARG, "ppf: null model");
+    if (edge != h->edges())
+        return fail(M3D_ERR_INVALID_ARG, edge ? "ppf: the model was trained in SampledPoints mode: vote with m3d_ppf_vote / m3d_ppf_estimate"
+                                              : "ppf: the model was trained in EdgePoints mode: vote with m3d_ppf_vote_edges / m3d_ppf_estimate_edges");
     if (!scene_points || !scene_normals || !reference || !n_maxima) return fail(M3D_ERR_INVALID_ARG, "ppf: null argument");
     if (capacity && (!ref_pos || !model_index || !alpha_index || !votes)) return fail(M3D_ERR_INVALID_ARG, "ppf: null result array");
     if (n_ref == 0) return fail(M3D_ERR_INVALID_ARG, "ppf: no reference points");
     if (m == 0 || m >= ((size_t)1 << 31) || n_ref >= ((size_t)1 << 31)) return fail(M3D_ERR_INVALID_ARG, "ppf: the scene must have 1 .. 2^31 - 1 points");
     if (!finite3(scene_points, m) || !finite3(scene_normals, m)) return fail(M3D_ERR_INVALID_ARG, "ppf: a scene point or normal is not finite");
+    if (edge) {
+        if (!edge_points || !edge_normals) return fail(M3D_ERR_INVALID_ARG, "ppf: null scene edge points or normals");
+        if (m_e == 0 || m_e >= ((size_t)1 << 31)) return fail(M3D_ERR_INVALID_ARG, "ppf: the scene must have 1 .. 2^31 - 1 edge points");
+        if (!finite3(edge_points, m_e) || !finite3(edge_normals, m_e))
+            return fail(M3D_ERR_INVALID_ARG, "ppf: a scene edge point or normal is not finite");
+    }
     std::vector<uint32_t> ref32(n_ref);
     for (size_t s = 0; s < n_ref; ++s) {
         if (reference[s] >= m) return fail(M3D_ERR_INVALID_ARG, "ppf: a reference index is out of range");
@@ -399,6 +385,20 @@ int m3d_ppf_vote(const m3d_ppf_model* h, const double* scene_points, const doubl
         ppf_frame(scene_points + 3 * (size_t)ref32[s], scene_normals + 3 * (size_t)ref32[s], &tsg[16 * s]);
         frame_rows(&tsg[16 * s], &rows[8 * s]);
     }
+    // EdgePoints: the reference points alone, gathered in reference order; position s reads row s
+    std::vector<double> rp, rn;
+    if (edge) {
+        rp.resize(3 * n_ref);
+        rn.resize(3 * n_ref);
+        for (size_t s = 0; s < n_ref; ++s) {
+            std::memcpy(&rp[3 * s], scene_points + 3 * (size_t)ref32[s], sizeof(double) * 3);
+            std::memcpy(&rn[3 * s], scene_normals + 3 * (size_t)ref32[s], sizeof(double) * 3);
+            ref32[s] = (uint32_t)s;
+        }
+    }
+    const double* scan_points = edge ? edge_points : scene_points;   // the cloud the kernel scans, m_scan points
+    const double* scan_normals = edge ? edge_normals : scene_normals;
+    const size_t m_scan = edge ? m_e : m;
     const bool lds = ppf_acc_in_lds(n, A) && g_ppf_force_device.load() == 0;
     const size_t acc_words = ppf_acc_words(n, A);
     // the workgroups: what the flag arrays (and, in device memory, the accumulators) leave of the call's scratch
@@ -419,20 +419,26 @@ int m3d_ppf_vote(const m3d_ppf_model* h, const double* scene_points, const doubl
         HIPCHK(hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
         HIPCHK(hipEventRecord(ctx->ev0, st));
-        const size_t fixed = sizeof(double) * (6 * m + 8 * n_ref) + sizeof(uint32_t) * n_ref;
+        const size_t fixed = sizeof(double) * (6 * m_scan + (edge ? 14 : 8) * n_ref) + sizeof(uint32_t) * n_ref;
         size_t out_cap = std::max<size_t>(1024, 4 * n_ref);
         if (fixed + groups * (sizeof(unsigned long long) * table_size + per_group) + sizeof(PpfMaximum) * out_cap > kPpfScratchCap)
             return fail(M3D_ERR_INVALID_ARG, "ppf: the scene and its reference points do not fit the call's 256 MiB of scratch");
-        RESERVE(B.spts, sizeof(double) * 3 * m);
-        RESERVE(B.snrm, sizeof(double) * 3 * m);
+        RESERVE(B.spts, sizeof(double) * 3 * m_scan);
+        RESERVE(B.snrm, sizeof(double) * 3 * m_scan);
         RESERVE(B.ref, sizeof(uint32_t) * n_ref);
         RESERVE(B.sframes, sizeof(double) * 8 * n_ref);
         RESERVE(B.flags, sizeof(unsigned long long) * table_size * groups);
         if (!lds) RESERVE(B.acc, sizeof(uint32_t) * acc_words * groups);
         RESERVE(B.rowinfo, sizeof(uint32_t) * (size_t)n * groups);
         RESERVE(B.small, 64);
-        HIPCHK(hipMemcpyAsync(B.spts.p, scene_points, sizeof(double) * 3 * m, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(B.snrm.p, scene_normals, sizeof(double) * 3 * m, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(B.spts.p, scan_points, sizeof(double) * 3 * m_scan, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(B.snrm.p, scan_normals, sizeof(double) * 3 * m_scan, hipMemcpyHostToDevice, st));
+        if (edge) {
+            RESERVE(B.rpts, sizeof(double) * 3 * n_ref);
+            RESERVE(B.rnrm, sizeof(double) * 3 * n_ref);
+            HIPCHK(hipMemcpyAsync(B.rpts.p, rp.data(), sizeof(double) * 3 * n_ref, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(B.rnrm.p, rn.data(), sizeof(double) * 3 * n_ref, hipMemcpyHostToDevice, st));
+        }
         HIPCHK(hipMemcpyAsync(B.ref.p, ref32.data(), sizeof(uint32_t) * n_ref, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(B.sframes.p, rows.data(), sizeof(double) * 8 * n_ref, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemsetAsync(B.flags.p, 0, sizeof(unsigned long long) * table_size * groups, st));
@@ -440,14 +446,16 @@ int m3d_ppf_vote(const m3d_ppf_model* h, const double* scene_points, const doubl
         a.M = h->view();
         a.spts = B.spts.as<double>();
         a.snrm = B.snrm.as<double>();
-        a.m = (uint32_t)m;
+        a.rpts = edge ? B.rpts.as<double>() : a.spts;
+        a.rnrm = edge ? B.rnrm.as<double>() : a.snrm;
+        a.m = (uint32_t)m_scan;
         a.n_ref = (uint32_t)n_ref;
         a.ref = B.ref.as<uint32_t>();
         a.sframes = B.sframes.as<double>();
         a.r2 = h->r_min * h->r_min;
         a.dist_thresh = h->min_dist_thresh * h->r_min;
         a.cos_thresh = std::cos(h->min_angle_thresh);
-        a.gate = (uint32_t)(size_t)((double)n * 0.2);
+        a.gate = (uint32_t)(size_t)((double)(edge ? h->n_e : n) * 0.2);   // (refered_model_num: rules V3 / E7)
         a.acc_words = (uint32_t)acc_words;
         a.flags = B.flags.as<unsigned long long>();
         a.acc = lds ? nullptr : B.acc.as<uint32_t>();
@@ -507,6 +515,100 @@ int m3d_ppf_vote(const m3d_ppf_model* h, const double* scene_points, const doubl
                      &h->tmg[16 * (size_t)found[k].model_index], poses + 16 * k);
     }
     return M3D_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void m3d_ppf_default_params(m3d_ppf_params* out) {
+    if (!out) return;
+    out->rel_sample_dist = 0.05;
+    out->angle_step = 12.0 / 180.0 * M_PI;
+    out->min_dist_thresh = 1.0 / 3.0;
+    out->min_angle_thresh = 30.0 / 180.0 * M_PI;
+    out->faster_mode = 1;
+    out->reserved = 0;
+}
+
+m3d_ppf_model* m3d_ppf_model_create(const double* points, const double* normals, size_t n, double diameter, double r_min,
+                                    const m3d_ppf_params* params, int device, int* status) {
+    return ppf_model_create(points, normals, n, nullptr, nullptr, 0, false, diameter, r_min, params, device, status);
+}
+
+m3d_ppf_model* m3d_ppf_model_create_edges(const double* points, const double* normals, size_t n, const double* edge_points,
+                                          const double* edge_normals, size_t n_edge, double diameter, double r_min,
+                                          const m3d_ppf_params* params, int device, int* status) {
+    return ppf_model_create(points, normals, n, edge_points, edge_normals, n_edge, true, diameter, r_min, params, device, status);
+}
+
+void m3d_ppf_model_destroy(m3d_ppf_model* h) {
+    if (!h) return;
+    h->release();
+    delete h;
+}
+
+size_t m3d_ppf_model_size(const m3d_ppf_model* h) { return h ? h->n : 0; }
+
+size_t m3d_ppf_model_edge_size(const m3d_ppf_model* h) { return h ? h->n_e : 0; }
+
+int m3d_ppf_model_centroid(const m3d_ppf_model* h, double centroid[3]) {
+    if (!h || !centroid) return fail(M3D_ERR_INVALID_ARG, "ppf: null argument");
+    std::memcpy(centroid, h->centroid, sizeof(double) * 3);
+    return M3D_OK;
+}
+
+int m3d_ppf_model_table(const m3d_ppf_model* h, m3d_ppf_table_info* info, uint32_t* cell_offsets, uint16_t* entry_i,
+                        uint8_t* entry_alpha, uint32_t* nbr_offsets, uint32_t* nbr_indices, double* tmg) {
+    if (!h) return fail(M3D_ERR_INVALID_ARG, "ppf: null model");
+    if (info) {
+        info->table_size = (uint64_t)h->sizes.table_size;
+        info->n_entries = h->n_entries;
+        info->n_neighbors = h->n_neighbors;
+        info->angle_num = (int32_t)h->sizes.angle_num;
+        info->alpha_model_num = (int32_t)h->sizes.alpha_num;
+        info->dist_num = (int32_t)h->sizes.dist_num;
+        info->path = ppf_acc_in_lds(h->n, (int)h->sizes.alpha_num) ? M3D_PPF_PATH_LDS : M3D_PPF_PATH_DEVICE;
+    }
+    if (tmg) std::memcpy(tmg, h->tmg.data(), sizeof(double) * h->tmg.size());
+    if (!cell_offsets && !entry_i && !entry_alpha && !nbr_offsets && !nbr_indices) return M3D_OK;
+    LaneLock lane(h->device);
+    DeviceCtx* ctx = lane.ctx;
+    if (!ctx) return M3D_ERR_DEVICE;
+    return [&]() -> int {
+        HIPCHK(hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        std::vector<uint32_t> ent;
+        if (cell_offsets)
+            HIPCHK(hipMemcpyAsync(cell_offsets, h->cell_off.p, sizeof(uint32_t) * ((size_t)h->sizes.table_size + 1), hipMemcpyDeviceToHost, st));
+        if (nbr_offsets) HIPCHK(hipMemcpyAsync(nbr_offsets, h->nbr_off.p, sizeof(uint32_t) * (h->n + 1), hipMemcpyDeviceToHost, st));
+        if (nbr_indices) HIPCHK(hipMemcpyAsync(nbr_indices, h->nbr_idx.p, sizeof(uint32_t) * h->n_neighbors, hipMemcpyDeviceToHost, st));
+        if ((entry_i || entry_alpha) && h->n_entries) {
+            ent.resize(h->n_entries);
+            HIPCHK(hipMemcpyAsync(ent.data(), h->entries.p, sizeof(uint32_t) * h->n_entries, hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t t = 0; t < ent.size(); ++t) {
+            if (entry_i) entry_i[t] = (uint16_t)(ent[t] & 0xFFFFu);
+            if (entry_alpha) entry_alpha[t] = (uint8_t)(ent[t] >> 16);
+        }
+        return M3D_OK;
+    }();
+}
+
+int m3d_ppf_vote(const m3d_ppf_model* h, const double* scene_points, const double* scene_normals, size_t m,
+                 const size_t* reference, size_t n_ref, size_t capacity, size_t* n_maxima, uint32_t* ref_pos,
+                 uint32_t* model_index, uint32_t* alpha_index, uint32_t* votes, double* poses, m3d_ppf_vote_stats* stats) {
+    return ppf_vote(h, false, scene_points, scene_normals, m, reference, n_ref, nullptr, nullptr, 0, capacity, n_maxima, ref_pos,
+                    model_index, alpha_index, votes, poses, stats);
+}
+
+int m3d_ppf_vote_edges(const m3d_ppf_model* h, const double* scene_points, const double* scene_normals, size_t m,
+                       const size_t* reference, size_t n_ref, const double* scene_edge_points, const double* scene_edge_normals,
+                       size_t m_edge, size_t capacity, size_t* n_maxima, uint32_t* ref_pos, uint32_t* model_index,
+                       uint32_t* alpha_index, uint32_t* votes, double* poses, m3d_ppf_vote_stats* stats) {
+    return ppf_vote(h, true, scene_points, scene_normals, m, reference, n_ref, scene_edge_points, scene_edge_normals, m_edge, capacity,
+                    n_maxima, ref_pos, model_index, alpha_index, votes, poses, stats);
 }
 
 // measurement / test hook (include/misc3d_amd_bench.h)

@@ -1,5 +1,6 @@
 // m3d_ppf.hip -- the kernels of the PPF table (CalcHashTable, GenerateModelPCNeighbor) and of the vote (VotingAndGetPose,
-// CalcLocalMaximum) for gfx950.  Contract: include/misc3d_amd.h "PPF voting"; arithmetic: m3d_ppf_fp.hpp.  Every output is
+// CalcLocalMaximum) for gfx950, in both voting modes.  Contract: include/misc3d_amd.h "PPF voting" and "PPF voting,
+// EdgePoints mode"; arithmetic: m3d_ppf_fp.hpp.  Every output is
 // an integer: counts by atomics, sets by atomic-or, lists put in order by a stable sort or by the host.
 #include "m3d_ppf.hpp"
 #include "m3d_wave.hpp"
@@ -13,14 +14,15 @@ namespace m3d {
 namespace {
 
 __global__ void ppf_pair_keys_k(PpfModelView M, uint32_t* keys) {
-    const unsigned long long pairs = (unsigned long long)M.n * M.n;
+    const unsigned long long pairs = (unsigned long long)M.n * M.n_e;
     for (unsigned long long p = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; p < pairs;
          p += (unsigned long long)gridDim.x * blockDim.x) {
-        const uint32_t i = (uint32_t)(p / M.n), j = (uint32_t)(p % M.n);
+        const uint32_t i = (uint32_t)(p / M.n_e), j = (uint32_t)(p % M.n_e);
         uint32_t key = M.table_size;
         int q[4], qa;
-        if (i != j && ppf_pair_bins(M.T, M.pts + 3 * (size_t)i, M.nrm + 3 * (size_t)i, M.pts + 3 * (size_t)j, M.nrm + 3 * (size_t)j,
-                                    M.frames + 8 * (size_t)i, q, &qa))
+        if (!(M.same_set && i == j) &&
+            ppf_pair_bins(M.T, M.pts + 3 * (size_t)i, M.nrm + 3 * (size_t)i, M.epts + 3 * (size_t)j, M.enrm + 3 * (size_t)j,
+                          M.frames + 8 * (size_t)i, q, &qa))
             key = ppf_cell(M.T, q) | (uint32_t)qa << 24;
         keys[p] = key;
     }
@@ -37,13 +39,13 @@ __global__ void ppf_cell_offsets_k(const uint32_t* keys, uint32_t pairs, uint32_
         for (uint32_t c = cur + 1; c <= table_size; ++c) cell_off[c] = pairs;
 }
 
-__global__ void ppf_entries_k(const uint32_t* keys, const uint32_t* vals, uint32_t n_entries, uint32_t n, uint32_t table_size,
+__global__ void ppf_entries_k(const uint32_t* keys, const uint32_t* vals, uint32_t n_entries, uint32_t n_e, uint32_t table_size,
                               uint32_t* entries) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_entries) return;   // (the skipped pairs sort behind every cell)
     const uint32_t key = keys[t];
     if ((key & kPpfKeyCellMask) >= table_size) return;
-    entries[t] = vals[t] / n | (key >> 24) << 16;
+    entries[t] = vals[t] / n_e | (key >> 24) << 16;
 }
 
 __global__ void ppf_nbr_count_k(const double* pts, uint32_t n, double r2, uint32_t* counts) {
@@ -155,8 +157,8 @@ __global__ __launch_bounds__(kPpfVoteThreads) void ppf_vote_k(PpfVoteArgs a) {
         const uint32_t ri = a.ref[r];
         double p0[3], n0[3], frame[8];
         for (int c = 0; c < 3; ++c) {
-            p0[c] = a.spts[3 * (size_t)ri + c];
-            n0[c] = a.snrm[3 * (size_t)ri + c];
+            p0[c] = a.rpts[3 * (size_t)ri + c];
+            n0[c] = a.rnrm[3 * (size_t)ri + c];
         }
         for (int c = 0; c < 8; ++c) frame[c] = a.sframes[8 * (size_t)r + c];
         if (tid == 0) {
@@ -252,7 +254,7 @@ uint32_t blocks_of(unsigned long long n, uint32_t per) { return (uint32_t)((n + 
 }  // namespace
 
 void launch_ppf_pair_keys(const PpfModelView& M, uint32_t* keys, hipStream_t st) {
-    const unsigned long long pairs = (unsigned long long)M.n * M.n;
+    const unsigned long long pairs = (unsigned long long)M.n * M.n_e;
     const uint32_t blocks = (uint32_t)std::min<unsigned long long>((pairs + 255) / 256, 1u << 16);
     ppf_pair_keys_k<<<blocks, 256, 0, st>>>(M, keys);
 }
@@ -261,10 +263,10 @@ void launch_ppf_cell_offsets(const uint32_t* sorted_keys, uint32_t pairs, uint32
     ppf_cell_offsets_k<<<blocks_of(pairs, 256), 256, 0, st>>>(sorted_keys, pairs, table_size, cell_off);
 }
 
-void launch_ppf_entries(const uint32_t* sorted_keys, const uint32_t* sorted_pairs, uint32_t n_entries, uint32_t n, uint32_t table_size,
+void launch_ppf_entries(const uint32_t* sorted_keys, const uint32_t* sorted_pairs, uint32_t n_entries, uint32_t n_e, uint32_t table_size,
                         uint32_t* entries, hipStream_t st) {
     if (n_entries == 0) return;
-    ppf_entries_k<<<blocks_of(n_entries, 256), 256, 0, st>>>(sorted_keys, sorted_pairs, n_entries, n, table_size, entries);
+    ppf_entries_k<<<blocks_of(n_entries, 256), 256, 0, st>>>(sorted_keys, sorted_pairs, n_entries, n_e, table_size, entries);
 }
 
 void launch_ppf_nbr_count(const double* pts, uint32_t n, double r2, uint32_t* counts, hipStream_t st) {

@@ -19,6 +19,7 @@ struct PpfModelHost {
     double diameter, dist_step;
     const double* centroid;   // 3
     const double* centred;    // n x 3
+    bool edges;               // trained in EdgePoints mode (m3d_ppf_model_create_edges)
 };
 PpfModelHost ppf_model_host(const m3d_ppf_model* h);
 

@@ -189,6 +189,8 @@ M3D_PC_HD void pc_centre_shift(double *pose, const double *c) {
 
 /* K8: expected = ((ratio n) n) 0.25, score = min(1.0, votes / expected) */
 M3D_PC_HD double pc_expected_votes(double ratio, uint64_t n) { return ((ratio * (double)n) * (double)n) * 0.25; }
+/* EdgePoints mode (rule E9): reference_num_ refered_num_ are both the sample's size, and no reduction factor */
+M3D_PC_HD double pc_expected_votes_edges(double ratio, uint64_t n) { return (ratio * (double)n) * (double)n; }
 M3D_PC_HD double pc_score(uint64_t votes, double expected) {
     const double s = (double)votes / expected;
     return s < 1.0 ? s : 1.0;

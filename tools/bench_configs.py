@@ -17,6 +17,7 @@ bench.py); these lines feed DESIGN.md section 6 and check that the full sizes ru
           100-frame batch of the example
   PV1 PPFVoting: the table of a 2 000-point model and the vote of a 20 000-point scene at ratio 0.6, LDS / device memory A/B
   PC1 PPF pose clustering on PV1's scene: the vote's raw poses through m3d_ppf_cluster_poses, and the whole m3d_ppf_estimate
+  PV2 PPFVoting in EdgePoints mode at PV1's sizes: a plate with holes, its edge sets by detect_boundary_points; table, vote, estimate
 """
 import json
 import os
@@ -1095,5 +1096,75 @@ if "PC1" in which or ALL:
                    "top_pose_error": float(np.abs(est["poses"][0] - ppf_util.pose(1)).max()) if len(est["votes"]) else None,
                    "ms_total_no_refine": ms_norefine},
          roofline={"bound": "fp64 VALU of the all-pairs loops (three launches a level) and the LDS broadcast feeding them",
+                   "share_of_peak": "not measured"},
+         cpu_baseline=cpu_b)
+
+if "PV2" in which or ALL:
+    # pose_estimation.PPFVoting in EdgePoints mode ("PPF EdgePoints mode") at PV1's sizes: a plate with holes
+    # sampled by about 2 000 points, its edge points those detect_boundary_points finds on a dense sampling of the same plate; the
+    # scene is the posed sample in 18 000 points of clutter (12 000 reference points at ratio 0.6), the scene's edges the posed
+    # model edges and as many clutter edge points again.  Median of 5 calls after 1 warm-up for the table and the vote (once more
+    # through device memory), of 3 for m3d_ppf_estimate_edges.  cpu_baseline = the contract's C restatement
+    # (tests/cpp/ppf_edge_ref.c) under OpenMP on 16 threads: the table whole, the vote on every tenth reference point, scaled.
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ppf_edge_ref_util as edge_util
+    import ppf_ref_util as ppf_util
+
+    pts, nrm, _, _, diameter = edge_util.plate_with_holes(n_side=57)
+    dense, dense_n, _, _, _ = edge_util.plate_with_holes(n_side=130)
+    eidx = capi.detect_boundary_points(dense, dense_n, capi.SEARCH_HYBRID, 0.03 * diameter, 30, 90.0).astype(np.int64)
+    ept, enr = np.ascontiguousarray(dense[eidx]), np.ascontiguousarray(dense_n[eidx])
+    r_min = 0.45 * diameter
+    T = ppf_util.pose(1)
+    sp, sn, _ = ppf_util.scene_of(pts, nrm, T, 20_000 - len(pts), 1)
+    sep, sen, _ = ppf_util.scene_of(ept, enr, T, len(ept), 51)
+    refs = np.sort(np.random.default_rng(1).permutation(len(sp))[: int(0.6 * len(sp))])
+
+    def pv2_median(fn, reps=5):
+        fn()
+        runs = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            r = fn()
+            runs.append(((time.perf_counter() - t0) * 1e3, r))
+        runs.sort(key=lambda t: t[0])
+        return runs[len(runs) // 2]
+
+    ms_table, model = pv2_median(lambda: capi.PpfModel(pts, nrm, diameter, r_min, edge_points=ept, edge_normals=enr))
+    ms_vote, (res, st) = pv2_median(lambda: model.vote(sp, sn, refs, stats=True, edge_points=sep, edge_normals=sen))
+    capi.ppf_force(True, 0)
+    try:
+        ms_vote_dev, (res_dev, st_dev) = pv2_median(lambda: model.vote(sp, sn, refs, stats=True, edge_points=sep, edge_normals=sen))
+    finally:
+        capi.ppf_force(False, 0)
+    ms_estimate, est = pv2_median(lambda: capi.ppf_estimate(model, sp, sn, refs, edge_points=sep, edge_normals=sen, score_thresh=0.0), 3)
+    es = est["stats"]
+    cpu_b = None
+    if not NO_CPU:
+        os.environ.setdefault("OMP_NUM_THREADS", "16")
+        ref = edge_util.PpfEdgeRef(tempfile.mkdtemp(), openmp=True)
+        t0 = time.perf_counter()
+        rm = ref.edge_model(pts, nrm, ept, enr, diameter, r_min)
+        t1 = time.perf_counter()
+        rv = rm.vote(sp, sn, refs[::10], sep, sen)
+        t2 = time.perf_counter()
+        cpu_b = {"ms_table": (t1 - t0) * 1e3, "ms_vote": (t2 - t1) * 1e3 * len(refs) / len(refs[::10]), "unit": "ms",
+                 "vote_sampled": "every 10th reference point, scaled by the count", "increments_sampled": rv["increments"],
+                 "same_table_size": bool(rm.n_entries == model.info()["n_entries"]),
+                 "what": "tests/cpp/ppf_edge_ref.c: the contract's restatement, gcc -O2 -ffp-contract=off -fopenmp, 16 threads"}
+    emit("PV2 ppf EdgePoints: table of a plate with holes + vote and estimate on a 20 000-point scene, 12 000 reference points",
+         n=len(pts), n_edge=len(ept), m=len(sp), m_edge=len(sep), n_ref=len(refs), table_entries=model.info()["n_entries"],
+         ms_table=ms_table, ms_vote=ms_vote, ms_vote_device=st["ms_device"], path=st["path"], groups=st["groups"],
+         launches=st["launches"], neighbours_visited=st["neighbours_visited"], increments=st["increments"], maxima=len(res["votes"]),
+         increments_per_second=st["increments"] / (st["ms_device"] * 1e-3) if st["ms_device"] > 0 else None,
+         device_memory_path={"ms_vote": ms_vote_dev, "ms_vote_device": st_dev["ms_device"], "path": st_dev["path"],
+                             "same_result": bool(all(np.array_equal(res[k], res_dev[k]) for k in res))},
+         estimate={"ms_total": ms_estimate, "ms_vote": es["ms_vote"], "ms_cluster": es["ms_cluster"], "ms_refine": es["ms_refine"],
+                   "ms_host": es["ms_host"], "icp_calls": es["icp_calls"], "icp_iterations": es["icp_iterations"],
+                   "results": len(est["votes"]), "top_votes": int(est["votes"][0]) if len(est["votes"]) else 0,
+                   "top_score": float(est["scores"][0]) if len(est["votes"]) else 0.0,
+                   "top_pose_error": float(np.abs(est["poses"][0] - T).max()) if len(est["votes"]) else None},
+         roofline={"bound": "atomic increments (LDS or L2) and the divergent walk over table cells; no HBM or VALU ceiling is meaningful",
                    "share_of_peak": "not measured"},
          cpu_baseline=cpu_b)
