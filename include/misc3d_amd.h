@@ -1152,7 +1152,7 @@ int m3d_ppf_vote(const m3d_ppf_model *model, const double *scene_points, const d
  * The reference's second voting mode, for flat parts whose shape is in their boundary: the table pairs the model sample with
  * the model's EDGE points (Train, :572-593, CalcHashTable with b_same_pointset == false), the vote pairs a scene sample point
  * with the scene's edge points (Estimate, :319-328).  Only what differs from M1 - M6, V1 - V8, U1 - U6 and K1 - K8 is said
- * here; tests/cpp/ppf_edge_ref.c restates it in serial C.
+ * here; tests/cpp/ppf_ref.c restates both modes in serial C (its edge arrays are optional: null means SampledPoints).
  *   E1. Inputs: points[n], normals[n] (the model sample), edge_points[n_e], edge_normals[n_e], diameter, r_min, params.  Sizes
  *       as M1.  The centroid is M2's, from the n sample points alone; BOTH sets are centred by it.
  *   E2. tmg[i] as M3, for the sample points.

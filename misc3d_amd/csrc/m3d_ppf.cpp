@@ -214,10 +214,11 @@ int ppf_build_table(DeviceCtx* ctx, m3d_ppf_model* h) {
     return rc;
 }
 
-// Train (:537-593) in either mode.  edge == false: rules M1 - M6; edge == true: E1 - E5, the referred set being the n_e edge points.
-m3d_ppf_model* ppf_model_create(const double* points, const double* normals, size_t n, const double* edge_points,
-                                const double* edge_normals, size_t n_e, bool edge, double diameter, double r_min,
+// Train (:537-593).  edges == null: rules M1 - M6; else E1 - E5, the referred set being the model's edge points.
+m3d_ppf_model* ppf_model_create(const PpfCloud& sample, const PpfCloud* edges, double diameter, double r_min,
                                 const m3d_ppf_params* params, int device, int* status) {
+    const double *points = sample.pts, *normals = sample.nrm;
+    const size_t n = sample.n, n_e = edges ? edges->n : 0;
     if (status) *status = M3D_ERR_INVALID_ARG;
     m3d_ppf_params P;
     m3d_ppf_default_params(&P);
@@ -230,11 +231,11 @@ m3d_ppf_model* ppf_model_create(const double* points, const double* normals, siz
         fail(M3D_ERR_INVALID_ARG, "ppf: the model must have 2 .. 65535 points, got " + std::to_string(n));
         return nullptr;
     }
-    if (edge && (!edge_points || !edge_normals)) {
+    if (edges && (!edges->pts || !edges->nrm)) {
         fail(M3D_ERR_INVALID_ARG, "ppf: null edge points or normals");
         return nullptr;
     }
-    if (edge && (n_e < 1 || n_e > kPpfMaxPoints)) {
+    if (edges && (n_e < 1 || n_e > kPpfMaxPoints)) {
         fail(M3D_ERR_INVALID_ARG, "ppf: the model must have 1 .. 65535 edge points, got " + std::to_string(n_e));
         return nullptr;
     }
@@ -244,20 +245,20 @@ m3d_ppf_model* ppf_model_create(const double* points, const double* normals, siz
         fail(M3D_ERR_INVALID_ARG, "ppf: a model point or normal is not finite");
         return nullptr;
     }
-    if (edge && (!finite3(edge_points, n_e) || !finite3(edge_normals, n_e))) {
+    if (edges && (!finite3(edges->pts, n_e) || !finite3(edges->nrm, n_e))) {
         fail(M3D_ERR_INVALID_ARG, "ppf: a model edge point or normal is not finite");
         return nullptr;
     }
     if (status) *status = M3D_ERR_DEVICE;
-    if ((uint64_t)n * (edge ? n_e : n) > kPpfMaxSortPairs) {
-        fail(M3D_ERR_DEVICE, edge ? "ppf: the table's sort scratch (16 bytes a pair) is capped at 4 GiB: n x n_edge <= 2^28"
-                                  : "ppf: the table's sort scratch (16 bytes a pair) is capped at 4 GiB: n <= 16383");
+    if ((uint64_t)n * (edges ? n_e : n) > kPpfMaxSortPairs) {
+        fail(M3D_ERR_DEVICE, edges ? "ppf: the table's sort scratch (16 bytes a pair) is capped at 4 GiB: n x n_edge <= 2^28"
+                                   : "ppf: the table's sort scratch (16 bytes a pair) is capped at 4 GiB: n <= 16383");
         return nullptr;
     }
     m3d_ppf_model* h = new m3d_ppf_model;
     h->device = device;
     h->n = (uint32_t)n;
-    h->n_e = edge ? (uint32_t)n_e : 0;
+    h->n_e = (uint32_t)n_e;
     h->diameter = diameter;
     h->r_min = r_min;
     h->angle_step = P.angle_step;
@@ -280,10 +281,10 @@ m3d_ppf_model* ppf_model_create(const double* points, const double* normals, siz
         frame_rows(&h->tmg[16 * i], &rows[8 * i]);
     }
     // rule E1: the edge points are centred by the SAMPLE's centroid
-    std::vector<double> ecentred(edge ? 3 * n_e : 0);
-    for (size_t j = 0; j < ecentred.size() / 3; ++j)
-        for (int k = 0; k < 3; ++k) ecentred[3 * j + k] = edge_points[3 * j + k] - h->centroid[k];
-    if (!finite3(centred.data(), n) || !finite3(ecentred.data(), ecentred.size() / 3)) {
+    std::vector<double> ecentred(3 * n_e);
+    for (size_t j = 0; j < n_e; ++j)
+        for (int k = 0; k < 3; ++k) ecentred[3 * j + k] = edges->pts[3 * j + k] - h->centroid[k];
+    if (!finite3(centred.data(), n) || !finite3(ecentred.data(), n_e)) {
         fail(M3D_ERR_INVALID_ARG, "ppf: a centred model point is not finite");
         if (status) *status = M3D_ERR_INVALID_ARG;
         delete h;
@@ -305,11 +306,11 @@ m3d_ppf_model* ppf_model_create(const double* points, const double* normals, siz
                 HIPCHK(hipMemcpyAsync(h->nrm.p, normals, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
                 HIPCHK(hipMemcpyAsync(h->frames.p, rows.data(), sizeof(double) * 8 * n, hipMemcpyHostToDevice, st));
                 HIPCHK(hipMemcpyAsync(h->d_edge2.p, h->edge2.data(), sizeof(double) * h->edge2.size(), hipMemcpyHostToDevice, st));
-                if (edge) {
+                if (edges) {
                     RESERVE(h->epts, sizeof(double) * 3 * n_e);
                     RESERVE(h->enrm, sizeof(double) * 3 * n_e);
                     HIPCHK(hipMemcpyAsync(h->epts.p, ecentred.data(), sizeof(double) * 3 * n_e, hipMemcpyHostToDevice, st));
-                    HIPCHK(hipMemcpyAsync(h->enrm.p, edge_normals, sizeof(double) * 3 * n_e, hipMemcpyHostToDevice, st));
+                    HIPCHK(hipMemcpyAsync(h->enrm.p, edges->nrm, sizeof(double) * 3 * n_e, hipMemcpyHostToDevice, st));
                 }
                 HIPCHK(hipStreamSynchronize(st));
                 return ppf_build_table(ctx, h);
@@ -344,61 +345,63 @@ m3d::PpfModelHost m3d::ppf_model_host(const m3d_ppf_model* h) {
     return v;
 }
 
-namespace {
-
-// VotingAndGetPose (:399-524) in either mode.  edge == false (m3d_ppf_vote): the scene is scanned and holds the reference points.
-// edge == true (m3d_ppf_vote_edges, rules E6 - E8): the reference points are read from the scene sample, the scene's m_e edge
-// points are scanned; only the n_ref reference points (gathered) and the edge points go to the device.
-int ppf_vote(const m3d_ppf_model* h, bool edge, const double* scene_points, const double* scene_normals, size_t m,
-             const size_t* reference, size_t n_ref, const double* edge_points, const double* edge_normals, size_t m_e, size_t capacity,
-             size_t* n_maxima, uint32_t* ref_pos, uint32_t* model_index, uint32_t* alpha_index, uint32_t* votes, double* poses,
-             m3d_ppf_vote_stats* stats) {
-    const double t0 = now_ms();
-    m3d_ppf_vote_stats S{};
-    if (stats) *stats = S;
-    if (n_maxima) *n_maxima = 0;
+// VotingAndGetPose (:399-524), the part that needs no device (m3d_ppf_cluster.hpp).  scene.edges == null (m3d_ppf_vote): the scene
+// is scanned and holds the reference points.  Else (m3d_ppf_vote_edges, rules E6 - E8): the reference points are read from the scene
+// sample, the scene's edge points are scanned; only the n_ref reference points (gathered) and the edge points go to the device.
+int m3d::ppf_check_vote(const m3d_ppf_model* h, const PpfScene& scene, const PpfVoteOut* out, PpfVote* V) {
+    const PpfCloud& sc = scene.sample;
+    const size_t n_ref = scene.n_ref;
     if (!h) return fail(M3D_ERR_INVALID_ARG, "ppf: null model");
-    if (edge != h->edges())
-        return fail(M3D_ERR_INVALID_ARG, edge ? "ppf: the model was trained in SampledPoints mode: vote with m3d_ppf_vote / m3d_ppf_estimate"
-                                              : "ppf: the model was trained in EdgePoints mode: vote with m3d_ppf_vote_edges / m3d_ppf_estimate_edges");
-    if (!scene_points || !scene_normals || !reference || !n_maxima) return fail(M3D_ERR_INVALID_ARG, "ppf: null argument");
-    if (capacity && (!ref_pos || !model_index || !alpha_index || !votes)) return fail(M3D_ERR_INVALID_ARG, "ppf: null result array");
+    if ((scene.edges != nullptr) != h->edges())
+        return fail(M3D_ERR_INVALID_ARG, scene.edges ? "ppf: the model was trained in SampledPoints mode: vote with m3d_ppf_vote / m3d_ppf_estimate"
+                                                     : "ppf: the model was trained in EdgePoints mode: vote with m3d_ppf_vote_edges / m3d_ppf_estimate_edges");
+    if (!sc.pts || !sc.nrm || !scene.reference || (out && !out->n_maxima)) return fail(M3D_ERR_INVALID_ARG, "ppf: null argument");
+    if (out && out->capacity && (!out->ref_pos || !out->model_index || !out->alpha_index || !out->votes))
+        return fail(M3D_ERR_INVALID_ARG, "ppf: null result array");
     if (n_ref == 0) return fail(M3D_ERR_INVALID_ARG, "ppf: no reference points");
-    if (m == 0 || m >= ((size_t)1 << 31) || n_ref >= ((size_t)1 << 31)) return fail(M3D_ERR_INVALID_ARG, "ppf: the scene must have 1 .. 2^31 - 1 points");
-    if (!finite3(scene_points, m) || !finite3(scene_normals, m)) return fail(M3D_ERR_INVALID_ARG, "ppf: a scene point or normal is not finite");
-    if (edge) {
-        if (!edge_points || !edge_normals) return fail(M3D_ERR_INVALID_ARG, "ppf: null scene edge points or normals");
-        if (m_e == 0 || m_e >= ((size_t)1 << 31)) return fail(M3D_ERR_INVALID_ARG, "ppf: the scene must have 1 .. 2^31 - 1 edge points");
-        if (!finite3(edge_points, m_e) || !finite3(edge_normals, m_e))
-            return fail(M3D_ERR_INVALID_ARG, "ppf: a scene edge point or normal is not finite");
+    if (sc.n == 0 || sc.n >= ((size_t)1 << 31) || n_ref >= ((size_t)1 << 31)) return fail(M3D_ERR_INVALID_ARG, "ppf: the scene must have 1 .. 2^31 - 1 points");
+    if (!finite3(sc.pts, sc.n) || !finite3(sc.nrm, sc.n)) return fail(M3D_ERR_INVALID_ARG, "ppf: a scene point or normal is not finite");
+    if (const PpfCloud* e = scene.edges) {
+        if (!e->pts || !e->nrm) return fail(M3D_ERR_INVALID_ARG, "ppf: null scene edge points or normals");
+        if (e->n == 0 || e->n >= ((size_t)1 << 31)) return fail(M3D_ERR_INVALID_ARG, "ppf: the scene must have 1 .. 2^31 - 1 edge points");
+        if (!finite3(e->pts, e->n) || !finite3(e->nrm, e->n)) return fail(M3D_ERR_INVALID_ARG, "ppf: a scene edge point or normal is not finite");
     }
-    std::vector<uint32_t> ref32(n_ref);
+    V->ref.resize(n_ref);
     for (size_t s = 0; s < n_ref; ++s) {
-        if (reference[s] >= m) return fail(M3D_ERR_INVALID_ARG, "ppf: a reference index is out of range");
-        ref32[s] = (uint32_t)reference[s];
+        if (scene.reference[s] >= sc.n) return fail(M3D_ERR_INVALID_ARG, "ppf: a reference index is out of range");
+        V->ref[s] = (uint32_t)scene.reference[s];
     }
+    V->tsg.resize(16 * n_ref);
+    V->rows.resize(8 * n_ref);
+    for (size_t s = 0; s < n_ref; ++s) {
+        ppf_frame(sc.pts + 3 * (size_t)V->ref[s], sc.nrm + 3 * (size_t)V->ref[s], &V->tsg[16 * s]);
+        frame_rows(&V->tsg[16 * s], &V->rows[8 * s]);
+    }
+    // EdgePoints: the reference points alone, gathered in reference order; position s reads row s
+    if (scene.edges) {
+        V->rpts.resize(3 * n_ref);
+        V->rnrm.resize(3 * n_ref);
+        for (size_t s = 0; s < n_ref; ++s) {
+            std::memcpy(&V->rpts[3 * s], sc.pts + 3 * (size_t)V->ref[s], sizeof(double) * 3);
+            std::memcpy(&V->rnrm[3 * s], sc.nrm + 3 * (size_t)V->ref[s], sizeof(double) * 3);
+            V->ref[s] = (uint32_t)s;
+        }
+    }
+    return M3D_OK;
+}
+
+// ... and the part on a lane the caller holds: the upload, the kernel, the maxima in rule V8's order
+int m3d::ppf_vote_on(DeviceCtx* ctx, const m3d_ppf_model* h, const PpfScene& scene, PpfVote* V) {
+    const bool edge = scene.edges != nullptr;
+    const PpfCloud& scan = edge ? *scene.edges : scene.sample;   // the cloud the kernel scans
+    const size_t m_scan = scan.n, n_ref = scene.n_ref;
     const uint32_t n = h->n;
     const int A = (int)h->sizes.alpha_num;
     const uint32_t table_size = (uint32_t)h->sizes.table_size;
-    std::vector<double> tsg(16 * n_ref), rows(8 * n_ref);
-    for (size_t s = 0; s < n_ref; ++s) {
-        ppf_frame(scene_points + 3 * (size_t)ref32[s], scene_normals + 3 * (size_t)ref32[s], &tsg[16 * s]);
-        frame_rows(&tsg[16 * s], &rows[8 * s]);
-    }
-    // EdgePoints: the reference points alone, gathered in reference order; position s reads row s
-    std::vector<double> rp, rn;
-    if (edge) {
-        rp.resize(3 * n_ref);
-        rn.resize(3 * n_ref);
-        for (size_t s = 0; s < n_ref; ++s) {
-            std::memcpy(&rp[3 * s], scene_points + 3 * (size_t)ref32[s], sizeof(double) * 3);
-            std::memcpy(&rn[3 * s], scene_normals + 3 * (size_t)ref32[s], sizeof(double) * 3);
-            ref32[s] = (uint32_t)s;
-        }
-    }
-    const double* scan_points = edge ? edge_points : scene_points;   // the cloud the kernel scans, m_scan points
-    const double* scan_normals = edge ? edge_normals : scene_normals;
-    const size_t m_scan = edge ? m_e : m;
+    m3d_ppf_vote_stats& S = V->stats;
+    S = m3d_ppf_vote_stats{};
+    std::vector<PpfMaximum>& found = V->maxima;
+    found.clear();
     const bool lds = ppf_acc_in_lds(n, A) && g_ppf_force_device.load() == 0;
     const size_t acc_words = ppf_acc_words(n, A);
     // the workgroups: what the flag arrays (and, in device memory, the accumulators) leave of the call's scratch
@@ -410,17 +413,15 @@ int ppf_vote(const m3d_ppf_model* h, bool edge, const double* scene_points, cons
     S.path = lds ? M3D_PPF_PATH_LDS : M3D_PPF_PATH_DEVICE;
     S.groups = (uint32_t)groups;
 
-    LaneLock lane(h->device);
-    DeviceCtx* ctx = lane.ctx;
-    if (!ctx) return M3D_ERR_DEVICE;
     VoteBufs B;
-    std::vector<PpfMaximum> found;
     const int rc = [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
         hipStream_t st = ctx->stream;
         HIPCHK(hipEventRecord(ctx->ev0, st));
         const size_t fixed = sizeof(double) * (6 * m_scan + (edge ? 14 : 8) * n_ref) + sizeof(uint32_t) * n_ref;
-        size_t out_cap = std::max<size_t>(1024, 4 * n_ref);
+        // room for the maxima of the first launch: the guess m3d_ppf_estimate used to make for its own arrays, and never more
+        // than there can be (a maximum is a model row of a reference position)
+        size_t out_cap = std::min<size_t>(n_ref * (size_t)n, std::max<size_t>(4096, 4 * n_ref));
         if (fixed + groups * (sizeof(unsigned long long) * table_size + per_group) + sizeof(PpfMaximum) * out_cap > kPpfScratchCap)
             return fail(M3D_ERR_INVALID_ARG, "ppf: the scene and its reference points do not fit the call's 256 MiB of scratch");
         RESERVE(B.spts, sizeof(double) * 3 * m_scan);
@@ -431,16 +432,16 @@ int ppf_vote(const m3d_ppf_model* h, bool edge, const double* scene_points, cons
         if (!lds) RESERVE(B.acc, sizeof(uint32_t) * acc_words * groups);
         RESERVE(B.rowinfo, sizeof(uint32_t) * (size_t)n * groups);
         RESERVE(B.small, 64);
-        HIPCHK(hipMemcpyAsync(B.spts.p, scan_points, sizeof(double) * 3 * m_scan, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(B.snrm.p, scan_normals, sizeof(double) * 3 * m_scan, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(B.spts.p, scan.pts, sizeof(double) * 3 * m_scan, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(B.snrm.p, scan.nrm, sizeof(double) * 3 * m_scan, hipMemcpyHostToDevice, st));
         if (edge) {
             RESERVE(B.rpts, sizeof(double) * 3 * n_ref);
             RESERVE(B.rnrm, sizeof(double) * 3 * n_ref);
-            HIPCHK(hipMemcpyAsync(B.rpts.p, rp.data(), sizeof(double) * 3 * n_ref, hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(B.rnrm.p, rn.data(), sizeof(double) * 3 * n_ref, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(B.rpts.p, V->rpts.data(), sizeof(double) * 3 * n_ref, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(B.rnrm.p, V->rnrm.data(), sizeof(double) * 3 * n_ref, hipMemcpyHostToDevice, st));
         }
-        HIPCHK(hipMemcpyAsync(B.ref.p, ref32.data(), sizeof(uint32_t) * n_ref, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(B.sframes.p, rows.data(), sizeof(double) * 8 * n_ref, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(B.ref.p, V->ref.data(), sizeof(uint32_t) * n_ref, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(B.sframes.p, V->rows.data(), sizeof(double) * 8 * n_ref, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemsetAsync(B.flags.p, 0, sizeof(unsigned long long) * table_size * groups, st));
         PpfVoteArgs a;
         a.M = h->view();
@@ -500,19 +501,40 @@ int ppf_vote(const m3d_ppf_model* h, bool edge, const double* scene_points, cons
     for (const PpfMaximum& x : found)
         if (x.ref_pos >= n_ref || x.model_index >= n || x.alpha_index >= (uint32_t)A)
             return fail(M3D_ERR_INTERNAL, "ppf: a maximum is out of range (self-check)");
-    *n_maxima = found.size();
-    S.ms_total = now_ms() - t0;
-    if (stats) *stats = S;
-    if (found.size() > capacity)
-        return fail(M3D_ERR_CAPACITY, "ppf: " + std::to_string(found.size()) + " maxima, the result arrays hold " + std::to_string(capacity));
-    for (size_t k = 0; k < found.size(); ++k) {
-        ref_pos[k] = found[k].ref_pos;
-        model_index[k] = found[k].model_index;
-        alpha_index[k] = found[k].alpha_index;
-        votes[k] = found[k].votes;
-        if (poses)
-            ppf_pose(&tsg[16 * (size_t)found[k].ref_pos], (double)found[k].alpha_index * h->angle_step,
-                     &h->tmg[16 * (size_t)found[k].model_index], poses + 16 * k);
+    return M3D_OK;
+}
+
+void m3d::ppf_vote_pose(const m3d_ppf_model* h, const PpfVote& V, size_t k, double* pose16) {
+    const PpfMaximum& x = V.maxima[k];
+    ppf_pose(&V.tsg[16 * (size_t)x.ref_pos], (double)x.alpha_index * h->angle_step, &h->tmg[16 * (size_t)x.model_index], pose16);
+}
+
+namespace {
+
+// m3d_ppf_vote / m3d_ppf_vote_edges: check, take a lane, vote on it, then the capacity test and the copy-out
+int ppf_vote(const m3d_ppf_model* h, const PpfScene& scene, const PpfVoteOut& out, m3d_ppf_vote_stats* stats) {
+    const double t0 = now_ms();
+    PpfVote V;
+    if (stats) *stats = V.stats;
+    if (out.n_maxima) *out.n_maxima = 0;
+    if (const int rc = ppf_check_vote(h, scene, &out, &V); rc != M3D_OK) return rc;
+    {
+        LaneLock lane(h->device);
+        if (!lane.ctx) return M3D_ERR_DEVICE;
+        if (const int rc = ppf_vote_on(lane.ctx, h, scene, &V); rc != M3D_OK) return rc;
+    }
+    const size_t found = V.maxima.size();
+    *out.n_maxima = found;
+    V.stats.ms_total = now_ms() - t0;
+    if (stats) *stats = V.stats;
+    if (found > out.capacity)
+        return fail(M3D_ERR_CAPACITY, "ppf: " + std::to_string(found) + " maxima, the result arrays hold " + std::to_string(out.capacity));
+    for (size_t k = 0; k < found; ++k) {
+        out.ref_pos[k] = V.maxima[k].ref_pos;
+        out.model_index[k] = V.maxima[k].model_index;
+        out.alpha_index[k] = V.maxima[k].alpha_index;
+        out.votes[k] = V.maxima[k].votes;
+        if (out.poses) ppf_vote_pose(h, V, k, out.poses + 16 * k);
     }
     return M3D_OK;
 }
@@ -533,13 +555,14 @@ void m3d_ppf_default_params(m3d_ppf_params* out) {
 
 m3d_ppf_model* m3d_ppf_model_create(const double* points, const double* normals, size_t n, double diameter, double r_min,
                                     const m3d_ppf_params* params, int device, int* status) {
-    return ppf_model_create(points, normals, n, nullptr, nullptr, 0, false, diameter, r_min, params, device, status);
+    return ppf_model_create({points, normals, n}, nullptr, diameter, r_min, params, device, status);
 }
 
 m3d_ppf_model* m3d_ppf_model_create_edges(const double* points, const double* normals, size_t n, const double* edge_points,
                                           const double* edge_normals, size_t n_edge, double diameter, double r_min,
                                           const m3d_ppf_params* params, int device, int* status) {
-    return ppf_model_create(points, normals, n, edge_points, edge_normals, n_edge, true, diameter, r_min, params, device, status);
+    const PpfCloud edges{edge_points, edge_normals, n_edge};
+    return ppf_model_create({points, normals, n}, &edges, diameter, r_min, params, device, status);
 }
 
 void m3d_ppf_model_destroy(m3d_ppf_model* h) {
@@ -599,16 +622,17 @@ int m3d_ppf_model_table(const m3d_ppf_model* h, m3d_ppf_table_info* info, uint32
 int m3d_ppf_vote(const m3d_ppf_model* h, const double* scene_points, const double* scene_normals, size_t m,
                  const size_t* reference, size_t n_ref, size_t capacity, size_t* n_maxima, uint32_t* ref_pos,
                  uint32_t* model_index, uint32_t* alpha_index, uint32_t* votes, double* poses, m3d_ppf_vote_stats* stats) {
-    return ppf_vote(h, false, scene_points, scene_normals, m, reference, n_ref, nullptr, nullptr, 0, capacity, n_maxima, ref_pos,
-                    model_index, alpha_index, votes, poses, stats);
+    return ppf_vote(h, {{scene_points, scene_normals, m}, reference, n_ref, nullptr},
+                    {capacity, n_maxima, ref_pos, model_index, alpha_index, votes, poses}, stats);
 }
 
 int m3d_ppf_vote_edges(const m3d_ppf_model* h, const double* scene_points, const double* scene_normals, size_t m,
                        const size_t* reference, size_t n_ref, const double* scene_edge_points, const double* scene_edge_normals,
                        size_t m_edge, size_t capacity, size_t* n_maxima, uint32_t* ref_pos, uint32_t* model_index,
                        uint32_t* alpha_index, uint32_t* votes, double* poses, m3d_ppf_vote_stats* stats) {
-    return ppf_vote(h, true, scene_points, scene_normals, m, reference, n_ref, scene_edge_points, scene_edge_normals, m_edge, capacity,
-                    n_maxima, ref_pos, model_index, alpha_index, votes, poses, stats);
+    const PpfCloud edges{scene_edge_points, scene_edge_normals, m_edge};
+    return ppf_vote(h, {{scene_points, scene_normals, m}, reference, n_ref, &edges},
+                    {capacity, n_maxima, ref_pos, model_index, alpha_index, votes, poses}, stats);
 }
 
 // measurement / test hook (include/misc3d_amd_bench.h)

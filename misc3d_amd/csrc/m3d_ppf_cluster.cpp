@@ -222,49 +222,57 @@ int pc_cluster_on(DeviceCtx* ctx, const double* poses, const uint32_t* votes, si
 
 namespace {
 
-// Estimate from the vote on (:304-395) in either mode.  edge == true (rule E9): the vote reads the scene's edge points, the
-// refinement still runs against the scene sample, and K8's expected votes drop the 0.25.
-int ppf_estimate(const m3d_ppf_model* model, bool edge, const double* scene_points, const double* scene_normals, size_t m,
-                 const size_t* reference, size_t n_ref, const double* edge_points, const double* edge_normals, size_t m_e,
-                 const m3d_ppf_cluster_params* params, size_t capacity, size_t* n_results, double* poses, double* q, double* t,
-                 uint64_t* votes, double* scores, m3d_ppf_estimate_stats* stats) {
+// m3d_ppf_estimate's result arrays, `capacity` entries each
+struct PpfEstimateOut {
+    size_t capacity;
+    size_t* n_results;
+    double *poses, *q, *t;
+    uint64_t* votes;
+    double* scores;
+};
+
+// Estimate from the vote on (:304-395), the vote, the clustering and the refinement on one lane.  With scene.edges (rule E9) the
+// vote reads the scene's edge points, the refinement still runs against the scene sample, and K8's expected votes drop the 0.25.
+int ppf_estimate(const m3d_ppf_model* model, const PpfScene& scene, const m3d_ppf_cluster_params* params, const PpfEstimateOut& out,
+                 m3d_ppf_estimate_stats* stats) {
     const double t0 = now_ms();
     m3d_ppf_estimate_stats S{};
     if (stats) *stats = S;
-    if (n_results) *n_results = 0;
-    if (!model || !n_results) return fail(M3D_ERR_INVALID_ARG, "ppf estimate: null argument");
-    if (capacity && (!poses || !q || !t || !votes || !scores)) return fail(M3D_ERR_INVALID_ARG, "ppf estimate: null result array");
+    if (out.n_results) *out.n_results = 0;
+    if (!model || !out.n_results) return fail(M3D_ERR_INVALID_ARG, "ppf estimate: null argument");
+    if (out.capacity && (!out.poses || !out.q || !out.t || !out.votes || !out.scores))
+        return fail(M3D_ERR_INVALID_ARG, "ppf estimate: null result array");
     m3d_ppf_cluster_params prm;
     m3d_ppf_default_cluster_params(model, &prm);
     if (params) prm = *params;
     if (const int rc = pc_check_params(prm); rc != M3D_OK) return rc;
     const PpfModelHost M = ppf_model_host(model);
-    // the vote (it checks the scene and the reference indices): twice when the first guess at the number of maxima is short
-    std::vector<uint32_t> ref_pos, model_index, alpha_index, raw_votes;
-    std::vector<double> raw_poses;
-    size_t n_raw = 0, cap = std::max<size_t>(4096, 4 * n_ref);
-    for (int attempt = 0;; ++attempt) {
-        for (std::vector<uint32_t>* v : {&ref_pos, &model_index, &alpha_index, &raw_votes}) v->resize(cap);
-        raw_poses.resize(16 * cap);
-        const int rc = edge ? m3d_ppf_vote_edges(model, scene_points, scene_normals, m, reference, n_ref, edge_points, edge_normals, m_e,
-                                                 cap, &n_raw, ref_pos.data(), model_index.data(), alpha_index.data(), raw_votes.data(),
-                                                 raw_poses.data(), &S.vote)
-                            : m3d_ppf_vote(model, scene_points, scene_normals, m, reference, n_ref, cap, &n_raw, ref_pos.data(),
-                                           model_index.data(), alpha_index.data(), raw_votes.data(), raw_poses.data(), &S.vote);
-        S.ms_vote += S.vote.ms_total;
-        if (rc == M3D_OK) break;
-        if (rc != M3D_ERR_CAPACITY || attempt == 1) return rc;
-        cap = n_raw;
-    }
-    S.n_raw = n_raw;
+    const double *scene_points = scene.sample.pts, *scene_normals = scene.sample.nrm;
+    const size_t m = scene.sample.n;
+    // the vote's own checks of the scene and the reference indices, in front of the lane
+    const double tv = now_ms();
+    PpfVote V;
+    if (const int rc = ppf_check_vote(model, scene, nullptr, &V); rc != M3D_OK) return rc;
     struct Result {
         double T[16];
         uint64_t votes;
     };
     std::vector<Result> results;
+    LaneLock lane(M.device);   // one lane, one configuration snapshot: the vote, the clustering and every ICP call run on it
+    if (!lane.ctx) return M3D_ERR_DEVICE;
+    if (const int rc = ppf_vote_on(lane.ctx, model, scene, &V); rc != M3D_OK) return rc;
+    V.stats.ms_total = now_ms() - tv;
+    S.vote = V.stats;
+    S.ms_vote = V.stats.ms_total;
+    const size_t n_raw = V.maxima.size();
+    S.n_raw = n_raw;
     if (n_raw) {
-        LaneLock lane(M.device);
-        if (!lane.ctx) return M3D_ERR_DEVICE;
+        std::vector<uint32_t> raw_votes(n_raw);
+        std::vector<double> raw_poses(16 * n_raw);
+        for (size_t k = 0; k < n_raw; ++k) {
+            raw_votes[k] = V.maxima[k].votes;
+            ppf_vote_pose(model, V, k, &raw_poses[16 * k]);
+        }
         PcResult R;
         const double tc = now_ms();
         if (const int rc = pc_cluster_on(lane.ctx, raw_poses.data(), raw_votes.data(), n_raw, prm, &R); rc != M3D_OK) return rc;
@@ -303,24 +311,24 @@ int ppf_estimate(const m3d_ppf_model* model, bool edge, const double* scene_poin
     // K8
     for (Result& r : results) pc_centre_shift(r.T, M.centroid);
     std::stable_sort(results.begin(), results.end(), [](const Result& a, const Result& b) { return a.votes > b.votes; });
-    const double expected = edge ? pc_expected_votes_edges(prm.ratio, M.n) : pc_expected_votes(prm.ratio, M.n);
+    const double expected = scene.edges ? pc_expected_votes_edges(prm.ratio, M.n) : pc_expected_votes(prm.ratio, M.n);
     size_t keep = 0;
     while (keep < results.size() && !(pc_score(results[keep].votes, expected) < prm.score_thresh)) ++keep;
     if (prm.num_result >= 0 && keep > (size_t)prm.num_result) keep = (size_t)prm.num_result;
-    *n_results = keep;
+    *out.n_results = keep;
     S.ms_total = now_ms() - t0;
     S.ms_host = S.ms_total - S.ms_vote - S.ms_cluster - S.ms_refine;
     if (stats) *stats = S;
-    if (keep > capacity)
-        return fail(M3D_ERR_CAPACITY, "ppf estimate: " + std::to_string(keep) + " results, the result arrays hold " + std::to_string(capacity));
+    if (keep > out.capacity)
+        return fail(M3D_ERR_CAPACITY, "ppf estimate: " + std::to_string(keep) + " results, the result arrays hold " + std::to_string(out.capacity));
     for (size_t k = 0; k < keep; ++k) {
         double Rm[9];
-        std::memcpy(poses + 16 * k, results[k].T, sizeof(double) * 16);
+        std::memcpy(out.poses + 16 * k, results[k].T, sizeof(double) * 16);
         pc_pose_rotation(results[k].T, Rm);
-        pc_mat_to_quat(Rm, q + 4 * k);
-        for (int a = 0; a < 3; ++a) t[3 * k + a] = results[k].T[4 * a + 3];
-        votes[k] = results[k].votes;
-        scores[k] = pc_score(results[k].votes, expected);
+        pc_mat_to_quat(Rm, out.q + 4 * k);
+        for (int a = 0; a < 3; ++a) out.t[3 * k + a] = results[k].T[4 * a + 3];
+        out.votes[k] = results[k].votes;
+        out.scores[k] = pc_score(results[k].votes, expected);
     }
     return M3D_OK;
 }
@@ -403,16 +411,17 @@ int m3d_ppf_estimate(const m3d_ppf_model* model, const double* scene_points, con
                      const size_t* reference, size_t n_ref, const m3d_ppf_cluster_params* params, size_t capacity,
                      size_t* n_results, double* poses, double* q, double* t, uint64_t* votes, double* scores,
                      m3d_ppf_estimate_stats* stats) {
-    return ppf_estimate(model, false, scene_points, scene_normals, m, reference, n_ref, nullptr, nullptr, 0, params, capacity, n_results,
-                        poses, q, t, votes, scores, stats);
+    return ppf_estimate(model, {{scene_points, scene_normals, m}, reference, n_ref, nullptr}, params,
+                        {capacity, n_results, poses, q, t, votes, scores}, stats);
 }
 
 int m3d_ppf_estimate_edges(const m3d_ppf_model* model, const double* scene_points, const double* scene_normals, size_t m,
                            const size_t* reference, size_t n_ref, const double* scene_edge_points, const double* scene_edge_normals,
                            size_t m_edge, const m3d_ppf_cluster_params* params, size_t capacity, size_t* n_results, double* poses,
                            double* q, double* t, uint64_t* votes, double* scores, m3d_ppf_estimate_stats* stats) {
-    return ppf_estimate(model, true, scene_points, scene_normals, m, reference, n_ref, scene_edge_points, scene_edge_normals, m_edge,
-                        params, capacity, n_results, poses, q, t, votes, scores, stats);
+    const PpfCloud edges{scene_edge_points, scene_edge_normals, m_edge};
+    return ppf_estimate(model, {{scene_points, scene_normals, m}, reference, n_ref, &edges}, params,
+                        {capacity, n_results, poses, q, t, votes, scores}, stats);
 }
 
 // measurement / test hook (include/misc3d_amd_bench.h)

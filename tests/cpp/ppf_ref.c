@@ -1,7 +1,10 @@
-/* ppf_ref.c -- the "PPF voting" contract of include/misc3d_amd.h in plain C, serial: the table (rules M1 - M6), the vote
- * (V1 - V8) and the undefined places (U1 - U6).  Built by tests/ppf_ref_util.py with -ffp-contract=off; with -fopenmp the two
- * outer loops run in parallel (the cpu_baseline of tools/bench_configs.py) and give the same output: every reference position
- * has its own accumulator and its own list of maxima.  Nothing here is shared with the library's sources. */
+/* ppf_ref.c -- the "PPF voting" and "PPF voting, EdgePoints mode" contracts of include/misc3d_amd.h in plain C, serial: the
+ * table (rules M1 - M6, E1 - E5), the vote (V1 - V8, E6 - E8), the undefined places (U1 - U6) and K8's expected votes in
+ * EdgePoints mode (E9).  The table pairs the sample with a referred set and the vote scans a cloud: in SampledPoints mode both
+ * are the sample (the scene) itself, in EdgePoints mode the model's (the scene's) edge points.  Built by tests/ppf_ref_util.py
+ * with -ffp-contract=off; with -fopenmp the two outer loops run in parallel (the cpu_baseline of tools/bench_configs.py) and
+ * give the same output: every reference position has its own accumulator and its own list of maxima.  Nothing here is shared
+ * with the library's sources. */
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -15,6 +18,8 @@ typedef struct ppf_ref_model {
     double *cos_edge, *alpha_c, *alpha_s, *dist_edge2;
     double centroid[3];
     double *pts, *nrm, *tmg;
+    size_t n_e;          /* the referred set: the model's edge points as the table saw them; */
+    double *epts, *enrm; /* NULL (and n_e == 0) in SampledPoints mode: the referred set is the sample */
     uint32_t *cell_off, *nbr_off, *nbr_idx;
     uint16_t* entry_i;
     uint8_t* entry_alpha;
@@ -129,6 +134,8 @@ void ppf_ref_destroy(ppf_ref_model* M) {
     free(M->pts);
     free(M->nrm);
     free(M->tmg);
+    free(M->epts);
+    free(M->enrm);
     free(M->cell_off);
     free(M->nbr_off);
     free(M->nbr_idx);
@@ -137,10 +144,14 @@ void ppf_ref_destroy(ppf_ref_model* M) {
     free(M);
 }
 
-/* the sizes and edge tables alone (n may be 0: no points, no table): the hand cases use it */
-ppf_ref_model* ppf_ref_create(const double* points, const double* normals, size_t n, double diameter, double r_min,
-                              double rel_sample_dist, double angle_step, double min_dist_thresh, double min_angle_thresh,
-                              int faster_mode) {
+/* M1 - M6, or E1 - E5 when edge_points / edge_normals (n_e of them) are given: NULL means SampledPoints.  centre_edges == 0
+ * leaves the edge set uncentred, as the reference does (ppf_estimation.cpp:588-589): the variant tests/test_ppf_edge.py uses
+ * to show why E1 deviates; every other caller passes 1.  n may be 0: the sizes and edge tables alone (no points, no table),
+ * which the hand cases use. */
+ppf_ref_model* ppf_ref_create(const double* points, const double* normals, size_t n, const double* edge_points,
+                              const double* edge_normals, size_t n_e, double diameter, double r_min, double rel_sample_dist,
+                              double angle_step, double min_dist_thresh, double min_angle_thresh, int faster_mode,
+                              int centre_edges) {
     ppf_ref_model* M = (ppf_ref_model*)calloc(1, sizeof(ppf_ref_model));
     M->n = n;
     M->r_min = r_min;
@@ -183,38 +194,53 @@ ppf_ref_model* ppf_ref_create(const double* points, const double* normals, size_
         }
         ppf_ref_frame(M->pts + 3 * i, M->nrm + 3 * i, M->tmg + 16 * i);
     }
-    /* M4, M5: keys of all ordered pairs, then a counting sort in (i, j) order */
+    /* E1: the edge set is centred by the centroid of the sample alone */
+    const int same = edge_points == NULL;
+    if (!same) {
+        M->n_e = n_e;
+        M->epts = (double*)malloc(sizeof(double) * 3 * n_e);
+        M->enrm = (double*)malloc(sizeof(double) * 3 * n_e);
+        for (size_t j = 0; j < n_e; ++j)
+            for (int k = 0; k < 3; ++k) {
+                M->epts[3 * j + k] = centre_edges ? edge_points[3 * j + k] - M->centroid[k] : edge_points[3 * j + k];
+                M->enrm[3 * j + k] = edge_normals[3 * j + k];
+            }
+    }
+    const double *rp = same ? M->pts : M->epts, *rn = same ? M->nrm : M->enrm;   /* the referred set, n_r points */
+    const size_t n_r = same ? n : n_e, pairs = n * n_r;
+    /* M4, M5 / E3, E4: keys of all ordered pairs (i in the sample, j in the referred set; i == j is left out only when the two
+     * are the same set), then a counting sort in (i, j) order */
     const size_t H = M->table_size;
-    uint32_t* cell = (uint32_t*)malloc(sizeof(uint32_t) * n * n);
-    uint8_t* qal = (uint8_t*)malloc(n * n);
+    uint32_t* cell = (uint32_t*)malloc(sizeof(uint32_t) * pairs);
+    uint8_t* qal = (uint8_t*)malloc(pairs);
 #pragma omp parallel for schedule(static)
     for (long long i = 0; i < (long long)n; ++i)
-        for (size_t j = 0; j < n; ++j) {
+        for (size_t j = 0; j < n_r; ++j) {
             int q[4], qa = 0;
             uint32_t key = (uint32_t)H;
-            if ((size_t)i != j && ppf_ref_pair_bins(M, M->pts + 3 * i, M->nrm + 3 * i, M->pts + 3 * j, M->nrm + 3 * j, M->tmg + 16 * i, q, &qa))
+            if (!(same && (size_t)i == j) && ppf_ref_pair_bins(M, M->pts + 3 * i, M->nrm + 3 * i, rp + 3 * j, rn + 3 * j, M->tmg + 16 * i, q, &qa))
                 key = (uint32_t)(q[0] + M->angle_num * (q[1] + M->angle_num * (q[2] + (size_t)M->angle_num * q[3])));
-            cell[(size_t)i * n + j] = key;
-            qal[(size_t)i * n + j] = (uint8_t)qa;
+            cell[(size_t)i * n_r + j] = key;
+            qal[(size_t)i * n_r + j] = (uint8_t)qa;
         }
     M->cell_off = (uint32_t*)calloc(H + 2, sizeof(uint32_t));
-    for (size_t p = 0; p < n * n; ++p) ++M->cell_off[cell[p] + 1];
+    for (size_t p = 0; p < pairs; ++p) ++M->cell_off[cell[p] + 1];
     for (size_t c2 = 0; c2 <= H; ++c2) M->cell_off[c2 + 1] += M->cell_off[c2];
     M->n_entries = M->cell_off[H];
     M->entry_i = (uint16_t*)malloc(sizeof(uint16_t) * (M->n_entries + 1));
     M->entry_alpha = (uint8_t*)malloc(M->n_entries + 1);
     uint32_t* fill = (uint32_t*)malloc(sizeof(uint32_t) * (H + 1));
     memcpy(fill, M->cell_off, sizeof(uint32_t) * (H + 1));
-    for (size_t p = 0; p < n * n; ++p) {
+    for (size_t p = 0; p < pairs; ++p) {
         if (cell[p] >= H) continue;
         const uint32_t at = fill[cell[p]]++;
-        M->entry_i[at] = (uint16_t)(p / n);
+        M->entry_i[at] = (uint16_t)(p / n_r);
         M->entry_alpha[at] = qal[p];
     }
     free(fill);
     free(cell);
     free(qal);
-    /* M6 */
+    /* M6 = E5, over the sample */
     const double r = 0.5 * r_min, r2 = r * r;
     M->nbr_off = (uint32_t*)calloc(n + 1, sizeof(uint32_t));
     for (int pass = 0; pass < 2; ++pass) {
@@ -319,13 +345,32 @@ static void mul4(const double* A, const double* B, double* C) {
             C[4 * r + c] = ((A[4 * r] * B[c] + A[4 * r + 1] * B[4 + c]) + A[4 * r + 2] * B[8 + c]) + A[4 * r + 3] * B[12 + c];
 }
 
-/* V1 - V8.  The result arrays hold cap entries each (poses cap x 16, may be NULL); n_searched (may be NULL): n_ref counts;
- * stats[0] += neighbours visited, stats[1] += increments.  Returns the number of maxima (nothing is written past cap). */
+/* rule V8: tsg^-1 Rx(alpha) tmg, the inverse being [R^T | -R^T t] */
+static void pose_product(const double* tsg, double alpha, const double* tmg, double* out) {
+    double inv[16], tmp[16];
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) inv[4 * r + c] = tsg[4 * c + r];
+        inv[4 * r + 3] = -((tsg[r] * tsg[3] + tsg[4 + r] * tsg[7]) + tsg[8 + r] * tsg[11]);
+    }
+    inv[12] = inv[13] = inv[14] = 0.0;
+    inv[15] = 1.0;
+    const double ca = cos(alpha), sa = sin(alpha);
+    const double rx[16] = {1, 0, 0, 0, 0, ca, -sa, 0, 0, sa, ca, 0, 0, 0, 0, 1};
+    mul4(inv, rx, tmp);
+    mul4(tmp, tmg, out);
+}
+
+/* V1 - V8, or E6 - E8 when the scene's edge points ep / en (m_e of them) are given: NULL means SampledPoints.  The reference
+ * points are read from the scene sample sp / sn (m points); the neighbours are searched in the scanned cloud: the sample itself,
+ * or the edge points.  The result arrays hold cap entries each (poses cap x 16, may be NULL); n_searched (may be NULL): n_ref
+ * counts; stats[0] += neighbours visited, stats[1] += increments.  Returns the number of maxima (nothing is written past cap). */
 size_t ppf_ref_vote(const ppf_ref_model* M, const double* sp, const double* sn, size_t m, const size_t* reference, size_t n_ref,
-                    size_t cap, uint32_t* ref_pos, uint32_t* model_index, uint32_t* alpha_index, uint32_t* votes, double* poses,
-                    uint32_t* n_searched, uint64_t* stats) {
+                    const double* ep, const double* en, size_t m_e, size_t cap, uint32_t* ref_pos, uint32_t* model_index,
+                    uint32_t* alpha_index, uint32_t* votes, double* poses, uint32_t* n_searched, uint64_t* stats) {
     const size_t n = M->n, A = (size_t)M->alpha_num, H = M->table_size;
-    const size_t gate = (size_t)((double)n * 0.2);
+    const size_t gate = (size_t)((double)(M->epts ? M->n_e : n) * 0.2);   /* V3 / E7: refered_model_num */
+    const double *cp = ep ? ep : sp, *cn = ep ? en : sn;                  /* the scanned cloud, m_c points */
+    const size_t m_c = ep ? m_e : m;
     const double r2 = M->r_min * M->r_min, dist_thresh = M->min_dist_thresh * M->r_min, cos_thresh = cos(M->min_angle_thresh);
     uint32_t** found = (uint32_t**)calloc(n_ref, sizeof(uint32_t*));
     size_t* n_found = (size_t*)calloc(n_ref, sizeof(size_t));
@@ -337,8 +382,8 @@ size_t ppf_ref_vote(const ppf_ref_model* M, const double* sp, const double* sn, 
         double tsg[16];
         ppf_ref_frame(p0, n0, tsg);
         size_t searched = 0;
-        for (size_t j = 0; j < m; ++j) {
-            const double dx = sp[3 * j] - p0[0], dy = sp[3 * j + 1] - p0[1], dz = sp[3 * j + 2] - p0[2];
+        for (size_t j = 0; j < m_c; ++j) {
+            const double dx = cp[3 * j] - p0[0], dy = cp[3 * j + 1] - p0[1], dz = cp[3 * j + 2] - p0[2];
             if ((dx * dx + dy * dy) + dz * dz < r2) ++searched;
         }
         if (n_searched) n_searched[s] = (uint32_t)searched;
@@ -346,9 +391,9 @@ size_t ppf_ref_vote(const ppf_ref_model* M, const double* sp, const double* sn, 
         if (!(searched > gate)) continue;
         uint32_t* acc = (uint32_t*)calloc(n * A, sizeof(uint32_t));
         uint64_t* flags = (uint64_t*)calloc(H, sizeof(uint64_t));
-        for (size_t j = 0; j < m; ++j) {
-            const double* p1 = sp + 3 * j;
-            const double* n1 = sn + 3 * j;
+        for (size_t j = 0; j < m_c; ++j) {
+            const double* p1 = cp + 3 * j;
+            const double* n1 = cn + 3 * j;
             const double dx = p1[0] - p0[0], dy = p1[1] - p0[1], dz = p1[2] - p0[2];
             const double d2 = (dx * dx + dy * dy) + dz * dz;
             if (!(d2 < r2)) continue;
@@ -382,18 +427,9 @@ size_t ppf_ref_vote(const ppf_ref_model* M, const double* sp, const double* sn, 
             alpha_index[total] = f[1];
             votes[total] = f[2];
             if (poses) {
-                double tsg[16], inv[16], tmp[16];
+                double tsg[16];
                 ppf_ref_frame(sp + 3 * reference[s], sn + 3 * reference[s], tsg);
-                for (int r = 0; r < 3; ++r) {
-                    for (int c = 0; c < 3; ++c) inv[4 * r + c] = tsg[4 * c + r];
-                    inv[4 * r + 3] = -((tsg[r] * tsg[3] + tsg[4 + r] * tsg[7]) + tsg[8 + r] * tsg[11]);
-                }
-                inv[12] = inv[13] = inv[14] = 0.0;
-                inv[15] = 1.0;
-                const double alpha = (double)f[1] * M->angle_step, ca = cos(alpha), sa = sin(alpha);
-                const double rx[16] = {1, 0, 0, 0, 0, ca, -sa, 0, 0, sa, ca, 0, 0, 0, 0, 1};
-                mul4(inv, rx, tmp);
-                mul4(tmp, M->tmg + 16 * (size_t)f[0], poses + 16 * total);
+                pose_product(tsg, (double)f[1] * M->angle_step, M->tmg + 16 * (size_t)f[0], poses + 16 * total);
             }
         }
         free(found[s]);
@@ -405,4 +441,23 @@ size_t ppf_ref_vote(const ppf_ref_model* M, const double* sp, const double* sn, 
         stats[1] += increments;
     }
     return total;
+}
+
+/* E9: K8's score in EdgePoints mode, expected = (ratio n) n without the 0.25; votes sorted descending.  scores (k) are filled;
+ * -> the number of results kept by score_thresh and num_result. */
+size_t ppf_ref_edge_scores(const uint64_t* votes, size_t k, double ratio, uint64_t n_model, double score_thresh, int num_result,
+                           double* scores) {
+    const double expected = (ratio * (double)n_model) * (double)n_model;
+    size_t keep = k;
+    for (size_t i = 0; i < k; ++i) {
+        const double s = (double)votes[i] / expected;
+        scores[i] = s < 1.0 ? s : 1.0;
+    }
+    for (size_t i = 0; i < k; ++i)
+        if (scores[i] < score_thresh) {
+            keep = i;
+            break;
+        }
+    if (num_result >= 0 && keep > (size_t)num_result) keep = (size_t)num_result;
+    return keep;
 }

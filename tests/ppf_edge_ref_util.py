@@ -1,179 +1,13 @@
-"""The plain-C restatement of the "PPF voting, EdgePoints mode" contract (tests/cpp/ppf_edge_ref.c) built into a temporary
-directory and loaded with ctypes, the independent judge in numpy longdouble for that mode (it is made of ppf_ref_util's judge_pairs,
-judge_frame, spread_cells and local_maximum_py: acos / atan2 called directly, no edge tables), and the cases both EdgePoints test
-files use.  tests/test_ppf_edge.py holds the restatement to the judge on every case, and checks that no case has a pair within
-EDGE_BAND of a bin edge."""
-import ctypes as C
+"""The cases both EdgePoints test files use: a sample and an edge set dealt from one ppf_ref_util family, the table shapes, the
+vote cases and the end-to-end scene (a flat plate with holes in clutter).  The restatement (tests/cpp/ppf_ref.c) and the judge
+take them through ppf_ref_util, as they take the SampledPoints cases; tests/test_ppf_edge.py holds the restatement to the judge on
+every case, and checks that no case has a pair within EDGE_BAND of a bin edge."""
 import functools
-import os
-import subprocess
 
 import numpy as np
 
 import ppf_ref_util as pu
-from ppf_ref_util import LD, _f, _p, judge_frame, judge_pairs, local_maximum_py, params, sizes, spread_cells
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-# ---- ppf_edge_ref.c
-class EdgeRefModel(pu.RefModel):
-    """an EdgePoints model of the restatement; table() and the size fields are RefModel's, read from the inner model"""
-
-    def __init__(self, lib, points, normals, edge_points, edge_normals, diameter, r_min, p, centre_edges=True):
-        self.L = lib
-        self.n, self.n_e = len(points), len(edge_points)
-        self.e = lib.ppf_edge_ref_create(_p(_f(points)), _p(_f(normals)), self.n, _p(_f(edge_points)), _p(_f(edge_normals)), self.n_e,
-                                         float(diameter), float(r_min), p["rel_sample_dist"], p["angle_step"], p["min_dist_thresh"],
-                                         p["min_angle_thresh"], int(bool(p["faster_mode"])), int(bool(centre_edges)))
-        self.h = lib.ppf_edge_ref_inner(self.e)
-        s = np.zeros(6, np.uint64)
-        lib.ppf_ref_sizes(self.h, _p(s))
-        self.table_size, self.n_entries, self.n_neighbors, self.angle_num, self.alpha_num, self.dist_num = (int(v) for v in s)
-
-    def __del__(self):
-        if getattr(self, "e", None):
-            self.L.ppf_edge_ref_destroy(self.e)
-            self.e = self.h = None
-
-    def vote(self, scene_points, scene_normals, reference, edge_points, edge_normals):
-        """-> dict(ref_pos, model_index, alpha_index, votes, poses, n_searched, visited, increments)"""
-        sp, sn, ep, en = _f(scene_points), _f(scene_normals), _f(edge_points), _f(edge_normals)
-        ref = np.ascontiguousarray(reference, dtype=np.uint64)
-        cap = max(64, 8 * len(ref))
-        while True:
-            out = [np.zeros(cap, np.uint32) for _ in range(4)]
-            poses = np.zeros((cap, 4, 4))
-            searched = np.zeros(len(ref), np.uint32)
-            st = np.zeros(2, np.uint64)
-            k = self.L.ppf_edge_ref_vote(self.e, _p(sp), _p(sn), len(sp), _p(ref), len(ref), _p(ep), _p(en), len(ep), cap,
-                                         *(_p(o) for o in out), _p(poses), _p(searched), _p(st))
-            if k <= cap:
-                break
-            cap = k
-        return dict(ref_pos=out[0][:k], model_index=out[1][:k], alpha_index=out[2][:k], votes=out[3][:k], poses=poses[:k],
-                    n_searched=searched, visited=int(st[0]), increments=int(st[1]))
-
-
-class PpfEdgeRef(pu.PpfRef):
-    """ppf_edge_ref.c, built as PpfRef builds ppf_ref.c (gcc into a temporary directory)"""
-
-    def __init__(self, tmpdir, openmp=False):
-        so = os.path.join(str(tmpdir), "ppf_edge_ref_omp.so" if openmp else "ppf_edge_ref.so")
-        if not os.path.exists(so):
-            subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC"] + (["-fopenmp"] if openmp else []) +
-                           [os.path.join(HERE, "cpp", "ppf_edge_ref.c"), "-o", so, "-lm"], check=True)
-        super().__init__(tmpdir, openmp)   # (ppf_ref.c on its own, for SampledPoints models and the shared pieces)
-        L = C.CDLL(so)
-        for name in ("ppf_ref_sizes", "ppf_ref_table"):
-            getattr(L, name).argtypes = getattr(self.L, name).argtypes
-        L.ppf_edge_ref_create.restype = C.c_void_p
-        L.ppf_edge_ref_create.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_double] * 6 + [C.c_int] * 2
-        L.ppf_edge_ref_destroy.argtypes = [C.c_void_p]
-        L.ppf_edge_ref_destroy.restype = None
-        L.ppf_edge_ref_inner.restype = C.c_void_p
-        L.ppf_edge_ref_inner.argtypes = [C.c_void_p]
-        L.ppf_edge_ref_vote.restype = C.c_size_t
-        L.ppf_edge_ref_vote.argtypes = ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
-                                         C.c_size_t, C.c_size_t] + [C.c_void_p] * 7)
-        L.ppf_edge_ref_scores.restype = C.c_size_t
-        L.ppf_edge_ref_scores.argtypes = [C.c_void_p, C.c_size_t, C.c_double, C.c_uint64, C.c_double, C.c_int, C.c_void_p]
-        self.E = L
-
-    def edge_model(self, points, normals, edge_points, edge_normals, diameter, r_min, p=None, centre_edges=True):
-        return EdgeRefModel(self.E, points, normals, edge_points, edge_normals, diameter, r_min, p or params(), centre_edges)
-
-    def scores(self, votes, ratio, n_model, score_thresh, num_result):
-        """E9: -> (the scores of votes sorted descending, the number kept)"""
-        v = np.ascontiguousarray(votes, dtype=np.uint64)
-        s = np.zeros(max(len(v), 1))
-        keep = self.E.ppf_edge_ref_scores(_p(v), len(v), float(ratio), int(n_model), float(score_thresh), int(num_result), _p(s))
-        return s[:len(v)], int(keep)
-
-
-# ---- the judge
-def judge_edge_model(points, normals, edge_points, edge_normals, diameter, r_min, p, centre_edges=True):
-    """E1 - E5 -> dict like ppf_ref_util.judge_model's, + n_e"""
-    pts, nrm, ept, enr = _f(points), _f(normals), _f(edge_points), _f(edge_normals)
-    n, n_e = len(pts), len(ept)
-    sz = sizes(diameter, p)
-    c = np.zeros(3)
-    for i in range(n):
-        c += pts[i]
-    c /= float(n)
-    cen = pts - c
-    ecen = ept - c if centre_edges else ept.copy()
-    frames = [judge_frame(cen[i], nrm[i]) for i in range(n)]
-    cells = np.full((n, n_e), sz["table_size"], np.int64)
-    qas = np.zeros((n, n_e), np.int64)
-    undecided = 0
-    a = sz["angle_num"]
-    for i in range(n):
-        valid, q, qa, und = judge_pairs(cen[i], nrm[i], frames[i], ecen, enr, sz, p)     # (every j: equal indices are pairs too)
-        undecided += int(und.sum())
-        cells[i] = np.where(valid, q[:, 0] + a * (q[:, 1] + a * (q[:, 2] + a * q[:, 3])), sz["table_size"])
-        qas[i] = qa
-    flat = cells.reshape(-1)
-    order = np.argsort(flat, kind="stable")
-    order = order[flat[order] < sz["table_size"]]
-    off = np.zeros(sz["table_size"] + 1, np.uint32)
-    off[1:] = np.cumsum(np.bincount(flat[order], minlength=sz["table_size"]))
-    r = 0.5 * r_min
-    nbr_off, nbr_idx = [0], []
-    for i in range(n):
-        dd = cen - cen[i]
-        d2 = (dd[:, 0] * dd[:, 0] + dd[:, 1] * dd[:, 1]) + dd[:, 2] * dd[:, 2]
-        nbr_idx.append(np.nonzero(d2 < r * r)[0])
-        nbr_off.append(nbr_off[-1] + len(nbr_idx[-1]))
-    return dict(cell_offsets=off, entry_i=(order // n_e).astype(np.uint16), entry_alpha=qas.reshape(-1)[order].astype(np.uint8),
-                nbr_offsets=np.asarray(nbr_off, np.uint32), nbr_indices=np.concatenate(nbr_idx).astype(np.uint32),
-                tmg=np.stack(frames), centroid=c, undecided=undecided, points=cen, normals=nrm, sizes=sz, n=n, n_e=n_e)
-
-
-def judge_edge_vote(jm, r_min, p, scene_points, scene_normals, reference, edge_points, edge_normals):
-    """E6 - E8 against a judge_edge_model -> dict(ref_pos, model_index, alpha_index, votes, poses, n_searched, undecided)"""
-    sp, sn, ep, en = _f(scene_points), _f(scene_normals), _f(edge_points), _f(edge_normals)
-    sz, n = jm["sizes"], jm["n"]
-    A, k = sz["alpha_num"], 2 if p["faster_mode"] else 3
-    gate = int(float(jm["n_e"]) * 0.2)
-    dist_thresh, cos_thresh = p["min_dist_thresh"] * r_min, np.cos(p["min_angle_thresh"])
-    off, ei, ea = jm["cell_offsets"].astype(np.int64), jm["entry_i"].astype(np.int64), jm["entry_alpha"].astype(np.int64)
-    nbrs = [jm["nbr_indices"][jm["nbr_offsets"][i]:jm["nbr_offsets"][i + 1]] for i in range(n)]
-    res = dict(ref_pos=[], model_index=[], alpha_index=[], votes=[], poses=[], n_searched=[], undecided=0)
-    for s, ri in enumerate(reference):
-        p0, n0 = sp[ri], sn[ri]
-        dd = ep - p0
-        d2 = (dd[:, 0] * dd[:, 0] + dd[:, 1] * dd[:, 1]) + dd[:, 2] * dd[:, 2]
-        near = d2 < r_min * r_min
-        res["n_searched"].append(int(near.sum()))
-        if not int(near.sum()) > gate:
-            continue
-        dots = (en[:, 0] * n0[0] + en[:, 1] * n0[1]) + en[:, 2] * n0[2]
-        keep = np.nonzero(near & ~((np.sqrt(d2) < dist_thresh) & (dots > cos_thresh)))[0]
-        tsg = judge_frame(p0, n0)
-        valid, q, qa, und = judge_pairs(p0, n0, tsg, ep[keep], en[keep], sz, p)
-        res["undecided"] += int(und.sum())
-        seen = set()
-        for t in np.nonzero(valid)[0]:
-            for cell in spread_cells(q[t], sz, k):
-                seen.add((cell, int(qa[t])))
-        acc = np.zeros(n * A, np.int64)
-        for cell, a in seen:
-            e = slice(off[cell], off[cell + 1])
-            np.add.at(acc, ei[e] * A + (ea[e] - a + A) % A, 1)
-        for i, col, v in local_maximum_py(acc.reshape(n, A), gate, nbrs):
-            al = LD(col) * LD(p["angle_step"])
-            rx = np.eye(4, dtype=LD)
-            rx[1, 1], rx[1, 2], rx[2, 1], rx[2, 2] = np.cos(al), -np.sin(al), np.sin(al), np.cos(al)
-            inv = np.eye(4, dtype=LD)
-            inv[:3, :3] = tsg[:3, :3].T
-            inv[:3, 3] = -(tsg[:3, :3].T @ tsg[:3, 3])
-            res["ref_pos"].append(s)
-            res["model_index"].append(i)
-            res["alpha_index"].append(col)
-            res["votes"].append(v)
-            res["poses"].append((inv @ rx @ jm["tmg"][i]).astype(np.float64))
-    return res
+from ppf_ref_util import params
 
 
 # ---- the cases

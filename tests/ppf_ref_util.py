@@ -1,6 +1,7 @@
-"""The plain-C restatement of the PPF voting contract (tests/cpp/ppf_ref.c) built into a temporary directory and loaded with
-ctypes, an independent judge in numpy longdouble (acos / atan2 called directly, its own frame construction, no edge tables),
-and the input families and cases both PPF test files use."""
+"""The plain-C restatement of the PPF voting contract in both modes (tests/cpp/ppf_ref.c) built into a temporary directory and
+loaded with ctypes, an independent judge in numpy longdouble (acos / atan2 called directly, its own frame construction, no edge
+tables), the input families and SampledPoints cases (the EdgePoints cases are in ppf_edge_ref_util), and what the GPU test files
+of both modes ask of the library.  The mode is whether edge points are given: the model's to the table, the scene's to the vote."""
 import ctypes as C
 import functools
 import os
@@ -39,11 +40,15 @@ def sizes(diameter, p):
 
 # ---- ppf_ref.c
 class RefModel:
-    def __init__(self, lib, points, normals, diameter, r_min, p):
+    """a model of the restatement; edge_points / edge_normals make it an EdgePoints model (n_e > 0)"""
+
+    def __init__(self, lib, points, normals, diameter, r_min, p, edge_points=None, edge_normals=None, centre_edges=True):
         self.L = lib
-        self.n = len(points)
-        self.h = lib.ppf_ref_create(_p(_f(points)), _p(_f(normals)), self.n, float(diameter), float(r_min), p["rel_sample_dist"],
-                                    p["angle_step"], p["min_dist_thresh"], p["min_angle_thresh"], int(bool(p["faster_mode"])))
+        self.n, self.n_e = len(points), 0 if edge_points is None else len(edge_points)
+        ep, en = (None, None) if edge_points is None else (_f(edge_points), _f(edge_normals))
+        self.h = lib.ppf_ref_create(_p(_f(points)), _p(_f(normals)), self.n, _p(ep), _p(en), self.n_e, float(diameter), float(r_min),
+                                    p["rel_sample_dist"], p["angle_step"], p["min_dist_thresh"], p["min_angle_thresh"],
+                                    int(bool(p["faster_mode"])), int(bool(centre_edges)))
         s = np.zeros(6, np.uint64)
         lib.ppf_ref_sizes(self.h, _p(s))
         self.table_size, self.n_entries, self.n_neighbors, self.angle_num, self.alpha_num, self.dist_num = (int(v) for v in s)
@@ -62,9 +67,11 @@ class RefModel:
                                                           "tmg", "centroid")))
         return t
 
-    def vote(self, scene_points, scene_normals, reference):
-        """-> dict(ref_pos, model_index, alpha_index, votes, poses, n_searched, visited, increments)"""
+    def vote(self, scene_points, scene_normals, reference, edge_points=None, edge_normals=None):
+        """edge_points / edge_normals: the scene's edge points (an EdgePoints model scans them, not the scene)
+        -> dict(ref_pos, model_index, alpha_index, votes, poses, n_searched, visited, increments)"""
         sp, sn = _f(scene_points), _f(scene_normals)
+        ep, en = (None, None) if edge_points is None else (_f(edge_points), _f(edge_normals))
         ref = np.ascontiguousarray(reference, dtype=np.uint64)
         cap = max(64, 8 * len(ref))
         while True:
@@ -72,8 +79,8 @@ class RefModel:
             poses = np.zeros((cap, 4, 4))
             searched = np.zeros(len(ref), np.uint32)
             st = np.zeros(2, np.uint64)
-            k = self.L.ppf_ref_vote(self.h, _p(sp), _p(sn), len(sp), _p(ref), len(ref), cap, *(_p(o) for o in out), _p(poses),
-                                    _p(searched), _p(st))
+            k = self.L.ppf_ref_vote(self.h, _p(sp), _p(sn), len(sp), _p(ref), len(ref), _p(ep), _p(en), 0 if ep is None else len(ep), cap,
+                                    *(_p(o) for o in out), _p(poses), _p(searched), _p(st))
             if k <= cap:
                 break
             cap = k
@@ -101,13 +108,16 @@ class PpfRef:
                            [os.path.join(HERE, "cpp", "ppf_ref.c"), "-o", so, "-lm"], check=True)
         L = C.CDLL(so)
         L.ppf_ref_create.restype = C.c_void_p
-        L.ppf_ref_create.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_double] * 6 + [C.c_int]
+        L.ppf_ref_create.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_double] * 6 + [C.c_int] * 2
         L.ppf_ref_destroy.argtypes = [C.c_void_p]
         L.ppf_ref_destroy.restype = None
         L.ppf_ref_sizes.argtypes = [C.c_void_p, C.c_void_p]
         L.ppf_ref_table.argtypes = [C.c_void_p] * 8
         L.ppf_ref_vote.restype = C.c_size_t
-        L.ppf_ref_vote.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t] + [C.c_void_p] * 7
+        L.ppf_ref_vote.argtypes = ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                    C.c_size_t, C.c_size_t] + [C.c_void_p] * 7)
+        L.ppf_ref_edge_scores.restype = C.c_size_t
+        L.ppf_ref_edge_scores.argtypes = [C.c_void_p, C.c_size_t, C.c_double, C.c_uint64, C.c_double, C.c_int, C.c_void_p]
         L.ppf_ref_pair_bins.argtypes = [C.c_void_p] * 6 + [C.c_void_p, C.c_void_p]
         L.ppf_ref_spread.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.ppf_ref_frame.argtypes = [C.c_void_p] * 3
@@ -116,8 +126,15 @@ class PpfRef:
         L.ppf_ref_local_maximum.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         self.L = L
 
-    def model(self, points, normals, diameter, r_min, p=None):
-        return RefModel(self.L, points, normals, diameter, r_min, p or params())
+    def model(self, points, normals, diameter, r_min, p=None, edge_points=None, edge_normals=None, centre_edges=True):
+        return RefModel(self.L, points, normals, diameter, r_min, p or params(), edge_points, edge_normals, centre_edges)
+
+    def scores(self, votes, ratio, n_model, score_thresh, num_result):
+        """E9: -> (the scores of votes sorted descending, the number kept)"""
+        v = np.ascontiguousarray(votes, dtype=np.uint64)
+        s = np.zeros(max(len(v), 1))
+        keep = self.L.ppf_ref_edge_scores(_p(v), len(v), float(ratio), int(n_model), float(score_thresh), int(num_result), _p(s))
+        return s[:len(v)], int(keep)
 
     def frame(self, p, n):
         T = np.zeros((4, 4))
@@ -182,8 +199,9 @@ def judge_pairs(p0, n0, T0, p1, n1, sz, p):
     return valid, np.concatenate([q, qd[:, None]], axis=1), qa, und & ~zero
 
 
-def judge_model(points, normals, diameter, r_min, p):
-    """-> dict like RefModel.table() + undecided (count) + points (centred, float64)"""
+def judge_model(points, normals, diameter, r_min, p, edge_points=None, edge_normals=None, centre_edges=True):
+    """M1 - M6, or E1 - E5 with the model's edge points -> dict like RefModel.table() + undecided (count) + points (centred,
+    float64) + n_e (0 in SampledPoints mode)"""
     pts, nrm = _f(points), _f(normals)
     n = len(pts)
     sz = sizes(diameter, p)
@@ -192,15 +210,19 @@ def judge_model(points, normals, diameter, r_min, p):
         c += pts[i]
     c /= float(n)
     cen = pts - c
+    same = edge_points is None                  # the referred set is the sample: equal indices are no pairs
+    rp, rn = (cen, nrm) if same else (_f(edge_points) - c if centre_edges else _f(edge_points).copy(), _f(edge_normals))
+    n_r = len(rp)
     frames = [judge_frame(cen[i], nrm[i]) for i in range(n)]
-    cells = np.full((n, n), sz["table_size"], np.int64)
-    qas = np.zeros((n, n), np.int64)
+    cells = np.full((n, n_r), sz["table_size"], np.int64)
+    qas = np.zeros((n, n_r), np.int64)
     undecided = 0
     a = sz["angle_num"]
     for i in range(n):
-        valid, q, qa, und = judge_pairs(cen[i], nrm[i], frames[i], cen, nrm, sz, p)
-        valid[i] = False
-        und[i] = False
+        valid, q, qa, und = judge_pairs(cen[i], nrm[i], frames[i], rp, rn, sz, p)
+        if same:
+            valid[i] = False
+            und[i] = False
         undecided += int(und.sum())
         cells[i] = np.where(valid, q[:, 0] + a * (q[:, 1] + a * (q[:, 2] + a * q[:, 3])), sz["table_size"])
         qas[i] = qa
@@ -216,9 +238,9 @@ def judge_model(points, normals, diameter, r_min, p):
         d2 = (dd[:, 0] * dd[:, 0] + dd[:, 1] * dd[:, 1]) + dd[:, 2] * dd[:, 2]
         nbr_idx.append(np.nonzero(d2 < r * r)[0])
         nbr_off.append(nbr_off[-1] + len(nbr_idx[-1]))
-    return dict(cell_offsets=off, entry_i=(order // n).astype(np.uint16), entry_alpha=qas.reshape(-1)[order].astype(np.uint8),
+    return dict(cell_offsets=off, entry_i=(order // n_r).astype(np.uint16), entry_alpha=qas.reshape(-1)[order].astype(np.uint8),
                 nbr_offsets=np.asarray(nbr_off, np.uint32), nbr_indices=np.concatenate(nbr_idx).astype(np.uint32),
-                tmg=np.stack(frames), centroid=c, undecided=undecided, points=cen, normals=nrm, sizes=sz, n=n)
+                tmg=np.stack(frames), centroid=c, undecided=undecided, points=cen, normals=nrm, sizes=sz, n=n, n_e=0 if same else n_r)
 
 
 def spread_cells(q, sz, k):
@@ -270,18 +292,31 @@ def local_maximum_py(acc, vote_threshold, nbr_lists):
     return out
 
 
-def judge_vote(jm, r_min, p, scene_points, scene_normals, reference):
-    """the vote against a judge_model -> dict(ref_pos, model_index, alpha_index, votes, poses, n_searched, undecided)"""
-    sp, sn = _f(scene_points), _f(scene_normals)
+def judge_pose(tsg, alpha_index, angle_step, tmg):
+    """rule V8 in longdouble: tsg^-1 Rx(alpha index * angle_step) tmg -> float64"""
+    al = LD(int(alpha_index)) * LD(angle_step)
+    rx = np.eye(4, dtype=LD)
+    rx[1, 1], rx[1, 2], rx[2, 1], rx[2, 2] = np.cos(al), -np.sin(al), np.sin(al), np.cos(al)
+    inv = np.eye(4, dtype=LD)
+    inv[:3, :3] = tsg[:3, :3].T
+    inv[:3, 3] = -(tsg[:3, :3].T @ tsg[:3, 3])
+    return (inv @ rx @ tmg).astype(np.float64)
+
+
+def judge_vote(jm, r_min, p, scene_points, scene_normals, reference, edge_points=None, edge_normals=None):
+    """the vote against a judge_model (V1 - V8; E6 - E8 with the scene's edge points, which are then the cloud that is scanned)
+    -> dict(ref_pos, model_index, alpha_index, votes, poses, n_searched, undecided)"""
+    rp, rn = _f(scene_points), _f(scene_normals)            # the reference points are read from the scene sample
+    sp, sn = (rp, rn) if edge_points is None else (_f(edge_points), _f(edge_normals))
     sz, n = jm["sizes"], jm["n"]
     A, k = sz["alpha_num"], 2 if p["faster_mode"] else 3
-    gate = int(float(n) * 0.2)
+    gate = int(float(jm["n_e"] or n) * 0.2)
     dist_thresh, cos_thresh = p["min_dist_thresh"] * r_min, np.cos(p["min_angle_thresh"])
     off, ei, ea = jm["cell_offsets"].astype(np.int64), jm["entry_i"].astype(np.int64), jm["entry_alpha"].astype(np.int64)
     nbrs = [jm["nbr_indices"][jm["nbr_offsets"][i]:jm["nbr_offsets"][i + 1]] for i in range(n)]
     res = dict(ref_pos=[], model_index=[], alpha_index=[], votes=[], poses=[], n_searched=[], undecided=0)
     for s, ri in enumerate(reference):
-        p0, n0 = sp[ri], sn[ri]
+        p0, n0 = rp[ri], rn[ri]
         dd = sp - p0
         d2 = (dd[:, 0] * dd[:, 0] + dd[:, 1] * dd[:, 1]) + dd[:, 2] * dd[:, 2]
         near = d2 < r_min * r_min
@@ -302,17 +337,11 @@ def judge_vote(jm, r_min, p, scene_points, scene_normals, reference):
             e = slice(off[cell], off[cell + 1])
             np.add.at(acc, ei[e] * A + (ea[e] - a + A) % A, 1)
         for i, col, v in local_maximum_py(acc.reshape(n, A), gate, nbrs):
-            al = LD(col) * LD(p["angle_step"])
-            rx = np.eye(4, dtype=LD)
-            rx[1, 1], rx[1, 2], rx[2, 1], rx[2, 2] = np.cos(al), -np.sin(al), np.sin(al), np.cos(al)
-            inv = np.eye(4, dtype=LD)
-            inv[:3, :3] = tsg[:3, :3].T
-            inv[:3, 3] = -(tsg[:3, :3].T @ tsg[:3, 3])
             res["ref_pos"].append(s)
             res["model_index"].append(i)
             res["alpha_index"].append(col)
             res["votes"].append(v)
-            res["poses"].append((inv @ rx @ jm["tmg"][i]).astype(np.float64))
+            res["poses"].append(judge_pose(tsg, col, p["angle_step"], jm["tmg"][i]))
     return res
 
 
@@ -328,13 +357,7 @@ def judge_poses(c, ref_pos, model_index, alpha_index):
         ri = int(c["reference"][int(s)])
         tsg = judge_frame(c["scene_points"][ri], c["scene_normals"][ri])
         tmg = judge_frame(pts[int(i)] - cen, nrm[int(i)])
-        al = LD(int(col)) * LD(c["params"]["angle_step"])
-        rx = np.eye(4, dtype=LD)
-        rx[1, 1], rx[1, 2], rx[2, 1], rx[2, 2] = np.cos(al), -np.sin(al), np.sin(al), np.cos(al)
-        inv = np.eye(4, dtype=LD)
-        inv[:3, :3] = tsg[:3, :3].T
-        inv[:3, 3] = -(tsg[:3, :3].T @ tsg[:3, 3])
-        out.append((inv @ rx @ tmg).astype(np.float64))
+        out.append(judge_pose(tsg, col, c["params"]["angle_step"], tmg))
     return np.asarray(out).reshape(-1, 4, 4)
 
 
@@ -508,3 +531,63 @@ def case(name):
         pts, nrm, diameter, r_min, sp, sn, ref, _ = vote_case("box", n=n, n_ref=4, clutter=300)
         return _case((pts, nrm, diameter, r_min), params(angle_step=ANGLE_STEPS["6"]), (sp, sn), ref)
     raise KeyError(name)
+
+
+# ---- a case through the restatement and through the library.  A case dict with edge_points / edge_normals and scene_edge_points /
+# scene_edge_normals (ppf_edge_ref_util) is an EdgePoints case; without them it is a SampledPoints case
+INTS = ("ref_pos", "model_index", "alpha_index", "votes")
+TABLE = ("cell_offsets", "entry_i", "entry_alpha", "nbr_offsets", "nbr_indices")
+
+# the SampledPoints cases that tests/test_ppf_edge.py also runs as EdgePoints cases on themselves
+OWN_EDGE_CASES = ("family_box", "family_plate", "count_grid_65", "count_random_64", "step_6", "full_spread", "lds_edge_plus_1")
+
+
+def with_own_edges(c):
+    """the SampledPoints case c as an EdgePoints case: the sample is its own edge set, the scene its own edge cloud"""
+    return dict(c, edge_points=c["points"], edge_normals=c["normals"], scene_edge_points=c["scene_points"],
+                scene_edge_normals=c["scene_normals"])
+
+
+def ref_model(ref, c, **kw):
+    return ref.model(c["points"], c["normals"], c["diameter"], c["r_min"], c["params"], c.get("edge_points"), c.get("edge_normals"), **kw)
+
+
+def ref_vote(m, c):
+    return m.vote(c["scene_points"], c["scene_normals"], c["reference"], c.get("scene_edge_points"), c.get("scene_edge_normals"))
+
+
+def lib_model(capi, c):
+    p = c["params"]
+    return capi.PpfModel(c["points"], c["normals"], c["diameter"], c["r_min"], edge_points=c.get("edge_points"),
+                         edge_normals=c.get("edge_normals"), rel_sample_dist=p["rel_sample_dist"], angle_step=p["angle_step"],
+                         min_dist_thresh=p["min_dist_thresh"], min_angle_thresh=p["min_angle_thresh"], faster_mode=p["faster_mode"])
+
+
+def lib_vote(m, c, **kw):
+    return m.vote(c["scene_points"], c["scene_normals"], c["reference"], edge_points=c.get("scene_edge_points"),
+                  edge_normals=c.get("scene_edge_normals"), **kw)
+
+
+def forced_vote(capi, c, device_memory=False, max_groups=0, model=None):
+    """the vote with its accumulators forced into device memory and / or its workgroups capped -> (model, (result, stats))"""
+    capi.ppf_force(device_memory, max_groups)
+    try:
+        m = model or lib_model(capi, c)
+        return m, lib_vote(m, c, stats=True)
+    finally:
+        capi.ppf_force(False, 0)
+
+
+def assert_table(t, want):
+    for k in TABLE:
+        assert np.array_equal(t[k], want[k]), k
+    assert np.array_equal(t["centroid"], want["centroid"])
+    assert np.abs(t["tmg"] - want["tmg"]).max() < 1e-12      # (host arithmetic on both sides)
+
+
+def assert_vote(c, got, stats, want):
+    for k in INTS:
+        assert np.array_equal(got[k], want[k]), k
+    assert stats["neighbours_visited"] == want["visited"] and stats["increments"] == want["increments"]
+    if len(want["votes"]):
+        assert np.abs(got["poses"] - judge_poses(c, got["ref_pos"], got["model_index"], got["alpha_index"])).max() < 1e-12

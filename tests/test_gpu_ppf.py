@@ -11,9 +11,6 @@ import ppf_ref_util as pu
 
 pytestmark = pytest.mark.gpu
 
-INTS = ("ref_pos", "model_index", "alpha_index", "votes")
-TABLE = ("cell_offsets", "entry_i", "entry_alpha", "nbr_offsets", "nbr_indices")
-
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
@@ -28,41 +25,13 @@ def expected(ref):
     def get(name):
         if name not in cache:
             c = pu.case(name)
-            m = ref.model(c["points"], c["normals"], c["diameter"], c["r_min"], c["params"])
-            cache[name] = (m.table(), m.vote(c["scene_points"], c["scene_normals"], c["reference"]))
+            m = pu.ref_model(ref, c)
+            cache[name] = (m.table(), pu.ref_vote(m, c))
         return cache[name]
     return get
 
 
-def _model(capi, c):
-    p = c["params"]
-    return capi.PpfModel(c["points"], c["normals"], c["diameter"], c["r_min"], rel_sample_dist=p["rel_sample_dist"],
-                         angle_step=p["angle_step"], min_dist_thresh=p["min_dist_thresh"], min_angle_thresh=p["min_angle_thresh"],
-                         faster_mode=p["faster_mode"])
-
-
-def _vote(capi, c, device_memory=False, max_groups=0, model=None):
-    capi.ppf_force(device_memory, max_groups)
-    try:
-        m = model or _model(capi, c)
-        return m, m.vote(c["scene_points"], c["scene_normals"], c["reference"], stats=True)
-    finally:
-        capi.ppf_force(False, 0)
-
-
-def _assert_table(t, want):
-    for k in TABLE:
-        assert np.array_equal(t[k], want[k]), k
-    assert np.array_equal(t["centroid"], want["centroid"])
-    assert np.abs(t["tmg"] - want["tmg"]).max() < 1e-12      # (host arithmetic on both sides)
-
-
-def _assert_vote(c, got, stats, want):
-    for k in INTS:
-        assert np.array_equal(got[k], want[k]), k
-    assert stats["neighbours_visited"] == want["visited"] and stats["increments"] == want["increments"]
-    if len(want["votes"]):
-        assert np.abs(got["poses"] - pu.judge_poses(c, got["ref_pos"], got["model_index"], got["alpha_index"])).max() < 1e-12
+_model, _vote, _assert_table, _assert_vote = pu.lib_model, pu.forced_vote, pu.assert_table, pu.assert_vote
 
 
 @pytest.mark.parametrize("n", pu.TABLE_SIZES + (pu.TABLE_LARGE,))
@@ -135,7 +104,7 @@ def test_run_to_run_and_capacity(capi, expected):
     m = _model(capi, c)
     a = m.vote(c["scene_points"], c["scene_normals"], c["reference"])
     b = m.vote(c["scene_points"], c["scene_normals"], c["reference"])
-    for k in INTS + ("poses",):
+    for k in pu.INTS + ("poses",):
         assert np.array_equal(a[k], b[k]) and a[k].tobytes() == b[k].tobytes(), k
     K = len(want["votes"])
     assert K > 2
@@ -154,6 +123,28 @@ def test_run_to_run_and_capacity(capi, expected):
     with pytest.raises(capi.M3DError) as e:
         m.vote(c["scene_points"], c["scene_normals"], c["reference"], capacity=0)
     assert e.value.code == capi.ERR_CAPACITY and e.value.needed == K
+
+
+def test_more_maxima_than_the_first_launch_has_room_for(capi):
+    """The first launch has room for max(4096, 4 n_ref) maxima; beyond it the vote counts them and launches once more.  The
+    1 200-point box of the estimate scene with every point of its copy a reference point has 7 177 maxima (counted with the
+    restatement), more than 4 800: two launches.  A maximum belongs to its reference position alone, so the same vote taken in
+    three parts of 400 reference points (under 2 500 maxima and one launch each) is the whole, part after part."""
+    import ppf_cluster_ref_util as cu
+    c = cu.estimate_case()
+    _, _, where = pu.scene_of(c["points"], c["normals"], c["T"], 1500, 3)
+    refs = np.sort(where)
+    m = capi.PpfModel(c["points"], c["normals"], c["diameter"], c["r_min"])
+    whole, stats = m.vote(c["scene_points"], c["scene_normals"], refs, stats=True)
+    assert stats["launches"] == 2 and len(whole["votes"]) == 7177 > max(4096, 4 * len(refs))
+    parts = [m.vote(c["scene_points"], c["scene_normals"], refs[lo:lo + 400], stats=True) for lo in (0, 400, 800)]
+    assert [st["launches"] for _, st in parts] == [1, 1, 1] and all(len(r["votes"]) <= 4096 for r, _ in parts)
+    assert sum(st["neighbours_visited"] for _, st in parts) == stats["neighbours_visited"]
+    assert sum(st["increments"] for _, st in parts) == stats["increments"]
+    assert np.array_equal(np.concatenate([r["ref_pos"] + 400 * k for k, (r, _) in enumerate(parts)]), whole["ref_pos"])
+    for k in ("model_index", "alpha_index", "votes", "poses"):
+        joined = np.concatenate([r[k] for r, _ in parts])
+        assert joined.shape == whole[k].shape and joined.tobytes() == whole[k].tobytes(), k
 
 
 def test_two_threads_vote_on_one_model(capi, expected):

@@ -192,6 +192,9 @@ def test_estimate_against_the_restatement(capi, ref, icp, scene, method):
         assert got["stats"]["icp_calls"] == len(want["refined"])
     if method == "PointToPlane":
         assert _pose_err(got["poses"][0], scene["T"]) < 1e-9     # the top pose is the true pose
+    # one vote, and the same one: the estimate runs the vote on the lane it holds, once
+    assert got["stats"]["n_raw"] == len(scene["raw"]["votes"])
+    assert got["stats"]["vote"]["launches"] == 1                 # (1 771 maxima: within the first launch's room for 4 096)
 
 
 @pytest.mark.parametrize("method", ("PointToPlane", "PointToPoint"))
@@ -211,6 +214,33 @@ def test_estimate_two_instances(capi, ref, icp, method):
     for k in range(2):                                   # each copy is found, at its true pose
         assert min(e[k] for e in errs) < 1e-9
     assert errs[0][0] < 1e-9                             # the copy voted at more reference points comes first
+
+
+def test_two_threads_estimate_on_one_model(capi, scene):
+    """two threads, three estimates each (default refinement) on one model: every result is the single-threaded call's"""
+    want = _estimate(capi, scene, score_thresh=0.0)
+    assert len(want["votes"]) >= 1 and want["stats"]["icp_calls"] >= 1
+    results, errors = [[], []], []
+
+    def work(slot):
+        try:
+            for _ in range(3):
+                results[slot].append(_estimate(capi, scene, score_thresh=0.0))
+        except Exception as e:   # noqa: BLE001
+            errors.append(e)
+
+    threads = [threading.Thread(target=work, args=(i,)) for i in range(2)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors
+    assert [len(r) for r in results] == [3, 3]
+    for got in results[0] + results[1]:
+        assert np.array_equal(got["votes"], want["votes"]) and np.array_equal(got["scores"], want["scores"])
+        assert _pose_err(got["poses"], want["poses"]) < 1e-9
+        assert _pose_err(got["q"], want["q"]) < 1e-9 and _pose_err(got["t"], want["t"]) < 1e-9
+        assert got["stats"]["n_raw"] == want["stats"]["n_raw"] and got["stats"]["vote"]["launches"] == want["stats"]["vote"]["launches"]
 
 
 def test_estimate_cuts(capi, scene):

@@ -1,5 +1,5 @@
 """PPF voting in EdgePoints mode on the GPU: the edge table, the vote and m3d_ppf_estimate_edges of the library against the
-contract's restatement (tests/cpp/ppf_edge_ref.c), integer for integer; the poses against the numpy-longdouble judge.
+contract's restatement (tests/cpp/ppf_ref.c with edge points), integer for integer; the poses against the numpy-longdouble judge.
 tests/test_ppf_edge.py holds the restatement to the judge on every input used here, with no pair near a bin edge."""
 import ctypes as C
 import threading
@@ -12,21 +12,16 @@ import ppf_ref_util as pu
 
 pytestmark = pytest.mark.gpu
 
-INTS = ("ref_pos", "model_index", "alpha_index", "votes")
-TABLE = ("cell_offsets", "entry_i", "entry_alpha", "nbr_offsets", "nbr_indices")
+INTS = pu.INTS
 
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return eu.PpfEdgeRef(tmp_path_factory.mktemp("ppf_edge_ref"))
+    return pu.PpfRef(tmp_path_factory.mktemp("ppf_edge_ref"))
 
 
-def _ref_model(ref, c):
-    return ref.edge_model(c["points"], c["normals"], c["edge_points"], c["edge_normals"], c["diameter"], c["r_min"], c["params"])
-
-
-def _ref_vote(m, c):
-    return m.vote(c["scene_points"], c["scene_normals"], c["reference"], c["scene_edge_points"], c["scene_edge_normals"])
+_ref_model, _ref_vote = pu.ref_model, pu.ref_vote
+_model, _vote_on, _vote, _assert_table, _assert_vote = pu.lib_model, pu.lib_vote, pu.forced_vote, pu.assert_table, pu.assert_vote
 
 
 @pytest.fixture(scope="module")
@@ -41,42 +36,6 @@ def expected(ref):
             cache[name] = (m.table(), _ref_vote(m, c))
         return cache[name]
     return get
-
-
-def _model(capi, c):
-    p = c["params"]
-    return capi.PpfModel(c["points"], c["normals"], c["diameter"], c["r_min"], edge_points=c["edge_points"], edge_normals=c["edge_normals"],
-                         rel_sample_dist=p["rel_sample_dist"], angle_step=p["angle_step"], min_dist_thresh=p["min_dist_thresh"],
-                         min_angle_thresh=p["min_angle_thresh"], faster_mode=p["faster_mode"])
-
-
-def _vote_on(m, c, **kw):
-    return m.vote(c["scene_points"], c["scene_normals"], c["reference"], edge_points=c["scene_edge_points"],
-                  edge_normals=c["scene_edge_normals"], **kw)
-
-
-def _vote(capi, c, device_memory=False, max_groups=0, model=None):
-    capi.ppf_force(device_memory, max_groups)
-    try:
-        m = model or _model(capi, c)
-        return m, _vote_on(m, c, stats=True)
-    finally:
-        capi.ppf_force(False, 0)
-
-
-def _assert_table(t, want):
-    for k in TABLE:
-        assert np.array_equal(t[k], want[k]), k
-    assert np.array_equal(t["centroid"], want["centroid"])
-    assert np.abs(t["tmg"] - want["tmg"]).max() < 1e-12      # (host arithmetic on both sides)
-
-
-def _assert_vote(c, got, stats, want):
-    for k in INTS:
-        assert np.array_equal(got[k], want[k]), k
-    assert stats["neighbours_visited"] == want["visited"] and stats["increments"] == want["increments"]
-    if len(want["votes"]):
-        assert np.abs(got["poses"] - pu.judge_poses(c, got["ref_pos"], got["model_index"], got["alpha_index"])).max() < 1e-12
 
 
 # ---- the table
@@ -190,6 +149,33 @@ def test_two_threads_vote_on_one_model(capi, expected):
         _assert_vote(c, got, stats, want)
 
 
+@pytest.mark.parametrize("name", ("family_box", "count_grid_65", "count_random_64", "step_6", "lds_edge_plus_1"))
+def test_sampled_mode_is_edge_mode_on_the_sample_itself(capi, ref, name):
+    """A SampledPoints case of tests/test_gpu_ppf.py with the sample as the model's edge set and the scene as its own edge cloud
+    (the pairs i == j have d2 == 0 and are skipped by rule in either mode): the edge calls give the sampled restatement's table
+    and vote, and the library's own sampled result to the byte -- at the gate (65 / 64 neighbours), at 61 alpha bins and through
+    device memory (1 176 points).  tests/test_ppf_edge.py shows the same of the restatement and the judge."""
+    c = pu.case(name)
+    e = pu.with_own_edges(c)
+    want = pu.ref_model(ref, c)
+    want_vote = pu.ref_vote(want, c)
+    m, (got, stats) = _vote(capi, e)
+    assert (m.n, m.n_edge) == (len(c["points"]), len(c["points"]))
+    t = m.table()
+    assert (t["table_size"], t["n_entries"], t["n_neighbors"]) == (want.table_size, want.n_entries, want.n_neighbors)
+    _assert_table(t, want.table())
+    _assert_vote(e, got, stats, want_vote)
+    assert stats["path"] == (capi.PPF_PATH_DEVICE if name == "lds_edge_plus_1" else capi.PPF_PATH_LDS) and stats["launches"] == 1
+    sampled, (got_s, stats_s) = _vote(capi, c)
+    assert sampled.n_edge == 0
+    ts = sampled.table()
+    for k in pu.TABLE + ("tmg", "centroid"):
+        assert t[k].tobytes() == ts[k].tobytes(), k
+    for k in INTS + ("poses",):
+        assert got[k].shape == got_s[k].shape and got[k].tobytes() == got_s[k].tobytes(), k
+    assert (stats["neighbours_visited"], stats["increments"]) == (stats_s["neighbours_visited"], stats_s["increments"])
+
+
 def test_mode_mismatches_and_refusals(capi):
     c = eu.case("family_box")
     edge = _model(capi, c)
@@ -296,7 +282,7 @@ def test_raw_vote_of_the_estimate_scene(ref, scene):
 @pytest.mark.parametrize("method", ("PointToPlane", "PointToPoint", "NoRefine"))
 def test_estimate_against_the_restatement(capi, ref, cluster_ref, icp, scene, method):
     """K1 - K7 composed from the clustering and ICP restatements on the raw poses (the ICP against the scene SAMPLE), K8's scores
-    from ppf_edge_ref.c: expected = ratio n n"""
+    from ppf_ref.c: expected = ratio n n"""
     import ppf_cluster_ref_util as cu
     s = scene
     n = len(s["points"])
@@ -306,6 +292,9 @@ def test_estimate_against_the_restatement(capi, ref, cluster_ref, icp, scene, me
                            s["scene_normals"], s["dist_step"], s["dist_threshold"], score_thresh=0.0, refine_method=method)
     scores, keep = ref.scores(want["votes"], 0.6, n, 0.0, 10)
     print("%s: %d results, votes %s, scores %s" % (method, len(got["votes"]), list(got["votes"]), list(got["scores"])))
+    # one vote, and the same one: the estimate runs the vote on the lane it holds, once
+    assert got["stats"]["n_raw"] == len(scene["raw"]["votes"])
+    assert got["stats"]["vote"]["launches"] == 1
     print("pose differences to the restatement:", [_pose_err(a, b) for a, b in zip(got["poses"], want["poses"])])
     print("top pose to the truth:", _pose_err(got["poses"][0], s["T"]) if len(got["poses"]) else None)
     assert len(got["votes"]) == keep == len(want["votes"]) >= 1
@@ -328,6 +317,35 @@ def test_estimate_against_the_restatement(capi, ref, cluster_ref, icp, scene, me
         cut = capi.ppf_estimate(s["model"], s["scene_points"], s["scene_normals"], s["reference"], edge_points=s["scene_edge_points"],
                                 edge_normals=s["scene_edge_normals"], angle_threshold=cu.ANGLE, score_thresh=thr, refine_method="NoRefine")
         assert len(cut["votes"]) == ref.scores(want["votes"], 0.6, n, thr, 10)[1]
+
+
+def test_two_threads_estimate_on_one_model(capi, scene):
+    """two threads, three estimates each (default refinement) on one model: every result is the single-threaded call's"""
+    kw = dict(edge_points=scene["scene_edge_points"], edge_normals=scene["scene_edge_normals"], score_thresh=0.0)
+    args = (scene["model"], scene["scene_points"], scene["scene_normals"], scene["reference"])
+    want = capi.ppf_estimate(*args, **kw)
+    assert len(want["votes"]) >= 1 and want["stats"]["icp_calls"] >= 1
+    results, errors = [[], []], []
+
+    def work(slot):
+        try:
+            for _ in range(3):
+                results[slot].append(capi.ppf_estimate(*args, **kw))
+        except Exception as e:   # noqa: BLE001
+            errors.append(e)
+
+    threads = [threading.Thread(target=work, args=(i,)) for i in range(2)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors
+    assert [len(r) for r in results] == [3, 3]
+    for got in results[0] + results[1]:
+        assert np.array_equal(got["votes"], want["votes"]) and np.array_equal(got["scores"], want["scores"])
+        assert _pose_err(got["poses"], want["poses"]) < 1e-9
+        assert _pose_err(got["q"], want["q"]) < 1e-9 and _pose_err(got["t"], want["t"]) < 1e-9
+        assert got["stats"]["n_raw"] == want["stats"]["n_raw"] and got["stats"]["vote"]["launches"] == want["stats"]["vote"]["launches"]
 
 
 def test_estimate_python_class(capi, scene):

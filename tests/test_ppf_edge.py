@@ -1,7 +1,8 @@
-"""PPF voting in EdgePoints mode without a GPU: the contract's restatement (tests/cpp/ppf_edge_ref.c) on hand cases and against
-the independent numpy-longdouble judge on every input the GPU tests use (none of which has a pair near a bin edge), why rule E1
-centres the edge set, the restated estimate of the end-to-end scene, argument validation and mode refusals through the C ABI,
-the exported symbols, the C++ mirror and the host steps of m3d_ppf_prepare_scene."""
+"""PPF voting in EdgePoints mode without a GPU: the contract's restatement (tests/cpp/ppf_ref.c with edge points) on hand cases and
+against the independent numpy-longdouble judge on every input the GPU tests use (none of which has a pair near a bin edge), why
+rule E1 centres the edge set, SampledPoints as EdgePoints with the sample as its own edge set, the restated estimate of the
+end-to-end scene, argument validation and mode refusals through the C ABI, the exported symbols, the C++ mirror and the host steps
+of m3d_ppf_prepare_scene."""
 import ctypes as C
 import os
 import subprocess
@@ -13,7 +14,6 @@ import ppf_edge_ref_util as eu
 import ppf_ref_util as pu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TABLE = ("cell_offsets", "entry_i", "entry_alpha", "nbr_offsets", "nbr_indices")
 
 # What the restatement does on the end-to-end scene (eu.estimate_case: a flat plate with holes in clutter), asserted by
 # test_estimate_case_restated -- the truth check of tests/test_gpu_ppf_edge.py is a condition on this input, established here:
@@ -25,11 +25,10 @@ ESTIMATE_TRUTH = {"PointToPlane": 1e-9, "PointToPoint": 1e-9, "NoRefine": 0.03}
 
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
-    return eu.PpfEdgeRef(tmp_path_factory.mktemp("ppf_edge_ref"))
+    return pu.PpfRef(tmp_path_factory.mktemp("ppf_edge_ref"))
 
 
-def _ref_model(ref, c, **kw):
-    return ref.edge_model(c["points"], c["normals"], c["edge_points"], c["edge_normals"], c["diameter"], c["r_min"], c["params"], **kw)
+_ref_model = pu.ref_model
 
 
 # ---- hand cases: diameter 1, 12 degrees: dist_step 0.05, cell = q0 + 16 (q1 + 16 (q2 + 16 q3))
@@ -38,7 +37,7 @@ E0, NE0 = [0.3, 0.4, 0.0], [0.6, 0.0, 0.8]                  # one edge point
 
 
 def _hand(ref, edge_points, edge_normals):
-    return ref.edge_model([S0, S1], [[1.0, 0, 0], [1.0, 0, 0]], edge_points, edge_normals, 1.0, 0.3, pu.params())
+    return ref.model([S0, S1], [[1.0, 0, 0], [1.0, 0, 0]], 1.0, 0.3, pu.params(), edge_points, edge_normals)
 
 
 def test_two_sample_points_one_edge_point_by_hand(ref):
@@ -78,10 +77,10 @@ def test_equal_indices_are_pairs(ref):
 # ---- the restatement against the judge on every GPU case
 def _assert_ref_equals_judge(ref, c):
     m = _ref_model(ref, c)
-    jm = eu.judge_edge_model(c["points"], c["normals"], c["edge_points"], c["edge_normals"], c["diameter"], c["r_min"], c["params"])
+    jm = pu.judge_model(c["points"], c["normals"], c["diameter"], c["r_min"], c["params"], c["edge_points"], c["edge_normals"])
     assert jm["undecided"] == 0          # a condition on the inputs, not a tolerance: no pair near a bin edge
     t = m.table()
-    for k in TABLE:
+    for k in pu.TABLE:
         assert np.array_equal(t[k], jm[k]), k
     assert np.array_equal(t["centroid"], jm["centroid"])
     assert np.abs(t["tmg"] - jm["tmg"].astype(np.float64)).max() < 1e-12
@@ -102,7 +101,7 @@ def test_vote_restatement_equals_judge(ref, name):
     m, jm = _assert_ref_equals_judge(ref, c)
     args = (c["scene_points"], c["scene_normals"], c["reference"], c["scene_edge_points"], c["scene_edge_normals"])
     v = m.vote(*args)
-    j = eu.judge_edge_vote(jm, c["r_min"], c["params"], *args)
+    j = pu.judge_vote(jm, c["r_min"], c["params"], *args)
     assert j["undecided"] == 0
     assert list(v["n_searched"]) == j["n_searched"]
     for k in ("ref_pos", "model_index", "alpha_index", "votes"):
@@ -133,7 +132,7 @@ def test_centring_both_sets_recovers_the_pose_and_the_reference_way_does_not(ref
     refs = np.arange(0, len(sp), 16)
     errs = {}
     for centre in (True, False):
-        m = ref.edge_model(pts, c["normals"], ept, c["edge_normals"], c["diameter"], c["r_min"], c["params"], centre_edges=centre)
+        m = ref.model(pts, c["normals"], c["diameter"], c["r_min"], c["params"], ept, c["edge_normals"], centre_edges=centre)
         v = m.vote(sp, sn, refs, ep, en)
         S = np.eye(4)
         S[:3, 3] = -m.table()["centroid"]
@@ -142,6 +141,40 @@ def test_centring_both_sets_recovers_the_pose_and_the_reference_way_does_not(ref
           (min(errs[True]), len(errs[True]), "min %.3g of %d" % (min(errs[False]), len(errs[False])) if errs[False] else "no maxima"))
     assert len(errs[True]) > 0 and min(errs[True]) < 0.1
     assert all(e > 0.1 for e in errs[False])
+
+
+# ---- the two modes are one: SampledPoints is EdgePoints with the sample as its own referred set
+@pytest.mark.parametrize("name", pu.OWN_EDGE_CASES)
+def test_sampled_mode_is_edge_mode_on_the_sample_itself(ref, name):
+    """The pairs i == j have d2 == 0 and are skipped by rule U2 in either mode, so a model trained with its sample as its edge set
+    and voted with the scene as its own edge cloud is the sampled model: the table, every integer of the vote, the counters and
+    the poses to the byte, in the restatement; the integers in the judge."""
+    c = pu.case(name)
+    e = pu.with_own_edges(c)
+    sampled, edge = pu.ref_model(ref, c), pu.ref_model(ref, e)
+    n = len(c["points"])
+    assert (sampled.n_e, edge.n_e) == (0, n)
+    assert (edge.table_size, edge.n_entries, edge.n_neighbors) == (sampled.table_size, sampled.n_entries, sampled.n_neighbors)
+    assert sampled.n_entries == n * (n - 1)                     # (no pair beyond the table in these cases)
+    ts, te = sampled.table(), edge.table()
+    for k in ts:
+        assert te[k].tobytes() == ts[k].tobytes(), k
+    vs, ve = pu.ref_vote(sampled, c), pu.ref_vote(edge, e)
+    for k in pu.INTS + ("n_searched", "poses"):
+        assert ve[k].shape == vs[k].shape and ve[k].tobytes() == vs[k].tobytes(), k
+    assert (ve["visited"], ve["increments"]) == (vs["visited"], vs["increments"])
+    assert len(vs["votes"]) > 0 or name == "count_random_64"    # 64 neighbours: below the gate, no vote
+    js = pu.judge_model(c["points"], c["normals"], c["diameter"], c["r_min"], c["params"])
+    je = pu.judge_model(c["points"], c["normals"], c["diameter"], c["r_min"], c["params"], e["edge_points"], e["edge_normals"])
+    assert js["undecided"] == je["undecided"] == 0 and (js["n_e"], je["n_e"]) == (0, n)
+    for k in pu.TABLE:
+        assert np.array_equal(je[k], js[k]) and np.array_equal(je[k], ts[k]), k
+    scene = (c["scene_points"], c["scene_normals"], c["reference"])
+    vjs = pu.judge_vote(js, c["r_min"], c["params"], *scene)
+    vje = pu.judge_vote(je, c["r_min"], c["params"], *scene, e["scene_edge_points"], e["scene_edge_normals"])
+    assert vjs["undecided"] == vje["undecided"] == 0
+    for k in pu.INTS + ("n_searched",):
+        assert vje[k] == vjs[k] == list(vs[k]), k
 
 
 # ---- the restated estimate of the end-to-end scene (K1 - K7 from the clustering and ICP restatements, K8's scores from E9)

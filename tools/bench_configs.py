@@ -991,6 +991,18 @@ if any(t in which for t in ("R1", "R2", "R3")) or ALL:
             frames.append([a, b])
         ray_line("R3", "ray cast, a 100-frame batch of the reference example (one call)", [mesh, mesh], frames, ex_cam, reps=7)
 
+def ppf_median(fn, reps=5):
+    """PV1, PC1, PV2: one warm-up call, then the median of `reps` timed ones -> (ms, that call's result)"""
+    fn()
+    runs = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        r = fn()
+        runs.append(((time.perf_counter() - t0) * 1e3, r))
+    runs.sort(key=lambda t: t[0])
+    return runs[len(runs) // 2]
+
+
 if "PV1" in which or ALL:
     # pose_estimation.PPFVoting (DESIGN.md section 4, "PPF voting") through the C ABI: the table of a 2 000-point model (box
     # family of the PPF tests) and the vote of a 20 000-point scene -- the posed model in 18 000 points of clutter -- at ratio 0.6:
@@ -1004,16 +1016,6 @@ if "PV1" in which or ALL:
     pts, nrm, diameter, r_min = ppf_util.model_case("box", 2000)
     sp, sn, _ = ppf_util.scene_of(pts, nrm, ppf_util.pose(1), 18_000, 1)
     refs = np.sort(np.random.default_rng(1).permutation(len(sp))[: int(0.6 * len(sp))])
-
-    def ppf_median(fn, reps=5):
-        fn()
-        runs = []
-        for _ in range(reps):
-            t0 = time.perf_counter()
-            r = fn()
-            runs.append(((time.perf_counter() - t0) * 1e3, r))
-        runs.sort(key=lambda t: t[0])
-        return runs[len(runs) // 2]
 
     ms_table, model = ppf_median(lambda: capi.PpfModel(pts, nrm, diameter, r_min))
     ms_vote, (res, st) = ppf_median(lambda: model.vote(sp, sn, refs, stats=True))
@@ -1059,21 +1061,11 @@ if "PC1" in which or ALL:
     sp, sn, _ = ppf_util.scene_of(pts, nrm, ppf_util.pose(1), 18_000, 1)
     refs = np.sort(np.random.default_rng(1).permutation(len(sp))[: int(0.6 * len(sp))])
 
-    def pc_median(fn, reps):
-        fn()
-        runs = []
-        for _ in range(reps):
-            t0 = time.perf_counter()
-            r = fn()
-            runs.append(((time.perf_counter() - t0) * 1e3, r))
-        runs.sort(key=lambda t: t[0])
-        return runs[len(runs) // 2]
-
     model = capi.PpfModel(pts, nrm, diameter, r_min)
     raw = model.vote(sp, sn, refs)
-    ms_cluster, cl = pc_median(lambda: capi.ppf_cluster_poses(raw["poses"], raw["votes"], model=model), 5)
-    ms_estimate, est = pc_median(lambda: capi.ppf_estimate(model, sp, sn, refs, score_thresh=0.0), 3)
-    ms_norefine, est0 = pc_median(lambda: capi.ppf_estimate(model, sp, sn, refs, score_thresh=0.0, refine_method="NoRefine"), 3)
+    ms_cluster, cl = ppf_median(lambda: capi.ppf_cluster_poses(raw["poses"], raw["votes"], model=model), 5)
+    ms_estimate, est = ppf_median(lambda: capi.ppf_estimate(model, sp, sn, refs, score_thresh=0.0), 3)
+    ms_norefine, est0 = ppf_median(lambda: capi.ppf_estimate(model, sp, sn, refs, score_thresh=0.0, refine_method="NoRefine"), 3)
     es = est["stats"]
     cpu_b = None
     if not NO_CPU:
@@ -1105,7 +1097,7 @@ if "PV2" in which or ALL:
     # scene is the posed sample in 18 000 points of clutter (12 000 reference points at ratio 0.6), the scene's edges the posed
     # model edges and as many clutter edge points again.  Median of 5 calls after 1 warm-up for the table and the vote (once more
     # through device memory), of 3 for m3d_ppf_estimate_edges.  cpu_baseline = the contract's C restatement
-    # (tests/cpp/ppf_edge_ref.c) under OpenMP on 16 threads: the table whole, the vote on every tenth reference point, scaled.
+    # (tests/cpp/ppf_ref.c with edge points) under OpenMP on 16 threads: the table whole, the vote on every tenth reference point, scaled.
     import tempfile
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import ppf_edge_ref_util as edge_util
@@ -1121,38 +1113,28 @@ if "PV2" in which or ALL:
     sep, sen, _ = ppf_util.scene_of(ept, enr, T, len(ept), 51)
     refs = np.sort(np.random.default_rng(1).permutation(len(sp))[: int(0.6 * len(sp))])
 
-    def pv2_median(fn, reps=5):
-        fn()
-        runs = []
-        for _ in range(reps):
-            t0 = time.perf_counter()
-            r = fn()
-            runs.append(((time.perf_counter() - t0) * 1e3, r))
-        runs.sort(key=lambda t: t[0])
-        return runs[len(runs) // 2]
-
-    ms_table, model = pv2_median(lambda: capi.PpfModel(pts, nrm, diameter, r_min, edge_points=ept, edge_normals=enr))
-    ms_vote, (res, st) = pv2_median(lambda: model.vote(sp, sn, refs, stats=True, edge_points=sep, edge_normals=sen))
+    ms_table, model = ppf_median(lambda: capi.PpfModel(pts, nrm, diameter, r_min, edge_points=ept, edge_normals=enr))
+    ms_vote, (res, st) = ppf_median(lambda: model.vote(sp, sn, refs, stats=True, edge_points=sep, edge_normals=sen))
     capi.ppf_force(True, 0)
     try:
-        ms_vote_dev, (res_dev, st_dev) = pv2_median(lambda: model.vote(sp, sn, refs, stats=True, edge_points=sep, edge_normals=sen))
+        ms_vote_dev, (res_dev, st_dev) = ppf_median(lambda: model.vote(sp, sn, refs, stats=True, edge_points=sep, edge_normals=sen))
     finally:
         capi.ppf_force(False, 0)
-    ms_estimate, est = pv2_median(lambda: capi.ppf_estimate(model, sp, sn, refs, edge_points=sep, edge_normals=sen, score_thresh=0.0), 3)
+    ms_estimate, est = ppf_median(lambda: capi.ppf_estimate(model, sp, sn, refs, edge_points=sep, edge_normals=sen, score_thresh=0.0), 3)
     es = est["stats"]
     cpu_b = None
     if not NO_CPU:
         os.environ.setdefault("OMP_NUM_THREADS", "16")
-        ref = edge_util.PpfEdgeRef(tempfile.mkdtemp(), openmp=True)
+        ref = ppf_util.PpfRef(tempfile.mkdtemp(), openmp=True)
         t0 = time.perf_counter()
-        rm = ref.edge_model(pts, nrm, ept, enr, diameter, r_min)
+        rm = ref.model(pts, nrm, diameter, r_min, edge_points=ept, edge_normals=enr)
         t1 = time.perf_counter()
         rv = rm.vote(sp, sn, refs[::10], sep, sen)
         t2 = time.perf_counter()
         cpu_b = {"ms_table": (t1 - t0) * 1e3, "ms_vote": (t2 - t1) * 1e3 * len(refs) / len(refs[::10]), "unit": "ms",
                  "vote_sampled": "every 10th reference point, scaled by the count", "increments_sampled": rv["increments"],
                  "same_table_size": bool(rm.n_entries == model.info()["n_entries"]),
-                 "what": "tests/cpp/ppf_edge_ref.c: the contract's restatement, gcc -O2 -ffp-contract=off -fopenmp, 16 threads"}
+                 "what": "tests/cpp/ppf_ref.c: the contract's restatement, gcc -O2 -ffp-contract=off -fopenmp, 16 threads"}
     emit("PV2 ppf EdgePoints: table of a plate with holes + vote and estimate on a 20 000-point scene, 12 000 reference points",
          n=len(pts), n_edge=len(ept), m=len(sp), m_edge=len(sep), n_ref=len(refs), table_entries=model.info()["n_entries"],
          ms_table=ms_table, ms_vote=ms_vote, ms_vote_device=st["ms_device"], path=st["path"], groups=st["groups"],
