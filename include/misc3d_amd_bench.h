@@ -132,6 +132,18 @@ int m3d_bench_ppf_force(int device_memory_path, int max_groups);
  * default).  The result does not depend on it. */
 int m3d_bench_ppf_cluster_force(int splits);
 
+/* TEST hook (tests/test_gpu_scratch_fill.py): what a block of device or page-locked scratch holds when the library hands it
+ * out -- pattern -1 = whatever it held (the default: a fresh allocation, or a block of the lane's free list with the last
+ * call's contents), 0..255 = every byte of the block set to `pattern` before it is handed out, fresh or recycled.  A buffer
+ * that is large enough already is not handed out again and keeps its contents.  Filling waits for the whole device on both
+ * sides of the write.  Switching resets the counters of m3d_bench_scratch_fill_stats.  No result depends on it. */
+int m3d_bench_scratch_fill(int pattern);
+/* ... out[0] = the blocks, out[1] = the bytes filled since the last m3d_bench_scratch_fill. */
+int m3d_bench_scratch_fill_stats(uint64_t out[2]);
+/* ... takes a lane of `device` as a one-call entry point does, takes one block of device scratch of `bytes` (>= 64) bytes,
+ * copies the block's first 64 bytes to first_last[0..63] and its last 64 to first_last[64..127], and gives the block back. */
+int m3d_bench_scratch_probe(int device, size_t bytes, unsigned char first_last[128]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@ object is missing, importing fails loudly; if there is no HIP device every compu
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import threading
 import os
@@ -241,6 +242,9 @@ def lib():
         L.m3d_ppf_estimate_edges.argtypes = ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                               C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_void_p] * 7)
         L.m3d_bench_ppf_cluster_force.argtypes = [C.c_int]
+        L.m3d_bench_scratch_fill.argtypes = [C.c_int]
+        L.m3d_bench_scratch_fill_stats.argtypes = [C.c_void_p]
+        L.m3d_bench_scratch_probe.argtypes = [C.c_int, C.c_size_t, C.c_void_p]
         L.m3d_estimate_normals.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                            C.c_void_p, C.c_void_p]
         L.m3d_compute_fpfh.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p,
@@ -1858,6 +1862,38 @@ def ppf_cluster_force(splits=0):
 def ppf_force(device_memory_path=False, max_groups=0):
     """test / measurement hook m3d_bench_ppf_force: accumulators in device memory, at most max_groups workgroups (0: default)"""
     _check(lib().m3d_bench_ppf_force(int(bool(device_memory_path)), int(max_groups)))
+
+
+_scratch_pattern = -1   # what m3d_bench_scratch_fill was last set to (the library starts with the hook off)
+
+
+@contextlib.contextmanager
+def scratch_fill(pattern):
+    """test hook m3d_bench_scratch_fill: inside the block every piece of scratch the library hands out is set to the byte
+    `pattern` (0..255; -1: left as it is) first; the previous setting comes back on exit.  Switching resets scratch_fill_stats."""
+    global _scratch_pattern
+    prev = _scratch_pattern
+    _check(lib().m3d_bench_scratch_fill(int(pattern)))
+    _scratch_pattern = int(pattern)
+    try:
+        yield
+    finally:
+        _check(lib().m3d_bench_scratch_fill(prev))
+        _scratch_pattern = prev
+
+
+def scratch_fill_stats():
+    """m3d_bench_scratch_fill_stats -> (blocks, bytes) filled since the hook was last switched"""
+    out = np.zeros(2, np.uint64)
+    _check(lib().m3d_bench_scratch_fill_stats(_p(out)))
+    return int(out[0]), int(out[1])
+
+
+def scratch_probe(nbytes, device=0):
+    """m3d_bench_scratch_probe -> 128 uint8: the first and the last 64 bytes of a block of device scratch of `nbytes` bytes as handed out"""
+    out = np.zeros(128, np.uint8)
+    _check(lib().m3d_bench_scratch_probe(int(device), int(nbytes), _p(out)))
+    return out
 
 
 class FpfhStats(C.Structure):

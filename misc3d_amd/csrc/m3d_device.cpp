@@ -35,6 +35,21 @@ thread_local int t_lane = 0;   // the lane the calling thread holds (CtxLock / L
 thread_local int t_dev = -1;   // ... and its LOGICAL device (free lists are per logical device: two aliases of one physical device
                                // have streams of their own, and a list is ordered by one stream only); -1 outside of any: hipGetDevice
 inline int pool_index(int dev, int lane) { return dev * kMaxLanes + lane; }
+
+// m3d_bench_scratch_fill (include/misc3d_amd_bench.h): -1 = off, else the byte every block is set to as it is handed out
+std::atomic<int> g_scratch_fill{-1};
+std::atomic<uint64_t> g_scratch_fill_blocks{0}, g_scratch_fill_bytes{0};
+// The block may still be named by work its lane queued before releasing it, and the caller may queue work on any stream
+// the moment reserve returns: the device is idle on both sides of the write.  (Outside the pool mutex.)
+bool scratch_fill_device(void* p, size_t cap, int pattern) {
+    if (hipDeviceSynchronize() != hipSuccess || hipMemset(p, pattern, cap) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        set_error("scratch fill failed (" + std::to_string(cap) + " bytes)");
+        return false;
+    }
+    g_scratch_fill_blocks.fetch_add(1, std::memory_order_relaxed);
+    g_scratch_fill_bytes.fetch_add(cap, std::memory_order_relaxed);
+    return true;
+}
 }  // namespace
 
 bool DevBuf::reserve(size_t bytes) {
@@ -52,24 +67,27 @@ bool DevBuf::reserve(size_t bytes) {
         if (it != pool.blocks[pi].end() && it->first <= 2 * want + ((size_t)1 << 20)) {
             p = it->second;
             cap = it->first;
-            dev = d;
-            lane = ln;
             pool.bytes[pi] -= cap;
             pool.blocks[pi].erase(it);
-            return true;
         }
     }
-    if (hipMalloc(&p, want) != hipSuccess) {
-        dev_pool_trim(d);   // give the parked blocks back and try once more
+    if (!p) {
         if (hipMalloc(&p, want) != hipSuccess) {
-            p = nullptr;
-            set_error("hipMalloc failed (" + std::to_string(want) + " bytes)");
-            return false;
+            dev_pool_trim(d);   // give the parked blocks back and try once more
+            if (hipMalloc(&p, want) != hipSuccess) {
+                p = nullptr;
+                set_error("hipMalloc failed (" + std::to_string(want) + " bytes)");
+                return false;
+            }
         }
+        cap = want;
     }
-    cap = want;
     dev = d;
     lane = ln;
+    if (const int pattern = g_scratch_fill.load(std::memory_order_relaxed); pattern >= 0 && !scratch_fill_device(p, cap, pattern)) {
+        release();
+        return false;
+    }
     return true;
 }
 bool CellSort::reserve(size_t n_points, uint32_t ncell) {
@@ -152,6 +170,11 @@ bool PinBuf::reserve(size_t bytes) {
         return false;
     }
     cap = want;
+    if (const int pattern = g_scratch_fill.load(std::memory_order_relaxed); pattern >= 0) {
+        memset(p, pattern, cap);
+        g_scratch_fill_blocks.fetch_add(1, std::memory_order_relaxed);
+        g_scratch_fill_bytes.fetch_add(cap, std::memory_order_relaxed);
+    }
     return true;
 }
 void PinBuf::release() {
@@ -641,6 +664,38 @@ void m3d_release_cached(int device) {
         ctx->seg_staging_cap = 0;
     }
     dev_pool_trim(device);
+}
+
+// test hooks (include/misc3d_amd_bench.h)
+int m3d_bench_scratch_fill(int pattern) {
+    if (pattern < -1 || pattern > 255) return fail(M3D_ERR_INVALID_ARG, "pattern: -1 = off, 0..255 = the byte every block handed out is set to");
+    g_scratch_fill.store(pattern);
+    g_scratch_fill_blocks.store(0);
+    g_scratch_fill_bytes.store(0);
+    return M3D_OK;
+}
+int m3d_bench_scratch_fill_stats(uint64_t out[2]) {
+    if (!out) return fail(M3D_ERR_INVALID_ARG, "invalid argument");
+    out[0] = g_scratch_fill_blocks.load();
+    out[1] = g_scratch_fill_bytes.load();
+    return M3D_OK;
+}
+int m3d_bench_scratch_probe(int device, size_t bytes, unsigned char first_last[128]) {
+    if (!first_last || bytes < 64) return fail(M3D_ERR_INVALID_ARG, "scratch_probe: at least 64 bytes, and room for 128");
+    LaneLock lane(device);
+    DeviceCtx* ctx = lane.ctx;
+    if (!ctx) return M3D_ERR_DEVICE;
+    DevBuf b;
+    const int rc = [&]() -> int {
+        HIPCHK(hipSetDevice(ctx->device));
+        RESERVE(b, bytes);
+        HIPCHK(hipMemcpyAsync(first_last, b.p, 64, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(first_last + 64, b.as<unsigned char>() + b.cap - 64, 64, hipMemcpyDeviceToHost, ctx->stream));
+        return M3D_OK;
+    }();
+    (void)hipStreamSynchronize(ctx->stream);
+    b.release();
+    return rc;
 }
 
 size_t m3d_cloud_size(const m3d_cloud* c) { return c ? c->n : 0; }
