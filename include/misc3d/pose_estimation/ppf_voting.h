@@ -5,7 +5,7 @@
 //
 // All take ALREADY SAMPLED points with unit normals, in either voting mode: Train / Vote / Estimate are SampledPoints,
 // TrainEdges / VoteEdges / EstimateEdges are EdgePoints; PrepareScene is PreprocessEstimate.  PreprocessTrain and the
-// PPFEstimator / PPFEstimatorConfig classes themselves are not part of this build; the contract of what is here is written down
+// PPFEstimator / PPFEstimatorConfig classes are in ppf_estimation.h beside this header; the contract of what is here is written down
 // next to m3d_ppf_vote, m3d_ppf_vote_edges and m3d_ppf_estimate in include/misc3d_amd.h.
 #pragma once
 #include <array>

@@ -1036,7 +1036,7 @@ int m3d_set_config(const m3d_config *in);
  * m3d_ppf_model_create, VotingAndGetPose (:399-524) with CalcLocalMaximum (:1170-1234) behind m3d_ppf_vote.  Both take
  * ALREADY SAMPLED points with unit normals (row-major n x 3 doubles).  ClusterPoses / PoseAverage, the refinement and the
  * scoring are below ("PPF pose clustering"), the EdgePoints mode and PreprocessEstimate below this block ("PPF voting,
- * EdgePoints mode", m3d_ppf_prepare_scene); PreprocessTrain and the PPFEstimator class itself are not part of this build.
+ * EdgePoints mode", m3d_ppf_prepare_scene); PreprocessTrain is m3d_ppf_prepare_model ("PPF model preprocessing"), the PPFEstimator class the host mirrors' (python pose_estimation.PPFEstimator, include/misc3d/pose_estimation/ppf_estimation.h).
  * The text below is the contract; tests/cpp/ppf_ref.c restates it in serial C.
  *
  * MODEL (Train, :537-570, VotingMode::SampledPoints).  points[n], normals[n], diameter, r_min and m3d_ppf_params.
@@ -1214,12 +1214,96 @@ int m3d_ppf_prepare_scene(const double *xyz, const double *normals, size_t n, do
                           double *sample_normals, size_t *n_sample, double *dense_xyz, double *dense_normals, size_t *n_dense,
                           size_t *edge_indices, size_t *n_edges);
 
+/* ---- PPF model preprocessing: PPFEstimator::PreprocessTrain, src/ppf_estimation.cpp:206-241 with :1018-1160 -----------------
+ * ORIENTATION (m3d_orient_normals_mst).  The reference's priority-queue walk (CalcModelNormalAndSampling, :1083-1148) is lazy
+ * Prim: the first done neighbour of the point it pops is that point's parent in the minimum spanning tree of the radius
+ * graph, rooted at the seed ("PPF model preprocessing").  The device builds that tree by Boruvka rounds
+ * (m3d_orient.hip), the host walks it once (m3d_ppf_train.hpp).  tests/cpp/ppf_train_ref.c restates the heap walk in serial C.
+ *   O1. Vertices are the n points; all coordinates must be finite (M3D_ERR_INVALID_ARG otherwise).  {i, j} is an edge iff
+ *       i != j and d2(i, j) < radius radius, d2 = (dx dx + dy dy) + dz dz without contraction (m3d_proximity_fp.hpp's prox_d2;
+ *       nanoflann's strict cut-off, the library's neighbourhood rule K3).  d2 is symmetric bit for bit.
+ *   O2. Edges are ordered by (d2, min(i, j), max(i, j)); T is the minimum spanning forest under that order.  The reference's
+ *       own order is looser at ties (sqrt merges distinct d2, its sort and heap are not stable): this build differs from it
+ *       only where its result depends on its standard library.
+ *   O3. parent[seed] = -1; for every other point of the seed's component, parent is the neighbour on the tree path to the
+ *       seed; parent = -2 outside the component.
+ *   O4. s(seed) = +1 (the caller has oriented the seed).  Walking away from the seed, s(i) = -1 iff s(parent) dot3(n_i,
+ *       n_parent) < 0, dot3 the library's uncontracted one (m3d_fp.hpp) on the normals AS GIVEN: a zero or NaN dot leaves i
+ *       unflipped whatever its parent's sign.  out_normals = s(i) n_i -- negation only, no renormalisation; points with
+ *       parent = -2 are returned unchanged.
+ *   O5. stats: rounds = the Boruvka rounds run (the last one adds no edge unless the forest is complete before: at most
+ *       ceil(log2 n) + 1), tree_edges = the edges of the whole forest, component = the size of the seed's component, flips.
+ * radius must be finite and > 0, seed < n, n < 2^31; n == 0 is M3D_ERR_INVALID_ARG.  out_normals: n x 3, parent: n.
+ * Results do not depend on what recycled device scratch holds. */
+typedef struct m3d_orient_stats {
+    uint64_t rounds, tree_edges, component, flips;
+    double ms_total;  /* host clock, the whole call */
+    double ms_grid;   /* upload + grid build (host clock around their wait) */
+    double ms_rounds; /* the Boruvka rounds, edge list on the host included */
+    double ms_signs;  /* the host's breadth-first pass */
+} m3d_orient_stats;
+int m3d_orient_normals_mst(const double *xyz, const double *normals, size_t n, double radius, size_t seed, int device,
+                           double *out_normals, int64_t *parent, m3d_orient_stats *stats);
+
+/* MODEL PREPARATION (m3d_ppf_prepare_model): a host composition on one device.
+ *   B1. Box.  Mean and covariance of all points as Open3D's ComputeMeanAndCovariance: nine cumulants (x, y, z, xx, xy, xz,
+ *       yy, yz, zz) summed serially in index order, divided by n, cov(a, b) = E[ab] - E[a] E[b].  Axes: the Jacobi sweeps of
+ *       m3d_eig3.hpp.  extent_k = max - min of dot3(axis_k, p - mean); centre = mean + sum_k axis_k (max_k + min_k) / 2.
+ *       With box_center and box_extent (3 doubles each, both or neither) they are used as given: a caller who has Open3D
+ *       passes GetOrientedBoundingBox()'s and gets the reference's parameters.  The reference's box is the PCA box of Qhull's
+ *       convex-hull vertices, which this build does not restate; only the extent and the centre are used, and both are
+ *       invariant under the axes' order and signs.
+ *   B2. diameter = sqrt(d0 d0 + d1 d1 + d2 d2); r_min = sqrt of the sum of the two smallest extents squared; dist_step =
+ *       diameter rel_sample_dist; dist_step_dense = diameter rel_dense_sample_dist; normal_r = diameter calc_normal_relative;
+ *       view_pt = centre + (0, 0, 2 diameter).
+ *   B3. normals == NULL: m3d_estimate_normals(Hybrid, normal_r, 30, no orientation).  Then NormalizeNormals: s = (x x + y y) +
+ *       z z, each component divided by sqrt(s) when s > 0.
+ *   B4. seed = the point nearest view_pt (d2, lowest index at ties).  Unless normals were given and use_external_normal is
+ *       set: the seed's normal is negated iff dot3(view_pt - p_seed, n_seed) < 0, once more if invert_model_normal, then
+ *       O1 - O4 with radius = normal_r.
+ *   B5. Sampler S(step), DownSamplePCNormal (:1018-1061) as written: a FIFO starts at the seed; pop cur, skip it if checked,
+ *       else mark it checked and select it; its neighbours are the points with d2 < (2 step)^2 in ascending (d2, index); each
+ *       one not checked is marked checked if sqrt(d2) < step, else pushed.  The result is the selection order.  Host.
+ *   B6. sample = S(dist_step).  rel_dense_sample_dist > 0: dense = S(dist_step_dense) and edge_indices =
+ *       m3d_detect_boundary_points(dense points, dense normals, Hybrid(normal_r, pts_num), 90 degrees), ascending, into dense.
+ * out_normals: n x 3, the prepared normals of all points.  sample_indices / dense_indices / edge_indices: capacity n each;
+ * dense_indices and edge_indices may be NULL when rel_dense_sample_dist <= 0.  n == 0: M3D_ERR_INVALID_ARG "There is no input
+ * points"; a non-finite point is M3D_ERR_INVALID_ARG. */
+typedef struct m3d_ppf_train_params {
+    double rel_sample_dist;       /* 0.05 */
+    double rel_dense_sample_dist; /* 0.025; <= 0: no dense sample, no edges (SampledPoints mode) */
+    double calc_normal_relative;  /* 0.01 */
+    int32_t invert_model_normal;  /* 0 */
+    int32_t use_external_normal;  /* 0 */
+    int32_t pts_num;              /* 20: edge_param_.pts_num */
+    int32_t reserved;
+} m3d_ppf_train_params;
+void m3d_ppf_train_params_default_(m3d_ppf_train_params *p);
+typedef struct m3d_ppf_model_info {
+    double box_center[3], box_extent[3];
+    double diameter, r_min, dist_step, dist_step_dense, normal_r, view_pt[3];
+    uint64_t seed;          /* B4 */
+    int32_t seed_flipped;   /* the seed's normal was negated in B4 */
+    int32_t oriented;       /* O1 - O4 ran */
+    m3d_orient_stats orient;
+    uint64_t sample_distance_evaluations, dense_distance_evaluations;
+    double ms_total, ms_box, ms_normals, ms_sample, ms_dense, ms_edges;
+} m3d_ppf_model_info;
+int m3d_ppf_prepare_model(const double *xyz, const double *normals, size_t n, const m3d_ppf_train_params *params,
+                          const double *box_center, const double *box_extent, int device, double *out_normals,
+                          size_t *sample_indices, size_t *n_sample, size_t *dense_indices, size_t *n_dense,
+                          size_t *edge_indices, size_t *n_edges, m3d_ppf_model_info *info);
+/* Estimate's reference points (:304-309): RandomSampler<size_t>(num).SampleWithoutDuplicate(sample) on std::mt19937(seed),
+ * include/misc3d/utils.h:101-116 as written (its swap(indices[i], indices[rng() % num]) is not Fisher-Yates).  Host only.
+ * out: `sample` entries; sample <= num < 2^32 (M3D_ERR_INVALID_ARG otherwise). */
+int m3d_ppf_reference_indices(size_t num, size_t sample, uint32_t seed, size_t *out);
+
 /* ---- PPF pose clustering: ClusterPoses, PoseAverage, RefineSparsePose, the centre shift and the scoring of
  * misc3d::pose_estimation::PPFEstimator, src/ppf_estimation.cpp -------------------------------------------------------------
  * Raw poses in, ranked and refined Pose6D results out: ClusterPoses (:871-935) with GatherPose (:778-836), CalcPoseNeighbor
  * (:838-869) and MatchPose (:745-776), PoseAverage (:992-1016), RefineSparsePose (:937-990), the centre shift (:342-351) and the
  * scoring (:353-392).  m3d_ppf_cluster_poses is K1 - K6, m3d_ppf_estimate is the vote and K1 - K8 (Estimate from :304 on).
- * PreprocessTrain and the PPFEstimator / PPFEstimatorConfig classes are not part of this build.  The text below is the contract; tests/cpp/ppf_cluster_ref.c restates it in serial C.
+ * PreprocessTrain is the block "PPF model preprocessing" above.  The text below is the contract; tests/cpp/ppf_cluster_ref.c restates it in serial C.
  *
  * INPUT.  poses[P] (row-major 4 x 4 doubles, poses of the CENTRED model as m3d_ppf_vote returns them) and votes[P].
  *   K1. Order: by votes descending, ties by ascending input index (the reference's std::sort leaves ties open; m3d_ppf_vote's

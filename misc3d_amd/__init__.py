@@ -27,6 +27,8 @@ Drop-in for the reference's python API on this path (module layout of python/py_
     depth    = renderer.get_depth_map().numpy(); instance = renderer.get_instance_map().numpy()        # ray_cast_renderer.cpp
     voting   = m3d.pose_estimation.PPFVoting(model_points, model_normals, diameter, r_min)             # ppf_estimation.cpp:603-640
     poses, num_votes, corr_mi, reference = voting.vote(scene_points, scene_normals, reference_indices) # ppf_estimation.cpp:399-524
+    ppf      = m3d.pose_estimation.PPFEstimator(m3d.pose_estimation.PPFEstimatorConfig()); ppf.train(model_points)   # ppf_estimation.cpp:526-601
+    ret, results = ppf.estimate(scene_points); pose = results[0].pose                                 # ppf_estimation.cpp:280-397
 
 Layout (only what the path needs):
   csrc/      HIP kernels, host driver, C ABI            -> lib/libmisc3d_amd.so
@@ -611,8 +613,8 @@ class PPFVoting:
     turn the raw poses into ranked, refined results (ClusterPoses, PoseAverage, RefineSparsePose, the centre shift and the
     scoring).  With edge_points / edge_normals (the model's edge points, 1 <= N_e <= 65535, N N_e <= 2^28) the model is
     trained in VotingMode::EdgePoints (Train, :572-593): the table pairs the sample with the edge points, and vote / estimate
-    take the scene's edge points as well; pose_estimation.ppf_prepare_scene is PreprocessEstimate.  PreprocessTrain and the
-    PPFEstimator / PPFEstimatorConfig classes themselves are not part of this build: the caller samples the model."""
+    take the scene's edge points as well; pose_estimation.ppf_prepare_scene is PreprocessEstimate, ppf_prepare_model is
+    PreprocessTrain, and PPFEstimator puts them together as the reference's class does."""
 
     def __init__(self, points, normals, diameter, r_min, *, edge_points=None, edge_normals=None, device=0, **params):
         from . import capi as _capi
@@ -686,6 +688,220 @@ class PPFVoting:
                 for k in range(len(r["votes"]))]
 
 
+def _log_error(msg):
+    if int(get_verbosity_level()) >= int(VerbosityLevel.Error):
+        print(f"[Misc3D ERROR] {msg}")
+
+
+class PPFEstimatorConfig:
+    """misc3d.pose_estimation.PPFEstimatorConfig (include/misc3d/pose_estimation/ppf_estimation.h, defaults
+    src/ppf_estimation.cpp:1392-1405): the reference's fields, nesting, defaults and enum names.  rel_dist_thresh and
+    rel_angle_thresh, which the reference's binding forgets, are exposed too."""
+
+    class ReferencePointSelection(_enum.IntEnum):
+        Random = 0
+
+    class RefineMethod(_enum.IntEnum):
+        NoRefine = 0
+        PointToPoint = 1
+        PointToPlane = 2
+
+    class VotingMode(_enum.IntEnum):
+        SampledPoints = 0
+        EdgePoints = 1
+
+    Random = ReferencePointSelection.Random                       # (export_values)
+    NoRefine, PointToPoint, PointToPlane = RefineMethod.NoRefine, RefineMethod.PointToPoint, RefineMethod.PointToPlane
+    SampledPoints, EdgePoints = VotingMode.SampledPoints, VotingMode.EdgePoints
+
+    class TrainingParam:
+        def __init__(self):
+            self.invert_model_normal, self.use_external_normal = False, False
+            self.rel_sample_dist, self.rel_dense_sample_dist, self.calc_normal_relative = 0.05, 0.025, 0.01
+
+    class ReferenceParam:
+        def __init__(self):
+            self.method, self.ratio = PPFEstimatorConfig.ReferencePointSelection.Random, 0.6
+
+    class VotingParam:
+        def __init__(self):
+            import math as _math
+            self.method, self.faster_mode = PPFEstimatorConfig.VotingMode.SampledPoints, True
+            self.angle_step, self.min_dist_thresh, self.min_angle_thresh = 12.0 / 180.0 * _math.pi, 1.0 / 3, 30.0 / 180.0 * _math.pi
+
+    class EdgeParam:
+        def __init__(self):
+            self.pts_num = 20
+
+    class RefineParam:
+        def __init__(self):
+            self.method, self.rel_dist_sparse_thresh = PPFEstimatorConfig.RefineMethod.PointToPlane, 5.0
+
+    def __init__(self):
+        import math as _math
+        self.training_param, self.ref_param, self.voting_param = self.TrainingParam(), self.ReferenceParam(), self.VotingParam()
+        self.edge_param, self.refine_param = self.EdgeParam(), self.RefineParam()
+        self.rel_dist_thresh, self.rel_angle_thresh = 0.05, 12.0 / 180.0 * _math.pi
+        self.score_thresh, self.num_result, self.object_id = 0.6, 10, 0
+
+
+class PPFEstimator:
+    """misc3d.pose_estimation.PPFEstimator (src/ppf_estimation.cpp: Train :526-601, Estimate :280-397): ppf_prepare_model
+    (PreprocessTrain, the contract "PPF model preprocessing" of include/misc3d_amd.h) and a PPFVoting of its sample; then
+    ppf_prepare_scene, the reference indices of SampleWithoutDuplicate and PPFVoting.estimate.  Clouds are (N, 3) arrays and come
+    back as (points, normals) pairs.  The model's box is rule B1's, not Qhull's: pass the reference's box as
+    train(..., bounding_box=(center, extent)) to get the reference's diameter.  dist_threshold = rel_dist_thresh x diameter is
+    computed afresh by every train; the reference multiplies its member again on each call (a bug not reproduced)."""
+
+    def __init__(self, config=None, device=0):
+        self._device = device
+        self._config = PPFEstimatorConfig()
+        self._reset()
+        if config is not None and not self.set_config(config):
+            raise ValueError("PPFEstimator: invalid config")
+
+    def _reset(self):
+        import numpy as _np
+        e = (_np.zeros((0, 3)), _np.zeros((0, 3)))
+        self._voting, self._info, self._diameter, self._dist_threshold, self._poses = None, None, 0.0, 0.0, []
+        self._model_sample, self._model_edges, self._scene_sample, self._scene_edges = e, e, e, e
+
+    @staticmethod
+    def check_config(config):
+        """CheckConfig (:1409-1418)"""
+        if config.training_param.rel_dense_sample_dist >= config.training_param.rel_sample_dist:
+            _log_error("Dense_sample_dist should be smaller than sample_dist.")
+            return False
+        return True
+
+    def set_config(self, config):
+        if not self.check_config(config):
+            return False
+        import copy as _copy
+        self._config = _copy.deepcopy(config)
+        return True
+
+    @property
+    def _edge_mode(self):
+        return int(self._config.voting_param.method) == int(PPFEstimatorConfig.VotingMode.EdgePoints)
+
+    def train(self, points, normals=None, *, bounding_box=None):
+        import numpy as _np
+
+        from . import capi as _capi
+        cfg, tp, vp = self._config, self._config.training_param, self._config.voting_param
+        self._reset()
+        pts = _np.ascontiguousarray(points, dtype=_np.float64).reshape(-1, 3)
+        if len(pts) == 0:
+            _log_error("There is no input points")
+            return False
+        bc, be = (None, None) if bounding_box is None else bounding_box
+        try:
+            m = _capi.ppf_prepare_model(pts, normals, box_center=bc, box_extent=be, device=self._device,
+                                        rel_sample_dist=tp.rel_sample_dist, rel_dense_sample_dist=tp.rel_dense_sample_dist if self._edge_mode else 0.0,
+                                        calc_normal_relative=tp.calc_normal_relative, invert_model_normal=int(bool(tp.invert_model_normal)),
+                                        use_external_normal=int(bool(tp.use_external_normal)), pts_num=int(cfg.edge_param.pts_num))
+        except _capi.M3DError as e:
+            raise RuntimeError(str(e)) from e
+        info, si = m["info"], m["sample_indices"]
+        if len(si) == 0:
+            _log_error("There is no input points after preprocessing")
+            return False
+        sample = (_np.ascontiguousarray(pts[si]), _np.ascontiguousarray(m["normals"][si]))
+        edges = (None, None)
+        if self._edge_mode:
+            if len(m["edge_indices"]) == 0:
+                _log_error("Fail to extract edge points!")
+                return False
+            ei = m["dense_indices"][m["edge_indices"]]
+            edges = (_np.ascontiguousarray(pts[ei]), _np.ascontiguousarray(m["normals"][ei]))
+        try:
+            voting = PPFVoting(sample[0], sample[1], info["diameter"], info["r_min"], edge_points=edges[0], edge_normals=edges[1],
+                               device=self._device, rel_sample_dist=tp.rel_sample_dist, angle_step=vp.angle_step,
+                               min_dist_thresh=vp.min_dist_thresh, min_angle_thresh=vp.min_angle_thresh, faster_mode=bool(vp.faster_mode))
+        except RuntimeError as e:
+            # the sample exceeds what PPFVoting accepts (m3d_ppf_model_create's three size refusals); anything else is raised
+            if not any(s in str(e) for s in ("ppf: the model must have", "ppf: the table's sort scratch")):
+                raise
+            _log_error(str(e))
+            return False
+        self._voting, self._info, self._diameter = voting, info, info["diameter"]
+        self._dist_threshold = cfg.rel_dist_thresh * info["diameter"]
+        self._model_sample = sample
+        if self._edge_mode:
+            self._model_edges = edges
+        return True
+
+    def estimate(self, points, normals=None, *, seed=None):
+        """-> (ret, [Pose6D]).  seed: of the reference points' std::mt19937 (None: drawn from the OS, as std::random_device)"""
+        import os as _os
+
+        import numpy as _np
+
+        from . import capi as _capi
+        cfg = self._config
+        self._poses = []
+        if self._voting is None:
+            _log_error("Need training before estimating!")
+            return False, []
+        info = self._info
+        try:
+            s = _capi.ppf_prepare_scene(points, normals, info["diameter"], cfg.training_param.calc_normal_relative, info["dist_step"],
+                                        info["dist_step_dense"] if self._edge_mode else 0.0, int(cfg.edge_param.pts_num), self._device)
+        except _capi.M3DError as e:
+            raise RuntimeError(str(e)) from e
+        self._scene_sample = (s["sample_points"], s["sample_normals"])
+        num = len(s["sample_points"])
+        if num == 0:
+            return False, []
+        ep = en = None
+        if self._edge_mode:
+            if len(s["edge_indices"]) == 0:
+                return False, []
+            ep = _np.ascontiguousarray(s["dense_points"][s["edge_indices"]])
+            en = _np.ascontiguousarray(s["dense_normals"][s["edge_indices"]])
+            self._scene_edges = (ep, en)
+        if seed is None:
+            seed = int.from_bytes(_os.urandom(4), "little")
+        ref = _capi.ppf_reference_indices(num, int(cfg.ref_param.ratio * num), seed)
+        results = self._voting.estimate(s["sample_points"], s["sample_normals"], ref, edge_points=ep, edge_normals=en,
+                                        **self._estimate_params())
+        self._poses = results
+        return len(results) > 0, results
+
+    def _estimate_params(self):
+        cfg = self._config
+        return dict(dist_threshold=self._dist_threshold, angle_threshold=cfg.rel_angle_thresh, ratio=cfg.ref_param.ratio,
+                    score_thresh=cfg.score_thresh, rel_dist_sparse_thresh=cfg.refine_param.rel_dist_sparse_thresh,
+                    num_result=int(cfg.num_result), refine_method=PPFEstimatorConfig.RefineMethod(int(cfg.refine_param.method)).name,
+                    object_id=int(cfg.object_id))
+
+    def get_model_diameter(self):
+        return self._diameter
+
+    def get_pose(self):
+        return list(self._poses)
+
+    getl_pose = get_pose          # (the reference's binding spells it so)
+
+    def get_sampled_model(self):
+        return self._model_sample
+
+    def get_sampled_scene(self):
+        return self._scene_sample
+
+    def _edges(self, which, what):
+        if not self._edge_mode:
+            _log_warning(f"Can not get {what} edge points due to edge support is not enabled.")
+        return which
+
+    def get_model_edges(self):
+        return self._edges(self._model_edges, "model")
+
+    def get_scene_edges(self):
+        return self._edges(self._scene_edges, "scene")
+
+
 class Pose6D:
     """misc3d.pose_estimation.Pose6D's fields (data_structure.h): pose (4, 4), q (w, x, y, z), t, num_votes, score, object_id"""
     __slots__ = ("pose", "q", "t", "num_votes", "score", "object_id")
@@ -698,12 +914,41 @@ class Pose6D:
 
 
 class _PoseEstimation:
-    """misc3d.pose_estimation (python/py_pose_estimation.cpp): RayCastRenderer.  PPFEstimator is not part of this build as a
-    class; its table and its voting in both modes (SampledPoints, EdgePoints), its pose clustering, refinement and scoring are
-    here, as PPFVoting, and its PreprocessEstimate as ppf_prepare_scene (PreprocessTrain is the caller's)."""
+    """misc3d.pose_estimation (python/py_pose_estimation.cpp): RayCastRenderer, PPFEstimator with PPFEstimatorConfig and Pose6D.
+    The estimator's stages are here on their own too: its table and its voting in both modes (SampledPoints, EdgePoints), its
+    pose clustering, refinement and scoring as PPFVoting, PreprocessEstimate as ppf_prepare_scene, PreprocessTrain as
+    ppf_prepare_model and its normal orientation as orient_normals.
+    One piece of the reference's PPFEstimator is not part of this build: Open3D's oriented bounding box of Qhull's convex hull.
+    The model's box is the PCA box of all points (rule B1 of include/misc3d_amd.h) unless the caller passes one."""
     RayCastRenderer = RayCastRenderer
     PPFVoting = PPFVoting
+    PPFEstimator = PPFEstimator
+    PPFEstimatorConfig = PPFEstimatorConfig
     Pose6D = Pose6D
+
+    @staticmethod
+    def orient_normals(points, normals, radius, seed, device=0):
+        """The normal orientation of PreprocessTrain (CalcModelNormalAndSampling, ppf_estimation.cpp:1083-1148) from an already
+        oriented seed: signs propagated along the minimum spanning tree of the radius graph (rules O1 - O5 of
+        include/misc3d_amd.h).  -> (normals (n, 3), parent (n,) int64: -1 the seed, -2 outside its component, stats dict)"""
+        from . import capi as _capi
+        try:
+            return _capi.orient_normals_mst(points, normals, radius, seed, device)
+        except _capi.M3DError as e:
+            raise RuntimeError(str(e)) from e
+
+    @staticmethod
+    def ppf_prepare_model(points, normals=None, *, box_center=None, box_extent=None, device=0, **params):
+        """PPFEstimator::PreprocessTrain (ppf_estimation.cpp:206-241, :1063-1160; rules B1 - B6): the box and what is derived from
+        it, normals estimated when None, oriented from the point nearest the view point, the distance-interval samples and the
+        dense sample's edge points.  params: rel_sample_dist, rel_dense_sample_dist (<= 0: no dense sample),
+        calc_normal_relative, invert_model_normal, use_external_normal, pts_num.  -> dict(normals, sample_indices, dense_indices,
+        edge_indices (into the dense sample), info)"""
+        from . import capi as _capi
+        try:
+            return _capi.ppf_prepare_model(points, normals, box_center=box_center, box_extent=box_extent, device=device, **params)
+        except _capi.M3DError as e:
+            raise RuntimeError(str(e)) from e
 
     @staticmethod
     def ppf_prepare_scene(points, normals, diameter, calc_normal_relative, dist_step, dist_step_dense=0.0, pts_num=30, device=0):

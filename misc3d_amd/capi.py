@@ -233,6 +233,11 @@ def lib():
         L.m3d_ppf_vote_edges.argtypes = ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                           C.c_size_t, C.c_size_t] + [C.c_void_p] * 7)
         L.m3d_ppf_prepare_scene.argtypes = ([C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_double] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 8)
+        L.m3d_orient_normals_mst.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_size_t, C.c_int] + [C.c_void_p] * 3
+        L.m3d_ppf_train_params_default_.restype = None
+        L.m3d_ppf_train_params_default_.argtypes = [C.c_void_p]
+        L.m3d_ppf_prepare_model.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
+        L.m3d_ppf_reference_indices.argtypes = [C.c_size_t, C.c_size_t, C.c_uint32, C.c_void_p]
         L.m3d_bench_ppf_force.argtypes = [C.c_int, C.c_int]
         L.m3d_ppf_default_cluster_params.restype = None
         L.m3d_ppf_default_cluster_params.argtypes = [C.c_void_p, C.c_void_p]
@@ -1852,6 +1857,94 @@ def ppf_prepare_scene(points, normals, diameter, calc_normal_relative, dist_step
                 dense_points=dp[:nd.value].copy() if dense else np.zeros((0, 3)),
                 dense_normals=dn[:nd.value].copy() if dense else np.zeros((0, 3)),
                 edge_indices=ei[:ne.value].astype(np.int64) if dense else np.zeros(0, np.int64))
+
+
+class OrientStats(C.Structure):
+    """m3d_orient_stats"""
+    _fields_ = [("rounds", C.c_uint64), ("tree_edges", C.c_uint64), ("component", C.c_uint64), ("flips", C.c_uint64),
+                ("ms_total", C.c_double), ("ms_grid", C.c_double), ("ms_rounds", C.c_double), ("ms_signs", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PpfTrainParams(C.Structure):
+    """m3d_ppf_train_params"""
+    _fields_ = [("rel_sample_dist", C.c_double), ("rel_dense_sample_dist", C.c_double), ("calc_normal_relative", C.c_double),
+                ("invert_model_normal", C.c_int32), ("use_external_normal", C.c_int32), ("pts_num", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PpfModelInfo(C.Structure):
+    """m3d_ppf_model_info"""
+    _fields_ = [("box_center", C.c_double * 3), ("box_extent", C.c_double * 3), ("diameter", C.c_double), ("r_min", C.c_double),
+                ("dist_step", C.c_double), ("dist_step_dense", C.c_double), ("normal_r", C.c_double), ("view_pt", C.c_double * 3),
+                ("seed", C.c_uint64), ("seed_flipped", C.c_int32), ("oriented", C.c_int32), ("orient", OrientStats),
+                ("sample_distance_evaluations", C.c_uint64), ("dense_distance_evaluations", C.c_uint64), ("ms_total", C.c_double),
+                ("ms_box", C.c_double), ("ms_normals", C.c_double), ("ms_sample", C.c_double), ("ms_dense", C.c_double),
+                ("ms_edges", C.c_double)]
+
+    def asdict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        for k in ("box_center", "box_extent", "view_pt"):
+            d[k] = np.array(d[k][:])
+        d["orient"] = self.orient.asdict()
+        return d
+
+
+def orient_normals_mst(points, normals, radius, seed, device=0):
+    """m3d_orient_normals_mst (rules O1 - O5) -> (oriented normals (n, 3), parent (n,) int64, the stats dict)"""
+    xyz, nrm = _f64(points).reshape(-1, 3), _f64(normals).reshape(-1, 3)
+    if len(nrm) != len(xyz):
+        raise ValueError("orient normals: one normal per point")
+    out, parent = np.zeros((max(len(xyz), 1), 3)), np.zeros(max(len(xyz), 1), np.int64)
+    st = OrientStats()
+    if int(seed) < 0:
+        raise ValueError("orient normals: the seed is an index")
+    _check(lib().m3d_orient_normals_mst(_p(xyz), _p(nrm), len(xyz), float(radius), int(seed), int(device), _p(out), _p(parent),
+                                        C.cast(C.byref(st), C.c_void_p)))
+    return out[:len(xyz)], parent[:len(xyz)], st.asdict()
+
+
+def ppf_train_params(**kw):
+    """m3d_ppf_train_params_default_ with the given fields changed"""
+    P = PpfTrainParams()
+    lib().m3d_ppf_train_params_default_(C.cast(C.byref(P), C.c_void_p))
+    for k, v in kw.items():
+        if k not in dict(PpfTrainParams._fields_) or k == "reserved":
+            raise TypeError("ppf train params: unknown field " + k)
+        setattr(P, k, v)
+    return P
+
+
+def ppf_prepare_model(points, normals=None, box_center=None, box_extent=None, device=0, **params):
+    """m3d_ppf_prepare_model (PreprocessTrain, rules B1 - B6): normals may be None (then estimated); params: the fields of
+    m3d_ppf_train_params.  -> dict(normals (n, 3), sample_indices, dense_indices, edge_indices (into the dense sample), info)"""
+    xyz = _f64(points).reshape(-1, 3)
+    nrm = None if normals is None else _f64(normals).reshape(-1, 3)
+    if nrm is not None and len(nrm) != len(xyz):
+        raise ValueError("ppf: one normal per point")
+    if (box_center is None) != (box_extent is None):
+        raise ValueError("ppf: box_center and box_extent come together")
+    bc = None if box_center is None else _f64(box_center).reshape(3)
+    be = None if box_extent is None else _f64(box_extent).reshape(3)
+    P = ppf_train_params(**params)
+    n = len(xyz)
+    out = np.zeros((max(n, 1), 3))
+    si, di, ei = (np.zeros(max(n, 1), np.uint64) for _ in range(3))
+    ns, nd, ne = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    info = PpfModelInfo()
+    ref = lambda x: C.cast(C.byref(x), C.c_void_p)
+    _check(lib().m3d_ppf_prepare_model(_p(xyz), _p(nrm), n, ref(P), _p(bc), _p(be), int(device), _p(out), _p(si), ref(ns), _p(di),
+                                       ref(nd), _p(ei), ref(ne), ref(info)))
+    return dict(normals=out[:n], sample_indices=si[:ns.value].astype(np.int64), dense_indices=di[:nd.value].astype(np.int64),
+                edge_indices=ei[:ne.value].astype(np.int64), info=info.asdict())
+
+
+def ppf_reference_indices(num, sample, seed):
+    """m3d_ppf_reference_indices: SampleWithoutDuplicate(sample) of RandomSampler(num) on std::mt19937(seed) -> (sample,) int64"""
+    out = np.zeros(max(int(sample), 1), np.uint64)
+    _check(lib().m3d_ppf_reference_indices(int(num), int(sample), int(seed) & 0xFFFFFFFF, _p(out)))
+    return out[:int(sample)].astype(np.int64)
 
 
 def ppf_cluster_force(splits=0):

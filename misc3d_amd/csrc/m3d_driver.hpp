@@ -223,6 +223,19 @@ int voxel_levels_on(DeviceCtx* ctx, const double* xyz, const double* normals, si
                     double* const* out_xyz, double* const* out_normals, size_t* m, double* level_ms,
                     const double* colors = nullptr, double* const* out_colors = nullptr /* the levels' colour means too */);
 int voxel_sizes_check(const double* voxel_sizes, size_t n_levels);
+// m3d_proximity.cpp: the radius grid of a walk over the radius graph (ProximityExtractor, the normal orientation), built on the
+// lane's stream: cell edge 1.001 radius, the points counting-sorted by cell into qx / qy / qz with their indices in cell_orig
+int radius_graph_grid(DeviceCtx* ctx, const m3d_cloud* c, double radius, CellSort& grid, DevBuf& qx, DevBuf& qy, DevBuf& qz,
+                      DevBuf& cell_orig, GridDesc* g_out);
+// m3d_estimate_normals (m3d_fpfh.cpp) and m3d_detect_boundary_points (m3d_registration.cpp) with their argument checks; held != null:
+// on that lane, which the caller holds (m3d_ppf_prepare_model), else the call takes a lane of `device` itself
+int estimate_normals_on(DeviceCtx* held, const double* xyz, size_t n, int search, double radius, int max_nn, int orient,
+                        const double camera[3], int device, double* normals_out, m3d_normals_stats* stats);
+int detect_boundary_points_on(DeviceCtx* held, const double* xyz, const double* normals, size_t n, int search, double radius, int max_nn,
+                              double angle_threshold_deg, int device, size_t* indices, size_t* k_out);
+// m3d_orient.cpp: m3d_orient_normals_mst on a lane the caller holds; arguments checked by the callers
+int orient_normals_mst_on(DeviceCtx* ctx, const double* xyz, const double* normals, size_t n, double radius, size_t seed,
+                          double* out_normals, int64_t* parent, m3d_orient_stats* stats);
 
 void dev_pool_trim(int device);
 int logical_device_count();           // what m3d_device_count returns: max(physical devices, m3d_config.device_aliases)

@@ -11,9 +11,9 @@
 
 namespace m3d {
 
-M3D_HD void j3x3_smallest_eigvec(const double* Ain, double* n) {
-    double A[9], V[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    for (int k = 0; k < 9; ++k) A[k] = Ain[k];
+// the sweeps: A (row-major, symmetric) is driven to its diagonal, V (the identity on entry) collects the rotations -- its
+// COLUMN k is the eigenvector of the eigenvalue A[3 k + k]
+M3D_HD void j3x3_jacobi(double* A, double* V) {
     for (int sweep = 0; sweep < 24; ++sweep) {
         if (A[1] == 0.0 && A[2] == 0.0 && A[5] == 0.0) break;
 #pragma unroll
@@ -43,6 +43,12 @@ M3D_HD void j3x3_smallest_eigvec(const double* Ain, double* n) {
             }
         }
     }
+}
+
+M3D_HD void j3x3_smallest_eigvec(const double* Ain, double* n) {
+    double A[9], V[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    for (int k = 0; k < 9; ++k) A[k] = Ain[k];
+    j3x3_jacobi(A, V);
     int m = 0;
     if (A[4] < A[3 * m + m]) m = 1;
     if (A[8] < A[3 * m + m]) m = 2;

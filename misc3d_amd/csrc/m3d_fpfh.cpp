@@ -9,6 +9,8 @@
 
 #include "../../include/misc3d_amd_bench.h"
 
+#include <optional>
+
 #pragma clang fp contract(off)
 
 using namespace m3d;
@@ -141,12 +143,14 @@ int redo_tie_rows(DeviceCtx* ctx, Work& W, const Job& J, const uint32_t* sidx, u
     return M3D_OK;
 }
 
-int run_job(const Job& J, int device, m3d_fpfh_stats* stats) {
+// held != null: on that lane, which the caller holds (m3d_ppf_prepare_model); else the call takes a lane of `device` itself
+int run_job(const Job& J, int device, m3d_fpfh_stats* stats, DeviceCtx* held = nullptr) {
     const double t0 = now_ms();
     m3d_fpfh_stats st{};
     const size_t n = J.n;
-    LaneLock lane(device);
-    DeviceCtx* ctx = lane.ctx;
+    std::optional<LaneLock> lane;
+    if (!held) lane.emplace(device);
+    DeviceCtx* ctx = held ? held : lane->ctx;
     if (!ctx) return M3D_ERR_DEVICE;
     Work W;
     std::vector<uint8_t> finite(n);
@@ -277,10 +281,8 @@ int check_cloud(const char* who, const double* xyz, size_t n) {
 
 }  // namespace
 
-extern "C" {
-
-int m3d_estimate_normals(const double* xyz, size_t n, int search, double radius, int max_nn, int orient,
-                         const double camera[3], int device, double* normals_out, m3d_normals_stats* stats) {
+int m3d::estimate_normals_on(DeviceCtx* held, const double* xyz, size_t n, int search, double radius, int max_nn, int orient,
+                             const double camera[3], int device, double* normals_out, m3d_normals_stats* stats) {
     if (stats) *stats = m3d_normals_stats{};
     const SearchArg a{search, radius, max_nn};
     if (const int r = check_search("estimate_normals", a); r != M3D_OK) return r;
@@ -296,7 +298,14 @@ int m3d_estimate_normals(const double* xyz, size_t n, int search, double radius,
     J.orient = orient ? 1 : 0;
     for (int k = 0; k < 3; ++k) J.cam[k] = orient ? camera[k] : 0.0;
     J.normals_out = normals_out;
-    return run_job(J, device, stats);
+    return run_job(J, device, stats, held);
+}
+
+extern "C" {
+
+int m3d_estimate_normals(const double* xyz, size_t n, int search, double radius, int max_nn, int orient,
+                         const double camera[3], int device, double* normals_out, m3d_normals_stats* stats) {
+    return estimate_normals_on(nullptr, xyz, n, search, radius, max_nn, orient, camera, device, normals_out, stats);
 }
 
 int m3d_compute_fpfh(const double* xyz, const double* normals, size_t n, int search, double radius, int max_nn, int device,

@@ -12,22 +12,12 @@
 
 using namespace m3d;
 
-namespace {
-
-struct ProxBufs {
-    CellSort grid;
-    DevBuf qx, qy, qz, cell_orig, snx, sny, snz, parent, size, root, off, idx, nb_d2;
-    void release() {
-        grid.release();
-        for (DevBuf* b : {&qx, &qy, &qz, &cell_orig, &snx, &sny, &snz, &parent, &size, &root, &off, &idx, &nb_d2}) b->release();
-    }
-};
-
 // The uniform grid of detect_boundary_points' Radius search (radius_grid_geom with K0 = 1, m3d_grid_geom.hpp): cell edge 1.001
 // radius, three pad cells per side, the edge doubled while the dense table would exceed 2^27 cells (a coarser cell still covers
 // the radius, its 3x3x3 block only holds more points).  Points counting-sorted by cell with their original indices
-// (B.cell_orig); B.grid.total[0] = the points the grid holds (those with three finite coordinates).
-int prox_grid(DeviceCtx* ctx, ProxBufs& B, const m3d_cloud* c, double radius, GridDesc* g_out) {
+// (cell_orig); grid.total[0] = the points the grid holds (those with three finite coordinates).
+int m3d::radius_graph_grid(DeviceCtx* ctx, const m3d_cloud* c, double radius, CellSort& grid, DevBuf& qx, DevBuf& qy, DevBuf& qz,
+                           DevBuf& cell_orig, GridDesc* g_out) {
     double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
     if (c->bb_known)
         for (int k = 0; k < 3; ++k) {
@@ -40,16 +30,31 @@ int prox_grid(DeviceCtx* ctx, ProxBufs& B, const m3d_cloud* c, double radius, Gr
     if (!std::isfinite(geom.h)) return fail(M3D_ERR_INVALID_ARG, "proximity: the cloud's extent does not allow a grid");
     const GridDesc g = radius_grid_desc(geom, radius * radius, 0.0);
     const size_t n = c->n;
-    if (!B.grid.reserve(n, g.nx * g.ny * g.nz)) return M3D_ERR_DEVICE;
-    RESERVE(B.qx, sizeof(double) * n);
-    RESERVE(B.qy, sizeof(double) * n);
-    RESERVE(B.qz, sizeof(double) * n);
-    RESERVE(B.cell_orig, sizeof(uint32_t) * n);
-    launch_grid_build(c->view(), g, B.grid, B.qx.as<double>(), B.qy.as<double>(), B.qz.as<double>(), ctx->stream,
-                      B.cell_orig.as<uint32_t>());
+    if (!grid.reserve(n, g.nx * g.ny * g.nz)) return M3D_ERR_DEVICE;
+    RESERVE(qx, sizeof(double) * n);
+    RESERVE(qy, sizeof(double) * n);
+    RESERVE(qz, sizeof(double) * n);
+    RESERVE(cell_orig, sizeof(uint32_t) * n);
+    launch_grid_build(c->view(), g, grid, qx.as<double>(), qy.as<double>(), qz.as<double>(), ctx->stream,
+                      cell_orig.as<uint32_t>());
     HIPCHK(hipGetLastError());
     *g_out = g;
     return M3D_OK;
+}
+
+namespace {
+
+struct ProxBufs {
+    CellSort grid;
+    DevBuf qx, qy, qz, cell_orig, snx, sny, snz, parent, size, root, off, idx, nb_d2;
+    void release() {
+        grid.release();
+        for (DevBuf* b : {&qx, &qy, &qz, &cell_orig, &snx, &sny, &snz, &parent, &size, &root, &off, &idx, &nb_d2}) b->release();
+    }
+};
+
+int prox_grid(DeviceCtx* ctx, ProxBufs& B, const m3d_cloud* c, double radius, GridDesc* g_out) {
+    return radius_graph_grid(ctx, c, radius, B.grid, B.qx, B.qy, B.qz, B.cell_orig, g_out);
 }
 
 // Components (root[i]: the smallest index of i's component, size[r]: the size of root r's) -> the reference's output:

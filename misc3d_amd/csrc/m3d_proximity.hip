@@ -3,10 +3,11 @@
 // extraction"), found with a lock-free union-find over original point indices.
 //
 // The union-find (uf_find, uf_unite), its parent[] invariant and its coherence argument are in m3d_union_find.hpp; the
-// flatten kernel runs after the union launch has ended and reads with plain loads.
+// flatten kernel runs after the union launch has ended and reads with plain loads.  The scan of a point's 3x3x3 block
+// (prox_scan_block) is m3d_prox_scan.hpp's.
 #include <hip/hip_runtime.h>
 
-#include "m3d_grid_cell.hpp"
+#include "m3d_prox_scan.hpp"
 #include "m3d_proximity.hpp"
 #include "m3d_union_find.hpp"
 
@@ -15,25 +16,6 @@
 namespace m3d {
 
 namespace {
-
-// visit(u, d2) for every grid slot u of the 3x3x3 block around sorted point t whose d2 is within the radius (t included)
-template <class F>
-__device__ __forceinline__ void prox_scan_block(const GridDesc& g, const uint32_t* __restrict__ cell_start,
-                                                const double* __restrict__ qx, const double* __restrict__ qy,
-                                                const double* __restrict__ qz, uint32_t t, F visit) {
-    const double px = qx[t], py = qy[t], pz = qz[t];
-    int ix, iy, iz;
-    if (!grid_cell(g, px, py, pz, 1, &ix, &iy, &iz)) return;
-    for (int dz = -1; dz <= 1; ++dz)
-        for (int dy = -1; dy <= 1; ++dy) {
-            uint32_t b, e;
-            grid_row_span(cell_start, grid_cell_id(g, ix, iy + dy, iz + dz), -1, 1, &b, &e);
-            for (uint32_t u = b; u < e; ++u) {
-                const double d2 = prox_d2(px - qx[u], py - qy[u], pz - qz[u]);
-                if (prox_in_radius(d2, g.r2)) visit(u, d2);
-            }
-        }
-}
 
 __global__ void prox_init_k(uint32_t* __restrict__ parent, uint32_t* __restrict__ size, uint32_t n) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;

@@ -1609,12 +1609,11 @@ int m3d::information_matrix_on(DeviceCtx* ctx, m3d_cloud* csrc, m3d_cloud* cdst,
     }
     return rc;
 }
-extern "C" {
-
 // misc3d::features::DetectBoundaryPoints, src/boundary_detection.cpp:68-113: the step the
 // reference's showcase example runs right after fit_plane (examples/python/ransac_and_boundary.py:35-36).
-int m3d_detect_boundary_points(const double* xyz, const double* normals, size_t n, int search, double radius,
-                               int max_nn, double angle_threshold_deg, int device, size_t* indices, size_t* k_out) {
+// held != null: on that lane, which the caller holds (m3d_ppf_prepare_model); else the call takes a lane of `device` itself
+int m3d::detect_boundary_points_on(DeviceCtx* held, const double* xyz, const double* normals, size_t n, int search, double radius,
+                                   int max_nn, double angle_threshold_deg, int device, size_t* indices, size_t* k_out) {
     if (!k_out || (!xyz && n) || (!indices && n)) return fail(M3D_ERR_INVALID_ARG, "invalid argument");
     *k_out = 0;
     if (n == 0) return fail(M3D_ERR_INVALID_ARG, "No PointCloud data.");   // :72-76 LogError
@@ -1622,8 +1621,9 @@ int m3d_detect_boundary_points(const double* xyz, const double* normals, size_t 
     if ((search != 0 && !(radius > 0.0)) || (search != 1 && (max_nn < 1 || max_nn > kBoundaryMaxNb)))
         return fail(M3D_ERR_INVALID_ARG, "invalid search parameter (radius > 0, 1 <= max_nn <= 128)");
     if (n >= ((size_t)1 << 31)) return fail(M3D_ERR_INVALID_ARG, "too many points");
-    LaneLock lane(device);
-    DeviceCtx* ctx = lane.ctx;
+    std::optional<LaneLock> lane;
+    if (!held) lane.emplace(device);
+    DeviceCtx* ctx = held ? held : lane->ctx;
     if (!ctx) return M3D_ERR_DEVICE;
     m3d_cloud* c = m3d_cloud_create_on(ctx, xyz, normals, n, 0);
     if (!c) return M3D_ERR_DEVICE;
@@ -1678,6 +1678,13 @@ int m3d_detect_boundary_points(const double* xyz, const double* normals, size_t 
     }
     m3d_cloud_destroy_on(c);
     return rc;
+}
+
+extern "C" {
+
+int m3d_detect_boundary_points(const double* xyz, const double* normals, size_t n, int search, double radius,
+                               int max_nn, double angle_threshold_deg, int device, size_t* indices, size_t* k_out) {
+    return detect_boundary_points_on(nullptr, xyz, normals, n, search, radius, max_nn, angle_threshold_deg, device, indices, k_out);
 }
 
 }  // extern "C"

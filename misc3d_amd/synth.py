@@ -141,3 +141,22 @@ def registration_pair_c4(n=200_000, seed=5, dim=33, true_fraction=0.3, sigma=0.0
     return dict(src=np.ascontiguousarray(src), dst=np.ascontiguousarray(dst),
                 feat_src=np.ascontiguousarray(feat_src), feat_dst=np.ascontiguousarray(feat_dst), T=T, perm=perm,
                 good=good)
+
+
+def box_surface_cloud(n=1_000_000, seed=8, size=(1.0, 0.7, 0.4), sigma=0.0005):
+    """A closed surface for the PPF model preprocessing (tools/bench_configs.py PT1): n points on the six faces of a box of
+    `size`, each face by its share of the area, sigma of noise along the face normal, off the origin and turned out of the
+    axes.  Returns (points, outward unit normals)."""
+    rng = np.random.default_rng(seed)
+    size = np.asarray(size, dtype=np.float64)
+    area = np.array([size[1] * size[2], size[0] * size[2], size[0] * size[1]])
+    face = rng.choice(6, size=n, p=np.repeat(area / (2.0 * area.sum()), 2))
+    pts = rng.uniform(-0.5, 0.5, size=(n, 3)) * size
+    nrm = np.zeros((n, 3))
+    ax, sg = face // 2, np.where(face % 2 == 1, 1.0, -1.0)
+    rows = np.arange(n)
+    pts[rows, ax] = sg * 0.5 * size[ax] + rng.normal(0, sigma, size=n)
+    nrm[rows, ax] = sg
+    T = rigid_transform(25.0, (1, 2, 3), (0.4, -0.3, 1.1))
+    R, t = T[:3, :3], T[:3, 3]
+    return np.ascontiguousarray(pts @ R.T + t), np.ascontiguousarray(nrm @ R.T)

@@ -18,6 +18,8 @@ bench.py); these lines feed DESIGN.md section 6 and check that the full sizes ru
   PV1 PPFVoting: the table of a 2 000-point model and the vote of a 20 000-point scene at ratio 0.6, LDS / device memory A/B
   PC1 PPF pose clustering on PV1's scene: the vote's raw poses through m3d_ppf_cluster_poses, and the whole m3d_ppf_estimate
   PV2 PPFVoting in EdgePoints mode at PV1's sizes: a plate with holes, its edge sets by detect_boundary_points; table, vote, estimate
+  PT1 PPF model preprocessing (PreprocessTrain) and PPFEstimator.train on a synthetic closed surface of 1 M and of 100 k points,
+      default config: the orientation's Boruvka rounds against the restatement's heap walk, the host samplers, boundary detection
 """
 import json
 import os
@@ -1150,3 +1152,72 @@ if "PV2" in which or ALL:
          roofline={"bound": "atomic increments (LDS or L2) and the divergent walk over table cells; no HBM or VALU ceiling is meaningful",
                    "share_of_peak": "not measured"},
          cpu_baseline=cpu_b)
+
+if "PT1" in which or ALL:
+    # pose_estimation.PPFEstimator.train ("PPF model preprocessing") on synth.box_surface_cloud at 1 M and at
+    # 100 k points with the default config, normals estimated; m3d_ppf_prepare_model is also run with the dense sample, so that
+    # the dense sampler and boundary detection are timed too (a closed box has no boundary: it finds no edge point).  One warm-up call, then the median of 3: the stages are m3d_ppf_model_info's own host clocks of that call.
+    # cpu_baseline = the restatement (tests/cpp/ppf_train_ref.c, gcc -O2, one thread) on the normals the library's orientation was
+    # given.  Its heap walk is timed APART from the brute-force neighbour lists it walks over (those are quadratic and no part of
+    # the comparison) and from the samplers.  At 100 k it is run whole.  At 1 M the lists cannot be built: the walk's figure there is
+    # SCALED from the 100 k run -- the walk is O(E log E) in the list entries E, and at a fixed radius E grows with n^2 (ten times
+    # the points, each with ten times the neighbours), so ms_walk x 100 x log2(100 E) / log2(E); the samplers are not scaled.
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import misc3d_amd as m3d
+    import ppf_train_ref_util as train_util
+
+    walk_100k = None
+    for n in (100_000, 1_000_000):
+        pts, _ = synth.box_surface_cloud(n)
+        runs = []
+        for rep in range(4):
+            t0 = time.perf_counter()
+            r = capi.ppf_prepare_model(pts, None)
+            runs.append(((time.perf_counter() - t0) * 1e3, r))
+        ms_prepare, r = sorted(runs[1:], key=lambda x: x[0])[1]
+        info, o = r["info"], r["info"]["orient"]
+        est = m3d.pose_estimation.PPFEstimator(m3d.pose_estimation.PPFEstimatorConfig())
+        train = []
+        for rep in range(3):
+            t0 = time.perf_counter()
+            ok = est.train(pts)
+            train.append((time.perf_counter() - t0) * 1e3)
+        cpu_b = None
+        if not NO_CPU and n <= 100_000:
+            ref = train_util.TrainRef(tempfile.mkdtemp())
+            nrm0 = capi.estimate_normals(pts, capi.SEARCH_HYBRID, info["normal_r"], 30)
+            nrm0 = nrm0 / np.sqrt((nrm0[:, 0] * nrm0[:, 0] + nrm0[:, 1] * nrm0[:, 1]) + nrm0[:, 2] * nrm0[:, 2])[:, None]   # B3 (no zero normal here)
+            if info["seed_flipped"]:
+                nrm0[info["seed"]] = -nrm0[info["seed"]]                                                                   # B4
+            on, _, ost, oms = ref.orient_timed(pts, nrm0, info["normal_r"], info["seed"])
+            t0 = time.perf_counter()
+            s_sparse = ref.sample(pts, info["dist_step"], info["seed"])
+            t1 = time.perf_counter()
+            ref.sample(pts, info["dist_step_dense"], info["seed"])
+            t2 = time.perf_counter()
+            walk_100k = (oms["ms_walk"], oms["list_entries"])
+            cpu_b = {"ms_heap_walk": oms["ms_walk"], "list_entries": oms["list_entries"], "ms_brute_force_lists_not_compared": oms["ms_lists"],
+                     "ms_sampler": (t1 - t0) * 1e3, "ms_dense_sampler": (t2 - t1) * 1e3, "unit": "ms",
+                     "same_normals": bool(on.tobytes() == r["normals"].tobytes()), "same_stats": bool(all(ost[k] == o[k] for k in ost)),
+                     "same_sample": bool(np.array_equal(s_sparse, r["sample_indices"])),
+                     "what": "tests/cpp/ppf_train_ref.c, gcc -O2 -ffp-contract=off, one thread; the walk timed apart from its brute-force lists"}
+        elif not NO_CPU and walk_100k:
+            ms_w, e = walk_100k
+            cpu_b = {"ms_heap_walk_scaled": ms_w * 100.0 * np.log2(100.0 * e) / np.log2(float(e)), "unit": "ms",
+                     "scaled_from": "the 100 k run: ms_heap_walk x 100 (list entries grow with n^2 at a fixed radius) x log2(100 E) / log2(E)",
+                     "ms_heap_walk_100k": ms_w, "list_entries_100k": e,
+                     "what": "tests/cpp/ppf_train_ref.c's heap walk, not run at this size (its brute-force lists are quadratic)"}
+        emit("PT1 ppf model preprocessing (with the dense sample) + PPFEstimator.train, synthetic box surface, default config", n=n,
+             diameter=info["diameter"], normal_r=info["normal_r"], ms_prepare_model=ms_prepare, ms_box=info["ms_box"],
+             ms_normals_and_orientation=info["ms_normals"],
+             orientation={"ms_total": o["ms_total"], "ms_upload_and_grid": o["ms_grid"], "ms_rounds": o["ms_rounds"], "rounds": o["rounds"],
+                          "ms_per_round": o["ms_rounds"] / max(o["rounds"], 1), "ms_tree_to_signs_host": o["ms_signs"],
+                          "tree_edges": o["tree_edges"], "component": o["component"], "flips": o["flips"]},
+             sampler={"ms": info["ms_sample"], "selected": len(r["sample_indices"]), "distance_evaluations": info["sample_distance_evaluations"]},
+             dense_sampler={"ms": info["ms_dense"], "selected": len(r["dense_indices"]), "distance_evaluations": info["dense_distance_evaluations"]},
+             boundary_detection={"ms": info["ms_edges"], "edges": len(r["edge_indices"])},
+             train={"ok": bool(ok), "ms_median_of_3": sorted(train)[1], "ms_all": train, "model_sample": len(est.get_sampled_model()[0])},
+             roofline={"bound": "the scan rounds re-read every 3x3x3 block once per round (latency- and L2-bound gathers of fp64 coordinates); not measured against a peak",
+                       "share_of_peak": "not measured"},
+             cpu_baseline=cpu_b)
