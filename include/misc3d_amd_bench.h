@@ -110,6 +110,15 @@ int m3d_bench_voxel_force_path(int path);
  * d2 >= d2_cut), out[1..4] = lo1, hi1, lo2, hi2 (the angle test accepts dot exactly on [lo1, hi1] u [lo2, hi2]). */
 int m3d_bench_proximity_cutoffs(double dist, double angle_deg, double out[5]);
 
+/* TEST hook (tests/test_grid_ladder.py, tests/test_gpu_grid_ladder.py): the rung of the cell-table ladder a radius grid lands on
+ * (radius_grid_geom, m3d_grid_geom.hpp) for the box [lo, hi], searches within `edge` (> 0) and K0 (1..16) cells per edge --
+ * K = the cells per edge that fitted, h = the cell edge, dims = the cells per axis, pads included.  The tests assert through it
+ * that each of their scenes sits on the rung it is meant for. */
+int m3d_bench_radius_grid_geom(const double lo[3], const double hi[3], double edge, int K0, int *K, double *h, uint64_t dims[3]);
+/* ... and the K0 the registration validation starts that ladder from for m3d_config.reg_cells_per_radius = k_cfg and a target
+ * of n_dst points (reg_grid_k0). */
+int m3d_bench_reg_grid_k0(int k_cfg, uint64_t n_dst);
+
 /* TEST hook (tests/test_fpfh.py): the FPFH pair features and the bin rule evaluated on the HOST by the very code the
  * kernels compile (m3d_fpfh_fp.hpp) -- pairs: m x 12 doubles (p1, n1, p2, n2), bins: m x 3 (columns of the 33-row),
  * features (may be NULL): m x 3 (f0, f1, f2). */

@@ -202,6 +202,8 @@ def lib():
         L.m3d_radius_neighbors.argtypes = [C.c_void_p, C.c_size_t, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_size_t, C.c_void_p]
         L.m3d_bench_proximity_cutoffs.argtypes = [C.c_double, C.c_double, C.c_void_p]
+        L.m3d_bench_radius_grid_geom.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.m3d_bench_reg_grid_k0.argtypes = [C.c_int, C.c_uint64]
         L.m3d_knn_create.restype = C.c_void_p
         L.m3d_knn_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
         L.m3d_knn_destroy.restype = None
@@ -2051,6 +2053,23 @@ def proximity_cutoffs(dist, angle_deg):
     out = np.zeros(5)
     _check(lib().m3d_bench_proximity_cutoffs(float(dist), float(angle_deg), _p(out)))
     return tuple(float(v) for v in out)
+
+
+def radius_grid_geom(lo, hi, edge, k0):
+    """test hook m3d_bench_radius_grid_geom -> (K, h, (nx, ny, nz)): the rung of the cell-table ladder for the box [lo, hi]"""
+    lo = _f64(lo).reshape(3)
+    hi = _f64(hi).reshape(3)
+    K = C.c_int(0)
+    h = C.c_double(0.0)
+    dims = np.zeros(3, dtype=np.uint64)
+    _check(lib().m3d_bench_radius_grid_geom(_p(lo), _p(hi), float(edge), int(k0), C.cast(C.byref(K), C.c_void_p),
+                                            C.cast(C.byref(h), C.c_void_p), _p(dims)))
+    return int(K.value), float(h.value), tuple(int(d) for d in dims)
+
+
+def reg_grid_k0(k_cfg, n_dst):
+    """test hook m3d_bench_reg_grid_k0: the K0 of the registration validation's grid for reg_cells_per_radius = k_cfg"""
+    return int(lib().m3d_bench_reg_grid_k0(int(k_cfg), int(n_dst)))
 
 
 def information_matrix(src, dst, max_correspondence_distance, T, device=0):

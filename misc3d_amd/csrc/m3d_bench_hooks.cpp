@@ -14,6 +14,18 @@ int m3d_bench_last_segment_ms(double out[6]) {
     return M3D_OK;
 }
 
+int m3d_bench_radius_grid_geom(const double lo[3], const double hi[3], double edge, int K0, int* K, double* h, uint64_t dims[3]) {
+    if (!lo || !hi || !K || !h || !dims || !(edge > 0.0) || K0 < 1 || K0 > 16)
+        return fail(M3D_ERR_INVALID_ARG, "invalid argument");
+    const RadiusGridGeom g = radius_grid_geom(lo, hi, edge, K0);
+    *K = g.K;
+    *h = g.h;
+    for (int k = 0; k < 3; ++k) dims[k] = g.dims[k];
+    return M3D_OK;
+}
+
+int m3d_bench_reg_grid_k0(int k_cfg, uint64_t n_dst) { return reg_grid_k0(k_cfg, n_dst); }
+
 int m3d_bench_cloud_setup_ms(const m3d_cloud* c, double out[5]) {
     if (!c || !out) return fail(M3D_ERR_INVALID_ARG, "null argument");
     for (int k = 0; k < 5; ++k) out[k] = c->setup_ms[k];

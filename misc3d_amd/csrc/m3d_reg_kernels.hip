@@ -366,8 +366,9 @@ __global__ void nl_fill_sorted_k(GridDesc g, const uint32_t* __restrict__ cell_s
     // the screen's copy (sorted_walk32): the three columns merged in ascending fp32 x (left column reversed, own, right --
     // a merge because the columns may overlap by a rounding at the cell faces), every entry 8 BYTES: x, y, z as 16-bit
     // fixed point over the block [-h, 2h) of the list's own cell -- q = rint(v S + 21845), S = 21845 / h, monotone in v:
-    // the order is kept -- and the 16-bit position of the fp64 entry in the list; pads at both ends that lie farther from
-    // every query of the cell than the search radius (corner of the block), position 0
+    // the order is kept -- and the 16-bit position of the fp64 entry in the list; pads at both ends on the corners of the block
+    // (1.73 h to 3.46 h from every query of the cell: beyond the search radius for K = 1 only -- sorted_walk32 hands a query
+    // whose pad wins to the fp64 walk when K > 1), position 0
     const uint32_t n_mid = n_col[0], n_lr = n_col[0] + n_col[1], n_tot = n_lr + n_col[2];
     if (n_tot > 65535u) {
         atomicOr(overflow, 1u);   // (the 16-bit offsets of nl_rec and of the entries: the caller drops the screen)
@@ -607,8 +608,9 @@ __device__ __forceinline__ double sorted_walk64(const GridDesc& g, uint32_t cell
 //     everything behind that entry is at least |dx| - eps, i.e. at least the true distance of entry i1.  For this CUT
 //     E(m1) is replaced by the square-root-free m1 (2^-9 + 2^-18) + 567 >= E(m1) (AM-GM): a cut 0.1 % later.  Where the
 //     walks start affects their length only: right covers [start, n), left [0, start), every entry is visited at most
-//     once; a pad that shares the last batch lies beyond the search radius and can only win when nothing real is within
-//     it (its position is 0: the result is then a real entry's distance, larger than the radius like the true minimum).
+//     once; a pad that shares the last batch lies, with K = 1, beyond the search radius and can only win when nothing real
+//     is within it (its position is 0: the result is then a real entry's distance, larger than the radius like the true
+//     minimum).  With K > 1 the radius reaches past the block's corners: a query whose pad wins takes the fp64 walk (below).
 __device__ __forceinline__ float walk_err_bound(float s) {   // E(s), units^2 (tests/cpp/test_nn_screen.cpp checks it)
     return __builtin_fmaf(s, 0x1p-18f, __builtin_fmaf(2.1f, __builtin_sqrtf(s), 2.0f));
 }
@@ -705,8 +707,14 @@ __device__ __forceinline__ double sorted_walk32(const GridDesc& g, uint32_t cell
 #endif
     const float bound = walk_err_bound(m1) + walk_err_bound(m2);   // E(m1) + E(m2)
     const bool decided = m2 == __builtin_inff() ? m1 < __builtin_inff() /* one candidate */ : m2 > m1 + bound * 1.0001f;
-    if (!decided) {
-        if (g.nl32_fallbacks) atomicAdd(g.nl32_fallbacks, 1ull);
+    // A pad that won (second word 0 or 0x0000FFFF; a real entry clamped onto a corner with position 0 looks the same and may take
+    // the fp64 walk as well): with K = 1 the block's corners lie beyond the search radius and entry 0's distance, beyond it too,
+    // serves.  With K > 1 they do not (1.73 h to 3.46 h from the query, the radius is K h / 1.001): real entries of the block
+    // farther away than the pad may still be within the radius, the cut above has skipped them, and nearest_phase2 does not
+    // come back to the 3x3x3 block -- the fp64 walk finds the block's minimum.  (Not counted as a fallback: no tie was seen.)
+    const bool pad_won = g.K > 1 && (w1 == 0u || w1 == 0x0000FFFFu);
+    if (!decided || pad_won) {
+        if (!decided && g.nl32_fallbacks) atomicAdd(g.nl32_fallbacks, 1ull);
         return sorted_walk64(g, cell, px, py, pz);
     }
     const double4* __restrict__ w = g.nl_pts + pos0 + i1;

@@ -5,7 +5,8 @@
 //      lo_pad and n - lo_pad with their neighbouring doubles on both sides.
 //   2. the padding contract of radius_grid_geom (m3d_grid_geom.hpp): every point of [lo, hi] has a cell with lo_pad = 0, every
 //      query of [lo - edge, hi + edge] has one with lo_pad = K, and the x-rows row + (-K .. K + 1) of all (2K + 1)^2 rows of
-//      its block stay inside [0, ncell].  The lower margin is K + 1 - K / 1.001 cells, the upper just under one cell: far above
+//      its block stay inside [0, ncell], and the block covers the edge (a point one edge from the query along any diagonal
+//      lies within K cells of it) -- for K kept, halved from a power of two and from 3, 5, 6, 7 and 12.  The lower margin is K + 1 - K / 1.001 cells, the upper just under one cell: far above
 //      any rounding, so the check is exact.
 //   3. grid_cell_id and grid_row_span on triples worked out by hand.
 #include <cmath>
@@ -154,6 +155,13 @@ int main() {
         {{0, 0, 0}, {1000, 1000, 1000}, 0.5, 4, 1},        // K halved twice, the cell doubled four times
         {{-1, -1, -1}, {-1, -1, -1}, 0.25, 1, 1},          // a single point
         {{0, 0, 0}, {100, 100, 100}, 0.5, 4, 2},           // K halved once: 410^3 cells
+        // K0 no power of two (the registration's rule gives any of 1..16), after a forced halving
+        {{0, 0, 0}, {100, 100, 100}, 0.5, 3, 1},           // 3 -> 1
+        {{0, 0, 0}, {100, 100, 100}, 0.5, 5, 2},           // 5 -> 2
+        {{0, 0, 0}, {80, 80, 80}, 0.5, 6, 3},              // 6 -> 3
+        {{0, 0, 0}, {80, 80, 80}, 0.5, 7, 3},              // 7 -> 3
+        {{0, 0, 0}, {80, 80, 80}, 0.5, 12, 3},             // 12 -> 6 -> 3
+        {{0, 0, 0}, {100, 100, 100}, 0.5, 12, 1},          // 12 -> 6 -> 3 -> 1
     };
     for (const Row& r : rows) {
         const RadiusGridGeom geom = radius_grid_geom(r.lo, r.hi, r.edge, r.K0);
@@ -188,6 +196,11 @@ int main() {
             int ix, iy, iz;
             CHECK(grid_cell(g, p[0], p[1], p[2], 0, &ix, &iy, &iz));
             query_fits(g, q);
+            // ... and the block covers the edge: a query one edge from p along any diagonal has p's cell within K cells of its own
+            int jx, jy, jz;
+            for (int k = 0; k < 3; ++k) q[k] = p[k] + (((i >> k) & 1) ? r.edge : -r.edge);
+            CHECK(grid_cell(g, q[0], q[1], q[2], g.K, &jx, &jy, &jz));
+            CHECK(std::abs(jx - ix) <= g.K && std::abs(jy - iy) <= g.K && std::abs(jz - iz) <= g.K);
         }
     }
     {   // a Hilbert sort's descriptor (hilbert_sort_desc): 2^bits cells per axis from the box's corner, no pads

@@ -1,7 +1,8 @@
 // Host-side pin of the grid arithmetic every cell-sorted grid is built from (misc3d_amd/csrc/m3d_grid_geom.hpp): no GPU, no
 // library.  radius_grid_geom (registration's target grid, boundary detection, ProximityExtractor) against rows worked out by
 // hand from its definition -- K, h, the dimensions and the origin compared with ==: results downstream are bit-exact only
-// while the order of the operations stays -- an extent no finite cell holds (it must return, not spin), and sort_grid_bits /
+// while the order of the operations stays -- an extent no finite cell holds (it must return, not spin), the ladder's invariant
+// (the table fits, K h >= 1.0009 edge, K <= K0) for every K0 of 1..16 over cubic, flat and rod-shaped boxes, and sort_grid_bits /
 // sort_grid_inv_h of the Hilbert sorts at their steps.
 #include <cmath>
 #include <cstdint>
@@ -71,10 +72,97 @@ int main() {
         for (int k = 0; k < 3; ++k) CHECK(g.dims[k] == 19);
     }
 
+    {   // the ladder's invariant at every rung, for every K0 the registration's rule can produce (1..16, not only the powers of
+        // two): the table fits, K cells cover the edge (a (2K + 1)^3 block holds everything within `edge` of its centre cell),
+        // and K never grows.  Cubic, flat (one extent 0) and rod-shaped (two extents 0) boxes, extent / edge from 1 to 1e12 in
+        // steps of 10^(1/16).  For K0 a power of two the rungs are, bit for bit, those of the ladder that doubled h at every
+        // step (restated below): a multiplication by two against a division by a power of two.
+        auto doubling_ladder = [](const double lo[3], const double hi[3], double edge, int K0, int* K_out) {
+            int K = K0;
+            double h = edge * 1.001 / K;
+            for (;;) {
+                bool fits = true;
+                uint64_t cells = 1;
+                for (int k = 0; k < 3; ++k) {
+                    const double ext = (hi[k] - lo[k]) / h;
+                    if (!(ext < 1e9)) {
+                        fits = false;
+                        break;
+                    }
+                    cells *= (uint64_t)ext + 1 + 2 * (uint64_t)(2 * K + 1);
+                    if (cells > ((uint64_t)1 << 27)) fits = false;
+                }
+                if (fits) break;
+                if (K > 1) K /= 2;
+                h *= 2.0;
+            }
+            *K_out = K;
+            return h;
+        };
+        const double edges[] = {0.5, 0.02, 1e-3, 7.0, 0.3};
+        const double corner[3] = {-3.25, 1e3, 0.1};
+        int rungs_seen[17][8] = {};   // [K0][K]: how often the sweep ended with K cells per edge (K <= 7) ...
+        int doubled_seen[17] = {};    // ... and with a doubled cell
+        uint64_t n_rows = 0;
+        for (int K0 = 1; K0 <= 16; ++K0)
+            for (double edge : edges)
+                for (int shape = 0; shape < 3; ++shape)
+                    for (int step = 0; step <= 12 * 16; ++step) {
+                        const double ext = edge * std::pow(10.0, step / 16.0);
+                        double lo[3], hi[3];
+                        for (int k = 0; k < 3; ++k) {
+                            lo[k] = corner[k];
+                            hi[k] = corner[k] + (k < 3 - shape ? ext : 0.0);
+                        }
+                        const RadiusGridGeom g = radius_grid_geom(lo, hi, edge, K0);
+                        ++n_rows;
+                        const bool ok = std::isfinite(g.h) && g.K >= 1 && g.K <= K0 && g.K * g.h >= 1.0009 * edge &&
+                                        g.dims[0] * g.dims[1] * g.dims[2] <= ((uint64_t)1 << 27) && g.dims[0] < (1u << 30) &&
+                                        g.dims[1] < (1u << 30) && g.dims[2] < (1u << 30);
+                        if (!ok)
+                            printf("K0 %d edge %g shape %d extent/edge %g: K %d h/edge %.6g dims %llu %llu %llu\n", K0, edge, shape,
+                                   ext / edge, g.K, g.h / edge, (unsigned long long)g.dims[0], (unsigned long long)g.dims[1],
+                                   (unsigned long long)g.dims[2]);
+                        CHECK(ok);
+                        for (int k = 0; k < 3; ++k) {
+                            CHECK(g.dims[k] == (uint64_t)((hi[k] - lo[k]) / g.h) + 1 + 2 * (uint64_t)(2 * g.K + 1));
+                            CHECK(g.origin[k] == lo[k] - (2 * g.K + 1) * g.h);
+                        }
+                        if (g.K < 8) ++rungs_seen[K0][g.K];
+                        if (g.K == 1 && g.h > 1.5 * edge) ++doubled_seen[K0];
+                        if ((K0 & (K0 - 1)) == 0) {
+                            int Kd = 0;
+                            const double hd = doubling_ladder(lo, hi, edge, K0, &Kd);
+                            CHECK(g.K == Kd && g.h == hd);
+                        }
+                    }
+        printf("ladder sweep: %llu boxes\n", (unsigned long long)n_rows);
+        for (int K0 = 1; K0 <= 16; ++K0) {   // the sweep reaches every rung: K0, each halving down to 1, a doubled cell
+            CHECK(doubled_seen[K0] > 0);
+            for (int K = K0; K >= 1; K /= 2)
+                if (K < 8) CHECK(rungs_seen[K0][K] > 0);
+        }
+        // the rows the defect showed on: one failed fit from K0 = 3, 5, 6, 7, 12
+        // (524^3 cells at K = 3 do not fit; 6, 7 and 12 pass through K = 3 on their way down, and stay there for extent 160)
+        const struct {
+            double ext;
+            int K0, K;
+            uint64_t dim;
+        } halved[] = {{170, 3, 1, 176}, {170, 5, 2, 350}, {170, 6, 1, 176}, {170, 7, 1, 176}, {170, 12, 1, 176},
+                      {160, 6, 3, 494}, {160, 7, 3, 494}, {160, 12, 3, 494}};
+        for (const auto& r : halved) {
+            const double lo[3] = {0, 0, 0}, hi[3] = {r.ext, r.ext, r.ext};
+            const RadiusGridGeom g = radius_grid_geom(lo, hi, 1.0, r.K0);
+            printf("K0 %d extent %g: K %d h %.17g dims %llu\n", r.K0, r.ext, g.K, g.h, (unsigned long long)g.dims[0]);
+            CHECK(g.K == r.K && g.h == 1.0 * 1.001 / r.K);
+            for (int k = 0; k < 3; ++k) CHECK(g.dims[k] == r.dim);
+        }
+    }
+
     const struct {
         uint64_t n;
         uint32_t bits;
-    } steps[] = {{1, 1},    {64, 1},   {65, 2},      {512, 2},           {513, 3},
+    } steps[] ={{1, 1},    {64, 1},   {65, 2},      {512, 2},           {513, 3},
                  {4096, 3}, {4097, 4}, {1000000, 6}, {((uint64_t)1 << 27) + 1, 8}, {((uint64_t)1 << 31) - 1, 8}};
     for (const auto& s : steps) {
         printf("sort_grid_bits(%llu) = %u\n", (unsigned long long)s.n, sort_grid_bits(s.n));
