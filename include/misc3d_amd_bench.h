@@ -124,6 +124,18 @@ int m3d_bench_reg_grid_k0(int k_cfg, uint64_t n_dst);
  * features (may be NULL): m x 3 (f0, f1, f2). */
 int m3d_bench_fpfh_pair_bins(const double *pairs, size_t m, int32_t *bins, double *features);
 
+/* TEST hook (tests/test_gpu_fpfh_stages.py): m3d_compute_fpfh's own job -- the same kernels in the same order on one grid, the
+ * normals given -- with its stages taken out after the call's last synchronisation, all by POINT index (not query order); every
+ * output may be NULL.  list_idx (n x max_nn), list_d2 (n x max_nn), cnt (n): the neighbour lists and the Hybrid counts as
+ * fpfh_spfh_k and fpfh_fpfh_k read them, that is entries [0, cnt); an entry at or past cnt is 0xFFFFFFFF / +inf, a non-finite
+ * point has cnt 0.  spfh_count (n x 33), spfh_incr (n): the SpfhRows as fpfh_fpfh_k reads them (after the host-decided rows
+ * were scattered); zeros for a non-finite point, whose row the device never writes.  tie_points (capacity n), *n_ties: the
+ * points fpfh_spfh_k listed for the host, ascending.  feature_out (n x 33): the call's result.  Arguments are checked as
+ * m3d_compute_fpfh checks them. */
+int m3d_bench_fpfh_stages(const double *xyz, const double *normals, size_t n, int search, double radius, int max_nn, int device,
+                          uint32_t *list_idx, double *list_d2, uint32_t *cnt, uint8_t *spfh_count, double *spfh_incr,
+                          uint32_t *tie_points, uint64_t *n_ties, double *feature_out, m3d_fpfh_stats *stats);
+
 /* TEST hook (tests/test_gpu_match_sliced.py): which way the CALLING THREAD's last m3d_match_mutual_nn went -- bit 0: the split-fp16
  * MFMA screen produced the result, bit 1: the matrices went up in slices under the scan (m3d_config.match_pipeline), bit 2: a
  * later slice did not fit the scale chosen from the first ones and the search was redone whole on the resident matrices,

@@ -259,6 +259,8 @@ def lib():
         L.m3d_preprocess_fragment.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_void_p]
         L.m3d_bench_fpfh_pair_bins.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.m3d_bench_fpfh_stages.argtypes = ([C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_int, C.c_int] +
+                                            [C.c_void_p] * 9)
         L.m3d_match_last_fallbacks.restype = C.c_uint64
         L.m3d_match_last_fallbacks.argtypes = []
         L.m3d_match_mutual_nn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
@@ -2046,6 +2048,29 @@ def fpfh_pair_bins(pairs, features=False):
     f = np.zeros((len(pairs), 3)) if features else None
     _check(lib().m3d_bench_fpfh_pair_bins(_p(pairs), len(pairs), _p(bins), _p(f)))
     return (bins, f) if features else bins
+
+
+def fpfh_stages(xyz, normals, search=SEARCH_HYBRID, radius=0.1, max_nn=100, device=0):
+    """test hook m3d_bench_fpfh_stages -> dict, everything by point index: list_idx uint32 (N, max_nn), list_d2 (N, max_nn), cnt
+    uint32 (N,), spfh_count uint8 (N, 33), spfh_incr (N,), tie_points uint32 (n_ties,) ascending, feature (N, 33), stats"""
+    xyz = _f64(xyz).reshape(-1, 3)
+    nrm = _f64(normals).reshape(-1, 3)
+    if len(nrm) != len(xyz):
+        raise ValueError("normals and points differ in length")
+    n, k = len(xyz), max(int(max_nn), 0)
+    o = dict(list_idx=np.zeros((n, k), np.uint32), list_d2=np.zeros((n, k)), cnt=np.zeros(n, np.uint32),
+             spfh_count=np.zeros((n, 33), np.uint8), spfh_incr=np.zeros(n), tie_points=np.zeros(n, np.uint32),
+             feature=np.zeros((n, 33)))
+    nt = C.c_uint64(0)
+    st = FpfhStats()
+    _check(lib().m3d_bench_fpfh_stages(_p(xyz), _p(nrm), n, int(search), float(radius), int(max_nn), device, _p(o["list_idx"]),
+                                       _p(o["list_d2"]), _p(o["cnt"]), _p(o["spfh_count"]), _p(o["spfh_incr"]),
+                                       _p(o["tie_points"]), C.cast(C.byref(nt), C.c_void_p), _p(o["feature"]),
+                                       C.cast(C.byref(st), C.c_void_p)))
+    o["tie_points"] = o["tie_points"][:nt.value].copy()
+    o["n_ties"] = int(nt.value)
+    o["stats"] = st.asdict()
+    return o
 
 
 def proximity_cutoffs(dist, angle_deg):

@@ -53,6 +53,17 @@ struct Work {
     }
 };
 
+// what m3d_bench_fpfh_stages takes out of a call, by POINT index; every pointer may be null
+struct Capture {
+    uint32_t* list_idx;     // n x max_nn; entries at and past cnt: 0xFFFFFFFF
+    double* list_d2;        // n x max_nn; entries at and past cnt: +inf
+    uint32_t* cnt;          // n
+    uint8_t* spfh_count;    // n x 33
+    double* spfh_incr;      // n
+    uint32_t* tie_points;   // capacity n, ascending
+    uint64_t* n_ties;
+};
+
 struct Job {
     const double* xyz;
     const double* normals_in;   // may be null
@@ -65,6 +76,7 @@ struct Job {
     SearchArg sf;
     double* normals_out;        // may be null
     double* feature_out;        // may be null
+    const Capture* cap = nullptr;   // test hook only: filled after the synchronisation that ends the call
 };
 
 float ev_ms(hipEvent_t a, hipEvent_t b) {
@@ -143,6 +155,52 @@ int redo_tie_rows(DeviceCtx* ctx, Work& W, const Job& J, const uint32_t* sidx, u
     return M3D_OK;
 }
 
+// The stages of an FPFH call as the kernels read them, downloaded after the call's last synchronisation and put in point
+// order (query t is point sidx[t]).  Only what this call wrote reaches the outputs: list entries below cnt, the SPFH rows of
+// finite points (fpfh_spfh_k writes no other; the rest of the downloaded array is not looked at), tie_list below n_ties.
+int capture_stages(DeviceCtx* ctx, Work& W, const Job& J, const uint32_t* sidx_dev, uint32_t nq, int kk, uint32_t n_ties) {
+    const Capture& c = *J.cap;
+    const size_t n = J.n, K = (size_t)J.sf.max_nn;
+    if (c.list_idx) std::fill(c.list_idx, c.list_idx + n * K, 0xFFFFFFFFu);
+    if (c.list_d2) std::fill(c.list_d2, c.list_d2 + n * K, (double)INFINITY);
+    if (c.cnt) std::fill(c.cnt, c.cnt + n, 0u);
+    if (c.spfh_count) std::fill(c.spfh_count, c.spfh_count + n * kFpfhDim, (uint8_t)0);
+    if (c.spfh_incr) std::fill(c.spfh_incr, c.spfh_incr + n, 0.0);
+    if (c.n_ties) *c.n_ties = n_ties;
+    if (!nq) return M3D_OK;
+    hipStream_t s = ctx->stream;
+    std::vector<uint32_t> sidx(nq), idx((size_t)nq * kk), cnt(nq), ties(n_ties);
+    std::vector<double> d2((size_t)nq * kk);
+    std::vector<SpfhRow> rows(n);
+    HIPCHK(hipMemcpyAsync(sidx.data(), sidx_dev, sizeof(uint32_t) * nq, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(idx.data(), W.l_idx.p, sizeof(uint32_t) * idx.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(d2.data(), W.l_d2.p, sizeof(double) * d2.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(cnt.data(), W.cnt.p, sizeof(uint32_t) * nq, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(rows.data(), W.spfh.p, sizeof(SpfhRow) * n, hipMemcpyDeviceToHost, s));
+    if (n_ties) HIPCHK(hipMemcpyAsync(ties.data(), W.tie_list.p, sizeof(uint32_t) * n_ties, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (uint32_t t = 0; t < nq; ++t) {
+        const size_t i = sidx[t];
+        const uint32_t m = cnt[t];
+        if (i >= n || m > (uint32_t)kk) return fail(M3D_ERR_INTERNAL, "fpfh stages: a query is out of range (self-check)");
+        if (c.cnt) c.cnt[i] = m;
+        for (uint32_t k = 0; k < m; ++k) {
+            if (c.list_idx) c.list_idx[i * K + k] = idx[(size_t)t * kk + k];
+            if (c.list_d2) c.list_d2[i * K + k] = d2[(size_t)t * kk + k];
+        }
+        if (c.spfh_count) std::memcpy(c.spfh_count + i * kFpfhDim, rows[i].count, kFpfhDim);
+        if (c.spfh_incr) c.spfh_incr[i] = rows[i].incr;
+    }
+    if (c.tie_points) {
+        for (uint32_t e = 0; e < n_ties; ++e) {
+            if (ties[e] >= nq) return fail(M3D_ERR_INTERNAL, "fpfh stages: a tie entry is out of range (self-check)");
+            c.tie_points[e] = sidx[ties[e]];
+        }
+        std::sort(c.tie_points, c.tie_points + n_ties);
+    }
+    return M3D_OK;
+}
+
 // held != null: on that lane, which the caller holds (m3d_ppf_prepare_model); else the call takes a lane of `device` itself
 int run_job(const Job& J, int device, m3d_fpfh_stats* stats, DeviceCtx* held = nullptr) {
     const double t0 = now_ms();
@@ -194,6 +252,7 @@ int run_job(const Job& J, int device, m3d_fpfh_stats* stats, DeviceCtx* held = n
             st.launches += 1;
         }
         int kk = 0;
+        uint32_t n_ties = 0;
         // ---- normals
         HIPCHK(hipEventRecord(W.ev[1], s));
         if (J.want_normals && nq)
@@ -228,7 +287,6 @@ int run_job(const Job& J, int device, m3d_fpfh_stats* stats, DeviceCtx* held = n
                              kk, W.spfh.as<SpfhRow>(), W.tie_list.as<uint32_t>(), tie_count, s);
             st.launches += 1;
             HIPCHK(hipGetLastError());
-            uint32_t n_ties = 0;
             HIPCHK(hipMemcpyAsync(&n_ties, tie_count, sizeof(n_ties), hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
             if (n_ties > nq) return fail(M3D_ERR_INTERNAL, "fpfh: the tie list overflowed (self-check)");
@@ -255,6 +313,7 @@ int run_job(const Job& J, int device, m3d_fpfh_stats* stats, DeviceCtx* held = n
         st.ms_spfh = ev_ms(W.ev[5], W.ev[6]);
         st.ms_fpfh = ev_ms(W.ev[6], W.ev[7]);
         st.ms_device = ev_ms(W.ev[0], W.ev[7]);
+        if (J.cap) return capture_stages(ctx, W, J, v.sidx, nq, kk, n_ties);
         return M3D_OK;
     }();
     (void)hipStreamSynchronize(ctx->stream);
@@ -364,6 +423,31 @@ int m3d_bench_fpfh_pair_bins(const double* pairs, size_t m, int32_t* bins, doubl
         }
     }
     return M3D_OK;
+}
+
+// test hook (include/misc3d_amd_bench.h): m3d_compute_fpfh's own job with the stages taken out of it
+int m3d_bench_fpfh_stages(const double* xyz, const double* normals, size_t n, int search, double radius, int max_nn, int device,
+                          uint32_t* list_idx, double* list_d2, uint32_t* cnt, uint8_t* spfh_count, double* spfh_incr,
+                          uint32_t* tie_points, uint64_t* n_ties, double* feature_out, m3d_fpfh_stats* stats) {
+    if (stats) *stats = m3d_fpfh_stats{};
+    if (n_ties) *n_ties = 0;
+    const SearchArg a{search, radius, max_nn};
+    if (const int r = check_search("fpfh_stages", a); r != M3D_OK) return r;
+    if (n == 0) return M3D_OK;
+    if (!normals) return fail(M3D_ERR_INVALID_ARG, "Failed because input point cloud has no normal.");
+    if (const int r = check_cloud("fpfh_stages", xyz, n); r != M3D_OK) return r;
+    std::vector<double> own;
+    if (!feature_out) own.resize(n * (size_t)kFpfhDim);
+    const Capture cap{list_idx, list_d2, cnt, spfh_count, spfh_incr, tie_points, n_ties};
+    Job J{};
+    J.xyz = xyz;
+    J.normals_in = normals;
+    J.n = n;
+    J.want_fpfh = true;
+    J.sf = a;
+    J.feature_out = feature_out ? feature_out : own.data();
+    J.cap = &cap;
+    return run_job(J, device, stats);
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import fpfh_ref_util as U
+import fpfh_stage_util as S
 
 
 @pytest.fixture(scope="module")
@@ -178,3 +179,45 @@ def test_host_evaluator_matches_restatement_bins(capi, ref):
         assert np.array_equal(gf, wf)
     assert (got[:, 0] >= 0).all() and (got[:, 0] <= 10).all() and (got[:, 1] >= 11).all() and (got[:, 2] <= 32).all()
     assert (got[1000:1100] == [5, 16, 27]).all()
+
+
+# ---- the stage references (tests/fpfh_stage_util.py) held to the restatement -------------------------------------------------
+def _sketch_inputs():
+    pts, nrm = U.three_surface_cloud(4000, seed=5)
+    return [S._case(f"sketch_{s}_{r}_{k}", pts, nrm, s, r, k)
+            for s, r, k in ((U.HYBRID, 0.2, 100), (U.HYBRID, 0.1, 30), (U.KNN, 0.0, 30), (U.KNN, 0.0, 128))]
+
+
+def test_stage_references_match_restatement(ref):
+    for c in _sketch_inputs() + list(S.seam_cases().values()):
+        pts, nrm, a = c["pts"], c["nrm"], (c["search"], c["radius"], c["k"])
+        want, sp = ref.fpfh(pts, nrm, *a, spfh=True)
+        lists = ref.neighbours(pts, *a)
+        counts, m = S.ref_counts(ref, pts, nrm, *a, lists=lists)
+        incr = S.incr_of(m)
+        assert np.allclose(counts * incr[:, None], sp, rtol=0, atol=1e-9), c["name"]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            back = np.where(incr[:, None] != 0, np.rint(sp / incr[:, None]), 0.0)
+        assert np.array_equal(back, counts), c["name"]
+        assert (counts.sum(1) == 3 * np.maximum(m - 1, 0)).all() and counts.max(initial=0) <= 127, c["name"]
+        got = S.assemble(lists[0], lists[1], m, counts, incr)
+        assert len(U.differing_points(got, want)) == 0, (c["name"], np.abs(got - want).max())
+
+
+def test_stage_inputs_have_no_undecided_pair(ref):
+    """every input of tests/test_gpu_fpfh_stages.py: no pair within 1e-9 of a bin edge (so the device's counts must equal the
+    restatement's on every point), and the points inside the 32 / 64 / 128 eps tie bands, pinned"""
+    cases = {**S.seam_cases(), **S.big_cases(), **S.tie_cases(ref)}
+    ties = {}
+    for name, c in cases.items():
+        r = S.reference(ref, c)
+        n_und = len(np.unique(r["own"][r["undecided"]]))
+        t = tuple(int(b.sum()) for b in r["bands"])
+        print(f"{name}: n={len(c['pts'])} pairs={len(r['own'])} undecided pairs={int(r['undecided'].sum())} points={n_und} "
+              f"tie points (32, 64, 128 eps)={t}")
+        assert n_und == 0, name
+        assert (r["bands"][0] <= r["bands"][1]).all() and (r["bands"][1] <= r["bands"][2]).all()
+        if any(t):
+            ties[name] = t
+    assert ties == S.TIE_COUNTS
+    assert ties["tie6000"][0] > 64 and ties["tie1500"][0] > 0       # more than one block of fpfh_tie_scatter_k; a strided gather

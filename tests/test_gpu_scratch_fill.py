@@ -323,6 +323,17 @@ def _(capi, big=False):
     return lambda: [capi.preprocess_fragment(p, 0.05, stats=True), capi.preprocess_fragment(p, 0.05, normals=q, stats=True)]
 
 
+@case("fpfh_stages")
+def _(capi, big=False):
+    # the stage hook of tests/test_gpu_fpfh_stages.py: non-finite points, whose SPFH rows the device never writes, and lists
+    # with unused tails (max_nn above the Hybrid count, and above the 65 points of the small cloud)
+    import fpfh_stage_util as su
+    (p, q), (tp, tq) = _fpfh_clouds()
+    p, q, _ = su.with_nonfinite(p, q)
+    tp, tq, _ = su.with_nonfinite(tp, tq)
+    return lambda: [capi.fpfh_stages(p, q, capi.SEARCH_HYBRID, 0.25, 100), capi.fpfh_stages(tp, tq, capi.SEARCH_KNN, 0.0, 128)]
+
+
 def _voxel_inputs():
     import voxel_ref_util as vu
     pts, cell = vu.voxel_seam_cloud(257, 4096, vu.SEAM_HEAD)
