@@ -34,6 +34,11 @@ int m3d_bench_fp64_issue_rate(int device, double ms_target, double *tera_lane_op
  * Hilbert counting sort, out[4] = tile boxes + the tiles' fp32 offsets ("report upload separately"). */
 int m3d_bench_cloud_setup_ms(const m3d_cloud *cloud, double out[5]);
 
+/* 1 when [p, p + bytes) lies inside a live block of m3d_host_alloc (the registry the fits consult before the device writes, or
+ * the host expands a mask, straight into a caller's array), else 0.  What tests/test_gpu_host_blocks.py holds the two kinds of
+ * block to: reported inside their bounds, not past them, not after m3d_host_free. */
+int m3d_bench_host_block(const void *p, size_t bytes);
+
 /* plane_bound_k (m3d_bound.hip) on its own: ub_out[h] = the histogram upper bound of hypothesis h's inlier count, for EVERY
  * hypothesis of the sample table (n_hypotheses x 3 indices, at most 16 384; nothing is pruned).  What
  * tests/test_gpu_plane_bound.py holds against the exact counts of m3d_cloud_score_range: ub >= count, hypothesis by hypothesis.

@@ -8,6 +8,8 @@ using namespace m3d;
 
 extern "C" {
 
+int m3d_bench_host_block(const void* p, size_t bytes) { return p && is_library_pinned(p, bytes) ? 1 : 0; }
+
 int m3d_bench_last_segment_ms(double out[6]) {
     if (!out) return fail(M3D_ERR_INVALID_ARG, "null argument");
     for (int k = 0; k < 6; ++k) out[k] = g_seg_ms[k];

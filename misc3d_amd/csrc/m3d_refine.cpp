@@ -3,150 +3,14 @@
 // into the caller's page-locked buffer), GeneralFit from the fused moments, the serial-order sum on demand.
 #include "m3d_driver_internal.hpp"
 #include "m3d_generalfit_fp.hpp"
-#include "m3d_mask_expand.hpp"
-
-#include <condition_variable>
-#include <mutex>
-#include <sched.h>
+#include "m3d_mask_pool.hpp"
 
 #pragma clang fp contract(off)
 
 namespace m3d {
 
-// ------------------------------------------------------------------------------------------------
-// The writers of a mask expansion (m3d_config.list_mask): one pool per process, created on first use, never torn down.
-// Helpers = min(writer cap, CPUs of the process' affinity mask) - 1; the caller's thread is always a writer as well.
-// arm() -- when a fit queues a mask compaction -- wakes the parked helpers: they spin on the job word for at most
-// wait_spin_us (so their wake-up hides under the device work still ahead), then park again.  expand() publishes the job as
-// tile ranges of equal output length, claimed through ONE word: (ranges << 32 | next range).  A claim is only made on the
-// current job (the word carries its range count), the caller works on ranges too and returns once every claimed range is
-// written.  A second caller while the pool is busy (another lane) expands alone: the result never depends on the helpers.
-// ------------------------------------------------------------------------------------------------
-namespace {
-class MaskPool {
-public:
-    static MaskPool& get() {
-        static MaskPool* p = new MaskPool();   // (leaked on purpose: helpers may still be parked at exit)
-        return *p;
-    }
-    static uint32_t writer_cap() {
-        const int lm = config().list_mask;
-        uint32_t cap = lm >= 2 ? (uint32_t)lm : 8u;
-        cpu_set_t set;
-        CPU_ZERO(&set);
-        if (sched_getaffinity(0, sizeof(set), &set) == 0) cap = std::min<uint32_t>(cap, (uint32_t)std::max(CPU_COUNT(&set), 1));
-        return std::max<uint32_t>(cap, 1u);
-    }
-    void arm() {
-        const uint32_t helpers = writer_cap() - 1;
-        spin_us_.store(std::max(config().wait_spin_us, 0), std::memory_order_relaxed);
-        if (helpers == 0) return;
-        std::lock_guard<std::mutex> lk(mu_);
-        try {
-            while (threads_ < helpers) {
-                std::thread(&MaskPool::helper, this, threads_).detach();
-                ++threads_;
-            }
-        } catch (...) {   // (no thread to be had: fewer helpers -- the caller writes what they do not)
-        }
-        want_ = std::min(helpers, threads_);
-        arm_seq_.fetch_add(1, std::memory_order_release);
-        if (parked_) cv_.notify_all();
-    }
-    // false: the mask disagrees with its counts (dst[0, total) may then hold anything, nothing beyond it was written)
-    bool expand(const uint64_t* mask, uint64_t n, const uint32_t* counts, uint64_t* dst) {
-        const uint32_t nb = (uint32_t)((n + 64ull * kMaskTileWords - 1) / (64ull * kMaskTileWords));
-        if (nb == 0) return true;
-        bool expected = false;
-        if (!busy_.compare_exchange_strong(expected, true, std::memory_order_acquire)) {
-            std::vector<uint64_t> prefix(nb + 1);
-            mask_tile_prefix(counts, nb, prefix.data());
-            return mask_expand_range(mask, n, prefix.data(), 0, nb, dst);
-        }
-        prefix_.resize(nb + 1);
-        mask_tile_prefix(counts, nb, prefix_.data());
-        const uint32_t ranges = std::min<uint32_t>(nb, 4u * writer_cap());
-        bounds_.resize(ranges + 1);
-        mask_split(prefix_.data(), nb, ranges, bounds_.data());
-        mask_ = mask;
-        n_ = n;
-        dst_ = dst;
-        failed_.store(false, std::memory_order_relaxed);
-        done_.store(0, std::memory_order_relaxed);
-        job_.store((uint64_t)ranges << 32, std::memory_order_release);   // (publishes the fields above)
-        work();
-        while (done_.load(std::memory_order_acquire) != ranges) {
-#if defined(__x86_64__) || defined(__i386__)
-            __builtin_ia32_pause();
-#endif
-        }
-        const bool ok = !failed_.load(std::memory_order_relaxed);
-        busy_.store(false, std::memory_order_release);
-        return ok;
-    }
-
-private:
-    // claim and write ranges of the current job until none is left; true if any was claimed
-    bool work() {
-        bool any = false;
-        for (;;) {
-            const uint64_t v = job_.load(std::memory_order_relaxed);
-            if ((v & 0xFFFFFFFFull) >= (v >> 32)) return any;
-            const uint64_t c = job_.fetch_add(1, std::memory_order_acq_rel);
-            const uint32_t k = (uint32_t)c, ranges = (uint32_t)(c >> 32);
-            if (k >= ranges) return any;
-            if (!mask_expand_range(mask_, n_, prefix_.data(), bounds_[k], bounds_[k + 1], dst_))
-                failed_.store(true, std::memory_order_relaxed);
-            done_.fetch_add(1, std::memory_order_release);
-            any = true;
-        }
-    }
-    void helper(uint32_t id) {
-        uint64_t seen = 0;
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> lk(mu_);
-                ++parked_;
-                cv_.wait(lk, [&] { return arm_seq_.load(std::memory_order_relaxed) != seen && id < want_; });
-                --parked_;
-                seen = arm_seq_.load(std::memory_order_relaxed);
-            }
-            auto t0 = std::chrono::steady_clock::now();
-            for (uint32_t spins = 1;; ++spins) {
-                if (work()) t0 = std::chrono::steady_clock::now();
-                const uint64_t a = arm_seq_.load(std::memory_order_relaxed);
-                if (a != seen) {   // armed again while awake: the spin starts over
-                    seen = a;
-                    t0 = std::chrono::steady_clock::now();
-                }
-                if ((spins & 0xFFu) == 0 &&
-                    std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() >=
-                        spin_us_.load(std::memory_order_relaxed))
-                    break;
-#if defined(__x86_64__) || defined(__i386__)
-                __builtin_ia32_pause();
-#endif
-            }
-        }
-    }
-    std::mutex mu_;
-    std::condition_variable cv_;
-    uint32_t threads_ = 0, want_ = 0, parked_ = 0;   // (mu_)
-    std::atomic<uint64_t> arm_seq_{0};
-    std::atomic<int> spin_us_{0};
-    std::atomic<bool> busy_{false};
-    // the job (written by the pool's owner while no range of it can be claimed)
-    std::atomic<uint64_t> job_{0};
-    std::atomic<uint32_t> done_{0};
-    std::atomic<bool> failed_{false};
-    const uint64_t* mask_ = nullptr;
-    uint64_t n_ = 0;
-    uint64_t* dst_ = nullptr;
-    std::vector<uint64_t> prefix_;
-    std::vector<uint32_t> bounds_;
-};
-}  // namespace
-
+// The writers of a mask expansion (m3d_config.list_mask): the process' pool of m3d_mask_pool.hpp, sized by the configuration
+static uint32_t mask_writers() { return MaskPool::writer_cap(config().list_mask); }
 
 // Scratch of launch_compact (m3d_kernels.hpp): one slot per compaction workgroup
 int compact_scratch(DeviceCtx* ctx, uint32_t nb, uint32_t** slots) {
@@ -249,7 +113,7 @@ int issue_refine_compaction(DeviceCtx* ctx, const CloudView& flag_view, const ui
             std::memset(ctx->h_sync.p, 0, 64);
         }
         if (++ctx->mask_seq == 0) ++ctx->mask_seq;   // (never 0: the words' initial value)
-        MaskPool::get().arm();   // (the helpers wake under the device work still ahead)
+        MaskPool::get().arm(mask_writers(), config().wait_spin_us);   // (the helpers wake under the device work still ahead)
     }
     launch_compact(kind, flag_view, model_dev, thr, 0, orig_dev,
                    idx_dev(ctx, fc), nullptr,
@@ -278,7 +142,7 @@ static bool expand_compaction_mask(DeviceCtx* ctx, uint32_t n, uint32_t expected
     uint64_t total = 0;
     for (uint32_t t = 0; t < nb; ++t) total += counts[t];
     if (total != expected) return false;
-    return MaskPool::get().expand(ctx->h_mask.as<const uint64_t>(), n, counts, dst);
+    return MaskPool::get().expand(ctx->h_mask.as<const uint64_t>(), n, counts, dst, mask_writers());
 }
 
 // GeneralFit's closed form on the inliers' mean and centred moments: 1 and the model refined in place, or 0 and the model
